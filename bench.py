@@ -14,6 +14,11 @@ once over RCCL/xGMI (oh_comm_broadcast_constants).  No torch anywhere: the commu
 liboptas_hip, Python only carries the 128-byte RCCL unique id from rank 0 to the others through a file
 (optas_amd/distributed.py); barriers and the MAX-reduce of the elapsed time go through oh_comm_* too.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything else this file measures or checks (the CPU
+baseline, the oracle-graded sample, the per-kernel roofline pass, the FK/Jacobian kernel, small-batch latency, the PCIe-inclusive solve,
+the other tolerance, batch_invariant, BASELINE configs 1, 3, 4, 5) runs only with --full.  --dump-outputs DIR writes what the last timed
+step returned (bench.py:dump_outputs) for an output-for-output comparison of two builds.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -59,6 +64,10 @@ BYTES = {"k_eval": 103 * 8, "k_couple": 68 * 8, "k_step": 76 * 8}
 #               which is -sum_t |L_t^-1 r_t|^2, a by-product of the backward substitutions)
 BYTES_ZC = {"k_eval": 117 * 8, "k_couple": 0, "k_step": 81 * 8}
 BYTES_FKJAC = 448  # q 56 B in, pose 56 B + J 336 B out
+# --dump-outputs: per-instance results of at most DUMP_ROWS instances, solutions x of at most DUMP_X_ROWS of them (693 doubles each):
+# at most 2**19 x (f 1 + kkt 3 + iters, status, row index 3) x 8 B + 4096 x 693 x 8 B = 52 MB in all
+DUMP_ROWS = 1 << 19
+DUMP_X_ROWS = 4096
 
 
 def make_inputs(B: int, rank: int):
@@ -235,6 +244,30 @@ def per_rank_block(elapsed_s, device_ms_per_step, rate, reduce_max, reduce_sum, 
             "sum_of_rank_rates_solves_per_s": reduce_sum(rate), "rccl_world": rccl_world, "note": note}
 
 
+def dump_outputs(path, B, nx, d_x, d_f, d_k, d_it, d_st):
+    """What oh_solve_device handed back in the last timed step, as DIR/<name>.npy (float64): f, kkt, iters, status of every instance (of a fixed
+    seeded sample of DUMP_ROWS instances beyond that batch size, listed in rows.npy) and x of a fixed seeded sample of DUMP_X_ROWS of those
+    (listed in x_rows.npy).  The samples depend on the batch size alone, so two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    rows = np.arange(B) if B <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(B, DUMP_ROWS, replace=False))
+    x_rows = rows if len(rows) <= DUMP_X_ROWS else np.sort(np.random.default_rng(1).choice(rows, DUMP_X_ROWS, replace=False))
+    x = np.empty((len(x_rows), nx))
+    lib, row_bytes = _lib.load(), nx * 8
+    for j, i in enumerate(x_rows):  # row by row: the whole x of the bench batch is 1.45 GB
+        _lib.check(lib.oh_memcpy_d2h(_lib._ptr(x[j]), C.c_void_p(d_x.ptr.value + int(i) * row_bytes), row_bytes), "oh_memcpy_d2h")
+    out = {
+        "x": x,
+        "f": d_f.download(np.float64, (B,))[rows],
+        "kkt": d_k.download(np.float64, (B, 3))[rows],
+        "iters": d_it.download(np.int32, (B,))[rows],
+        "status": d_st.download(np.int32, (B,))[rows],
+        "rows": rows,
+        "x_rows": x_rows,
+    }
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,16 +278,21 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-8, help="stopping tolerance on the reduced gradient, unscaled.  Default = IPOPT's `tol` default, what every reference "
                     "config runs with (setup('ipopt') without options: figure_eight_plan.py:111); rounds 1-5 quoted 1e-6, which the `tol_1e-6` block still reports")
     ap.add_argument("--hessian", choices=["gauss_newton", "exact", "hybrid"], default="hybrid")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="instances timed on one host core")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--fk-units", type=int, default=1 << 22)
-    ap.add_argument("--oracle-sample", type=int, default=16, help="instances of the timed batch graded by the oracle afterwards (rank 0, N=1)")
-    ap.add_argument("--timed-only", action="store_true", help="only the timed K steps and their per-kernel pass: no small-batch latency, no PCIe-inclusive solve, no "
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64, seeded samples of the larger arrays)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else: CPU baseline, oracle sample, per-kernel roofline pass, FK/Jacobian "
+                    "kernel, latency, PCIe-inclusive solve, the other tolerance, batch_invariant, BASELINE configs 1, 3, 4, 5 (the options below shape this part)")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="instances timed on one host core (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline and no oracle sample")
+    ap.add_argument("--fk-units", type=int, default=1 << 22, help="(--full) units of the FK/Jacobian kernel's roofline")
+    ap.add_argument("--oracle-sample", type=int, default=16, help="instances of the timed batch graded by the oracle afterwards (--full, rank 0, N=1)")
+    ap.add_argument("--timed-only", action="store_true", help="(--full) only the timed K steps and their per-kernel pass: no small-batch latency, no PCIe-inclusive solve, no "
                     "configs block (tools/profile.sh: the rocprofv3 averages then cover exactly the launches the roofline object is computed from)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the block that measures BASELINE configs 1, 3, 4, 5 after the timed region (rank 0, N=1)")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the block that measures BASELINE configs 1, 3, 4, 5 after the timed region (rank 0, N=1)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: run the multi-process plumbing only (rendezvous of the RCCL id with a stand-in id, "
                     "per-rank inputs) and print one JSON line per rank; everything of a --gpus N run except oh_comm_init and the solves")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -368,7 +406,7 @@ def main():
             comm.barrier()
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only; before the GPU phase so that the device work sits at the end of the run
+    if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only; before the GPU phase so that the device work sits at the end of the run
         cpu = cpu_baseline(args.cpu_sample, args.hessian, args.tol)
 
     streams_used = int(be.get_option("streams")) if B >= int(be.get_option("split_min")) else 1
@@ -391,6 +429,46 @@ def main():
         per_rank = per_rank_block(mine, dev, B * args.steps / mine, comm.max_over_ranks, comm.sum_over_ranks, rccl_world,
                                   "each rank's own wall time of the K steps between the two barriers, reduced through oh_comm_allreduce_{max,sum}; value uses the max")
         elapsed = per_rank["elapsed_s_max"]
+    out = {
+        "metric": "MPC solves/sec (KUKA 7-DoF, T=50)",
+        "value": world * B * args.steps / elapsed,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"figure_eight_plan T=50 KUKA LWR end_effector_ball (BASELINE configs[1]) x {B} perturbed instances per GPU "
+            f"(qc0 + U(-0.1,0.1)^7, seed=qc), solved to reduced-gradient tol {args.tol:g}, max_iter {args.max_iter}",
+            "batch_per_gpu": B,
+            "global_batch": world * B,
+            "T": T,
+            "parallelism": f"dp{world} (instances sharded, one RCCL broadcast of constants)",
+            "rccl_world": rccl_world,
+            **({"rccl_error": rccl_error} if rccl_error else {}),
+            "per_rank": per_rank,
+            "hessian": args.hessian,
+            "streams_per_gpu": streams_used,
+            "streams_note": "a batch at or above the handle's split_min is solved in `streams` contiguous parts, each on a HIP stream and host thread of its own "
+                            "(csrc/oh_api.hip:solve_split): the latency-bound phases of one part overlap the bandwidth-bound launches of the other",
+        },
+        "device_ms_per_step": solve_ms_plain / args.steps,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, B, nx, d_x, d_f, d_k, d_it, d_st)
+    if not args.full:
+        if comm is not None:
+            comm.barrier()
+            comm.destroy()
+        if rank == 0:
+            sys.stdout.flush()
+            print(json.dumps(out), file=result_out, flush=True)
+        return
     # second pass of the same K steps with one hipEventRecord after every kernel on the handle's stream: the per-kernel times behind the
     # roofline object (the timed pass above runs without them)
     be.set_profiling(True)
@@ -531,34 +609,7 @@ def main():
         "note": "units = running instances x (T-2) summed over the batched launches; iterations run inside the persistent tail kernel are excluded from units and time alike; k_eval is the pair of launches k_retract + k_evalb (rocprof lists them separately, profiles/*_kernel_stats.csv adds the pair)",
     }
     fk_achieved = nfk * BYTES_FKJAC / (fk_ms * 1e-3) / 1e9
-    out = {
-        "metric": "MPC solves/sec (KUKA 7-DoF, T=50)",
-        "value": world * B * args.steps / elapsed,
-        "unit": "solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"figure_eight_plan T=50 KUKA LWR end_effector_ball (BASELINE configs[1]) x {B} perturbed instances per GPU "
-            f"(qc0 + U(-0.1,0.1)^7, seed=qc), solved to reduced-gradient tol {args.tol:g}, max_iter {args.max_iter}",
-            "batch_per_gpu": B,
-            "global_batch": world * B,
-            "T": T,
-            "parallelism": f"dp{world} (instances sharded, one RCCL broadcast of constants)",
-            "rccl_world": rccl_world,
-            **({"rccl_error": rccl_error} if rccl_error else {}),
-            "per_rank": per_rank,
-            "hessian": args.hessian,
-            "streams_per_gpu": streams_used,
-            "streams_note": "a batch at or above the handle's split_min is solved in `streams` contiguous parts, each on a HIP stream and host thread of its own "
-                            "(csrc/oh_api.hip:solve_split): the latency-bound phases of one part overlap the bandwidth-bound launches of the other",
-        },
+    out.update({
         "roofline": roofline,
         "roofline_fk_jac": {
             "kernel": "k_fk_jac<SOA>",
@@ -583,7 +634,6 @@ def main():
             "f_mean": float(fvals.mean()),
             "oracle_sample": osample,
         },
-        "device_ms_per_step": solve_ms_plain / args.steps,
         "specialized_kernels": {**spec_info, "note": "k_retract / k_evalb / k_tail compiled with hiprtc behind a constexpr copy of the handle's kinematic chain (oh_specialize; automatic at the first solve of >= 4096 instances, before the timed region)"},
         "latency_b1_ms": lat[1],
         "latency_b1024_ms": lat[min(1024, B)],
@@ -593,7 +643,7 @@ def main():
         "tail_iteration_frac": tm["tail_iterations"] / max(1, tm["instance_launches"] + tm["tail_iterations"]),
         "compactions_per_step": tm["compactions"] / args.steps,
         "fused_coupling": zc,
-    }
+    })
     def tol_block(tol, ms, it, st, note):
         return {"tol": tol, "value": B / (1e-3 * ms), "unit": "solves/s", "ms_per_step": ms, "iters_p50": float(np.percentile(it, 50)), "iters_p90": float(np.percentile(it, 90)),
                 "iters_max": int(it.max()), "converged_frac": float((st == 0).mean()), "note": note}

@@ -6,7 +6,7 @@ out=gpurun_out/headline_options.txt
 : > $out
 for opt in "" "$@" ""; do
   echo "== $opt" >> $out
-  OH_DEBUG_OPTIONS="$opt" python bench.py --steps 5 --warmup 2 --no-cpu-baseline --timed-only 2>/dev/null | python -c "
+  OH_DEBUG_OPTIONS="$opt" python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --timed-only 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); q=d.get('quality',{}); print(round(d['value']), round(d['ms_per_step'],2), round(d['roofline']['frac'],4), d['roofline']['launches'], q.get('converged_frac'), q.get('iters_mean'))" >> $out
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 REPO=$(pwd); OUT=$REPO/gpurun_out/inv_prof; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-OH_DEBUG_OPTIONS="batch_invariant=1" rocprofv3 --kernel-trace --stats -d $OUT/trace -o inv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --timed-only > $OUT/bench.json 2> $OUT/log.txt
+OH_DEBUG_OPTIONS="batch_invariant=1" rocprofv3 --kernel-trace --stats -d $OUT/trace -o inv -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --timed-only > $OUT/bench.json 2> $OUT/log.txt
 cd $REPO
 python - <<PY
 import sqlite3, glob, re, json

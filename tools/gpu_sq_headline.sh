@@ -11,7 +11,7 @@ for set in "SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_V
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_WAVES" "SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM" \
            "GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   i=$((i+1))
-  timeout 900 rocprofv3 --kernel-trace --pmc $set -d $OUT/pmc$i -o sq -- python $REPO/bench.py $ARGS > $OUT/bench$i.json 2> $OUT/pmc$i.log
+  timeout 900 rocprofv3 --kernel-trace --pmc $set -d $OUT/pmc$i -o sq -- python $REPO/bench.py --full $ARGS > $OUT/bench$i.json 2> $OUT/pmc$i.log
 done
 cd $REPO
 python - <<PY

@@ -4,7 +4,7 @@ set -u
 CNT="$1"; TAG=$2; ARGS=${3:-"--steps 1 --warmup 1 --no-cpu-baseline"}
 REPO=$(pwd); OUT=$REPO/gpurun_out/pmc_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc $CNT -d $OUT -o pmc -- python $REPO/bench.py $ARGS > $OUT/bench.json 2> $OUT/log.txt
+rocprofv3 --kernel-trace --pmc $CNT -d $OUT -o pmc -- python $REPO/bench.py --full $ARGS > $OUT/bench.json 2> $OUT/log.txt
 cd $REPO
 python - <<PY
 import sqlite3, glob, collections
