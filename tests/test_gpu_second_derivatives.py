@@ -146,3 +146,32 @@ def test_inverse_dynamics_rows_are_exact(hip_lib):
         d = np.zeros(o.nx)
         d[j] = e
         assert np.abs(H[:, :, j] - (d1(x + d, p) - d1(x - d, p)) / (2 * e)).max() <= 1e-6 * max(1.0, np.abs(H).max())
+
+
+def test_inverse_dynamics_rows_are_exact_on_a_four_joint_arm(hip_lib, tmp_path):
+    """The same rows on a chain other than seven joints (med7 cut after its 4th joint, tests/dyn_robots.py): ddh of every knot's dynamics rows is
+    the oracle's complex-step Hessian, through k_rnea_hess<4> -- the instantiation the med7 problem never reaches."""
+    from dyn_robots import med7_cut
+    from examples.torque_mpc import build_problem
+    from optas_amd.models import RobotModel
+    from oracle.torque import RneaTables, rnea_ctau_hessian
+
+    T, n = 4, 4
+    kin = med7_cut(tmp_path, n)
+    _, _, o = build_problem(T=T, effort=60.0, robot=RobotModel(urdf_filename=kin, time_derivs=[0, 1, 2]), link="tool")
+    rng = np.random.default_rng(SEED + 6)
+    x, p = rng.uniform(-0.5, 0.5, o.nx), rng.uniform(-0.5, 0.5, o.np)
+    H = o.ddh(x, p)
+    assert H.shape == (o.nh, o.nx, o.nx) and o.nh >= n * T and np.isfinite(H).all()
+    assert np.abs(H - np.swapaxes(H, 1, 2)).max() <= 1e-12 * max(1.0, np.abs(H).max())
+    tb = RneaTables(OracleRobot(kin))
+    X = x.reshape(4, T, n)  # [vec(Q); vec(dQ); vec(ddQ); vec(TAU)], knot-major
+    for t in range(T):
+        idx = np.concatenate([np.arange(n) + n * t + n * T * k for k in range(3)])
+        for i in range(n):
+            Ho = -rnea_ctau_hessian(tb, X[0, t], X[1, t], X[2, t], np.eye(n)[i])  # h_i = TAU_i - rnea_i
+            blk = H[n * t + i][np.ix_(idx, idx)]
+            assert np.abs(blk - Ho).max() <= 1e-10 * max(1.0, np.abs(Ho).max()), (t, i)
+            rest = H[n * t + i].copy()
+            rest[np.ix_(idx, idx)] = 0.0
+            assert np.abs(rest).max() == 0.0  # a dynamics row of knot t touches nothing but knot t

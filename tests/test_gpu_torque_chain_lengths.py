@@ -5,14 +5,13 @@ layout is 8 x 8: up to seven joints and the vector column).  Robots: tests/golde
 and the KUKA med7 cut after its 3rd ... 6th joint with a 0.4 kg tool.  Every answer is compared with the numpy port of the same state machine
 (oracle/torque_ipm.py: objective 1e-9 relative, step counts +-2) and graded on the literal NLP (oracle/problems.py:TorqueMPCNLP) with the returned multipliers:
 stationarity <= 1e-6, linear rows <= 1e-12, dynamics rows <= 1e-10, inequality rows strictly inside, complementarity <= 1e-8."""
-import copy
-import json
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, MED7_KIN, SEED
+from conftest import GOLDEN, SEED
+from dyn_robots import med7_cut as _med7_cut
 from optas_amd import _lib
 from optas_amd.backend import TorqueBackend
 from optas_amd.models import RobotModel
@@ -26,23 +25,6 @@ pytestmark = pytest.mark.gpu
 TESTER_REV_KIN = os.path.join(GOLDEN, "tester_robot_revolute.kin.json")
 W = dict(w_path=1000.0, w_vel=0.1, w_tau=1e-4)
 T = 12
-
-
-def _med7_cut(tmp_path, n):
-    """med7.kin.json with n actuated joints: cut after joint n, a tool (0.4 kg) on a fixed joint behind it -- every body RobotModel.rnea counts carries <inertial>."""
-    d = json.load(open(MED7_KIN))
-    joints = {j["name"]: j for j in d["joints"]}
-    links = {l["name"]: l for l in d["links"]}
-    out = copy.deepcopy(d)
-    out["name"] = f"med{n}"
-    keep = ["world_lbr_joint"] + [f"lbr_joint_{i}" for i in range(n)]
-    out["joints"] = [joints[k] for k in keep] + [{"name": "tool_joint", "type": "fixed", "parent": joints[keep[-1]]["child"], "child": "tool", "xyz": [0.0, 0.0, 0.12],
-                                                 "rpy": [0.0, 0.0, 0.0]}]
-    out["links"] = [links[k] for k in ["world"] + [joints[k]["child"] for k in keep]] + [
-        {"name": "tool", "inertial": {"mass": 0.4, "xyz": [0.0, 0.0, 0.03], "rpy": [0.0, 0.0, 0.0], "inertia": [0.001, 0.0, 0.0, 0.001, 0.0, 0.0008]}}]
-    path = os.path.join(str(tmp_path), f"med{n}.kin.json")
-    json.dump(out, open(path, "w"))
-    return path
 
 
 def _robots(tmp_path):
