@@ -465,7 +465,9 @@ int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, double ramp, co
 int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, double mu_warm, const double* state0, const double* goal_table, double* states,
                   double* tau0, double* f, int* iters, int* status);
 
-/* Multipliers of the last oh_solve/oh_solve_device in the reference's form: lam_h [B][4*T] for the rows
+/* Multipliers of the handle's last successful solve or rollout (oh_solve, oh_solve_device, oh_tq_rollout; B must be its batch), forgotten by a
+   setter that replaces constants, guards or dynamics (oh_set_constants*, oh_comm_broadcast_constants, oh_set_guards, oh_set_dynamics): then, as after
+   a failed call, OH_ERR_STATE.  In the reference's form: lam_h [B][4*T] for the rows
    h = quat_c - quat(q_t) (signed mu = lam+ - lam- of the (h,-h) pair, optimization.py:47-51). Host buffer.
    OH_PROBLEM_IK: lam_h [B][3 + 2*ndof] = (mu of h = p_goal - p_link(q) (3), multipliers of q - lo >= 0 (ndof),
    multipliers of up - q >= 0 (ndof)).

@@ -39,6 +39,38 @@ static thread_local OhLaunchOpts g_launch_opts;
 OhLaunchOpts& oh_launch_opts() { return g_launch_opts; }
 #define OH_PINNED_STAGE_BYTES (256 * 1024)
 
+// Scheduling state of a handle, set by name through the field-backed options (FIELD_OPTS): a peer takes it over in one assignment.
+struct Sched {
+  int compaction = 1;
+  int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
+  int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see solve_device)
+  int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
+  int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
+  int compact_sort = 1;      // order the survivors of a compaction by progress (k_scan_*)
+  double compact_frac = 0.97;  // compact the batch once this fraction of it (or less) is still running (0.9 until the carried compaction
+                               // stopped copying back: 0.95 ... 0.99 are +1 ... 2 % over 0.9 on two boxes, interleaved runs)
+  double compact_frac_restart = 0.9;  // the same for the compaction that restarts the survivors (guarded handles, free family): it costs an evaluation
+  int tail_threshold = 16384;  // hand the last instances to the persistent one-wave-per-instance kernel (round 2: with the kernel compiled for the
+                               // chain 8192 against 2048 was +1.3 ... 3 % at B = 262 144 and -21 % on a batch of 4096; with four of its blocks per CU
+                               // (two-pass exchange, 40 KB of LDS) 16 384 is level at B = 262 144 and -6 ... 13 % on batches of 16 ... 24 k)
+  int sparse_check_below = 2048;  // OH_SPARSE_CHECK_BELOW (0: look every iteration whatever the batch)
+  int fuse_couple = 1;        // OH_FUSE_COUPLE=0 restores the three-kernel iteration (k_couple between evaluation and sweep) for A/B runs
+  int free_pcr_max = 1536;    // position-tracking family: K3 by cyclic reduction, one block per instance, while at most this many are in the launch
+  int specialize = OH_SPECIALIZE_AUTO;  // option "specialize": 0 never, 1 at the first solve, 2 auto: at the first solve of >= specialize_min_B instances
+  int tq_check = 4;  // the host looks at the running count every tq_check iterations
+  std::array<double, 4> inv_saved{1.0, 16384.0, 1.0, -2.0};  // compaction, tail_threshold, tail_vel, free_persist (-2: unset) as they were before batch_invariant
+};
+
+// The last successful solve or rollout of a handle: B, and where each instance's multipliers live -- on the handles of `parts` (n instances
+// each, in instance order) or, after a pipelined oh_solve, in the handle's d_pipe_mult.  Cleared by every entry that solves and by drop_peers.
+struct oh_handle;
+struct LastSolve {
+  struct Part { const oh_handle* q; int n; };
+  int B = 0;
+  std::vector<Part> parts;
+  bool pipe_cache = false;
+};
+
 struct oh_handle {
   oh_problem_desc desc;
   std::vector<double> local_path;
@@ -100,15 +132,13 @@ struct oh_handle {
   double* d_tq_mult = nullptr;
   double* d_tq_hc = nullptr;  // [tq_cap][T][TQ_HC] stored curvature terms (k_tq_curv)
   int tq_cap = 0;
-  int tq_check = 4;  // the host looks at the running count every tq_check iterations
-  std::array<double, 4> inv_saved{1.0, 16384.0, 1.0, -2.0};  // compaction, tail_threshold, tail_vel, free_persist (-2: unset) as they were before batch_invariant
   // solver buffers
   int cap_B = 0;
   FigBuffers D{};
   FigParams P{};
   void* pool = nullptr;
   size_t pool_bytes = 0;
-  int last_B = 0;
+  LastSolve last;  // where the results of the last successful solve live (oh_get_multipliers)
   // staging for the host-buffer entry points
   void* stage = nullptr;
   size_t stage_bytes = 0;
@@ -122,28 +152,11 @@ struct oh_handle {
   int* h_flag = nullptr;  // pinned
   // a large batch of the plain orientation-locked family is solved in parts on handles (streams, host threads) of their own: solve_split
   std::vector<oh_handle*> peers;
-  std::vector<int> split_parts;  // instances per part of the last solve (empty: it was not split)
-  bool pipe_last = false;        // the last solve was a pipelined oh_solve: its multipliers wait in d_pipe_mult (every chunk's, in instance order)
-  double* d_pipe_mult = nullptr;
+  double* d_pipe_mult = nullptr;  // multipliers of every chunk of a pipelined oh_solve, in instance order
   size_t pipe_mult_cap = 0;      // doubles
-  bool is_peer = false;
-  bool compaction = true;
-  int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
-  int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see oh_solve_device)
-  int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
-  int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
-  int compact_sort = 1;      // order the survivors of a compaction by progress (k_scan_*)
-  double compact_frac = 0.97;  // compact the batch once this fraction of it (or less) is still running (0.9 until the carried compaction
-                               // stopped copying back: 0.95 ... 0.99 are +1 ... 2 % over 0.9 on two boxes, interleaved runs)
-  double compact_frac_restart = 0.9;  // the same for the compaction that restarts the survivors (guarded handles, free family): it costs an evaluation
-  int tail_threshold = 16384;  // hand the last instances to the persistent one-wave-per-instance kernel (round 2: with the kernel compiled for the
-                               // chain 8192 against 2048 was +1.3 ... 3 % at B = 262 144 and -21 % on a batch of 4096; with four of its blocks per CU
-                               // (two-pass exchange, 40 KB of LDS) 16 384 is level at B = 262 144 and -6 ... 13 % on batches of 16 ... 24 k)
-  int sparse_check_below = 2048;  // OH_SPARSE_CHECK_BELOW (0: look every iteration whatever the batch)
-  int fuse_couple = 1;        // OH_FUSE_COUPLE=0 restores the three-kernel iteration (k_couple between evaluation and sweep) for A/B runs
-  int free_pcr_max = 1536;    // position-tracking family: K3 by cyclic reduction, one block per instance, while at most this many are in the launch
+  bool is_peer = false;          // this handle is a lane of another one (fan_out): it never fans out itself
+  Sched sch;
   // run-time specialised evaluation kernels of the orientation-locked figure-eight family (oh_jit.hip)
-  int specialize = OH_SPECIALIZE_AUTO;  // option "specialize": 0 never, 1 at the first solve, 2 auto: at the first solve of >= specialize_min_B instances
   int specialize_min_B = 4096;
   const FigSpec* spec = nullptr;
   bool spec_failed = false;
@@ -179,7 +192,7 @@ static double optv(const oh_handle* h, const char* name, double dflt) {
   return it == h->opt.end() ? dflt : it->second;
 }
 struct OptDoc { const char* name; double dflt; };
-// map-backed options and their defaults (field-backed ones are handled in set_option_impl / oh_get_option)
+// map-backed options and their defaults (field-backed ones: FIELD_OPTS)
 static const OptDoc OPT_TABLE[] = {
     {"check_every", 1},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
     {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30},
@@ -188,21 +201,33 @@ static const OptDoc OPT_TABLE[] = {
     {"tq_rebuild", 0.9},         {"compact_move_all", 1},  {"tq_curv_late", 1.0},  {"tq_kappa_eps", 10.0}, {"tq_max_back", 3},     {"tq_mu_dec", 1.0 / 3.0},     {"tq_ls_curv", 1},   {"tq_mu_dec_warm", 0.1}, {"tq_curv_lag", 3},
     {"tol", 0},                {"pipe", 1},               {"pipe_chunk", 32768},                {"invariant_compact_frac", 0.65}, {"invariant_split", 1}, {"invariant_move_slim", 1}, {"invariant_move_live", 1},
 };
+// field-backed options: the one list of name -> field of Sched that oh_set_option and oh_get_option read (a flag stores v != 0)
+struct FieldOpt {
+  const char* name;
+  int Sched::*i;
+  double Sched::*d = nullptr;
+  bool flag = false;
+  double get(const Sched& s) const { return d ? s.*d : s.*i; }
+  void set(Sched& s, const double v) const { if (d) s.*d = v; else s.*i = flag ? v != 0.0 : (int)v; }
+};
+static const FieldOpt FIELD_OPTS[] = {
+    {"tail_threshold", &Sched::tail_threshold}, {"free_pcr_max", &Sched::free_pcr_max}, {"compaction", &Sched::compaction, nullptr, true},
+    {"compact_frac", nullptr, &Sched::compact_frac}, {"compact_sort", &Sched::compact_sort}, {"compact_carry", &Sched::compact_carry},
+    {"tail_vel", &Sched::tail_vel}, {"lg_split", &Sched::lg_split}, {"tail_vel_threshold", &Sched::tail_vel_threshold},
+    {"fuse_couple", &Sched::fuse_couple, nullptr, true}, {"sparse_check_below", &Sched::sparse_check_below}, {"specialize", &Sched::specialize},
+    {"tq_check", &Sched::tq_check},
+};
+static const FieldOpt* field_opt(const std::string& name) {
+  for (const FieldOpt& f : FIELD_OPTS)
+    if (name == f.name) return &f;
+  return nullptr;
+}
 static int tape_configure(oh_handle* h);
 static int set_option_impl(oh_handle* h, const std::string& name, double v) {
-  if (name == "tail_threshold") h->tail_threshold = (int)v;
-  else if (name == "free_pcr_max") h->free_pcr_max = (int)v;
-  else if (name == "compaction") h->compaction = v != 0.0;
-  else if (name == "compact_frac") h->compact_frac = h->compact_frac_restart = v;
-  else if (name == "compact_sort") h->compact_sort = (int)v;
-  else if (name == "compact_carry") h->compact_carry = (int)v;
-  else if (name == "tail_vel") h->tail_vel = (int)v;
-  else if (name == "lg_split") h->lg_split = (int)v;
-  else if (name == "tail_vel_threshold") h->tail_vel_threshold = (int)v;
-  else if (name == "fuse_couple") h->fuse_couple = v != 0.0;
-  else if (name == "sparse_check_below") h->sparse_check_below = (int)v;
-  else if (name == "specialize") h->specialize = v == 0.0 ? OH_SPECIALIZE_NEVER : (v == 1.0 ? OH_SPECIALIZE_ALWAYS : OH_SPECIALIZE_AUTO);
-  else if (name == "tq_check") h->tq_check = v >= 1.0 ? (int)v : 1;
+  Sched& sc = h->sch;
+  if (name == "compact_frac") sc.compact_frac = sc.compact_frac_restart = v;
+  else if (name == "specialize") sc.specialize = v == 0.0 ? OH_SPECIALIZE_NEVER : (v == 1.0 ? OH_SPECIALIZE_ALWAYS : OH_SPECIALIZE_AUTO);
+  else if (name == "tq_check") sc.tq_check = v >= 1.0 ? (int)v : 1;
   else if (name == "batch_invariant") {
     // every instance takes the batched launches to the end, nothing restarts, nothing is handed to the persistent kernel; the batch is compacted only
     // by moving a survivor with everything it owns (move_everything): the path of an instance is then a function of the instance alone, bit for bit
@@ -212,13 +237,14 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     const bool was = optv(h, "batch_invariant", 0.0) != 0.0;
     h->opt[name] = v;
     if (v != 0.0 && !was) {
-      h->inv_saved = {h->compaction ? 1.0 : 0.0, (double)h->tail_threshold, (double)h->tail_vel, h->opt.count("free_persist") ? h->opt["free_persist"] : -2.0};
-      h->compaction = false; h->tail_threshold = 0; h->tail_vel = 0; h->opt["free_persist"] = 0;
+      sc.inv_saved = {sc.compaction ? 1.0 : 0.0, (double)sc.tail_threshold, (double)sc.tail_vel, h->opt.count("free_persist") ? h->opt["free_persist"] : -2.0};
+      sc.compaction = false; sc.tail_threshold = 0; sc.tail_vel = 0; h->opt["free_persist"] = 0;
     } else if (v == 0.0 && was) {
-      h->compaction = h->inv_saved[0] != 0.0; h->tail_threshold = (int)h->inv_saved[1]; h->tail_vel = (int)h->inv_saved[2];
-      if (h->inv_saved[3] == -2.0) h->opt.erase("free_persist"); else h->opt["free_persist"] = h->inv_saved[3];
+      sc.compaction = sc.inv_saved[0] != 0.0; sc.tail_threshold = (int)sc.inv_saved[1]; sc.tail_vel = (int)sc.inv_saved[2];
+      if (sc.inv_saved[3] == -2.0) h->opt.erase("free_persist"); else h->opt["free_persist"] = sc.inv_saved[3];
     }
-  } else {
+  } else if (const FieldOpt* f = field_opt(name)) f->set(sc, v);
+  else {
     bool known = false;
     for (const OptDoc& d : OPT_TABLE) known = known || name == d.name;
     if (!known) return fail(OH_ERR_INVALID, "oh_set_option: unknown option '" + name + "'");
@@ -234,20 +260,8 @@ extern "C" int oh_set_option(oh_handle* h, const char* name, double value) {
 extern "C" int oh_get_option(oh_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_option: null argument");
   const std::string n(name);
-  if (n == "tail_threshold") *value = h->tail_threshold;
-  else if (n == "free_pcr_max") *value = h->free_pcr_max;
-  else if (n == "compaction") *value = h->compaction ? 1 : 0;
-  else if (n == "compact_frac") *value = h->compact_frac;
-  else if (n == "compact_sort") *value = h->compact_sort;
-  else if (n == "compact_carry") *value = h->compact_carry;
-  else if (n == "tail_vel") *value = h->tail_vel;
-  else if (n == "lg_split") *value = h->lg_split;
-  else if (n == "tail_vel_threshold") *value = h->tail_vel_threshold;
-  else if (n == "fuse_couple") *value = h->fuse_couple ? 1 : 0;
-  else if (n == "sparse_check_below") *value = h->sparse_check_below;
-  else if (n == "specialize") *value = h->specialize;
-  else if (n == "tq_check") *value = h->tq_check;
-  else if (n == "batch_invariant") *value = optv(h, "batch_invariant", 0.0);
+  if (n == "batch_invariant") *value = optv(h, "batch_invariant", 0.0);
+  else if (const FieldOpt* f = field_opt(n)) *value = f->get(h->sch);
   else {
     for (const OptDoc& d : OPT_TABLE)
       if (n == d.name) { *value = optv(h, d.name, d.dflt); return OH_OK; }
@@ -298,6 +312,24 @@ static oh_handle* new_handle() {
     return nullptr;
   }
   return h;
+}
+
+// every solve reports counters of its own only (oh_get_timing)
+static void reset_counters(oh_handle* h) {
+  for (double& t : h->timing) t = 0.0;
+  h->timing_couple = h->rejects = h->tail_iters = 0.0;
+}
+// the tail every solve shares: wait for the launches since ev0, report a launch error, time the solve ([4]) and count its launches ([5])
+static int finish_solve(oh_handle* h, const double launched) {
+  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  reset_counters(h);
+  h->timing[4] = ms;
+  h->timing[5] = launched;
+  return OH_OK;
 }
 
 extern "C" int oh_device_count(int* n) {
@@ -641,16 +673,7 @@ static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* 
   else
     oh_launch_tape_solve(h->stream, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap, (const double*)d_x0,
                          (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult);
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms;
-  h->timing[5] = 1;
-  h->last_B = B;
-  return OH_OK;
+  return finish_solve(h, 1);
 }
 
 extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
@@ -680,6 +703,28 @@ extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
 }
 
 static size_t qp_np(const oh_qp_desc& q) { return (size_t)q.n * q.n + q.n + (size_t)q.m * q.n + q.m + (size_t)q.me * q.n + q.me; }
+
+// Doubles per instance of a handle's problem: x, p, and the multipliers oh_get_multipliers returns (0: the problem has none).
+struct Shape { size_t nx, npar, mult; };
+static Shape shape_of(const oh_handle* h) {
+  const size_t N = h->desc.ndof, T = h->desc.T;
+  switch (h->desc.kind) {
+    case OH_PROBLEM_TORQUE_MPC: return {4 * N * T, 2 * N + 3 * T, T * (h->tq.vel_limits ? 4 : 2) * N};
+    case OH_PROBLEM_TAPE: return {(size_t)h->TP.nx, (size_t)(h->TP.np > 0 ? h->TP.np : 1), (size_t)(h->TP.n_ineq + h->TP.n_eq)};
+    case OH_PROBLEM_QP: return {(size_t)h->qp.n, h->qp_tape ? (size_t)(h->TP.np > 0 ? h->TP.np : 1) : qp_np(h->qp), (size_t)(h->qp.m + h->qp.me)};
+    case OH_PROBLEM_POINT_MASS_MPC: return {4 * T, 4 + 4 * T, 0};
+    case OH_PROBLEM_IK: return {N, N + 3, 3 + 2 * N};
+    case OH_PROBLEM_FIGURE_EIGHT: {
+      const oh_guards& g = h->guards;
+      const size_t nx = N * T + N * (T - 1);
+      if (h->chain_host.has_lead) return {nx, N + 1 + T, h->desc.lock_orientation ? 4 * T : 0};
+      if (!h->have_guards) return {nx, N, h->desc.lock_orientation ? 4 * T : 0};
+      // [T][NC (+ 2 ndof velocity rows)]: limits, spheres x obstacles
+      return {nx, N + g.n_links + 4 * (size_t)g.n_obstacles, T * ((g.limits ? 2 * N : 0) + (size_t)g.n_links * g.n_obstacles + (g.vel_limits ? 2 * N : 0))};
+    }
+    default: return {0, 0, 0};
+  }
+}
 
 extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
   if (!h || !d) return fail(OH_ERR_INVALID, "oh_qp_set_tape: null argument");
@@ -770,16 +815,7 @@ static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   oh_launch_qp_solve(h->stream, Q, B, h->qp_cap, (const double*)d_x0, (const double*)d_p, h->d_qp_work, (double*)d_x, (double*)d_f, (double*)d_kkt,
                      (int*)d_iters, (int*)d_status, h->d_qp_mult);
   if (h->qp_tape && d_f) oh_launch_qp_add_constant(h->stream, B, (double*)d_f, h->d_qp_f0);
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms;
-  h->timing[5] = 1;
-  h->last_B = B;
-  return OH_OK;
+  return finish_solve(h, 1);
 }
 
 extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
@@ -902,8 +938,8 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     P.dq_lo[i] = h->tq.dq_lo[i];
     P.dq_up[i] = h->tq.dq_up[i];
   }
-  P.nx = 4 * N * T;
-  P.np = 2 * N + 3 * T;
+  P.nx = (int)shape_of(h).nx;
+  P.np = (int)shape_of(h).npar;
   TqBuffers& D = h->TqD;
   if (B > h->tq_cap) {
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -980,7 +1016,7 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     if (prof) HIPCHK(hipEventRecord(h->prof_events[ne++], s));
     ++launched;
     work += running;
-    if (launched % h->tq_check == 0 || launched == cap) {
+    if (launched % h->sch.tq_check == 0 || launched == cap) {
       HIPCHK(hipMemcpyAsync(h->h_flag, D.n_running, sizeof(int), hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       running = *h->h_flag;
@@ -994,12 +1030,7 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     }
   }
   oh_launch_tq_finalize(s, P, D, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tq_mult);
-  HIPCHK(hipEventRecord(h->ev1, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
+  if (const int rc = finish_solve(h, launched)) return rc;
   if (prof) {
     for (size_t i = 0; i + 3 <= ne; i += 3) {
       float a = 0.f, b2 = 0.f;
@@ -1010,13 +1041,7 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     }
     h->timing[1] = h->timing[3] = launched;
   }
-  h->timing[4] = ms;
-  h->timing[5] = launched;
   h->timing[6] = work;
-  h->timing_couple = 0;
-  h->rejects = 0;
-  h->tail_iters = 0;
-  h->last_B = B;
   return OH_OK;
 }
 
@@ -1049,16 +1074,7 @@ static int ik_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   if (!oh_launch_ik_solve(h->stream, h->d_chain, P, B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt,
                           (int*)d_iters, (int*)d_status, h->d_ik_mult))
     return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms;
-  h->timing[5] = 1;
-  h->last_B = B;
-  return OH_OK;
+  return finish_solve(h, 1);
 }
 
 static int pm_prepare(oh_handle* h, int B) {
@@ -1098,16 +1114,7 @@ static int pm_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   oh_launch_pm_solve(h->stream, h->PmP, h->PmD, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt,
                      (int*)d_iters, (int*)d_status);
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms;
-  h->timing[5] = 1;
-  h->last_B = B;
-  return OH_OK;
+  return finish_solve(h, 1);
 }
 
 static int validate_chain(const oh_handle* h, const oh_chain& c) {
@@ -1124,12 +1131,12 @@ static int validate_chain(const oh_handle* h, const oh_chain& c) {
 // The parts of a split solve run on peer handles that were given the chain, dynamics and inequality rows of this handle when they were created
 // (solve_split).  Any setter that changes one of those on the main handle destroys the peers: the next split solve builds them again from the new
 // data (parts 1.. used to go on solving with the old chain / limits / obstacles, and guards set after a first split solve left the peers
-// striding p by ndof only).
+// striding p by ndof only).  The record of the last solve goes with them: what it points at was computed with the old data.
 static void drop_peers(oh_handle* h) {
+  h->last = LastSolve{};
   if (h->is_peer) return;
   for (oh_handle* p : h->peers) oh_destroy(p);
   h->peers.clear();
-  h->split_parts.clear();
 }
 
 // the handle has new constants: everything compiled for, or remembered about, the previous chain goes (one place for the three entry
@@ -1187,7 +1194,7 @@ static bool stage_fits(const oh_handle* h, int B) {
   // handles with the coupling folded in: the sweep addresses G of either slot and the spare as one 32-bit offset from the lowest of the three
   // adjacent arrays (oh_figure8_units.h:step_instance_zc): 3 T N doubles per instance have to stay below 4 GiB (round 3: found by the batch
   // sweep -- 524 288 instances ran through with wrapped offsets and converged nowhere; they are now refused here and split by the host)
-  const bool zc = h->fuse_couple && !h->have_guards && !h->chain_host.has_lead;
+  const bool zc = h->sch.fuse_couple && !h->have_guards && !h->chain_host.has_lead;
   return !zc || 3.0 * (double)T * N * (double)row_stride(h, B) * 8.0 < 4294967296.0;
 }
 
@@ -1419,7 +1426,7 @@ static void fill_params(oh_handle* h) {
   P.t0 = d.fix_dq0 ? 2 : 1;
   P.lock = d.lock_orientation;
   P.path_in_frame = d.path_in_frame;
-  P.nx = d.ndof * d.T + d.ndof * (d.T - 1);
+  P.nx = (int)shape_of(h).nx;
   P.dt = d.dt;
   P.w_path = d.w_path;
   P.kappa = d.w_vel / (d.dt * d.dt);
@@ -1449,11 +1456,10 @@ static void fill_params(oh_handle* h) {
   P.settle_k = optv(h, "settle_k", 1.0);
   P.al_fuse = (int)optv(h, "al_fuse", 1.0);
   P.local_path = h->d_local_path;
-  P.np = d.ndof + (h->have_guards ? h->guards.n_links + 4 * h->guards.n_obstacles : 0);
-  if (h->chain_host.has_lead) P.np = d.ndof + 1 + d.T;
+  P.np = (int)shape_of(h).npar;
   // coupling folded into evaluation and sweep (no k_couple launch): the plain orientation-locked handles, i.e. the batched path of config 2
-  P.zc = (h->fuse_couple && d.lock_orientation && !h->have_guards && !h->chain_host.has_lead) ? 1 : 0;
-  P.zc_free = (h->fuse_couple && !d.lock_orientation && !(h->have_guards && h->guards.vel_limits)) ? 1 : 0;
+  P.zc = (h->sch.fuse_couple && d.lock_orientation && !h->have_guards && !h->chain_host.has_lead) ? 1 : 0;
+  P.zc_free = (h->sch.fuse_couple && !d.lock_orientation && !(h->have_guards && h->guards.vel_limits)) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) static void k_gather_int(const int* __restrict__ src, int* __restrict__ dst, const int B, const int* __restrict__ newidx) {
@@ -1528,12 +1534,6 @@ static int move_everything(oh_handle* h, hipStream_t s, int Bnew) {
 // each other's gaps: 262 144 instances 91.1 -> 84.6 ms on one box (2.88 -> 3.10 M solves/s; three parts 86.3, four 90.9: tools/gpu_two_streams.py).
 // Instances are independent, so this is the multi-GPU sharding of DESIGN section 7 applied once more inside a GPU.  Each part is a handle of its own (peer:
 // same description, constants, options, compiled kernels); profiling runs (events after every kernel) stay on one stream.
-static void copy_options(oh_handle* dst, const oh_handle* src) {
-  dst->tail_threshold = src->tail_threshold; dst->free_pcr_max = src->free_pcr_max; dst->compaction = src->compaction;
-  dst->compact_frac = src->compact_frac; dst->compact_frac_restart = src->compact_frac_restart; dst->compact_sort = src->compact_sort;
-  dst->compact_carry = src->compact_carry; dst->tail_vel = src->tail_vel; dst->lg_split = src->lg_split; dst->tail_vel_threshold = src->tail_vel_threshold;
-  dst->fuse_couple = src->fuse_couple; dst->sparse_check_below = src->sparse_check_below; dst->specialize = src->specialize; dst->tq_check = src->tq_check; dst->opt = src->opt;
-}
 // peer handles of a trajectory / torque handle: same description, constants, dynamics and inequality rows, a stream of their own (parts of a split solve,
 // lanes of the pipelined host-buffer solve)
 static int ensure_peers(oh_handle* h, const int n) {
@@ -1559,73 +1559,99 @@ static int ensure_peers(oh_handle* h, const int n) {
   }
   return OH_OK;
 }
-static int solve_split(oh_handle* h, const int S, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
-  const bool tqk = h->desc.kind == OH_PROBLEM_TORQUE_MPC;
-  int prc = ensure_peers(h, S - 1);
-  if (prc) return prc;
-  const int N = h->desc.ndof, T = h->desc.T;
-  const size_t nx = tqk ? 4 * (size_t)N * T : (size_t)N * T + (size_t)N * (T - 1);
-  const size_t npar = tqk ? 2 * (size_t)N + 3 * (size_t)T : (size_t)N + (h->have_guards ? h->guards.n_links + 4 * (size_t)h->guards.n_obstacles : 0);
-  std::vector<int> lo(S + 1, 0);
-  for (int i = 1; i <= S; ++i) lo[i] = (int)((long long)B * i / S / 64 * 64);  // (parts start on multiples of 64: whole wavefronts of the thread-per-instance kernels)
-  lo[S] = B;
-  std::vector<int> rcs(S, OH_OK);
-  std::vector<std::string> errs(S);
-  auto part = [&](const int i) {
+static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
+                        bool may_fan_out, LastSolve* rec);
+// counters of the solves one lane ran, merged into the handle's timing by fan_out
+struct Tally {
+  double launched = 0, work = 0, compactions = 0, rejects = 0, tails = 0;
+};
+// one solve of a lane: never fans out again (the lanes ARE the streams)
+static int lane_solve(oh_handle* q, Tally& t, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
+  if (const int rc = solve_device(q, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, false, nullptr)) return rc;
+  t.launched = std::max(t.launched, q->timing[5]);
+  t.work += q->timing[6];
+  t.compactions += q->timing[7];
+  t.rejects += q->rejects;
+  t.tails += q->tail_iters;
+  return OH_OK;
+}
+// Runs work(lane, handle, tally) on n lanes: lane 0 is the handle itself on the calling thread, lanes 1 .. n-1 its peers, each on a host thread bound
+// to the handle's device.  The first error of a lane is the call's; timing: [4] wall clock of the call, [5] the most launches of one solve, [6], [7],
+// rejects, tail iterations summed over every solve of every lane.
+template <class Work>
+static int fan_out(oh_handle* h, const int n, Work&& work) {
+  if (const int rc = ensure_peers(h, n - 1)) return rc;
+  for (int i = 0; i + 1 < n; ++i) {  // the peers run with this handle's options and share the kernels compiled for its chain
+    oh_handle* p = h->peers[i];
+    p->sch = h->sch;
+    p->opt = h->opt;
+    p->spec = h->spec;
+    p->spec_failed = h->spec_failed;
+    p->spec_cache_checked = true;
+  }
+  std::vector<int> rcs(n, OH_OK);
+  std::vector<std::string> errs(n);
+  std::vector<Tally> tally(n);
+  auto lane = [&](const int i) {
     oh_handle* q = i == 0 ? h : h->peers[i - 1];
-    if (hipSetDevice(h->device) != hipSuccess) { rcs[i] = OH_ERR_HIP; errs[i] = "solve_split: hipSetDevice failed"; return; }  // (a new host thread starts on device 0)
-    const size_t o = (size_t)lo[i];
-    const int n = lo[i + 1] - lo[i];
-    auto off = [&](const void* ptr, const size_t bytes_per) -> void* { return ptr ? (void*)((char*)ptr + o * bytes_per) : nullptr; };
-    rcs[i] = oh_solve_device(q, n, off(d_x0, nx * 8), off(d_p, npar * 8), off(d_x, nx * 8), off(d_f, 8), off(d_kkt, 24), off(d_iters, 4), off(d_status, 4));
+    if (hipSetDevice(h->device) != hipSuccess) rcs[i] = fail(OH_ERR_HIP, "hipSetDevice failed on a lane's host thread");  // (a new host thread starts on device 0)
+    else rcs[i] = work(i, q, tally[i]);
     if (rcs[i]) errs[i] = oh_last_error();
   };
-  for (int i = 1; i < S; ++i) {
-    copy_options(h->peers[i - 1], h);
-    h->peers[i - 1]->spec = h->spec;
-    h->peers[i - 1]->spec_failed = h->spec_failed;
-    h->peers[i - 1]->spec_cache_checked = true;
-  }
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<std::thread> th;
-  h->is_peer = true;  // (this handle takes part 0 itself and must not split again)
-  for (int i = 1; i < S; ++i) th.emplace_back(part, i);
-  part(0);
+  for (int i = 1; i < n; ++i) th.emplace_back(lane, i);
+  lane(0);
   for (std::thread& t : th) t.join();
-  h->is_peer = false;
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (int i = 0; i < S; ++i)
+  for (int i = 0; i < n; ++i)
     if (rcs[i]) return fail(rcs[i], errs[i]);
-  h->split_parts.assign(S, 0);
-  for (int i = 0; i < S; ++i) h->split_parts[i] = lo[i + 1] - lo[i];
+  reset_counters(h);
   h->timing[4] = ms;
-  for (int i = 1; i < S; ++i) {
-    const oh_handle* q = h->peers[i - 1];
-    h->timing[5] = std::max(h->timing[5], q->timing[5]);
-    h->timing[6] += q->timing[6];
-    h->timing[7] += q->timing[7];
-    h->rejects += q->rejects;
-    h->tail_iters += q->tail_iters;
+  for (const Tally& t : tally) {
+    h->timing[5] = std::max(h->timing[5], t.launched);
+    h->timing[6] += t.work;
+    h->timing[7] += t.compactions;
+    h->rejects += t.rejects;
+    h->tail_iters += t.tails;
   }
-  h->last_B = B;
+  return OH_OK;
+}
+// a batch in S contiguous parts, one per lane (parts start on multiples of 64: whole wavefronts of the thread-per-instance kernels)
+static int solve_split(oh_handle* h, const int S, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
+                       LastSolve* rec) {
+  const Shape sh = shape_of(h);
+  std::vector<int> lo(S + 1, 0);
+  for (int i = 1; i <= S; ++i) lo[i] = (int)((long long)B * i / S / 64 * 64);
+  lo[S] = B;
+  std::vector<LastSolve::Part> parts(S);
+  const int rc = fan_out(h, S, [&](const int i, oh_handle* q, Tally& t) {
+    const size_t o = (size_t)lo[i];
+    auto off = [&](const void* ptr, const size_t bytes_per) -> void* { return ptr ? (void*)((char*)ptr + o * bytes_per) : nullptr; };
+    parts[i] = {q, lo[i + 1] - lo[i]};
+    return lane_solve(q, t, parts[i].n, off(d_x0, sh.nx * 8), off(d_p, sh.npar * 8), off(d_x, sh.nx * 8), off(d_f, 8), off(d_kkt, 24), off(d_iters, 4),
+                      off(d_status, 4));
+  });
+  if (rc) return rc;
+  rec->parts = parts;
   return OH_OK;
 }
 
-extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt,
-                               void* d_iters, void* d_status) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_solve_device: null handle");
+// The solve of every entry point and every lane: without may_fan_out the batch is never split.  rec (may be null): where the results live, on success.
+static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
+                        const bool may_fan_out, LastSolve* rec) {
   if (B < 1) return fail(OH_ERR_INVALID, "oh_solve_device: B must be >= 1");
   if (!d_x0 || !d_p) return fail(OH_ERR_INVALID, "oh_solve_device: x0 and p are required");
+  if (rec) *rec = LastSolve{B, {{h, B}}, false};
   load_launch_opts(h);
   if (h->desc.kind == OH_PROBLEM_POINT_MASS_MPC) return pm_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
   if (h->desc.kind == OH_PROBLEM_IK) return ik_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
   if (h->desc.kind == OH_PROBLEM_QP) return qp_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
   if (h->desc.kind == OH_PROBLEM_TAPE) return tape_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
   if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) {
-    if (!h->is_peer) { h->split_parts.clear(); h->pipe_last = false; }
     const int S = std::min(8, (int)optv(h, "streams", 2.0));
-    if (!h->is_peer && !h->profiling && S >= 2 && B >= (int)optv(h, "tq_split_min", 1024.0) && B / S >= 64 && h->have_chain && h->have_dyn)
-      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    if (may_fan_out && !h->profiling && S >= 2 && B >= (int)optv(h, "tq_split_min", 1024.0) && B / S >= 64 && h->have_chain && h->have_dyn)
+      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
     return tq_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
   }
   if (h->desc.kind != OH_PROBLEM_FIGURE_EIGHT) return fail(OH_ERR_STATE, "oh_solve_device: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
@@ -1633,27 +1659,26 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   if (!solver_chain_ok(h->chain_host))
     return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->is_peer) { h->split_parts.clear(); h->pipe_last = false; }
   // (batch_invariant handles take part in the split too since their compaction moves everything: an instance's answer does not depend on its part)
-  if (!h->is_peer && !h->profiling && spec_applies(h) && (optv(h, "batch_invariant", 0.0) == 0.0 || optv(h, "invariant_split", 1.0) != 0.0)) {
+  if (may_fan_out && !h->profiling && spec_applies(h) && (optv(h, "batch_invariant", 0.0) == 0.0 || optv(h, "invariant_split", 1.0) != 0.0)) {
     const int S = std::min(8, (int)optv(h, "streams", 2.0));
     if (S >= 2 && B >= (int)optv(h, "split_min", 65536.0) && B / S >= 4096 && stage_fits(h, B)) {  // (a batch beyond oh_max_batch is refused below, as ever)
       // (the kernels compiled for the chain are shared: make sure they exist before the parts look for them)
-      if (!h->spec && !h->spec_failed && h->specialize != OH_SPECIALIZE_NEVER && oh_specialize(h) != OH_OK) h->spec_failed = true;
-      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+      if (!h->spec && !h->spec_failed && h->sch.specialize != OH_SPECIALIZE_NEVER && oh_specialize(h) != OH_OK) h->spec_failed = true;
+      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
     }
   }
-  if (!h->is_peer && !h->profiling && !h->desc.lock_orientation && !h->chain_host.has_lead && optv(h, "batch_invariant", 0.0) == 0.0) {
+  if (may_fan_out && !h->profiling && !h->desc.lock_orientation && !h->chain_host.has_lead && optv(h, "batch_invariant", 0.0) == 0.0) {
     // position-tracking family (every launch latency-bound, the machine far from full): two halves side by side -- 1024 arms 9.5 -> 7.3 ms
     const int S = std::min(8, (int)optv(h, "streams", 2.0));
-    if (S >= 2 && B >= (int)optv(h, "free_split_min", 256.0) && B / S >= 64) return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    if (S >= 2 && B >= (int)optv(h, "free_split_min", 256.0) && B / S >= 64) return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
   }
   int rc = ensure_capacity(h, B);
   if (rc) return rc;
   fill_params(h);
   if ((spec_applies(h) || spec_tail_vel_applies(h)) && !h->spec && !h->spec_failed) {
-    bool want = h->specialize == OH_SPECIALIZE_ALWAYS || (h->specialize == OH_SPECIALIZE_AUTO && B >= h->specialize_min_B);
-    if (!want && h->specialize == OH_SPECIALIZE_AUTO && !h->spec_cache_checked) {  // a compiled object is at hand: milliseconds, whatever the batch
+    bool want = h->sch.specialize == OH_SPECIALIZE_ALWAYS || (h->sch.specialize == OH_SPECIALIZE_AUTO && B >= h->specialize_min_B);
+    if (!want && h->sch.specialize == OH_SPECIALIZE_AUTO && !h->spec_cache_checked) {  // a compiled object is at hand: milliseconds, whatever the batch
       h->spec_cache_checked = true;
       want = oh_jit_figure8_cached(h->chain_host, h->desc.ndof);
     }
@@ -1664,7 +1689,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   {  // position-tracking family, 7 joints, every launch of this solve a block per instance (k_step_free_bb): stage blocks instance-major
     // (batch_invariant: the size-independent path -- knot-major blocks, the serial sweep on one lane per instance -- whatever the batch: the block-per-instance
     //  factorisations chosen by size round differently)
-    h->P.inst_major = (!h->desc.lock_orientation && h->desc.ndof == 7 && B <= h->free_pcr_max && h->desc.T - (h->desc.fix_dq0 ? 2 : 1) <= 128 && optv(h, "free_bb", 1.0) != 0.0 &&
+    h->P.inst_major = (!h->desc.lock_orientation && h->desc.ndof == 7 && B <= h->sch.free_pcr_max && h->desc.T - (h->desc.fix_dq0 ? 2 : 1) <= 128 && optv(h, "free_bb", 1.0) != 0.0 &&
                        optv(h, "batch_invariant", 0.0) == 0.0) ? 1 : 0;
   }
   if (lead && (guarded || !h->desc.lock_orientation || h->desc.ndof != 6))
@@ -1709,12 +1734,12 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   const int hard_cap = 2 * h->desc.max_iter + 2 + 40 + 64;  // a rejected step costs two launches, a compaction one
   const int NV = (guarded && h->GP.vel) ? 2 * N : 0;  // velocity rows per knot
   // persistent tail kernel: plain orientation-locked handles, and (round 3, k_tail_vel) those whose inequality rows are joint and / or joint-velocity limits (no sphere rows)
-  const bool tail_vel = guarded && (h->GP.vel || h->GP.limits) && h->GP.n_links == 0 && h->tail_vel;
-  const bool tail_ok = (h->desc.T - h->P.t0 <= 64) && h->tail_threshold > 0 && h->desc.lock_orientation && (!guarded || tail_vel) && !lead;
+  const bool tail_vel = guarded && (h->GP.vel || h->GP.limits) && h->GP.n_links == 0 && h->sch.tail_vel;
+  const bool tail_ok = (h->desc.T - h->P.t0 <= 64) && h->sch.tail_threshold > 0 && h->desc.lock_orientation && (!guarded || tail_vel) && !lead;
   // limit / velocity-limit handles: the batched launches (evaluation, velocity coupling in a launch of its own, sweep: 1.45 ms per iteration of
   // 40 000 instances) lose against the persistent kernel at every size measured -- 65 536 instances: 87.5 ms with the hand-over at 16 384,
   // 80.5 at 32 768, 76.3 when the whole batch starts there -- so these handles go to it whatever the batch (OH_TAIL_VEL_THRESHOLD overrides)
-  const int tail_threshold = tail_vel ? h->tail_vel_threshold : h->tail_threshold;
+  const int tail_threshold = tail_vel ? h->sch.tail_vel_threshold : h->sch.tail_threshold;
   const FigSpec* const spec = spec_applies(h) ? h->spec : nullptr;
   // evaluation / tail launches: the kernels compiled for this handle's chain when they are loaded, the generic ones otherwise
   auto launch_eval = [&](int slot, int part) {
@@ -1768,7 +1793,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
     rebase = false;
     const int slot = it & 1;
     if (h->P.lock && guarded) {
-      if (h->lg_split && h->GP.n_links == 0) {  // retraction and evaluation as two launches, like the plain family (k_evalb_lg in oh_kernels.hip)
+      if (h->sch.lg_split && h->GP.n_links == 0) {  // retraction and evaluation as two launches, like the plain family (k_evalb_lg in oh_kernels.hip)
         if (!(h->spec && spec_tail_vel_applies(h) && oh_spec_launch_eval(*h->spec, s, h->P, h->D, slot, 1) == hipSuccess))
           oh_launch_eval_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, 1);
         oh_launch_eval_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, 2);
@@ -1779,7 +1804,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
       launch_eval(slot, 1);
       if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(4); }
       finalize(1);
-      oh_launch_scan_running(s, h->D, h->compact_sort);
+      oh_launch_scan_running(s, h->D, h->sch.compact_sort);
       oh_launch_carry(s, N, h->P, h->D, 0, 0, slot);
       oh_launch_carry(s, N, h->P, h->D, 1, carry_pending, slot);
       // the knots were laid down densely in the spare arrays: they become q[] / Gfull[] for the launches that follow (no copy back)
@@ -1803,14 +1828,14 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
     // handles without a persistent tail kernel (inequality rows, position-only tracking, lead joint) end in launches of a few hundred instances that
     // are pure latency: there the host looks at the running count every 8th iteration only (a look is a copy + stream synchronisation, 20-30 us
     // of a ~150 us iteration; the price is up to 7 idle iterations of finished instances at the very end)
-    const int ce = (!tail_ok && check_every == 1 && h->D.B <= h->sparse_check_below) ? 8 : check_every;
+    const int ce = (!tail_ok && check_every == 1 && h->D.B <= h->sch.sparse_check_below) ? 8 : check_every;
     const bool check = ((it + 1) % ce == 0);
     if (check && !h->P.lock) HIPCHK(hipMemsetAsync(h->D.n_running, 0, sizeof(int), s));  // the locked family's k_couple resets it
     if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(3); }
     if (h->P.lock && guarded) oh_launch_step_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot);
     else if (h->P.lock) oh_launch_step(s, N, h->P, h->D, slot);
-    else if (guarded) oh_launch_step_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, !invariant && h->D.B <= h->free_pcr_max);
-    else oh_launch_step_free(s, N, h->P, h->D, slot, !invariant && h->D.B <= h->free_pcr_max);
+    else if (guarded) oh_launch_step_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, !invariant && h->D.B <= h->sch.free_pcr_max);
+    else oh_launch_step_free(s, N, h->P, h->D, slot, !invariant && h->D.B <= h->sch.free_pcr_max);
     if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(2); }
     ++launched;
     if (check) {
@@ -1823,7 +1848,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
         // drain: compact the survivors and let one wavefront per instance finish them without further launches
         finalize(1);
         if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->compact_sort);
+        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
         oh_launch_compact(s, N, h->P, h->D, 0, 0, 0);
         if (guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, NV, 0, 0);
         oh_launch_compact(s, N, h->P, h->D, 1, nrun, (it + 1) & 1);
@@ -1836,7 +1861,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
       }
       // (k_carry_* park 22 per-instance scalars in the first rows of the spare Dr slot: T x NZ(NZ+1)/2 rows must hold them)
       const bool carry_fits = (size_t)h->desc.T * ((N - 3) * (N - 2) / 2) >= 22;
-      if (h->compaction && h->compact_carry && carry_fits && h->P.lock && !guarded && !lead && h->D.B >= 512 && (double)nrun <= h->compact_frac * (double)h->D.B) {
+      if (h->sch.compaction && h->sch.compact_carry && carry_fits && h->P.lock && !guarded && !lead && h->D.B >= 512 && (double)nrun <= h->sch.compact_frac * (double)h->D.B) {
         carry_pending = nrun;  // done after the next k_retract
       } else if (invariant && h->P.lock && !lead && inv_frac > 0.0 && h->D.B >= 512 && (double)nrun <= inv_frac * (double)h->D.B) {
         // batch_invariant handles: the survivors move with everything they own (both slots' stage data, the pending step, every scalar and flag), so
@@ -1844,18 +1869,18 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
         // a third of the batch has finished, by default: a move costs an instance a few iterations' worth of bandwidth; tools/gpu_invariant_compaction.py)
         finalize(1);
         if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->compact_sort);
+        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
         const int mrc = move_everything(h, s, nrun);
         if (mrc) return mrc;
         h->D.B = nrun;
         ++compactions;
         if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(0); }
-      } else if (h->compaction && !lead && h->D.B >= 512 && (double)nrun <= h->compact_frac_restart * (double)h->D.B) {
+      } else if (h->sch.compaction && !lead && h->D.B >= 512 && (double)nrun <= h->sch.compact_frac_restart * (double)h->D.B) {
         // restart compaction: the survivors' accepted knots (and, with inequality rows, their multipliers and outer-loop state) are laid
         // down densely and re-evaluated
         finalize(1);
         if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->compact_sort);
+        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
         if (h->P.lock && guarded && optv(h, "compact_move_all", 1.0) != 0.0) {
           // orientation-locked handles with inequality rows (horizons beyond the persistent kernel): the instance moves with everything it owns,
           // nothing restarts -- the same iterates, bit for bit, as without compaction (round 5)
@@ -1878,14 +1903,7 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 0);
   h->D.B = B;
   if (guarded) oh_launch_guard_infeasible(s, N, h->P, h->D, h->GP, (const double*)d_p, B, ok, os);  // constant rows of the pinned knots
-  HIPCHK(hipEventRecord(h->ev1, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  h->last_B = B;
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->timing[4] = ms;
-  h->timing[5] = launched;
+  if (const int frc = finish_solve(h, launched)) return frc;
   unsigned long long work[3] = {0, 0, 0};
   // (on the handle's own stream: a hipMemcpy is an operation of the legacy null stream and waits for the kernels of every other handle's stream -- the other
   //  part of a split solve, the other lane of a pipelined one)
@@ -1917,6 +1935,16 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   return OH_OK;
 }
 
+extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt,
+                               void* d_iters, void* d_status) {
+  if (!h) return fail(OH_ERR_INVALID, "oh_solve_device: null handle");
+  h->last = LastSolve{};
+  LastSolve rec;
+  const int rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, !h->is_peer, &rec);
+  if (rc == OH_OK) h->last = rec;
+  return rc;
+}
+
 static int ensure_stage(oh_handle* h, size_t bytes) {
   if (bytes <= h->stage_bytes) return OH_OK;
   if (h->stage) hipFree(h->stage);
@@ -1928,83 +1956,95 @@ static int ensure_stage(oh_handle* h, size_t bytes) {
   return OH_OK;
 }
 
+// Staging area of a host-buffer solve of B instances: inputs [x0 | p], then outputs [x | f | kkt | iters | status], every array 256-byte aligned.
+struct StageLayout {
+  size_t b_x, b_p, b_f, b_k, b_i;              // bytes of x0 / x, p, f, kkt, iters / status
+  size_t o_p, o_x, o_f, o_k, o_it, o_st, total;  // offsets (x0 at 0)
+  StageLayout(const Shape& sh, const size_t B) {
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    b_x = sizeof(double) * sh.nx * B; b_p = sizeof(double) * sh.npar * B; b_f = sizeof(double) * B; b_k = sizeof(double) * 3 * B; b_i = sizeof(int) * B;
+    o_p = al(b_x); o_x = o_p + al(b_p); o_f = o_x + al(b_x); o_k = o_f + al(b_f); o_it = o_k + al(b_k); o_st = o_it + al(b_i);
+    total = o_st + al(b_i);
+  }
+};
+
+// device pointer of a handle's multipliers, [B][shape.mult] (nullptr: none, or the guarded SoA layout that copy_multipliers transposes)
+static const double* mult_ptr(const oh_handle* q) {
+  switch (q->desc.kind) {
+    case OH_PROBLEM_TORQUE_MPC: return q->d_tq_mult;
+    case OH_PROBLEM_TAPE: return q->d_tape_mult;
+    case OH_PROBLEM_QP: return q->d_qp_mult;
+    case OH_PROBLEM_IK: return q->d_ik_mult;
+    case OH_PROBLEM_FIGURE_EIGHT: return q->have_guards ? nullptr : q->D.lam_h;
+    default: return nullptr;
+  }
+}
+// the multipliers of the n instances handle q holds from the last solve, into the caller's layout [n][shape.mult]
+static int copy_multipliers(const oh_handle* q, const int n, double* out) {
+  const size_t per = shape_of(q).mult;
+  if (!per) return OH_OK;
+  if (!(q->desc.kind == OH_PROBLEM_FIGURE_EIGHT && q->have_guards)) {
+    HIPCHK(hipMemcpy(out, mult_ptr(q), sizeof(double) * per * n, hipMemcpyDeviceToHost));
+    return OH_OK;
+  }
+  // SoA [T][NC][Bp] on the device -> [B][T][NC (+ 2 ndof velocity rows)] for the caller
+  const int T = q->desc.T, NC = q->GP.NC, Bp = q->D.Bp, NV = q->GP.vel ? 2 * q->desc.ndof : 0, NT = NC + NV;
+  std::vector<double> tmp((size_t)T * NC * Bp);
+  if (NC) HIPCHK(hipMemcpy(tmp.data(), q->GB.lam_out, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));  // original order (k_guard_emit)
+  for (int b = 0; b < n; ++b)
+    for (int t = 0; t < T; ++t)
+      for (int i = 0; i < NC; ++i) out[((size_t)b * T + t) * NT + i] = tmp[((size_t)t * NC + i) * Bp + b];
+  if (NV) {  // the device keeps the rows of dq_t = interval (t, t+1) in row block t + 1
+    std::vector<double> tv((size_t)T * NV * Bp);
+    HIPCHK(hipMemcpy(tv.data(), q->GB.lamv_out, tv.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; ++b)
+      for (int t = 0; t < T; ++t)
+        for (int i = 0; i < NV; ++i) out[((size_t)b * T + t) * NT + NC + i] = (t + 1 < T) ? tv[((size_t)(t + 1) * NV + i) * Bp + b] : 0.0;
+  }
+  return OH_OK;
+}
+
 // oh_solve of a large batch: chunks of `chunk` instances alternate between two lanes; a lane uploads its chunk on its own stream, solves it on its own
 // handle (lane 0: the handle itself, lane 1: a peer) and downloads the results, while the other lane is one phase ahead or behind.  Every chunk is solved
 // as a batch of its own (like the parts of solve_split); timing[4] is the wall clock of the whole call.
-static int solve_pipelined(oh_handle* h, const int B, const int chunk, const size_t nx, const size_t npar, const double* x0, const double* p, double* x,
-                           double* f, double* kkt, int* iters, int* status) {
-  int rc = ensure_peers(h, 1);
-  if (rc) return rc;
-  oh_handle* lanes[2] = {h, h->peers[0]};
-  copy_options(lanes[1], h);
-  if (h->desc.kind == OH_PROBLEM_FIGURE_EIGHT) {
-    if (spec_applies(h) && !h->spec && !h->spec_failed && h->specialize != OH_SPECIALIZE_NEVER && chunk >= h->specialize_min_B && oh_specialize(h) != OH_OK) h->spec_failed = true;
-    lanes[1]->spec = h->spec; lanes[1]->spec_failed = h->spec_failed; lanes[1]->spec_cache_checked = true;
-  }
-  const int C = (B + chunk - 1) / chunk;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+static int solve_pipelined(oh_handle* h, const int B, const int chunk, const double* x0, const double* p, double* x, double* f, double* kkt, int* iters,
+                           int* status) {
+  if (spec_applies(h) && !h->spec && !h->spec_failed && h->sch.specialize != OH_SPECIALIZE_NEVER && chunk >= h->specialize_min_B && oh_specialize(h) != OH_OK)
+    h->spec_failed = true;
   // multipliers of every chunk, kept on the device in instance order for oh_get_multipliers (a handle only remembers its last solve)
-  const bool tqk = h->desc.kind == OH_PROBLEM_TORQUE_MPC;
-  const size_t per = tqk ? (size_t)h->tq.T * (h->tq.vel_limits ? 4 : 2) * h->tq.ndof : (h->desc.lock_orientation ? 4 * (size_t)h->desc.T : 0);
-  if (per * B > h->pipe_mult_cap) {
+  const Shape sh = shape_of(h);
+  if (sh.mult * B > h->pipe_mult_cap) {
     if (h->d_pipe_mult) hipFree(h->d_pipe_mult);
     h->d_pipe_mult = nullptr;
     h->pipe_mult_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_pipe_mult, sizeof(double) * per * B));
-    h->pipe_mult_cap = per * B;
+    HIPCHK(hipMalloc((void**)&h->d_pipe_mult, sizeof(double) * sh.mult * B));
+    h->pipe_mult_cap = sh.mult * B;
   }
-  int rcs[2] = {OH_OK, OH_OK};
-  std::string errs[2];
-  double launched = 0, work = 0, compactions = 0, rejects = 0, tails = 0;
-  std::mutex mtx;
-  auto lane = [&](const int l) {
-    oh_handle* q = lanes[l];
-    if (hipSetDevice(h->device) != hipSuccess) { rcs[l] = OH_ERR_HIP; errs[l] = "oh_solve: hipSetDevice failed"; return; }
+  const int C = (B + chunk - 1) / chunk;
+  return fan_out(h, 2, [&](const int l, oh_handle* q, Tally& t) {
     for (int c = l; c < C; c += 2) {
       const size_t lo = (size_t)c * chunk;
       const int n = (int)std::min((size_t)chunk, (size_t)B - lo);
-      const size_t b_x = sizeof(double) * nx * n, b_p = sizeof(double) * npar * n, b_f = sizeof(double) * n, b_k = sizeof(double) * 3 * n, b_i = sizeof(int) * (size_t)n;
-      if (ensure_stage(q, al(b_x) * 2 + al(b_p) + al(b_f) + al(b_k) + 2 * al(b_i))) { rcs[l] = OH_ERR_HIP; errs[l] = oh_last_error(); return; }
+      const StageLayout L(sh, n);
+      if (const int rc = ensure_stage(q, L.total)) return rc;
       char* base = (char*)q->stage;
-      void* d_x0 = base; void* d_p = base + al(b_x); void* d_x = (char*)d_p + al(b_p); void* d_f = (char*)d_x + al(b_x); void* d_k = (char*)d_f + al(b_f);
-      void* d_it = (char*)d_k + al(b_k); void* d_st = (char*)d_it + al(b_i);
       hipStream_t s = q->stream;
-      bool ok = hipMemcpyAsync(d_x0, x0 + lo * nx, b_x, hipMemcpyHostToDevice, s) == hipSuccess && hipMemcpyAsync(d_p, p + lo * npar, b_p, hipMemcpyHostToDevice, s) == hipSuccess &&
-                hipStreamSynchronize(s) == hipSuccess;
-      if (!ok) { rcs[l] = OH_ERR_HIP; errs[l] = "oh_solve: upload failed"; return; }
-      const bool was_peer = q->is_peer;
-      q->is_peer = true;  // (a chunk is not split again: the two lanes ARE the two streams)
-      const int r = oh_solve_device(q, n, d_x0, d_p, d_x, d_f, d_k, d_it, d_st);
-      q->is_peer = was_peer;
-      if (r) { rcs[l] = r; errs[l] = oh_last_error(); return; }
-      ok = true;
-      const double* mult = tqk ? q->d_tq_mult : q->D.lam_h;
-      if (per && mult) ok = ok && hipMemcpyAsync(h->d_pipe_mult + lo * per, mult, sizeof(double) * per * n, hipMemcpyDeviceToDevice, s) == hipSuccess;
-      if (x) ok = ok && hipMemcpyAsync(x + lo * nx, d_x, b_x, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (f) ok = ok && hipMemcpyAsync(f + lo, d_f, b_f, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (kkt) ok = ok && hipMemcpyAsync(kkt + 3 * lo, d_k, b_k, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (iters) ok = ok && hipMemcpyAsync(iters + lo, d_it, b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (status) ok = ok && hipMemcpyAsync(status + lo, d_st, b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
+      bool ok = hipMemcpyAsync(base, x0 + lo * sh.nx, L.b_x, hipMemcpyHostToDevice, s) == hipSuccess &&
+                hipMemcpyAsync(base + L.o_p, p + lo * sh.npar, L.b_p, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+      if (!ok) return fail(OH_ERR_HIP, "oh_solve: upload failed");
+      if (const int rc = lane_solve(q, t, n, base, base + L.o_p, base + L.o_x, base + L.o_f, base + L.o_k, base + L.o_it, base + L.o_st)) return rc;
+      const double* mult = mult_ptr(q);
+      if (sh.mult && mult) ok = ok && hipMemcpyAsync(h->d_pipe_mult + lo * sh.mult, mult, sizeof(double) * sh.mult * n, hipMemcpyDeviceToDevice, s) == hipSuccess;
+      if (x) ok = ok && hipMemcpyAsync(x + lo * sh.nx, base + L.o_x, L.b_x, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (f) ok = ok && hipMemcpyAsync(f + lo, base + L.o_f, L.b_f, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (kkt) ok = ok && hipMemcpyAsync(kkt + 3 * lo, base + L.o_k, L.b_k, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (iters) ok = ok && hipMemcpyAsync(iters + lo, base + L.o_it, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (status) ok = ok && hipMemcpyAsync(status + lo, base + L.o_st, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
       ok = ok && hipStreamSynchronize(s) == hipSuccess;
-      if (!ok) { rcs[l] = OH_ERR_HIP; errs[l] = "oh_solve: download failed"; return; }
-      std::lock_guard<std::mutex> g(mtx);
-      launched = std::max(launched, q->timing[5]); work += q->timing[6]; compactions += q->timing[7]; rejects += q->rejects; tails += q->tail_iters;
+      if (!ok) return fail(OH_ERR_HIP, "oh_solve: download failed");
     }
-  };
-  const auto t0 = std::chrono::steady_clock::now();
-  std::thread other(lane, 1);
-  lane(0);
-  other.join();
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (int l = 0; l < 2; ++l)
-    if (rcs[l]) return fail(rcs[l], errs[l]);
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms; h->timing[5] = launched; h->timing[6] = work; h->timing[7] = compactions;
-  h->rejects = rejects; h->tail_iters = tails;
-  h->split_parts.clear();
-  h->pipe_last = true;
-  h->last_B = B;
-  return OH_OK;
+    return (int)OH_OK;
+  });
 }
 
 extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, double* f, double* kkt, int* iters,
@@ -2016,66 +2056,59 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
       h->desc.kind != OH_PROBLEM_QP && h->desc.kind != OH_PROBLEM_TAPE && h->desc.kind != OH_PROBLEM_TORQUE_MPC)
     return fail(OH_ERR_STATE, "oh_solve: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
   HIPCHK(hipSetDevice(h->device));
-  const int N = h->desc.ndof, T = h->desc.T;
-  const bool pmk = h->desc.kind == OH_PROBLEM_POINT_MASS_MPC;
-  const bool ikk = h->desc.kind == OH_PROBLEM_IK;
-  const bool qpk = h->desc.kind == OH_PROBLEM_QP;
-  const bool tpk = h->desc.kind == OH_PROBLEM_TAPE;
+  h->last = LastSolve{};
+  // large batches of the trajectory families from host buffers: chunks on two lanes (handles, streams, host threads), so that one lane's transfers over
+  // PCIe run under the other lane's kernels (round 6; until then: upload everything, solve, download everything -- 38 % of the resident rate).  Such a
+  // call stages chunks only: the whole batch is never staged.
   const bool tqk = h->desc.kind == OH_PROBLEM_TORQUE_MPC;
-  const size_t nx = tqk ? 4 * (size_t)N * T : tpk ? (size_t)h->TP.nx : qpk ? (size_t)h->qp.n : pmk ? 4 * (size_t)T : (ikk ? (size_t)N : (size_t)N * T + (size_t)N * (T - 1));
-  const size_t npar = tqk ? 2 * (size_t)N + 3 * (size_t)T : tpk ? (size_t)(h->TP.np > 0 ? h->TP.np : 1) : qpk ? (h->qp_tape ? (size_t)(h->TP.np > 0 ? h->TP.np : 1) : qp_np(h->qp)) : pmk ? 4 + 4 * (size_t)T : (ikk ? (size_t)N + 3 : (h->chain_host.has_lead ? (size_t)N + 1 + T : (size_t)N + (h->have_guards ? h->guards.n_links + 4 * (size_t)h->guards.n_obstacles : 0)));
-  const size_t b_x = sizeof(double) * nx * B, b_p = sizeof(double) * npar * (size_t)B;
-  const size_t b_f = sizeof(double) * B, b_k = sizeof(double) * 3 * (size_t)B, b_i = sizeof(int) * (size_t)B;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t total = al(b_x) * 2 + al(b_p) + al(b_f) + al(b_k) + 2 * al(b_i);
-  int rc = ensure_stage(h, total);
+  const int chunk = std::max(1024, (int)optv(h, "pipe_chunk", 32768.0));
+  if ((h->desc.kind == OH_PROBLEM_FIGURE_EIGHT || tqk) && !h->is_peer && !h->profiling && optv(h, "pipe", 1.0) != 0.0 && h->have_chain && !h->have_guards &&
+      !h->chain_host.has_lead && B >= 2 * chunk && (!tqk || h->have_dyn)) {
+    const int rc = solve_pipelined(h, B, chunk, x0, p, x, f, kkt, iters, status);
+    if (rc == OH_OK) h->last = LastSolve{B, {}, true};
+    return rc;
+  }
+  const StageLayout L(shape_of(h), B);
+  int rc = ensure_stage(h, L.total);
   if (rc) return rc;
-  // device layout: inputs [x0 | p], then outputs [x | f | kkt | iters | status]
   char* base = (char*)h->stage;
-  const size_t o_x0 = 0, o_p = o_x0 + al(b_x), o_x = o_p + al(b_p), o_f = o_x + al(b_x), o_k = o_f + al(b_f), o_it = o_k + al(b_k), o_st = o_it + al(b_i);
-  void* d_x0 = base + o_x0; void* d_p = base + o_p; void* d_x = base + o_x; void* d_f = base + o_f; void* d_k = base + o_k;
-  void* d_it = base + o_it; void* d_st = base + o_st;
+  void* d_x0 = base; void* d_p = base + L.o_p; void* d_x = base + L.o_x; void* d_f = base + L.o_f; void* d_k = base + L.o_k;
+  void* d_it = base + L.o_it; void* d_st = base + L.o_st;
+  LastSolve rec;
   // a controller's tick moves a few hundred bytes in seven pieces: through one pinned mirror of the staging area that is two transfers (each
   // hipMemcpy of pageable memory is ~10-15 us of driver work whatever its size)
-  const bool small = total <= OH_PINNED_STAGE_BYTES;
+  const bool small = L.total <= OH_PINNED_STAGE_BYTES;
   if (small && !h->h_stage) {
     if (hipHostMalloc((void**)&h->h_stage, OH_PINNED_STAGE_BYTES) != hipSuccess) h->h_stage = nullptr;
   }
   if (small && h->h_stage) {
     char* hb = (char*)h->h_stage;
-    memcpy(hb + o_x0, x0, b_x);
-    memcpy(hb + o_p, p, b_p);
-    HIPCHK(hipMemcpy(base, hb, o_p + b_p, hipMemcpyHostToDevice));
-    rc = oh_solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st);
+    memcpy(hb, x0, L.b_x);
+    memcpy(hb + L.o_p, p, L.b_p);
+    HIPCHK(hipMemcpy(base, hb, L.o_p + L.b_p, hipMemcpyHostToDevice));
+    rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st, !h->is_peer, &rec);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(hb + o_x, base + o_x, o_st + b_i - o_x, hipMemcpyDeviceToHost));
-    if (x) memcpy(x, hb + o_x, b_x);
-    if (f) memcpy(f, hb + o_f, b_f);
-    if (kkt) memcpy(kkt, hb + o_k, b_k);
-    if (iters) memcpy(iters, hb + o_it, b_i);
-    if (status) memcpy(status, hb + o_st, b_i);
+    HIPCHK(hipMemcpy(hb + L.o_x, base + L.o_x, L.o_st + L.b_i - L.o_x, hipMemcpyDeviceToHost));
+    if (x) memcpy(x, hb + L.o_x, L.b_x);
+    if (f) memcpy(f, hb + L.o_f, L.b_f);
+    if (kkt) memcpy(kkt, hb + L.o_k, L.b_k);
+    if (iters) memcpy(iters, hb + L.o_it, L.b_i);
+    if (status) memcpy(status, hb + L.o_st, L.b_i);
+    h->last = rec;
     return OH_OK;
   }
-  // large batches of the trajectory families from host buffers: chunks on two lanes (handles, streams, host threads), so that one lane's transfers over
-  // PCIe run under the other lane's kernels (round 6; until then: upload everything, solve, download everything -- 38 % of the resident rate)
-  if ((h->desc.kind == OH_PROBLEM_FIGURE_EIGHT || tqk) && !h->is_peer && !h->profiling && optv(h, "pipe", 1.0) != 0.0 && h->have_chain && !h->have_guards &&
-      !h->chain_host.has_lead) {
-    const int chunk = std::max(1024, (int)optv(h, "pipe_chunk", 32768.0));
-    if (B >= 2 * chunk && (!tqk || h->have_dyn)) return solve_pipelined(h, B, chunk, nx, npar, x0, p, x, f, kkt, iters, status);
-  }
-  HIPCHK(hipMemcpy(d_x0, x0, b_x, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_p, p, b_p, hipMemcpyHostToDevice));
-  rc = oh_solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st);
+  HIPCHK(hipMemcpy(d_x0, x0, L.b_x, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_p, p, L.b_p, hipMemcpyHostToDevice));
+  rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st, !h->is_peer, &rec);
   if (rc) return rc;
-  if (x) HIPCHK(hipMemcpy(x, d_x, b_x, hipMemcpyDeviceToHost));
-  if (f) HIPCHK(hipMemcpy(f, d_f, b_f, hipMemcpyDeviceToHost));
-  if (kkt) HIPCHK(hipMemcpy(kkt, d_k, b_k, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, d_it, b_i, hipMemcpyDeviceToHost));
-  if (status) HIPCHK(hipMemcpy(status, d_st, b_i, hipMemcpyDeviceToHost));
+  if (x) HIPCHK(hipMemcpy(x, d_x, L.b_x, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(hipMemcpy(f, d_f, L.b_f, hipMemcpyDeviceToHost));
+  if (kkt) HIPCHK(hipMemcpy(kkt, d_k, L.b_k, hipMemcpyDeviceToHost));
+  if (iters) HIPCHK(hipMemcpy(iters, d_it, L.b_i, hipMemcpyDeviceToHost));
+  if (status) HIPCHK(hipMemcpy(status, d_st, L.b_i, hipMemcpyDeviceToHost));
+  h->last = rec;
   return OH_OK;
 }
-
-static int ensure_stage(oh_handle* h, size_t bytes);
 
 extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, double ramp, const double* state0, const double* obs_table,
                              double* states, double* f, int* iters, int* status) {
@@ -2083,6 +2116,7 @@ extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
   if (h->desc.kind != OH_PROBLEM_POINT_MASS_MPC) return fail(OH_ERR_STATE, "oh_pm_rollout: handle is not a point-mass MPC problem");
   const int T = h->pm.T;
   if (B < 1 || n_ticks < 1 || advance < 1 || advance >= T) return fail(OH_ERR_INVALID, "oh_pm_rollout: need B >= 1, n_ticks >= 1, 1 <= advance < T");
+  h->last = LastSolve{};
   int rc = pm_prepare(h, B);
   if (rc) return rc;
   auto al = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -2114,19 +2148,12 @@ extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
     oh_launch_pm_solve(s, h->PmP, h->PmD, x_seed, d_p, x_sol, d_f + (size_t)B * k, nullptr, d_it + (size_t)B * k, d_st + (size_t)B * k);
     oh_launch_pm_advance(s, B, T, advance, x_sol, st_k + 4 * (size_t)B);
   }
-  HIPCHK(hipEventRecord(h->ev1, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  for (double& t : h->timing) t = 0.0;
-  h->timing[4] = ms;
-  h->timing[5] = n_ticks;
-  h->last_B = B;
+  if ((rc = finish_solve(h, n_ticks))) return rc;
   if (states) HIPCHK(hipMemcpy(states, d_states, b_states, hipMemcpyDeviceToHost));
   if (f) HIPCHK(hipMemcpy(f, d_f, b_f, hipMemcpyDeviceToHost));
   if (iters) HIPCHK(hipMemcpy(iters, d_it, b_i, hipMemcpyDeviceToHost));
   if (status) HIPCHK(hipMemcpy(status, d_st, b_i, hipMemcpyDeviceToHost));
+  h->last = LastSolve{B, {{h, B}}, false};
   return OH_OK;
 }
 
@@ -2138,9 +2165,10 @@ extern "C" int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
   if (B < 1 || n_ticks < 1 || advance < 1 || advance >= T) return fail(OH_ERR_INVALID, "oh_tq_rollout: need B >= 1, n_ticks >= 1, 1 <= advance < T");
   if (!(mu_warm > 0.0)) mu_warm = 1e-6;
   HIPCHK(hipSetDevice(h->device));
+  h->last = LastSolve{};
   auto al = [](size_t v) { return (v + 255) / 256 * 256; };
   const size_t n_rows = (size_t)n_ticks * advance + T;
-  const size_t nx = 4 * (size_t)N * T, np_ = 2 * (size_t)N + 3 * (size_t)T;
+  const size_t nx = shape_of(h).nx, np_ = shape_of(h).npar;
   const size_t b_states = sizeof(double) * 2 * N * (size_t)B * (n_ticks + 1), b_goal = sizeof(double) * 3 * n_rows * B, b_p = sizeof(double) * np_ * B,
                b_x = sizeof(double) * nx * B, b_tau = sizeof(double) * N * (size_t)B * n_ticks, b_f = sizeof(double) * (size_t)B * n_ticks,
                b_i = sizeof(int) * (size_t)B * n_ticks;
@@ -2176,98 +2204,38 @@ extern "C" int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
   }
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
-  for (double& t : h->timing) t = 0.0;
+  reset_counters(h);
   h->timing[4] = ms_total;  // device time of the solves (HIP events around each)
   h->timing[5] = launched;
   h->timing[6] = work;
-  h->last_B = B;
   if (states) HIPCHK(hipMemcpy(states, d_states, b_states, hipMemcpyDeviceToHost));
   if (tau0) HIPCHK(hipMemcpy(tau0, d_tau, b_tau, hipMemcpyDeviceToHost));
   if (f) HIPCHK(hipMemcpy(f, d_f, b_f, hipMemcpyDeviceToHost));
   if (iters) HIPCHK(hipMemcpy(iters, d_it, b_i, hipMemcpyDeviceToHost));
   if (status) HIPCHK(hipMemcpy(status, d_st, b_i, hipMemcpyDeviceToHost));
+  h->last = LastSolve{B, {{h, B}}, false};
   return OH_OK;
 }
 
 extern "C" int oh_get_multipliers(oh_handle* h, int B, double* lam_h) {
   if (!h || !lam_h) return fail(OH_ERR_INVALID, "oh_get_multipliers: null argument");
+  const LastSolve& r = h->last;
   if ((h->desc.kind != OH_PROBLEM_FIGURE_EIGHT && h->desc.kind != OH_PROBLEM_IK && h->desc.kind != OH_PROBLEM_QP && h->desc.kind != OH_PROBLEM_TAPE &&
        h->desc.kind != OH_PROBLEM_TORQUE_MPC) ||
-      B != h->last_B || B < 1)
+      B != r.B || B < 1)
     return fail(OH_ERR_STATE, "oh_get_multipliers: B does not match the last solve");
   HIPCHK(hipSetDevice(h->device));
-  if (h->pipe_last) {  // the last solve was a pipelined oh_solve: every chunk left its multipliers in the handle's cache
-    const size_t per = h->desc.kind == OH_PROBLEM_TORQUE_MPC ? (size_t)h->tq.T * (h->tq.vel_limits ? 4 : 2) * h->tq.ndof : (h->desc.lock_orientation ? 4 * (size_t)h->desc.T : 0);
-    if (!per) return fail(OH_ERR_STATE, "oh_get_multipliers: this problem has no nonlinear equality rows");
+  const size_t per = shape_of(h).mult;
+  if (!per && h->desc.kind == OH_PROBLEM_FIGURE_EIGHT) return fail(OH_ERR_STATE, "oh_get_multipliers: this problem has no nonlinear equality rows");
+  if (r.pipe_cache) {  // the last solve was a pipelined oh_solve: every chunk left its multipliers in the handle's cache
     HIPCHK(hipMemcpy(lam_h, h->d_pipe_mult, sizeof(double) * per * B, hipMemcpyDeviceToHost));
     return OH_OK;
   }
-  if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) {
-    const size_t per = (size_t)h->tq.T * (h->tq.vel_limits ? 4 : 2) * h->tq.ndof;
-    if (!h->split_parts.empty()) {  // the last solve ran in parts (solve_split)
-      size_t o = 0;
-      for (size_t i = 0; i < h->split_parts.size(); ++i) {
-        const oh_handle* q = i == 0 ? h : h->peers[i - 1];
-        HIPCHK(hipMemcpy(lam_h + o * per, q->d_tq_mult, sizeof(double) * per * h->split_parts[i], hipMemcpyDeviceToHost));
-        o += (size_t)h->split_parts[i];
-      }
-      return OH_OK;
-    }
-    HIPCHK(hipMemcpy(lam_h, h->d_tq_mult, sizeof(double) * (size_t)B * per, hipMemcpyDeviceToHost));
-    return OH_OK;
+  size_t o = 0;
+  for (const LastSolve::Part& part : r.parts) {  // (several parts: the last solve ran in parts, solve_split)
+    if (const int rc = copy_multipliers(part.q, part.n, lam_h + o * per)) return rc;
+    o += (size_t)part.n;
   }
-  if (h->desc.kind == OH_PROBLEM_TAPE) {
-    if (h->TP.n_ineq + h->TP.n_eq > 0)
-      HIPCHK(hipMemcpy(lam_h, h->d_tape_mult, sizeof(double) * (size_t)(h->TP.n_ineq + h->TP.n_eq) * B, hipMemcpyDeviceToHost));
-    return OH_OK;
-  }
-  if (h->desc.kind == OH_PROBLEM_QP) {
-    if (h->qp.m + h->qp.me > 0) HIPCHK(hipMemcpy(lam_h, h->d_qp_mult, sizeof(double) * (size_t)(h->qp.m + h->qp.me) * B, hipMemcpyDeviceToHost));
-    return OH_OK;
-  }
-  if (h->desc.kind == OH_PROBLEM_IK) {
-    HIPCHK(hipMemcpy(lam_h, h->d_ik_mult, sizeof(double) * (3 + 2 * (size_t)h->ik.ndof) * B, hipMemcpyDeviceToHost));
-    return OH_OK;
-  }
-  if (h->have_guards) {
-    // SoA [T][NC][Bp] on the device -> [B][T][NC (+ 2 ndof velocity rows)] for the caller
-    auto fetch = [&](const oh_handle* q, const int n, double* out) -> int {
-      const int T = q->desc.T, NC = q->GP.NC, Bp = q->D.Bp, NV = q->GP.vel ? 2 * q->desc.ndof : 0, NT = NC + NV;
-      std::vector<double> tmp((size_t)T * NC * Bp);
-      if (NC) HIPCHK(hipMemcpy(tmp.data(), q->GB.lam_out, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));  // original order (k_guard_emit)
-      for (int b = 0; b < n; ++b)
-        for (int t = 0; t < T; ++t)
-          for (int i = 0; i < NC; ++i) out[((size_t)b * T + t) * NT + i] = tmp[((size_t)t * NC + i) * Bp + b];
-      if (NV) {  // the device keeps the rows of dq_t = interval (t, t+1) in row block t + 1
-        std::vector<double> tv((size_t)T * NV * Bp);
-        HIPCHK(hipMemcpy(tv.data(), q->GB.lamv_out, tv.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int b = 0; b < n; ++b)
-          for (int t = 0; t < T; ++t)
-            for (int i = 0; i < NV; ++i) out[((size_t)b * T + t) * NT + NC + i] = (t + 1 < T) ? tv[((size_t)(t + 1) * NV + i) * Bp + b] : 0.0;
-      }
-      return OH_OK;
-    };
-    if (h->split_parts.empty()) return fetch(h, B, lam_h);
-    const size_t per = (size_t)h->desc.T * ((h->guards.limits ? 2 * h->desc.ndof : 0) + h->guards.n_links * h->guards.n_obstacles + (h->guards.vel_limits ? 2 * h->desc.ndof : 0));
-    size_t o = 0;
-    for (size_t i = 0; i < h->split_parts.size(); ++i) {  // the last solve ran in parts (solve_split)
-      const int rc = fetch(i == 0 ? h : h->peers[i - 1], h->split_parts[i], lam_h + o * per);
-      if (rc) return rc;
-      o += (size_t)h->split_parts[i];
-    }
-    return OH_OK;
-  }
-  if (!h->D.lam_h) return fail(OH_ERR_STATE, "oh_get_multipliers: this problem has no nonlinear equality rows");
-  if (!h->split_parts.empty()) {  // the last solve ran in parts (solve_split): every part keeps the multipliers of its instances
-    size_t o = 0;
-    for (size_t i = 0; i < h->split_parts.size(); ++i) {
-      const oh_handle* q = i == 0 ? h : h->peers[i - 1];
-      HIPCHK(hipMemcpy(lam_h + o * 4 * (size_t)h->desc.T, q->D.lam_h, sizeof(double) * 4 * (size_t)h->desc.T * h->split_parts[i], hipMemcpyDeviceToHost));
-      o += (size_t)h->split_parts[i];
-    }
-    return OH_OK;
-  }
-  HIPCHK(hipMemcpy(lam_h, h->D.lam_h, sizeof(double) * 4 * (size_t)h->desc.T * B, hipMemcpyDeviceToHost));
   return OH_OK;
 }
 
@@ -2362,7 +2330,7 @@ static int fk_common(oh_handle* h, int n, bool soa, const void* d_q, void* d_pos
   if (n < 1 || !d_q) return fail(OH_ERR_INVALID, "oh_fk_jac: bad arguments");
   if (!h->have_chain) return fail(OH_ERR_STATE, "oh_fk_jac: call oh_set_constants first");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->fk_spec && !h->fk_spec_failed && (h->specialize == OH_SPECIALIZE_ALWAYS || (h->specialize == OH_SPECIALIZE_AUTO && n >= h->specialize_min_units)))
+  if (!h->fk_spec && !h->fk_spec_failed && (h->sch.specialize == OH_SPECIALIZE_ALWAYS || (h->sch.specialize == OH_SPECIALIZE_AUTO && n >= h->specialize_min_units)))
     specialize_fk(h);  // on failure the generic kernel runs; oh_last_error keeps the reason
   if (h->fk_spec) HIPCHK(oh_spec_launch_fk(*h->fk_spec, h->stream, soa, n, (const double*)d_q, (double*)d_pose, (double*)d_J));
   else oh_launch_fk_jac(h->stream, soa, h->d_chain, h->chain_host.n_chain, h->chain_host.ndof, n, (const double*)d_q, (double*)d_pose, (double*)d_J);
@@ -2656,7 +2624,7 @@ static bool spec_applies(const oh_handle* h) {
 // kernels stay generic
 static bool spec_tail_vel_applies(const oh_handle* h) {
   return h->desc.kind == OH_PROBLEM_FIGURE_EIGHT && h->have_chain && h->desc.lock_orientation && h->have_guards && !h->chain_host.has_lead &&
-         (h->guards.limits || h->guards.vel_limits) && h->guards.n_links == 0 && h->tail_vel;
+         (h->guards.limits || h->guards.vel_limits) && h->guards.n_links == 0 && h->sch.tail_vel;
 }
 static int specialize_fk(oh_handle* h) {
   if (h->fk_spec) return OH_OK;
@@ -2721,7 +2689,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (n == "fuse_couple") {
     fill_params(h);
     *value = h->P.zc;
-  } else if (n == "tail_threshold") *value = h->tail_threshold;
+  } else if (n == "tail_threshold") *value = h->sch.tail_threshold;
   else if (n == "specialized") *value = h->spec ? 1 : 0;
   else if (n == "tape_wave") *value = h->tape_wave.ready ? (h->tape_wave.hist_lds ? 2 : 1) : 0;
   else if (n == "tape_regs_lds") *value = h->tape_wave.ready && h->tape_wave.reg_lds ? 1 : 0;

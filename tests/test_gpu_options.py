@@ -54,6 +54,13 @@ def test_two_handles_with_different_schedules_in_one_process(hip_lib, monkeypatc
     assert (ra.status == 0).all() and (rb.status == 0).all()
     same = np.abs(ra.f - rb.f) <= 1e-9 * np.abs(ra.f)
     assert same.mean() >= 0.95  # two schedules, one problem: the same optimum wherever the paths do not fork
+    # kernel times come from profiled solves only: an unprofiled solve after a profiled one reports none of its predecessor's
+    b.set_profiling(True)
+    b.solve(x0[:512], qc[:512])
+    assert b.timing()["eval_ms"] > 0 and b.timing()["step_ms"] > 0
+    b.set_profiling(False)
+    b.solve(x0[:512], qc[:512])
+    assert b.timing()["eval_ms"] == 0 and b.timing()["step_ms"] == 0
     a.close()
     b.close()
 
@@ -225,6 +232,10 @@ def test_host_buffer_solve_of_a_large_batch_is_pipelined_in_chunks(hip_lib, monk
     la = a.multipliers(B)
     ta = a.timing()
     assert (ra.status == 0).all() and ta["solve_ms"] > 0 and ta["tail_iterations"] > 0
+    # new constants (the same chain) make the chunk cache stale: the handle no longer serves multipliers of that solve
+    lib = _lib.load()
+    _lib.check(lib.oh_set_constants(a.handle, C.byref(a.constants())), "oh_set_constants")
+    assert lib.oh_get_multipliers(a.handle, B, _lib._ptr(np.empty_like(la))) == _lib.OH_ERR_STATE
     b = _backend().set_options(pipe=0)
     for lo in range(0, B, chunk):
         hi = min(B, lo + chunk)

@@ -434,5 +434,13 @@ def test_parts_of_a_split_solve_follow_dynamics_set_again(hip_lib, ctx):
     r3 = fresh.solve(x0, p)
     assert not np.array_equal(r2.f, r1.f) and np.array_equal(r2.x, r3.x) and np.array_equal(r2.f, r3.f) and np.array_equal(r2.iters, r3.iters)
     assert (np.abs(r2.f[B // 2 :] - r1.f[B // 2 :]) > 1e-9).all()  # the second part (the peer's) saw the new dynamics too
+    # a rollout of the same batch after the split solve: the multipliers are the rollout's on every instance, not the split solve's on the peer's part
+    state0 = np.concatenate([qc, np.zeros((B, 7))], 1)
+    goal_rows = np.concatenate([goal, goal[:, -1:]], 1)  # one tick of one knot
+    a.rollout(state0, goal_rows, 1)
+    alone = TorqueBackend(robot.kinematic_chain(LINK), dyn2, T=T, dt=0.1, tau_lo=-58.0, tau_up=58.0, max_iter=600, **W)
+    alone.rollout(state0, goal_rows, 1)
+    assert np.array_equal(a.multipliers(B), alone.multipliers(B))
     a.close()
     fresh.close()
+    alone.close()
