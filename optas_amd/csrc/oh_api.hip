@@ -19,6 +19,7 @@
 
 #include "oh_kernels.h"
 #include "oh_jit.h"
+#include "oh_rnea.h"
 
 static thread_local std::string g_err;
 
@@ -2251,78 +2252,70 @@ extern "C" int oh_set_dynamics(oh_handle* h, const oh_dynamics* dyn) {
   drop_peers(h);
   return OH_OK;
 }
+// Launch, check the launch, wait: the one order of the dynamics entry points.  launch() returns false for an unsupported number of bodies.
+template <class Launch>
+static int run_dyn(oh_handle* h, const char* unsupported, Launch&& launch) {
+  if (!launch()) return fail(OH_ERR_INVALID, unsupported);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return OH_OK;
+}
+// oh_rnea, oh_rnea_jac, oh_rnea_hess: the host inputs (n x ndof each) staged one behind the other in 256-byte aligned slots, the output of
+// out_per_sample doubles per sample behind them; launch(d_in, d_out) runs on the staged copies, then the output is copied back.
+template <size_t NIN, class Launch>
+static int run_dyn_staged(oh_handle* h, const int n, const std::array<const double*, NIN>& in, double* out, const size_t out_per_sample,
+                          const char* unsupported, Launch&& launch) {
+  HIPCHK(hipSetDevice(h->device));
+  const size_t b_in = sizeof(double) * h->dyn_host.ndof * (size_t)n, bq = (b_in + 255) / 256 * 256, b_out = sizeof(double) * out_per_sample * (size_t)n;
+  if (const int rc = ensure_stage(h, NIN * bq + b_out)) return rc;
+  char* base = (char*)h->stage;
+  std::array<const double*, NIN> d_in;
+  for (size_t k = 0; k < NIN; ++k) {
+    HIPCHK(hipMemcpy(base + k * bq, in[k], b_in, hipMemcpyHostToDevice));
+    d_in[k] = (const double*)(base + k * bq);
+  }
+  double* d_out = (double*)(base + NIN * bq);
+  if (const int rc = run_dyn(h, unsupported, [&] { return launch(d_in, d_out); })) return rc;
+  HIPCHK(hipMemcpy(out, d_out, b_out, hipMemcpyDeviceToHost));
+  return OH_OK;
+}
+
 extern "C" int oh_rnea_device(oh_handle* h, int n, const void* d_q, const void* d_qd, const void* d_qdd, void* d_tau) {
   if (!h) return fail(OH_ERR_INVALID, "oh_rnea: null handle");
   if (n < 1 || !d_q || !d_qd || !d_qdd || !d_tau) return fail(OH_ERR_INVALID, "oh_rnea: bad arguments");
   if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea: call oh_set_dynamics first");
   HIPCHK(hipSetDevice(h->device));
-  if (!oh_launch_rnea(h->stream, h->d_dyn, h->dyn_host.n, n, (const double*)d_q, (const double*)d_qd, (const double*)d_qdd, (double*)d_tau))
-    return fail(OH_ERR_INVALID, "oh_rnea: unsupported number of bodies");
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OH_OK;
+  return run_dyn(h, "oh_rnea: unsupported number of bodies", [&] {
+    return oh_launch_rnea(h->stream, h->d_dyn, h->dyn_host.n, n, (const double*)d_q, (const double*)d_qd, (const double*)d_qdd, (double*)d_tau);
+  });
 }
 extern "C" int oh_rnea(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, double* tau) {
   if (!h) return fail(OH_ERR_INVALID, "oh_rnea: null handle");
   if (n < 1 || !q || !qd || !qdd || !tau) return fail(OH_ERR_INVALID, "oh_rnea: bad arguments");
   if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea: call oh_set_dynamics first");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t bq = (sizeof(double) * h->dyn_host.ndof * (size_t)n + 255) / 256 * 256;
-  int rc = ensure_stage(h, 4 * bq);
-  if (rc) return rc;
-  char* base = (char*)h->stage;
-  HIPCHK(hipMemcpy(base, q, sizeof(double) * h->dyn_host.ndof * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + bq, qd, sizeof(double) * h->dyn_host.ndof * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + 2 * bq, qdd, sizeof(double) * h->dyn_host.ndof * (size_t)n, hipMemcpyHostToDevice));
-  rc = oh_rnea_device(h, n, base, base + bq, base + 2 * bq, base + 3 * bq);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(tau, base + 3 * bq, sizeof(double) * h->dyn_host.ndof * (size_t)n, hipMemcpyDeviceToHost));
-  return OH_OK;
+  return run_dyn_staged<3>(h, n, {q, qd, qdd}, tau, h->dyn_host.ndof, "oh_rnea: unsupported number of bodies", [&](const auto& d, double* d_tau) {
+    return oh_launch_rnea(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d_tau);
+  });
 }
 
 extern "C" int oh_rnea_jac(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, double* J) {
   if (!h) return fail(OH_ERR_INVALID, "oh_rnea_jac: null handle");
   if (n < 1 || !q || !qd || !qdd || !J) return fail(OH_ERR_INVALID, "oh_rnea_jac: bad arguments");
   if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea_jac: call oh_set_dynamics first");
-  HIPCHK(hipSetDevice(h->device));
   const size_t nd = h->dyn_host.ndof;
-  const size_t bq = (sizeof(double) * nd * (size_t)n + 255) / 256 * 256, bj = sizeof(double) * nd * 3 * nd * (size_t)n;
-  int rc = ensure_stage(h, 3 * bq + bj);
-  if (rc) return rc;
-  char* base = (char*)h->stage;
-  HIPCHK(hipMemcpy(base, q, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + bq, qd, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + 2 * bq, qdd, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  if (!oh_launch_rnea_jac(h->stream, h->d_dyn, h->dyn_host.n, n, (const double*)base, (const double*)(base + bq), (const double*)(base + 2 * bq),
-                          (double*)(base + 3 * bq)))
-    return fail(OH_ERR_INVALID, "oh_rnea_jac: unsupported number of bodies");
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(J, base + 3 * bq, bj, hipMemcpyDeviceToHost));
-  return OH_OK;
+  return run_dyn_staged<3>(h, n, {q, qd, qdd}, J, 3 * nd * nd, "oh_rnea_jac: unsupported number of bodies", [&](const auto& d, double* d_J) {
+    return oh_launch_rnea_jac(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d_J);
+  });
 }
 
 extern "C" int oh_rnea_hess(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, const double* c, double* H) {
   if (!h) return fail(OH_ERR_INVALID, "oh_rnea_hess: null handle");
   if (n < 1 || !q || !qd || !qdd || !c || !H) return fail(OH_ERR_INVALID, "oh_rnea_hess: bad arguments");
   if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea_hess: call oh_set_dynamics first");
-  HIPCHK(hipSetDevice(h->device));
   const size_t nd = h->dyn_host.ndof;
-  const size_t bq = (sizeof(double) * nd * (size_t)n + 255) / 256 * 256, bh = sizeof(double) * 9 * nd * nd * (size_t)n;
-  int rc = ensure_stage(h, 4 * bq + bh);
-  if (rc) return rc;
-  char* base = (char*)h->stage;
-  HIPCHK(hipMemcpy(base, q, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + bq, qd, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + 2 * bq, qdd, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base + 3 * bq, c, sizeof(double) * nd * (size_t)n, hipMemcpyHostToDevice));
-  if (!oh_launch_rnea_hess(h->stream, h->d_dyn, h->dyn_host.n, n, (const double*)base, (const double*)(base + bq), (const double*)(base + 2 * bq),
-                           (const double*)(base + 3 * bq), (double*)(base + 4 * bq)))
-    return fail(OH_ERR_INVALID, "oh_rnea_hess: unsupported number of bodies");
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(H, base + 4 * bq, bh, hipMemcpyDeviceToHost));
-  return OH_OK;
+  return run_dyn_staged<4>(h, n, {q, qd, qdd, c}, H, 9 * nd * nd, "oh_rnea_hess: unsupported number of bodies", [&](const auto& d, double* d_H) {
+    return oh_launch_rnea_hess(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d[3], d_H);
+  });
 }
 
 static int fk_common(oh_handle* h, int n, bool soa, const void* d_q, void* d_pose, void* d_J) {

@@ -16,8 +16,6 @@ bool oh_kernel_info_figure8(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_fkjac(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_torque(const char* name, OhKernelInfo* out);
 
-bool oh_launch_rnea_jac(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, double* J);
-bool oh_launch_rnea(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, double* tau);
 void oh_launch_fk_jac(hipStream_t s, bool soa, const oh_chain* d_chain, int n_chain, int ndof, int n, const double* q, double* pose, double* J);
 bool oh_launch_setup(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const double* x0, const double* p);
 bool oh_launch_eval(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, int part = 0);
@@ -134,7 +132,6 @@ struct TqBuffers {
   int* n_list;     // [1]
   int n_run;       // length of the list the launches below cover
 };
-bool oh_launch_rnea_hess(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, const double* c, double* H);
 void oh_launch_tq_list(hipStream_t s, const TqBuffers& D);
 bool oh_launch_tq_setup(hipStream_t s, const TqParams& P, const TqBuffers& D, const double* x0, const double* p);
 bool oh_launch_tq_eval(hipStream_t s, const TqParams& P, const TqBuffers& D);

@@ -21,1233 +21,11 @@
 //   k_tq_curv   same mapping: second derivatives of the inverse dynamics and of the link position, added to H_t for instances in the Newton phase.
 //   k_tq_step   16 lanes per instance (4 instances per wavefront): ratio test, costate recursion for the stationarity measure, barrier update,
 //               Riccati sweep with the value matrix P (14 x 14) in LDS and one column per lane, fraction to the boundary, rollout of the trial.
-#include <type_traits>
-
-#include "oh_device.h"
 #include "oh_kernels.h"
+#include "oh_rnea.h"
 
 namespace {
-
-// ---- dual numbers -----------------------------------------------------------------------------------------------------------------
-struct Dual {
-  double v, d;
-};
-OH_DEV Dual operator+(const Dual a, const Dual b) { return {a.v + b.v, a.d + b.d}; }
-OH_DEV Dual operator-(const Dual a, const Dual b) { return {a.v - b.v, a.d - b.d}; }
-OH_DEV Dual operator*(const Dual a, const Dual b) { return {a.v * b.v, fma(a.v, b.d, a.d * b.v)}; }
-OH_DEV Dual operator+(const Dual a, const double b) { return {a.v + b, a.d}; }
-OH_DEV Dual operator+(const double a, const Dual b) { return {a + b.v, b.d}; }
-OH_DEV Dual operator-(const Dual a, const double b) { return {a.v - b, a.d}; }
-OH_DEV Dual operator-(const double a, const Dual b) { return {a - b.v, -b.d}; }
-OH_DEV Dual operator*(const Dual a, const double b) { return {a.v * b, a.d * b}; }
-OH_DEV Dual operator*(const double a, const Dual b) { return {a * b.v, a * b.d}; }
-OH_DEV Dual operator-(const Dual a) { return {-a.v, -a.d}; }
-
-OH_DEV void sincosT(const double x, double* s, double* c) { sincos_joint(x, s, c); }
-OH_DEV void sincosT(const Dual x, Dual* s, Dual* c) {
-  double sv, cv;
-  sincos_joint(x.v, &sv, &cv);
-  *s = {sv, cv * x.d};
-  *c = {cv, -sv * x.d};
-}
-
-// ---- one primal, three tangents (round 3) --------------------------------------------------------------------------------------------
-// k_tq_eval used to run the recursion once per tangent direction (21 lanes per unit, each carrying the primal: 63 primal-equivalents).  A
-// lane now owns one JOINT j and carries the tangents with respect to q_j, dq_j and ddq_j next to one primal.  What depends on the joint
-// angles alone -- sines, cosines, the joint rotations, the joint axes in their body frames -- has a single tangent (DualR); the velocities,
-// accelerations and wrenches have all three (Dual3); the products between the two classes never form the two tangents that are zero by
-// construction.  Per unit: 7 lanes x (1 primal + ~4 tangent-equivalents) instead of 21 x 3.
-struct DualR {
-  double v, d;  // d / d q_j
-};
-struct Dual3 {
-  double v, d0, d1, d2;  // d / d q_j, d / d dq_j, d / d ddq_j
-};
-OH_DEV DualR operator+(const DualR a, const DualR b) { return {a.v + b.v, a.d + b.d}; }
-OH_DEV DualR operator-(const DualR a, const DualR b) { return {a.v - b.v, a.d - b.d}; }
-OH_DEV DualR operator*(const DualR a, const DualR b) { return {a.v * b.v, fma(a.v, b.d, a.d * b.v)}; }
-OH_DEV DualR operator+(const DualR a, const double b) { return {a.v + b, a.d}; }
-OH_DEV DualR operator+(const double a, const DualR b) { return {a + b.v, b.d}; }
-OH_DEV DualR operator-(const DualR a, const double b) { return {a.v - b, a.d}; }
-OH_DEV DualR operator-(const double a, const DualR b) { return {a - b.v, -b.d}; }
-OH_DEV DualR operator*(const DualR a, const double b) { return {a.v * b, a.d * b}; }
-OH_DEV DualR operator*(const double a, const DualR b) { return {a * b.v, a * b.d}; }
-OH_DEV DualR operator-(const DualR a) { return {-a.v, -a.d}; }
-OH_DEV Dual3 operator+(const Dual3 a, const Dual3 b) { return {a.v + b.v, a.d0 + b.d0, a.d1 + b.d1, a.d2 + b.d2}; }
-OH_DEV Dual3 operator-(const Dual3 a, const Dual3 b) { return {a.v - b.v, a.d0 - b.d0, a.d1 - b.d1, a.d2 - b.d2}; }
-OH_DEV Dual3 operator*(const Dual3 a, const Dual3 b) {
-  return {a.v * b.v, fma(a.v, b.d0, a.d0 * b.v), fma(a.v, b.d1, a.d1 * b.v), fma(a.v, b.d2, a.d2 * b.v)};
-}
-OH_DEV Dual3 operator*(const DualR a, const Dual3 b) { return {a.v * b.v, fma(a.v, b.d0, a.d * b.v), a.v * b.d1, a.v * b.d2}; }
-OH_DEV Dual3 operator*(const Dual3 a, const DualR b) { return b * a; }
-OH_DEV Dual3 operator+(const Dual3 a, const DualR b) { return {a.v + b.v, a.d0 + b.d, a.d1, a.d2}; }
-OH_DEV Dual3 operator+(const DualR a, const Dual3 b) { return b + a; }
-OH_DEV Dual3 operator-(const Dual3 a, const DualR b) { return {a.v - b.v, a.d0 - b.d, a.d1, a.d2}; }
-OH_DEV Dual3 operator-(const DualR a, const Dual3 b) { return {a.v - b.v, a.d - b.d0, -b.d1, -b.d2}; }
-OH_DEV Dual3 operator+(const Dual3 a, const double b) { return {a.v + b, a.d0, a.d1, a.d2}; }
-OH_DEV Dual3 operator+(const double a, const Dual3 b) { return {a + b.v, b.d0, b.d1, b.d2}; }
-OH_DEV Dual3 operator-(const Dual3 a, const double b) { return {a.v - b, a.d0, a.d1, a.d2}; }
-OH_DEV Dual3 operator-(const double a, const Dual3 b) { return {a - b.v, -b.d0, -b.d1, -b.d2}; }
-OH_DEV Dual3 operator*(const Dual3 a, const double b) { return {a.v * b, a.d0 * b, a.d1 * b, a.d2 * b}; }
-OH_DEV Dual3 operator*(const double a, const Dual3 b) { return {a * b.v, a * b.d0, a * b.d1, a * b.d2}; }
-OH_DEV Dual3 operator-(const Dual3 a) { return {-a.v, -a.d0, -a.d1, -a.d2}; }
-
-// ---- two tangents (round 4): second derivatives of the inverse dynamics ----------------------------------------------------------------------
-// rnea_ctau_grad below is the hand-written adjoint of the recursion; run on (DualR, Dual2) scalars seeded with q_j and dq_j it returns rows q_j and
-// dq_j of  sum_i c_i d^2 tau_i / d(q, dq, ddq)^2  (the torques are linear in ddq, so the rows of ddq_j are the transposed columns of those).
-struct Dual2 {
-  double v, d0, d1;  // d / d q_j, d / d dq_j
-};
-OH_DEV Dual2 operator+(const Dual2 a, const Dual2 b) { return {a.v + b.v, a.d0 + b.d0, a.d1 + b.d1}; }
-OH_DEV Dual2 operator-(const Dual2 a, const Dual2 b) { return {a.v - b.v, a.d0 - b.d0, a.d1 - b.d1}; }
-OH_DEV Dual2 operator*(const Dual2 a, const Dual2 b) { return {a.v * b.v, fma(a.v, b.d0, a.d0 * b.v), fma(a.v, b.d1, a.d1 * b.v)}; }
-OH_DEV Dual2 operator*(const DualR a, const Dual2 b) { return {a.v * b.v, fma(a.v, b.d0, a.d * b.v), a.v * b.d1}; }
-OH_DEV Dual2 operator*(const Dual2 a, const DualR b) { return b * a; }
-OH_DEV Dual2 operator+(const Dual2 a, const DualR b) { return {a.v + b.v, a.d0 + b.d, a.d1}; }
-OH_DEV Dual2 operator+(const DualR a, const Dual2 b) { return b + a; }
-OH_DEV Dual2 operator-(const Dual2 a, const DualR b) { return {a.v - b.v, a.d0 - b.d, a.d1}; }
-OH_DEV Dual2 operator-(const DualR a, const Dual2 b) { return {a.v - b.v, a.d - b.d0, -b.d1}; }
-OH_DEV Dual2 operator+(const Dual2 a, const double b) { return {a.v + b, a.d0, a.d1}; }
-OH_DEV Dual2 operator+(const double a, const Dual2 b) { return {a + b.v, b.d0, b.d1}; }
-OH_DEV Dual2 operator-(const Dual2 a, const double b) { return {a.v - b, a.d0, a.d1}; }
-OH_DEV Dual2 operator-(const double a, const Dual2 b) { return {a - b.v, -b.d0, -b.d1}; }
-OH_DEV Dual2 operator*(const Dual2 a, const double b) { return {a.v * b, a.d0 * b, a.d1 * b}; }
-OH_DEV Dual2 operator*(const double a, const Dual2 b) { return {a * b.v, a * b.d0, a * b.d1}; }
-OH_DEV Dual2 operator-(const Dual2 a) { return {-a.v, -a.d0, -a.d1}; }
-OH_DEV void sincosT(const DualR x, DualR* s, DualR* c) {
-  double sv, cv;
-  sincos_joint(x.v, &sv, &cv);
-  *s = {sv, cv * x.d};
-  *c = {cv, -sv * x.d};
-}
-
-// scalar class of what depends on the joint angles alone, given the class of the velocities / accelerations / wrenches
-template <class S>
-struct RotOf {
-  using T = S;
-};
-template <>
-struct RotOf<Dual3> {
-  using T = DualR;
-};
-template <>
-struct RotOf<Dual2> {
-  using T = DualR;
-};
-
-template <class A, class B>
-struct Prom {
-  using T = Dual;
-};
-template <>
-struct Prom<double, double> {
-  using T = double;
-};
-template <> struct Prom<DualR, DualR> { using T = DualR; };
-template <> struct Prom<DualR, double> { using T = DualR; };
-template <> struct Prom<double, DualR> { using T = DualR; };
-template <> struct Prom<Dual3, Dual3> { using T = Dual3; };
-template <> struct Prom<Dual3, double> { using T = Dual3; };
-template <> struct Prom<double, Dual3> { using T = Dual3; };
-template <> struct Prom<Dual3, DualR> { using T = Dual3; };
-template <> struct Prom<DualR, Dual3> { using T = Dual3; };
-template <> struct Prom<Dual2, Dual2> { using T = Dual2; };
-template <> struct Prom<Dual2, double> { using T = Dual2; };
-template <> struct Prom<double, Dual2> { using T = Dual2; };
-template <> struct Prom<Dual2, DualR> { using T = Dual2; };
-template <> struct Prom<DualR, Dual2> { using T = Dual2; };
-template <class A, class B>
-OH_DEV void crossT(const A* a, const B* b, typename Prom<A, B>::T* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-// o = M v, o = M^T v (row-major 3x3)
-template <class A, class B>
-OH_DEV void mvT(const A* M, const B* v, typename Prom<A, B>::T* o) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) o[i] = M[3 * i] * v[0] + M[3 * i + 1] * v[1] + M[3 * i + 2] * v[2];
-}
-template <class A, class B>
-OH_DEV void mTvT(const A* M, const B* v, typename Prom<A, B>::T* o) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) o[i] = M[i] * v[0] + M[3 + i] * v[1] + M[6 + i] * v[2];
-}
-// R = R0 Rot(a, theta), Rot = c I + s [a]x + (1 - c) a a^T (spatialmath.py:89-99), row-wise as in rot_axis_right
-template <class S>
-OH_DEV void joint_rotation(const double* R0, const double* a, const S s, const S c, S* R) {
-  const S omc = 1.0 - c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double* r = R0 + 3 * i;
-    double x[3];
-    cross3(r, a, x);
-    const double d = dot3(r, a);
-    const S k = omc * d;
-    R[3 * i + 0] = c * r[0] + s * x[0] + k * a[0];
-    R[3 * i + 1] = c * r[1] + s * x[1] + k * a[1];
-    R[3 * i + 2] = c * r[2] + s * x[2] + k * a[2];
-  }
-}
-
-// RobotModel.rnea (models.py:1819-1880) on scalars S (double or Dual): NB bodies, the last one on a fixed joint.
-// The loops over the bodies are kept rolled (the per-body wrenches f, nn and sin/cos live in lane-private memory, indexed by the
-// loop counter): unrolled, the dual-number recursion needs ~1500 live registers and the compiler spills two thirds of them.
-template <int NB, class S, class SR = typename RotOf<S>::T>
-OH_DEV void rnea_forward_body(const oh_dynamics* __restrict__ dy, const int i, const bool moving, const SR qi, const S qdi, const S qddi, S (&om)[3],
-                              S (&omD)[3], S (&vD)[3], S* __restrict__ fi, S* __restrict__ ni, SR& sji, SR& cji) {
-  S omi[3], omDi[3], vDi[3];
-  S t1[3], t2[3], t3[3], acc[3];
-  crossT(omD, dy->xyz[i], t1);
-  crossT(om, dy->xyz[i], t2);
-  crossT(om, t2, t3);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) acc[k] = vD[k] + t1[k] + t3[k];
-  if (moving) {
-    SR Rp[9];
-    sincosT(qi, &sji, &cji);
-    joint_rotation(dy->R0[i], dy->axis[i], sji, cji, Rp);
-    SR a[3];
-    S omp[3], omDp[3];
-    mTvT(Rp, dy->axis[i], a);  // iaxisi
-    mTvT(Rp, om, omp);
-    mTvT(Rp, omD, omDp);
-    S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-    S cr[3];
-    crossT(omp, aq, cr);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      omi[k] = omp[k] + aq[k];
-      omDi[k] = omDp[k] + cr[k] + a[k] * qddi;
-    }
-    mTvT(Rp, acc, vDi);
-  } else {
-    mTvT(dy->R0[i], om, omi);
-    mTvT(dy->R0[i], omD, omDi);
-    mTvT(dy->R0[i], acc, vDi);
-  }
-  crossT(omDi, dy->com[i], t1);
-  crossT(omi, dy->com[i], t2);
-  crossT(omi, t2, t3);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) fi[k] = dy->mass[i] * (vDi[k] + t1[k] + t3[k]);
-  S Io[3], IoD[3];
-  mvT(dy->inertia[i], omi, Io);
-  mvT(dy->inertia[i], omDi, IoD);
-  crossT(omi, Io, t1);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    ni[k] = IoD[k] + t1[k];
-    om[k] = omi[k];
-    omD[k] = omDi[k];
-    vD[k] = vDi[k];
-  }
-}
-
-template <int NB, class S, class SR = typename RotOf<S>::T>
-OH_DEV void rnea_lit(const oh_dynamics* __restrict__ dy, const SR (&q)[NB - 1], const S (&qd)[NB - 1], const S (&qdd)[NB - 1], S (&tau)[NB - 1]) {
-  S f[NB][3], nn[NB][3];
-  SR sj[NB], cj[NB];
-  S om[3], omD[3], vD[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    om[k] = S{};
-    omD[k] = S{};
-    vD[k] = S{} + dy->vd0[k];
-  }
-#pragma unroll 1
-  for (int i = 0; i < NB - 1; ++i) rnea_forward_body<NB, S>(dy, i, true, q[i], qd[i], qdd[i], om, omD, vD, f[i], nn[i], sj[i], cj[i]);
-  rnea_forward_body<NB, S>(dy, NB - 1, false, SR{}, S{}, S{}, om, omD, vD, f[NB - 1], nn[NB - 1], sj[NB - 1], cj[NB - 1]);
-  // backward (models.py:1858-1880); the reference's fs/ns lists carry a leading zero entry: fs[i] == f[i-1]
-  S ifi[3] = {f[NB - 1][0], f[NB - 1][1], f[NB - 1][2]};
-  S ini[3], t1[3];
-  crossT(dy->com[NB - 1], f[NB - 1], t1);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) ini[k] = nn[NB - 1][k] + t1[k];
-#pragma unroll 1
-  for (int i = NB - 1; i >= 1; --i) {
-    S a1[3], a2[3], a3[3], a4[3];
-    if (i < NB - 1) {
-      SR pRi[9];
-      joint_rotation(dy->R0[i], dy->axis[i], sj[i], cj[i], pRi);
-      mvT(pRi, ini, a1);
-      mvT(pRi, ifi, a3);
-    } else {
-      mvT(dy->R0[i], ini, a1);
-      mvT(dy->R0[i], ifi, a3);
-    }
-    crossT(dy->com[i - 1], f[i - 1], a2);
-    crossT(dy->xyz[i], a3, a4);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      ini[k] = nn[i - 1][k] + a1[k] + a2[k] + a4[k];
-      ifi[k] = a3[k] + f[i - 1][k];
-    }
-    SR pR[9], ax[3];
-    joint_rotation(dy->R0[i - 1], dy->axis[i - 1], sj[i - 1], cj[i - 1], pR);
-    mTvT(pR, dy->axis[i - 1], ax);  // pRi^T axis
-    tau[i - 1] = ini[0] * ax[0] + ini[1] * ax[1] + ini[2] * ax[2];
-  }
-}
-
-// ---- the same torques by virtual work, outward pass only (round 4) -------------------------------------------------------------------------------
-// tau_k = sum_{b >= k} f_b . v_b^(k) + (n_b + com_b x f_b) . w_b^(k): the inertial wrench of body b (models.py:1819-1856, the outward pass of the
-// reference) paired with the twist (w^(k), v^(k)) a unit rate of joint k alone gives the frame of body b -- what the reference's inward pass
-// (models.py:1858-1880) sums by handing wrenches to the parents, summed the other way round.  The twists travel outward with the recursion itself,
-// so nothing has to wait for the last body: no per-body arrays.  rnea_lit keeps 8 bodies x (f, n, sin, cos) of dual numbers in lane-private memory
-// (1.8 KB per lane, written once and read once: 36 KB per unit of k_tq_eval3, which made that kernel HBM-bound on its own scratch at 1.6 % of the
-// bytes being useful); here the state is 7 twists in registers.  The twists depend on the joint angles alone (SR).  Equal to rnea_lit up to rounding.
-template <int NB, bool MOVING, class S, class SR>
-OH_DEV void vw_body(const oh_dynamics* __restrict__ dy, const int i, const SR qi, const S qdi, const S qddi, S (&om)[3], S (&omD)[3], S (&vD)[3],
-                    SR (&wk)[NB - 1][3], SR (&vk)[NB - 1][3], S (&tau)[NB - 1]) {
-  constexpr int NJ = NB - 1;
-  using RT = typename std::conditional<MOVING, SR, double>::type;
-  S t1[3], t2[3], t3[3], acc[3];
-  crossT(omD, dy->xyz[i], t1);
-  crossT(om, dy->xyz[i], t2);
-  crossT(om, t2, t3);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) acc[k] = vD[k] + t1[k] + t3[k];
-  RT Rp[9];
-  SR a[3];
-  if constexpr (MOVING) {
-    SR sj, cj;
-    sincosT(qi, &sj, &cj);
-    joint_rotation(dy->R0[i], dy->axis[i], sj, cj, Rp);
-    mTvT(Rp, dy->axis[i], a);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Rp[k] = dy->R0[i][k];
-  }
-  // twists first: they need the parent's values of nothing else, and the registers of (om, omD, vD) of the parent die right after
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    if (k < i) {
-      SR x[3], y[3], wn[3], vn[3];
-      crossT(wk[k], dy->xyz[i], x);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) y[c] = vk[k][c] + x[c];
-      mTvT(Rp, y, vn);
-      mTvT(Rp, wk[k], wn);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        wk[k][c] = wn[c];
-        vk[k][c] = vn[c];
-      }
-    } else if (MOVING && k == i) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        wk[k][c] = a[c];
-        vk[k][c] = SR{};
-      }
-    }
-  }
-  S omi[3], omDi[3], vDi[3];
-  {
-    S omp[3], omDp[3];
-    mTvT(Rp, om, omp);
-    mTvT(Rp, omD, omDp);
-    if constexpr (MOVING) {
-      S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-      S cr[3];
-      crossT(omp, aq, cr);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        omi[k] = omp[k] + aq[k];
-        omDi[k] = omDp[k] + cr[k] + a[k] * qddi;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        omi[k] = omp[k];
-        omDi[k] = omDp[k];
-      }
-    }
-    mTvT(Rp, acc, vDi);
-  }
-  S f[3], m[3];
-  crossT(omDi, dy->com[i], t1);
-  crossT(omi, dy->com[i], t2);
-  crossT(omi, t2, t3);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) f[k] = dy->mass[i] * (vDi[k] + t1[k] + t3[k]);
-  {
-    S Io[3], IoD[3];
-    mvT(dy->inertia[i], omi, Io);
-    mvT(dy->inertia[i], omDi, IoD);
-    crossT(omi, Io, t1);
-    crossT(dy->com[i], f, t2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      m[k] = IoD[k] + t1[k] + t2[k];
-      om[k] = omi[k];
-      omD[k] = omDi[k];
-      vD[k] = vDi[k];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NJ; ++k)
-    if (k <= i) tau[k] = tau[k] + (dotT(f, vk[k]) + dotT(m, wk[k]));
-}
-
-// qs: the unit's (q | dq | ddq) at offsets 0, 8, 16 (LDS or global: indexed by the loop counter); lane j seeds joint j.  Seed: S / SR from (value, is-seed).
-template <class S>
-struct VwSeed;
-template <>
-struct VwSeed<Dual3> {
-  static OH_DEV DualR q(double v, double one) { return {v, one}; }
-  static OH_DEV Dual3 qd(double v, double one) { return {v, 0.0, one, 0.0}; }
-  static OH_DEV Dual3 qdd(double v, double one) { return {v, 0.0, 0.0, one}; }
-};
-template <int NB, class S, class SR = typename RotOf<S>::T>
-OH_DEV void rnea_vw3(const oh_dynamics* __restrict__ dy, const double* qs, const int j, S (&tau)[NB - 1]) {
-  constexpr int NJ = NB - 1;
-  S om[3], omD[3], vD[3];
-  SR wk[NJ][3], vk[NJ][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    om[k] = S{};
-    omD[k] = S{};
-    vD[k] = S{} + dy->vd0[k];
-  }
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    tau[k] = S{};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) wk[k][c] = vk[k][c] = SR{};
-  }
-#pragma unroll 1
-  for (int i = 0; i < NJ; ++i) {
-    const double one = (i == j) ? 1.0 : 0.0;
-    vw_body<NB, true, S, SR>(dy, i, VwSeed<S>::q(qs[i], one), VwSeed<S>::qd(qs[8 + i], one), VwSeed<S>::qdd(qs[16 + i], one), om, omD, vD, wk, vk, tau);
-  }
-  vw_body<NB, false, S, SR>(dy, NJ, SR{}, S{}, S{}, om, omD, vD, wk, vk, tau);
-}
-
-// ---- d tau / d (q, dq, ddq) in closed form (round 4; numpy: oracle/torque.py:rnea_jacobian_spatial) ----------------------------------------------
-// The dual-number recursions above cost a unit 7 lanes x (1 primal + 3 tangents) of the whole chain: ~120 k instructions per unit, 0.45 of the batch's
-// device time.  In world coordinates (spatial vectors about the world origin, Featherstone 2008) the same derivative has a closed form.  With
-//     S_l = (z_l, o_l x z_l)            joint screw,  v_b = sum_{l<=b} S_l dq_l,  a_b = a_0 + sum_{l<=b} (S_l ddq_l + v_l x S_l dq_l),
-//     W_b = I_b a_b + v_b x* I_b v_b,   tau_k = S_k . sum_{b>=k} W_b          (what the reference's two passes compute, models.py:1819-1880)
-// and  dS_l/dq_m = S_m x S_l (m < l),  dI_b/dq_m = S_m x* I_b - I_b S_m x (m <= b)  the product rule collapses (Jacobi identity) to
-//     dW_b/dddq_j = I_b S_j,    dW_b/ddq_j = 2 (B_b S_j + I_b Sd_j),    dW_b/dq_j = S_j x* W_b + I_b Sdd_j + 2 B_b Sd_j          (b >= j)
-//     Sd_j = v_j x S_j,  Sdd_j = a_j x S_j + v_j x Sd_j,  2 B_b x = I_b (x x v_b) + x x* I_b v_b + v_b x* I_b x = (Xi_b w_x, -2 p_b x w_x)
-// (2 B_b sees only the angular part of x: Xi_b 3 x 3, p_b the linear momentum; Carpentier & Mansard 2018 and Singh, Russell & Wensing 2022 arrive at the
-// same terms).  Summed over the subtree (composites I^C, Xi^C, p^C, F^C of body m = max(k, j)):
-//     d tau_k / d(q_j, dq_j, ddq_j) = S_k . u(max(k, j)),   u_ddq = I^C S_j,  u_dq = 2 (B^C S_j + I^C Sd_j),  u_q = I^C Sdd_j + 2 B^C Sd_j (+ S_j x* F^C_j if k <= j).
-// Lane j of a unit: the serial world-frame chain (cheap, every lane), the world inertia / Xi / wrench of body j (the fixed last body rides on lane N-1),
-// exchange through LDS, then the inward composite sums and column j.  ~3 k instructions per lane.  Valid when the reference's recursion is the
-// dynamics of a rigid-body chain: unit axes that the joint-origin rotation leaves in place (R0^T axis = axis: the angular velocity the reference adds,
-// iRp @ axis, is then the axis Rot(axis, q) turns about; models.py:1821-1823).  oh_create_torque checks it; other tables take the dual-number path.
-template <int N>
-struct IdsWs {
-  // A unit's LDS in k_tq_eval3, 277 doubles for N = 7 (nine units: 19.9 KB, so that two blocks share a SIMD's quarter of the CU's 160 KB):
-  static constexpr int TW = 28;                  // pitch of the per-body slots: 28 = m, h (3), A (6), Xi (9), p (3), W (6) whatever the chain length; once phase 3 has consumed body
-                                                 // m its slot takes row m of d tau / dz (3 N entries) and, behind it, lane m's row coefficients (RW)
-  static constexpr int BD = 0;
-  static constexpr int RW = 3 * N + 1;           // offset inside a slot: cf, cb, dw, bar, nrel, viol (6 doubles; the slot has 28 - 22 = 6 to spare)
-  static constexpr int S = N * TW;               // joint screws, 6 each (phases 1-3); then, together with QS, the three rows of d p_link / dz (JP)
-  static constexpr int QS = S + 6 * N;           // (q | dq | ddq) at 0, 8, 16: read by the loop counter in phase 1 and by the chain walk
-  static constexpr int JP = S;                   // pitch 3 N + 1
-  static constexpr int RW2 = QS + 24;            // cmpl[N], fsum[N]
-  static constexpr int SIZE = (RW2 + 2 * N) | 1;  // odd: the units of a wavefront land in different banks
-  static_assert(3 * (3 * N + 1) <= 6 * N + 24, "the rows of d p_link / dz take the place of the screws and of (q | dq | ddq)");
-  static_assert(3 * N + 1 + 6 <= TW, "row m of d tau / dz and the six row coefficients behind it fit the slot of body m");
-};
-OH_DEV void mcross6(const double* x, const double* y, double* o) {  // motion x motion
-  double t[3];
-  cross3(x, y, o);
-  cross3(x, y + 3, o + 3);
-  cross3(x + 3, y, t);
-  o[3] += t[0]; o[4] += t[1]; o[5] += t[2];
-}
-OH_DEV void fcross6(const double* x, const double* f, double* o) {  // motion x* force
-  double t[3];
-  cross3(x, f, o);
-  cross3(x + 3, f + 3, t);
-  o[0] += t[0]; o[1] += t[1]; o[2] += t[2];
-  cross3(x, f + 3, o + 3);
-}
-// (n, f) = I (w, v) for a rigid-body inertia about the world origin: n = A w + h x v, f = m v - h x w;  A = (xx xy xz yy yz zz)
-OH_DEV void inert6(const double m, const double* h, const double* A, const double* x, double* o) {
-  double t[3];
-  cross3(h, x + 3, t);
-  o[0] = A[0] * x[0] + A[1] * x[1] + A[2] * x[2] + t[0];
-  o[1] = A[1] * x[0] + A[3] * x[1] + A[4] * x[2] + t[1];
-  o[2] = A[2] * x[0] + A[4] * x[1] + A[5] * x[2] + t[2];
-  cross3(h, x, t);
-  o[3] = m * x[3] - t[0];
-  o[4] = m * x[4] - t[1];
-  o[5] = m * x[5] - t[2];
-}
-OH_DEV double dot6(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5]; }
-
-// world inertia, momentum coupling and wrench of body b from its (R, o, v, a), added to acc[28]
-OH_DEV void ids_body(const oh_dynamics* __restrict__ dy, const int b, const double* __restrict__ p1, double* acc) {
-  const double* R = p1;
-  const double* o = p1 + 9;
-  const double* v = p1 + 12;
-  const double* a = p1 + 18;
-  double c[3], T[9], Ic[9];
-  mv3(R, dy->com[b], c);
-  c[0] += o[0]; c[1] += o[1]; c[2] += o[2];
-  mm3(R, dy->inertia[b], T);
-  mmT3(T, R, Ic);
-  const double m = dy->mass[b];
-  const double h[3] = {m * c[0], m * c[1], m * c[2]};
-  const double c2 = dot3(c, c);
-  double A[6];
-  A[0] = Ic[0] + m * (c2 - c[0] * c[0]);
-  A[1] = 0.5 * (Ic[1] + Ic[3]) - m * c[0] * c[1];
-  A[2] = 0.5 * (Ic[2] + Ic[6]) - m * c[0] * c[2];
-  A[3] = Ic[4] + m * (c2 - c[1] * c[1]);
-  A[4] = 0.5 * (Ic[5] + Ic[7]) - m * c[1] * c[2];
-  A[5] = Ic[8] + m * (c2 - c[2] * c[2]);
-  double Pm[6], W[6], t6[6];
-  inert6(m, h, A, v, Pm);
-  inert6(m, h, A, a, W);
-  fcross6(v, Pm, t6);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) W[k] += t6[k];
-  // Xi = [w]x A + ([w]x A)^T - (h vl^T + vl h^T - 2 (vl . h) 1) - [n_P]x
-  const double* w = v;
-  const double* vl = v + 3;
-  const double Af[9] = {A[0], A[1], A[2], A[1], A[3], A[4], A[2], A[4], A[5]};
-  double OA[9];  // columns w x A[:, k]
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double col[3] = {Af[k], Af[3 + k], Af[6 + k]};
-    double x[3];
-    cross3(w, col, x);
-    OA[k] = x[0]; OA[3 + k] = x[1]; OA[6 + k] = x[2];
-  }
-  const double vh = dot3(vl, h);
-  double Xi[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Xi[3 * r + k] = OA[3 * r + k] + OA[3 * k + r] - h[r] * vl[k] - vl[r] * h[k] + (r == k ? 2.0 * vh : 0.0);
-  Xi[1] += Pm[2]; Xi[2] -= Pm[1];
-  Xi[3] -= Pm[2]; Xi[5] += Pm[0];
-  Xi[6] += Pm[1]; Xi[7] -= Pm[0];
-  acc[0] += m;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) acc[1 + k] += h[k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) acc[4 + k] += A[k];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[10 + k] += Xi[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) acc[19 + k] += Pm[3 + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) acc[22 + k] += W[k];
-}
-
-// ws: the unit's LDS workspace (IdsWs<N>::SIZE doubles), qs: (q | dq | ddq) at 0, 8, 16; every lane of the unit calls (block of one wavefront).
-// Lane j leaves column j, N + j, 2 N + j of d tau / d (q, dq, ddq) in rows 0 .. N-1 of the tile at ws[0] and returns tau_j.
-template <int N>
-OH_DEV double rnea_idsva(const oh_dynamics* __restrict__ dy, double* __restrict__ ws, const int j, const bool writer) {
-  using L = IdsWs<N>;
-  const double* qs = ws + L::QS;
-  double Sj[6], Sdj[6], Sddj[6];
-  double own[24];  // (R, o, v, a) of body j, picked up on the way (every lane walks the whole chain)
-  {
-    double Rw[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, ow[3] = {0.0, 0.0, 0.0};
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, a[6] = {0.0, 0.0, 0.0, dy->vd0[0], dy->vd0[1], dy->vd0[2]};
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Sj[k] = Sdj[k] = Sddj[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 24; ++k) own[k] = 0.0;
-#pragma unroll 1
-    for (int i = 0; i < N; ++i) {
-      double o[3], Ri[9];
-      mv3(Rw, dy->xyz[i], o);
-      o[0] += ow[0]; o[1] += ow[1]; o[2] += ow[2];
-      double S[6], Sd[6], Sdd[6], t6[6], Rp[9], sj, cj;
-      mv3(Rw, dy->axis[i], S);
-      cross3(o, S, S + 3);
-      sincos_joint(qs[i], &sj, &cj);
-      joint_rotation(dy->R0[i], dy->axis[i], sj, cj, Rp);
-      mm3(Rw, Rp, Ri);
-      mcross6(v, S, Sd);
-      const double qd = qs[8 + i], qdd = qs[16 + i];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        v[k] = fma(S[k], qd, v[k]);
-        a[k] = fma(Sd[k], qd, fma(S[k], qdd, a[k]));
-      }
-      mcross6(a, S, Sdd);
-      mcross6(v, Sd, t6);
-      const bool mine = i == j;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        Sdd[k] += t6[k];
-        Sj[k] = mine ? S[k] : Sj[k];
-        Sdj[k] = mine ? Sd[k] : Sdj[k];
-        Sddj[k] = mine ? Sdd[k] : Sddj[k];
-        own[12 + k] = mine ? v[k] : own[12 + k];
-        own[18 + k] = mine ? a[k] : own[18 + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 9; ++k) own[k] = mine ? Ri[k] : own[k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) own[9 + k] = mine ? o[k] : own[9 + k];
-      if (writer && mine) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ws[L::S + 6 * i + k] = S[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rw[k] = Ri[k];
-      ow[0] = o[0]; ow[1] = o[1]; ow[2] = o[2];
-    }
-  }
-  {
-    double acc[28];
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-    ids_body(dy, j, own, acc);
-    {  // the fixed last body moves with body N - 1: its frame follows from that body's (lane N - 1 keeps the result)
-      double last[24], t3[3];
-      mm3(own, dy->R0[N], last);
-      mv3(own, dy->xyz[N], t3);
-      last[9] = own[9] + t3[0]; last[10] = own[10] + t3[1]; last[11] = own[11] + t3[2];
-#pragma unroll
-      for (int k = 12; k < 24; ++k) last[k] = own[k];
-      double acc2[28];
-#pragma unroll
-      for (int k = 0; k < 28; ++k) acc2[k] = 0.0;
-      ids_body(dy, N, last, acc2);
-#pragma unroll
-      for (int k = 0; k < 28; ++k) acc[k] += (j == N - 1) ? acc2[k] : 0.0;
-    }
-    if (writer) {
-#pragma unroll
-      for (int k = 0; k < 28; ++k) ws[L::BD + L::TW * j + k] = acc[k];
-    }
-  }
-  __syncthreads();
-  double C[28];
-  double u0s[6], u1s[6], u2s[6];
-  double tau_j = 0.0;
-#pragma unroll
-  for (int k = 0; k < 28; ++k) C[k] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) u0s[k] = u1s[k] = u2s[k] = 0.0;
-#pragma unroll 1
-  for (int m = N - 1; m >= 0; --m) {
-    const double* bd = ws + L::BD + L::TW * m;
-    double Sm[6];
-#pragma unroll
-    for (int k = 0; k < 28; ++k) C[k] += bd[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Sm[k] = ws[L::S + 6 * m + k];
-    const double* hC = C + 1;
-    const double* AC = C + 4;
-    const double* XC = C + 10;
-    const double* pC = C + 19;
-    const double* FC = C + 22;
-    double u0[6], u1[6], u2[6], t6[6], x[3];
-    inert6(C[0], hC, AC, Sj, u2);
-    inert6(C[0], hC, AC, Sdj, t6);
-    mv3(XC, Sj, u1);
-    cross3(pC, Sj, x);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      u1[k] = fma(2.0, t6[k], u1[k]);
-      u1[3 + k] = 2.0 * (t6[3 + k] - x[k]);
-    }
-    inert6(C[0], hC, AC, Sddj, u0);
-    mv3(XC, Sdj, t6);
-    cross3(pC, Sdj, x);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      u0[k] += t6[k];
-      u0[3 + k] -= 2.0 * x[k];
-    }
-    if (m == j) {
-      fcross6(Sj, FC, t6);
-      tau_j = dot6(Sm, FC);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        u0s[k] = u0[k] + t6[k];
-        u1s[k] = u1[k];
-        u2s[k] = u2[k];
-      }
-    }
-    const bool below = m > j;  // row below the diagonal: the composites of body m; else what column j froze at its own body
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      u0[k] = below ? u0[k] : u0s[k];
-      u1[k] = below ? u1[k] : u1s[k];
-      u2[k] = below ? u2[k] : u2s[k];
-    }
-    const double e0 = dot6(Sm, u0), e1 = dot6(Sm, u1), e2 = dot6(Sm, u2);
-    __syncthreads();  // every lane of the unit has taken body m out of its slot: the slot becomes row m of d tau / dz
-    if (writer) {
-      ws[m * L::TW + j] = e0;
-      ws[m * L::TW + N + j] = e1;
-      ws[m * L::TW + 2 * N + j] = e2;
-    }
-  }
-  return tau_j;
-}
-
-// d tau / d (q, qd, qdd) of RobotModel.rnea (what the reference obtains with casadi.jacobian of the same graph, optimization.py:8-24): one lane per
-// (sample, direction), the literal recursion on dual numbers.  q, qd, qdd [n][N] -> J [n][N][3 N] row-major.
-template <int N>
-__global__ __launch_bounds__(64) void k_rnea_jac(const oh_dynamics* __restrict__ dy, const int n, const double* __restrict__ q, const double* __restrict__ qd,
-                                                 const double* __restrict__ qdd, double* __restrict__ J) {
-  constexpr int NZ = 3 * N, UPW = 64 / NZ;
-  const int lane = threadIdx.x;
-  const int ul = lane / NZ, d = lane - ul * NZ;
-  const long long u = (long long)blockIdx.x * UPW + ul;
-  if (ul >= UPW || u >= n) return;
-  Dual a[N], b[N], c[N], tau[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    a[j] = {q[u * N + j], d == j ? 1.0 : 0.0};
-    b[j] = {qd[u * N + j], d == N + j ? 1.0 : 0.0};
-    c[j] = {qdd[u * N + j], d == 2 * N + j ? 1.0 : 0.0};
-  }
-  rnea_lit<N + 1, Dual>(dy, a, b, c, tau);
-#pragma unroll
-  for (int i = 0; i < N; ++i) J[((size_t)u * N + i) * NZ + d] = tau[i].d;
-}
-
-
-// ---- gradient of c^T tau (round 4; numpy: oracle/torque.py:rnea_ctau_gradient) ------------------------------------------------------------------
-// Virtual work: c^T rnea(q, qd, qdd) = sum_b f_b . v_b(c) + n_b . w_b(c), the inertial wrench of body b (models.py:1819-1856, the outward pass of the
-// reference) paired with the twist the joint rates c would give it.  Both come out of one outward recursion, so the gradient with respect to
-// (q, qd, qdd) is one inward adjoint recursion: body i hands the adjoints of its (om, omD, vD) and of the virtual (wc, vo) to its parent.  A joint
-// angle enters only through R_i^T = Rot(axis, q_i)^T R0^T, and d(R_i^T v)/dq_i = -axis x (R_i^T v), which is what `sw` collects.
-// Scalars: S for what depends on (q, qd, qdd), SR for what depends on the joint angles alone (rotations, axes, the virtual twists); qdd and c carry
-// no tangent (nothing is differentiated twice with respect to them: tau is linear in qdd, c is a multiplier).
-template <class A, class B>
-OH_DEV typename Prom<A, B>::T dotT(const A* a, const B* b) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-template <int NB, class S, class SR = typename RotOf<S>::T>
-OH_DEV void rnea_ctau_grad(const oh_dynamics* __restrict__ dy, const SR (&q)[NB - 1], const S (&qd)[NB - 1], const double (&qdd)[NB - 1], const double (&c)[NB - 1],
-                           S (&gq)[NB - 1], S (&gqd)[NB - 1], S (&gqdd)[NB - 1]) {
-  // outward pass: the state every body leaves to its child (lane-private memory, the loops stay rolled as in rnea_lit)
-  S om_[NB][3], omD_[NB][3], vD_[NB][3];
-  SR wc_[NB][3], vo_[NB][3];
-  SR sj[NB], cj[NB];
-  {
-    S om[3], omD[3], vD[3];
-    SR wc[3], vo[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      om[k] = S{};
-      omD[k] = S{};
-      vD[k] = S{} + dy->vd0[k];
-      wc[k] = SR{};
-      vo[k] = SR{};
-    }
-#pragma unroll 1
-    for (int i = 0; i < NB; ++i) {
-      const bool moving = i < NB - 1;
-      S t1[3], t2[3], t3[3], acc[3];
-      SR w[3], tw[3];
-      crossT(omD, dy->xyz[i], t1);
-      crossT(om, dy->xyz[i], t2);
-      crossT(om, t2, t3);
-      crossT(wc, dy->xyz[i], tw);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        acc[k] = vD[k] + t1[k] + t3[k];
-        w[k] = vo[k] + tw[k];
-      }
-      SR Rp[9];
-      if (moving) {
-        sincosT(q[i], &sj[i], &cj[i]);
-        joint_rotation(dy->R0[i], dy->axis[i], sj[i], cj[i], Rp);
-      } else {
-        sj[i] = SR{};
-        cj[i] = SR{};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rp[k] = SR{} + dy->R0[i][k];
-      }
-      S omp[3], omDp[3];
-      SR wcp[3];
-      mTvT(Rp, om, omp);
-      mTvT(Rp, omD, omDp);
-      mTvT(Rp, wc, wcp);
-      if (moving) {
-        SR a[3];
-        mTvT(Rp, dy->axis[i], a);
-        const S qdi = qd[i];
-        S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-        S cr[3];
-        crossT(omp, aq, cr);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          om[k] = omp[k] + aq[k];
-          omD[k] = omDp[k] + cr[k] + a[k] * qdd[i];
-          wc[k] = wcp[k] + a[k] * c[i];
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          om[k] = omp[k];
-          omD[k] = omDp[k];
-          wc[k] = wcp[k];
-        }
-      }
-      S vDi[3];
-      SR voi[3];
-      mTvT(Rp, acc, vDi);
-      mTvT(Rp, w, voi);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        vD[k] = vDi[k];
-        vo[k] = voi[k];
-        om_[i][k] = om[k];
-        omD_[i][k] = omD[k];
-        vD_[i][k] = vD[k];
-        wc_[i][k] = wc[k];
-        vo_[i][k] = vo[k];
-      }
-    }
-  }
-  // inward pass
-  S b_om[3], b_omD[3], b_vD[3], b_wc[3], b_vo[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b_om[k] = b_omD[k] = b_vD[k] = b_wc[k] = b_vo[k] = S{};
-#pragma unroll 1
-  for (int i = NB - 1; i >= 0; --i) {
-    const bool moving = i < NB - 1;
-    // what the parent left (the base: at rest, accelerating against gravity)
-    S om_p[3], omD_p[3], vD_p[3];
-    SR wc_p[3], vo_p[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (i > 0) {
-        om_p[k] = om_[i - 1][k];
-        omD_p[k] = omD_[i - 1][k];
-        vD_p[k] = vD_[i - 1][k];
-        wc_p[k] = wc_[i - 1][k];
-        vo_p[k] = vo_[i - 1][k];
-      } else {
-        om_p[k] = S{};
-        omD_p[k] = S{};
-        vD_p[k] = S{} + dy->vd0[k];
-        wc_p[k] = SR{};
-        vo_p[k] = SR{};
-      }
-    }
-    SR Rp[9];
-    if (moving) {
-      joint_rotation(dy->R0[i], dy->axis[i], sj[i], cj[i], Rp);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rp[k] = SR{} + dy->R0[i][k];
-    }
-    const double* cm = dy->com[i];
-    const double* r = dy->xyz[i];
-    const double m = dy->mass[i];
-    S omi[3], omDi[3], vDi[3];
-    SR wci[3], voi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      omi[k] = om_[i][k];
-      omDi[k] = omD_[i][k];
-      vDi[k] = vD_[i][k];
-      wci[k] = wc_[i][k];
-      voi[k] = vo_[i][k];
-    }
-    // local term f_i . vc_i + n_i . wc_i
-    {
-      S t1[3], t2[3], t3[3], fi[3], Io[3], IoD[3], ni[3];
-      crossT(omDi, cm, t1);
-      crossT(omi, cm, t2);
-      crossT(omi, t2, t3);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) fi[k] = m * (vDi[k] + t1[k] + t3[k]);
-      mvT(dy->inertia[i], omi, Io);
-      mvT(dy->inertia[i], omDi, IoD);
-      crossT(omi, Io, t1);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ni[k] = IoD[k] + t1[k];
-      SR tw[3], vci[3];
-      crossT(wci, cm, tw);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) vci[k] = voi[k] + tw[k];
-      S cf[3];
-      crossT(cm, fi, cf);
-      SR cv[3], Itw[3];
-      crossT(cm, vci, cv);
-      mTvT(dy->inertia[i], wci, Itw);
-      const S oc = dotT(omi, cm), ov = dotT(omi, vci);
-      const SR cvv = dotT(cm, vci);
-      S wxo[3], Itwo[3], Ixw[3];
-      crossT(wci, omi, wxo);
-      mTvT(dy->inertia[i], wxo, Itwo);
-      crossT(Io, wci, Ixw);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_vo[k] = b_vo[k] + fi[k];
-        b_wc[k] = b_wc[k] + cf[k] + ni[k];
-        b_vD[k] = b_vD[k] + m * vci[k];
-        b_omD[k] = b_omD[k] + m * cv[k] + Itw[k];
-        b_om[k] = b_om[k] + m * (vci[k] * oc + cm[k] * ov - 2.0 * (omi[k] * cvv)) + Itwo[k] + Ixw[k];
-      }
-    }
-    // through the step of body i
-    S b_omp[3];
-    if (moving) {
-      SR a[3];
-      S omp[3], omDp[3];
-      SR wcp[3];
-      mTvT(Rp, dy->axis[i], a);
-      mTvT(Rp, om_p, omp);
-      mTvT(Rp, omD_p, omDp);
-      mTvT(Rp, wc_p, wcp);
-      const S qdi = qd[i];
-      S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-      S x1[3], x2[3], b_aq[3], b_a[3];
-      crossT(aq, b_omD, x1);
-      crossT(b_omD, omp, x2);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_omp[k] = b_om[k] + x1[k];
-        b_aq[k] = b_om[k] + x2[k];
-        b_a[k] = b_aq[k] * qdi + b_omD[k] * qdd[i] + b_wc[k] * c[i];
-      }
-      gqd[i] = dotT(b_aq, a);
-      gqdd[i] = dotT(b_omD, a);
-      S s1[3], s2[3], s3[3], s4[3], s5[3], s6[3];
-      crossT(omp, b_omp, s1);
-      crossT(omDp, b_omD, s2);
-      crossT(wcp, b_wc, s3);
-      crossT(a, b_a, s4);
-      crossT(vDi, b_vD, s5);
-      crossT(voi, b_vo, s6);
-      S sw[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) sw[k] = s1[k] + s2[k] + s3[k] + s4[k] + s5[k] + s6[k];
-      gq[i] = -dotT(sw, dy->axis[i]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) b_omp[k] = b_om[k];
-    }
-    if (i > 0) {
-      S b_acc[3], b_w[3], Ro[3], RoD[3], Rw[3], x1[3], x2[3];
-      mvT(Rp, b_vD, b_acc);
-      mvT(Rp, b_vo, b_w);
-      mvT(Rp, b_omp, Ro);
-      mvT(Rp, b_omD, RoD);
-      mvT(Rp, b_wc, Rw);
-      crossT(r, b_acc, x1);
-      crossT(r, b_w, x2);
-      const S opr = dotT(om_p, r), opb = dotT(om_p, b_acc), rb = dotT(r, b_acc);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_om[k] = Ro[k] + b_acc[k] * opr + r[k] * opb - 2.0 * (om_p[k] * rb);
-        b_omD[k] = RoD[k] + x1[k];
-        b_vD[k] = b_acc[k];
-        b_wc[k] = Rw[k] + x2[k];
-        b_vo[k] = b_w[k];
-      }
-    }
-  }
-}
-
-// The same adjoint without per-body arrays (round 4).  rnea_ctau_grad keeps what every body left to its child -- 8 x (om, omD, vD, wc, vo, sin, cos) of
-// dual numbers, 2.7 KB per lane, plus the lane-indexed inputs and outputs: 3.7 KB of scratch per lane at one wavefront per SIMD, which is what
-// k_tq_curv spent its time on.  The outward recursion is invertible: from the state of body i and its joint, the state of the parent follows
-// (om_p = Rp (om_i - a dq_i), ...), so the inward pass rebuilds each parent on the way and stores nothing (~300 more instructions per body, no memory).
-// Inputs come from LDS by the loop counter: zs = the unit's (q | dq | ddq | c) at 0, 8, 16, 24; lane j seeds joint j.  sink(i, gq_i, gqd_i, gqdd_i).
-template <class S>
-struct CtSeed;
-template <>
-struct CtSeed<Dual2> {
-  static OH_DEV DualR q(double v, double one) { return {v, one}; }
-  static OH_DEV Dual2 qd(double v, double one) { return {v, 0.0, one}; }
-};
-template <>
-struct CtSeed<double> {
-  static OH_DEV double q(double v, double) { return v; }
-  static OH_DEV double qd(double v, double) { return v; }
-};
-template <int NB, class S, class SR, class Sink>
-OH_DEV void rnea_ctau_grad_inv(const oh_dynamics* __restrict__ dy, const double* zs, const int j, Sink&& sink) {
-  S om[3], omD[3], vD[3];
-  SR wc[3], vo[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    om[k] = S{};
-    omD[k] = S{};
-    vD[k] = S{} + dy->vd0[k];
-    wc[k] = SR{};
-    vo[k] = SR{};
-  }
-  // outward: only the state of the last body survives
-#pragma unroll 1
-  for (int i = 0; i < NB; ++i) {
-    const bool moving = i < NB - 1;
-    S t1[3], t2[3], t3[3], acc[3];
-    SR w[3], tw[3];
-    crossT(omD, dy->xyz[i], t1);
-    crossT(om, dy->xyz[i], t2);
-    crossT(om, t2, t3);
-    crossT(wc, dy->xyz[i], tw);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      acc[k] = vD[k] + t1[k] + t3[k];
-      w[k] = vo[k] + tw[k];
-    }
-    SR Rp[9];
-    if (moving) {
-      SR sj, cj;
-      sincosT(CtSeed<S>::q(zs[i], i == j ? 1.0 : 0.0), &sj, &cj);
-      joint_rotation(dy->R0[i], dy->axis[i], sj, cj, Rp);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rp[k] = SR{} + dy->R0[i][k];
-    }
-    S omp[3], omDp[3];
-    SR wcp[3];
-    mTvT(Rp, om, omp);
-    mTvT(Rp, omD, omDp);
-    mTvT(Rp, wc, wcp);
-    if (moving) {
-      SR a[3];
-      mTvT(Rp, dy->axis[i], a);
-      const S qdi = CtSeed<S>::qd(zs[8 + i], i == j ? 1.0 : 0.0);
-      const double qddi = zs[16 + i], ci = zs[24 + i];
-      S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-      S cr[3];
-      crossT(omp, aq, cr);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        om[k] = omp[k] + aq[k];
-        omD[k] = omDp[k] + cr[k] + a[k] * qddi;
-        wc[k] = wcp[k] + a[k] * ci;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        om[k] = omp[k];
-        omD[k] = omDp[k];
-        wc[k] = wcp[k];
-      }
-    }
-    S vDi[3];
-    SR voi[3];
-    mTvT(Rp, acc, vDi);
-    mTvT(Rp, w, voi);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      vD[k] = vDi[k];
-      vo[k] = voi[k];
-    }
-  }
-  // inward: (om, omD, vD, wc, vo) is the state of body i; its parent is rebuilt from it
-  S b_om[3], b_omD[3], b_vD[3], b_wc[3], b_vo[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b_om[k] = b_omD[k] = b_vD[k] = b_wc[k] = b_vo[k] = S{};
-#pragma unroll 1
-  for (int i = NB - 1; i >= 0; --i) {
-    const bool moving = i < NB - 1;
-    SR Rp[9], a[3];
-    S qdi = S{};
-    double qddi = 0.0, ci = 0.0;
-    if (moving) {
-      SR sj, cj;
-      sincosT(CtSeed<S>::q(zs[i], i == j ? 1.0 : 0.0), &sj, &cj);
-      joint_rotation(dy->R0[i], dy->axis[i], sj, cj, Rp);
-      mTvT(Rp, dy->axis[i], a);
-      qdi = CtSeed<S>::qd(zs[8 + i], i == j ? 1.0 : 0.0);
-      qddi = zs[16 + i];
-      ci = zs[24 + i];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rp[k] = SR{} + dy->R0[i][k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a[k] = SR{};
-    }
-    const double* cm = dy->com[i];
-    const double* r = dy->xyz[i];
-    const double m = dy->mass[i];
-    // the parent's state (the base: at rest, accelerating against gravity), and what it looked like in the frame of body i
-    S om_p[3], omD_p[3], vD_p[3], omp[3], omDp[3];
-    SR wc_p[3], vo_p[3], wcp[3];
-    {
-      S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) omp[k] = om[k] - aq[k];
-      S cr[3];
-      crossT(omp, aq, cr);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        omDp[k] = omD[k] - cr[k] - a[k] * qddi;
-        wcp[k] = wc[k] - a[k] * ci;
-      }
-      if (i > 0) {
-        S accp[3], t1[3], t2[3], t3[3];
-        SR wp[3], tw[3];
-        mvT(Rp, omp, om_p);
-        mvT(Rp, omDp, omD_p);
-        mvT(Rp, wcp, wc_p);
-        mvT(Rp, vD, accp);
-        mvT(Rp, vo, wp);
-        crossT(omD_p, r, t1);
-        crossT(om_p, r, t2);
-        crossT(om_p, t2, t3);
-        crossT(wc_p, r, tw);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          vD_p[k] = accp[k] - t1[k] - t3[k];
-          vo_p[k] = wp[k] - tw[k];
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          om_p[k] = S{};
-          omD_p[k] = S{};
-          vD_p[k] = S{} + dy->vd0[k];
-          wc_p[k] = SR{};
-          vo_p[k] = SR{};
-          omp[k] = S{};    // exactly, not up to the rounding of the inversion
-          omDp[k] = S{};
-          wcp[k] = SR{};
-        }
-      }
-    }
-    // local term f_i . vc_i + n_i . wc_i
-    {
-      S t1[3], t2[3], t3[3], fi[3], Io[3], IoD[3], ni[3];
-      crossT(omD, cm, t1);
-      crossT(om, cm, t2);
-      crossT(om, t2, t3);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) fi[k] = m * (vD[k] + t1[k] + t3[k]);
-      mvT(dy->inertia[i], om, Io);
-      mvT(dy->inertia[i], omD, IoD);
-      crossT(om, Io, t1);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ni[k] = IoD[k] + t1[k];
-      SR tw[3], vci[3];
-      crossT(wc, cm, tw);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) vci[k] = vo[k] + tw[k];
-      S cf[3];
-      crossT(cm, fi, cf);
-      SR cv[3], Itw[3];
-      crossT(cm, vci, cv);
-      mTvT(dy->inertia[i], wc, Itw);
-      const S oc = dotT(om, cm), ov = dotT(om, vci);
-      const SR cvv = dotT(cm, vci);
-      S wxo[3], Itwo[3], Ixw[3];
-      crossT(wc, om, wxo);
-      mTvT(dy->inertia[i], wxo, Itwo);
-      crossT(Io, wc, Ixw);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_vo[k] = b_vo[k] + fi[k];
-        b_wc[k] = b_wc[k] + cf[k] + ni[k];
-        b_vD[k] = b_vD[k] + m * vci[k];
-        b_omD[k] = b_omD[k] + m * cv[k] + Itw[k];
-        b_om[k] = b_om[k] + m * (vci[k] * oc + cm[k] * ov - 2.0 * (om[k] * cvv)) + Itwo[k] + Ixw[k];
-      }
-    }
-    // through the step of body i
-    S b_omp[3];
-    if (moving) {
-      S aq[3] = {a[0] * qdi, a[1] * qdi, a[2] * qdi};
-      S x1[3], x2[3], b_aq[3], b_a[3];
-      crossT(aq, b_omD, x1);
-      crossT(b_omD, omp, x2);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_omp[k] = b_om[k] + x1[k];
-        b_aq[k] = b_om[k] + x2[k];
-        b_a[k] = b_aq[k] * qdi + b_omD[k] * qddi + b_wc[k] * ci;
-      }
-      const S gqd_i = dotT(b_aq, a);
-      const S gqdd_i = dotT(b_omD, a);
-      S s1[3], s2[3], s3[3], s4[3], s5[3], s6[3];
-      crossT(omp, b_omp, s1);
-      crossT(omDp, b_omD, s2);
-      crossT(wcp, b_wc, s3);
-      crossT(a, b_a, s4);
-      crossT(vD, b_vD, s5);
-      crossT(vo, b_vo, s6);
-      S sw[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) sw[k] = s1[k] + s2[k] + s3[k] + s4[k] + s5[k] + s6[k];
-      sink(i, -dotT(sw, dy->axis[i]), gqd_i, gqdd_i);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) b_omp[k] = b_om[k];
-    }
-    if (i > 0) {
-      S b_acc[3], b_w[3], Ro[3], RoD[3], Rw[3], x1[3], x2[3];
-      mvT(Rp, b_vD, b_acc);
-      mvT(Rp, b_vo, b_w);
-      mvT(Rp, b_omp, Ro);
-      mvT(Rp, b_omD, RoD);
-      mvT(Rp, b_wc, Rw);
-      crossT(r, b_acc, x1);
-      crossT(r, b_w, x2);
-      const S opr = dotT(om_p, r), opb = dotT(om_p, b_acc), rb = dotT(r, b_acc);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b_om[k] = Ro[k] + b_acc[k] * opr + r[k] * opb - 2.0 * (om_p[k] * rb);
-        b_omD[k] = RoD[k] + x1[k];
-        b_vD[k] = b_acc[k];
-        b_wc[k] = Rw[k] + x2[k];
-        b_vo[k] = b_w[k];
-        om[k] = om_p[k];
-        omD[k] = omD_p[k];
-        vD[k] = vD_p[k];
-        wc[k] = wc_p[k];
-        vo[k] = vo_p[k];
-      }
-    }
-  }
-}
-
-// sum_i c_i d^2 tau_i / d (q, qd, qdd)^2 (what the reference obtains as ddh by AD of the CasADi graph, optimization.py:8-24): one lane per
-// (sample, joint); q, qd, qdd, c [n][N] -> H [n][3 N][3 N] row-major.  Lane j writes rows j and N + j and, by symmetry, column j of the ddq rows.
-template <int N>
-__global__ __launch_bounds__(64) void k_rnea_hess(const oh_dynamics* __restrict__ dy, const int n, const double* __restrict__ q, const double* __restrict__ qd,
-                                                  const double* __restrict__ qdd, const double* __restrict__ c, double* __restrict__ H) {
-  constexpr int NZ = 3 * N, UPW = 64 / N;
-  __shared__ double zs_l[UPW][32];
-  const int lane = threadIdx.x;
-  int ul = lane / N, j = lane - ul * N;
-  const bool lane_ok = ul < UPW;
-  if (!lane_ok) {
-    ul = UPW - 1;
-    j = N - 1;
-  }
-  long long u = (long long)blockIdx.x * UPW + ul;
-  const bool active = lane_ok && u < n;
-  if (u >= n) u = n - 1;
-  if (lane_ok) {
-    zs_l[ul][j] = q[u * N + j];
-    zs_l[ul][8 + j] = qd[u * N + j];
-    zs_l[ul][16 + j] = qdd[u * N + j];
-    zs_l[ul][24 + j] = c[u * N + j];
-  }
-  __syncthreads();
-  double* Hu = H + (size_t)u * NZ * NZ;
-  rnea_ctau_grad_inv<N + 1, Dual2, DualR>(dy, zs_l[ul], j, [&](const int k, const Dual2 gq, const Dual2 gqd, const Dual2 gqdd) {
-    if (!active) return;
-    Hu[j * NZ + k] = gq.d0;
-    Hu[j * NZ + N + k] = gqd.d0;
-    Hu[j * NZ + 2 * N + k] = gqdd.d0;
-    Hu[(N + j) * NZ + k] = gq.d1;
-    Hu[(N + j) * NZ + N + k] = gqd.d1;
-    Hu[(N + j) * NZ + 2 * N + k] = 0.0;
-    Hu[(2 * N + k) * NZ + j] = gqdd.d0;
-    Hu[(2 * N + k) * NZ + N + j] = 0.0;
-    Hu[(2 * N + k) * NZ + 2 * N + j] = 0.0;
-  });
-}
+using namespace oh_dyn;
 
 OH_DEV size_t xs_off(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return (((size_t)slot * D.B + b) * T + t) * TQ_XS; }
 OH_DEV size_t st_off(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return (((size_t)slot * D.B + b) * T + t) * TQ_SD; }
@@ -1355,7 +133,7 @@ OH_DEV TqRow tq_row(const double s, const double s_old, const double lam_old, co
   return r;
 }
 
-// One lane per (instance, knot, JOINT): 9 units x 7 joints per wavefront.  Lane j runs the reference's Newton-Euler recursion once on (DualR, Dual3)
+// One lane per (instance, knot, JOINT): 9 units x 7 joints per wavefront.  Lane j runs the reference's Newton-Euler recursion once on (Jet<1>, Jet<3>)
 // scalars seeded with q_j, dq_j and ddq_j (d tau / d z is the tangent output: the derivative of the literal recursion by construction), so it ends up
 // with columns j, N + j and 2 N + j of d tau / d z; the chain walk for p_link adds column j of its Jacobian.  The columns meet in LDS and every lane
 // writes ITS THREE columns of the packed stage block  J^T diag(2 w_tau + Sigma) J + 2 w_p Jp^T Jp + ...,  of the two gradients (cost, barrier per unit
@@ -1364,7 +142,7 @@ template <int N, bool VEL = false, bool IDS = true>
 __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuffers D) {
   constexpr int NZ = 3 * N;
   constexpr int UPW = 64 / N;  // units per wavefront (9)
-  // A unit's LDS.  Closed-form path: IdsWs<N> (277 doubles: two blocks per SIMD).  Dual-number path: tile [N + 3][NZ + 1], row coefficients, (q|dq|ddq).
+  // A unit's LDS.  Closed-form path: IdsWs<N> (277 doubles: two blocks per SIMD).  Jet path: tile [N + 3][NZ + 1], row coefficients, (q|dq|ddq).
   using L = IdsWs<N>;
   constexpr int TW = IDS ? L::TW : NZ + 1;                  // pitch of rows 0 .. N-1 of the tile (d tau / dz)
   constexpr int JP = IDS ? L::JP : N * (NZ + 1);            // rows of d p_link / dz, pitch NZ + 1
@@ -1415,16 +193,16 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
   if constexpr (IDS) {
     tvj = rnea_idsva<N>(D.dyn, tl, j, lane_ok);
   } else {
-    Dual3 tau[N];
-    rnea_vw3<N + 1, Dual3>(D.dyn, qs_u, j, tau);
+    Jet<3> tau[N];
+    rnea_vw3<N + 1, Jet<3>>(D.dyn, qs_u, j, tau);
     tvj = 0.0;
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       tvj = (i == j) ? tau[i].v : tvj;
       if (lane_ok) {
-        tl[i * TW + j] = tau[i].d0;
-        tl[i * TW + N + j] = tau[i].d1;
-        tl[i * TW + 2 * N + j] = tau[i].d2;
+        tl[i * TW + j] = tau[i].d[0];
+        tl[i * TW + N + j] = tau[i].d[1];
+        tl[i * TW + 2 * N + j] = tau[i].d[2];
       }
     }
   }
@@ -1605,7 +383,7 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
 //     sum_i cH_i d^2 tau_i / dz^2,  cH = 2 w_tau tau - lam_lo + lam_up   (the multiplier of the dynamics row TAU_i - rnea_i = 0 at a stationary point)
 //   + 2 w_p sum_k r_k d^2 p_k / dq^2,  d^2 p / dq_a dq_b = z_b x (z_a x (e - o_a)) for b <= a
 // to the stage block k_tq_eval3 has just written.  One lane per (instance, knot, joint) again: lane j runs the hand-written adjoint of the recursion on
-// (DualR, Dual2) scalars seeded with q_j and dq_j, which yields rows q_j and dq_j of the first term; every packed entry is owned by exactly one lane.
+// (Jet<1>, Jet<2>) scalars seeded with q_j and dq_j, which yields rows q_j and dq_j of the first term; every packed entry is owned by exactly one lane.
 // Round 5: the term also goes to a record of its own (D.hc), and an instance computes it afresh only at every
 // (curv_lag + 1)-th evaluation (D.curv: 1 compute here, 2 k_tq_eval3 adds the stored term as it writes the block and this kernel skips the instance).  Near the solution the term moves little between steps: with a lag of 3 the
 // port takes 24.70 instead of 24.64 steps on 256 instances and computes the term 3.2 times per solve instead of 11.3 (oracle/torque_ipm.py, HISTORY).
@@ -1683,23 +461,23 @@ __global__ __launch_bounds__(64, OH_TQ_CURV_WAVES) void k_tq_curv(TqParams P, Tq
         if (!direct) hc[j * (j + 1) / 2 + k] = v;
       }
   }
-  rnea_ctau_grad_inv<N + 1, Dual2, DualR>(D.dyn, zs_l[ul], j, [&](const int k, const Dual2 gq, const Dual2 gqd, const Dual2 gqdd) {
+  rnea_ctau_grad_inv<N + 1, Jet<2>, Jet<1>>(D.dyn, zs_l[ul], j, [&](const int k, const Jet<2> gq, const Jet<2> gqd, const Jet<2> gqdd) {
     if (!comp) return;
     // onto the stage block ...
     if (k <= j) {
-      sr[j * (j + 1) / 2 + k] += gq.d0;
-      sr[(N + j) * (N + j + 1) / 2 + N + k] += gqd.d1;
+      sr[j * (j + 1) / 2 + k] += gq.d[0];
+      sr[(N + j) * (N + j + 1) / 2 + N + k] += gqd.d[1];
     }
-    sr[(N + j) * (N + j + 1) / 2 + k] += gq.d1;
-    sr[(2 * N + k) * (2 * N + k + 1) / 2 + j] += gqdd.d0;
+    sr[(N + j) * (N + j + 1) / 2 + k] += gq.d[1];
+    sr[(2 * N + k) * (2 * N + k + 1) / 2 + j] += gqdd.d[0];
     if (direct) return;  // curv_lag = 0: nothing is kept
     // ... and into the record the next evaluations of this instance add instead (k_tq_eval3)
     if (k <= j) {  // rows q_j and dq_j, columns up to the diagonal
-      hc[j * (j + 1) / 2 + k] += gq.d0;
-      hc[(N + j) * (N + j + 1) / 2 + N + k] = gqd.d1;
+      hc[j * (j + 1) / 2 + k] += gq.d[0];
+      hc[(N + j) * (N + j + 1) / 2 + N + k] = gqd.d[1];
     }
-    hc[(N + j) * (N + j + 1) / 2 + k] = gq.d1;             // (dq_j, q_k)
-    hc[(2 * N + k) * (2 * N + k + 1) / 2 + j] = gqdd.d0;   // (ddq_k, q_j)
+    hc[(N + j) * (N + j + 1) / 2 + k] = gq.d[1];             // (dq_j, q_k)
+    hc[(2 * N + k) * (2 * N + k + 1) / 2 + j] = gqdd.d[0];   // (ddq_k, q_j)
   });
   }
 }
@@ -2228,28 +1006,6 @@ __global__ __launch_bounds__(64) void k_tq_finalize(TqParams P, TqBuffers D, dou
     case 7: C(7); break;     \
     default: return false;   \
   }
-bool oh_launch_rnea_jac(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, double* J) {
-#define OH_RJ(NN)                                                                                                                         \
-  case NN + 1:                                                                                                                            \
-    hipLaunchKernelGGL(k_rnea_jac<NN>, dim3((unsigned)((n + (64 / (3 * NN)) - 1) / (64 / (3 * NN)))), dim3(64), 0, s, d_dyn, n, q, qd, qdd, J); \
-    return true;
-  switch (nbodies) {
-    OH_RJ(1) OH_RJ(2) OH_RJ(3) OH_RJ(4) OH_RJ(5) OH_RJ(6) OH_RJ(7) OH_RJ(8)
-    default: return false;
-  }
-#undef OH_RJ
-}
-bool oh_launch_rnea_hess(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, const double* c, double* H) {
-#define OH_RH(NN)                                                                                                                       \
-  case NN + 1:                                                                                                                          \
-    hipLaunchKernelGGL(k_rnea_hess<NN>, dim3((unsigned)((n + (64 / NN) - 1) / (64 / NN))), dim3(64), 0, s, d_dyn, n, q, qd, qdd, c, H);  \
-    return true;
-  switch (nbodies) {
-    OH_RH(1) OH_RH(2) OH_RH(3) OH_RH(4) OH_RH(5) OH_RH(6) OH_RH(7) OH_RH(8)
-    default: return false;
-  }
-#undef OH_RH
-}
 bool oh_launch_tq_setup(hipStream_t s, const TqParams& P, const TqBuffers& D, const double* x0, const double* p) {
 #define C(NN) hipLaunchKernelGGL(k_tq_setup<NN>, dim3((D.B + 63) / 64), dim3(64), 0, s, P, D, x0, p)
   OH_TQ_DISPATCH(P.N, C)

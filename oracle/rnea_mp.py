@@ -2,7 +2,7 @@
 significant digits, from the numpy restatement oracle/torque.py:rnea_batch and its RneaTables.
 
 Derivatives come from finite differences in the high precision, so nothing here shares code with the kernels' dual numbers, their hand-written
-adjoint (csrc/oh_torque.hip:rnea_ctau_grad_inv) or the complex-step oracle (oracle/torque.py:rnea_jacobian, rnea_ctau_hessian, which
+adjoint (csrc/oh_rnea.h:rnea_ctau_grad_inv) or the complex-step oracle (oracle/torque.py:rnea_jacobian, rnea_ctau_hessian, which
 differentiate rnea_batch and a hand-written numpy adjoint):
   J = d tau / d (q, qd, qdd)   central differences, h = 1e-15: truncation ~ h^2 = 1e-30, rounding ~ 1e-50 / h = 1e-35;
   H = d^2 (c^T tau) / dz^2     4-point mixed (and 3-point diagonal) differences, h = 1e-12: truncation ~ 1e-24, rounding ~ 1e-50 / h^2 = 1e-26.

@@ -367,7 +367,7 @@ def solve_torque_lm(prob: TorqueProblem, qc, dqc, goal, U0=None, max_iter=300, t
 # vector c.  By the principle of virtual work  c^T tau = sum_b f_b . v_b(c) + n_b . w_b(c):  the inertial wrench of every body paired with the
 # velocity the joint rates c would give it.  Both factors come out of ONE outward recursion over the bodies (the reference's forward pass next to a
 # twist propagation), so the gradient is ONE inward adjoint recursion, written out by hand below; the Hessian is that gradient differentiated once
-# more -- complex steps here, dual numbers in csrc/oh_torque.hip:rnea_ctau_grad -- and nothing is differenced.
+# more -- complex steps here, dual numbers in csrc/oh_rnea.h:rnea_ctau_grad_inv -- and nothing is differenced.
 def rnea_virtual_work(tb: RneaTables, q, qd, qdd, c):
     """c^T rnea(q, qd, qdd) by the outward recursion alone (checked against rnea_batch in tests/test_torque_cpu.py)."""
     return _vw_forward(tb, np.asarray(q), np.asarray(qd), np.asarray(qdd), np.asarray(c))[0]
@@ -477,7 +477,7 @@ def rnea_ctau_hessian(tb: RneaTables, q, qd, qdd, c, h=1e-30):
     return 0.5 * (H + np.swapaxes(H, -1, -2))
 
 
-# ---- d tau / d (q, dq, ddq) in closed form (round 4; csrc/oh_torque.hip:rnea_idsva is this, lane by lane) ------------------------------------------
+# ---- d tau / d (q, dq, ddq) in closed form (round 4; csrc/oh_rnea.h:rnea_idsva is this, lane by lane) ------------------------------------------
 # World-frame spatial vectors (w, v_O) / (n_O, f) about the world origin (Featherstone 2008).  S_l = (z_l, o_l x z_l), v_b = sum S_l dq_l,
 # a_b = a_0 + sum (S_l ddq_l + v_l x S_l dq_l), W_b = I_b a_b + v_b x* I_b v_b, tau_k = S_k . sum_{b >= k} W_b  -- what RobotModel.rnea computes
 # (models.py:1819-1880) -- and, by the product rule with dS_l/dq_m = S_m x S_l, dI_b/dq_m = S_m x* I_b - I_b S_m x and the Jacobi identity,

@@ -262,17 +262,21 @@ def test_rnea_device_inside_nan_guards(robot):
                 b.free()
 
 
-def test_every_instantiation_is_run(kins):
+def test_every_launcher_instantiation_is_run(kins):
     """The launchers' instantiations, read from the sources, are exactly INSTANTIATIONS, and each one's robot has the chain length it needs: a new
     instantiation without a robot here fails."""
-    src = os.path.join(ROOT, "optas_amd", "csrc")
-    kern = open(os.path.join(src, "oh_kernels.hip")).read()
-    torq = open(os.path.join(src, "oh_torque.hip")).read()
-    found = {f"k_rnea<{m}>" for m in re.findall(r"hipLaunchKernelGGL\(k_rnea<(\d+)>", kern)}
-    launcher = lambda name: torq[torq.index(f"bool oh_launch_{name}("):]
-    rj = re.search(r"switch \(nbodies\) \{\s*((?:OH_RJ\(\d+\)\s*)+)", launcher("rnea_jac")).group(1)
-    rh = re.search(r"switch \(nbodies\) \{\s*((?:OH_RH\(\d+\)\s*)+)", launcher("rnea_hess")).group(1)
-    found |= {f"k_rnea_jac<{m}>" for m in re.findall(r"\d+", rj)} | {f"k_rnea_hess<{m}>" for m in re.findall(r"\d+", rh)}
+    src = open(os.path.join(ROOT, "optas_amd", "csrc", "oh_rnea.hip")).read()
+    macro = src[src.index("#define OH_RNEA_DISPATCH("):]
+    macro = macro[: macro.index("default: return false;")]
+    cases = [(int(nb), int(nj)) for nb, nj in re.findall(r"case (\d+): C\((\d+)\); break;", macro)]
+    assert cases and all(nb == nj + 1 for nb, nj in cases), cases
+    found = set()
+    for name in ("rnea", "rnea_jac", "rnea_hess"):
+        launcher = src[src.index(f"bool oh_launch_{name}("):]
+        launcher = launcher[: launcher.index("\n}\n")]
+        kernel, extra = re.search(r"#define C\(NN\) hipLaunchKernelGGL\((k_\w+)<NN( \+ 1)?>", launcher).groups()
+        assert kernel == f"k_{name}" and "OH_RNEA_DISPATCH(nbodies, C)" in launcher, launcher
+        found |= {f"{kernel}<{nj + (1 if extra else 0)}>" for _, nj in cases}
     assert found == set(INSTANTIATIONS), sorted(found ^ set(INSTANTIATIONS))
     for name, tag in INSTANTIATIONS.items():
         assert tag in TAGS

@@ -73,7 +73,7 @@ def test_complex_step_jacobian_against_differences_and_mass_matrix_identities(me
 
 
 def test_closed_form_jacobian_equals_the_derivative_of_the_literal_recursion(med7):
-    """oracle/torque.py:rnea_jacobian_spatial (the numpy statement of csrc/oh_torque.hip:rnea_idsva) against complex-step differentiation of the
+    """oracle/torque.py:rnea_jacobian_spatial (the numpy statement of csrc/oh_rnea.h:rnea_idsva) against complex-step differentiation of the
     literal recursion: 1e-12 relative, torques included; and on a second robot (tester_robot_revolute: other axes, other inertias)."""
     rng = np.random.default_rng(SEED + 21)
     for rob in (med7, OracleRobot(os.path.join(GOLDEN, "tester_robot_revolute.kin.json"))):
