@@ -36,15 +36,13 @@ static int fail(int code, const std::string& msg) {
     }                                                                                                  \
   } while (0)
 
-static thread_local OhLaunchOpts g_launch_opts;
-OhLaunchOpts& oh_launch_opts() { return g_launch_opts; }
 #define OH_PINNED_STAGE_BYTES (256 * 1024)
 
 // Scheduling state of a handle, set by name through the field-backed options (FIELD_OPTS): a peer takes it over in one assignment.
 struct Sched {
   int compaction = 1;
   int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
-  int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see solve_device)
+  int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see locked_loop)
   int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
   int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
   int compact_sort = 1;      // order the survivors of a compaction by progress (k_scan_*)
@@ -188,13 +186,9 @@ extern "C" int oh_abi_version(void) { return OH_ABI_VERSION; }
 // Until round 4 forty OH_* environment variables were read inside the library: two handles of one process could not differ and a result
 // depended on the caller's environment.  Now every knob is an option of ONE handle, set by name; the single environment hook left is
 // OH_DEBUG_OPTIONS ("name=value,name=value"), applied to every handle when it is created (tools/, A/B runs).
-static double optv(const oh_handle* h, const char* name, double dflt) {
-  auto it = h->opt.find(name);
-  return it == h->opt.end() ? dflt : it->second;
-}
 struct OptDoc { const char* name; double dflt; };
-// map-backed options and their defaults (field-backed ones: FIELD_OPTS)
-static const OptDoc OPT_TABLE[] = {
+// map-backed options and their defaults, the one place a default is written (field-backed ones: FIELD_OPTS; batch_invariant: set_option_impl)
+static constexpr OptDoc OPT_TABLE[] = {
     {"check_every", 1},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
     {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30},
     {"tape_wave", 1},          {"tape_lbfgs", -1},       {"tape_wave_nt", 256},  {"tape_wave_regs", -1}, {"tape_wave_hist", -1},  {"tq_stall", 25},
@@ -202,6 +196,32 @@ static const OptDoc OPT_TABLE[] = {
     {"tq_rebuild", 0.9},         {"compact_move_all", 1},  {"tq_curv_late", 1.0},  {"tq_kappa_eps", 10.0}, {"tq_max_back", 3},     {"tq_mu_dec", 1.0 / 3.0},     {"tq_ls_curv", 1},   {"tq_mu_dec_warm", 0.1}, {"tq_curv_lag", 3},
     {"tol", 0},                {"pipe", 1},               {"pipe_chunk", 32768},                {"invariant_compact_frac", 0.65}, {"invariant_split", 1}, {"invariant_move_slim", 1}, {"invariant_move_live", 1},
 };
+// row of a map-backed option in OPT_TABLE (-1: none)
+static constexpr int opt_row(const char* name) {
+  for (int i = 0; i < (int)(sizeof(OPT_TABLE) / sizeof(OPT_TABLE[0])); ++i) {
+    int k = 0;
+    while (OPT_TABLE[i].name[k] && OPT_TABLE[i].name[k] == name[k]) ++k;
+    if (OPT_TABLE[i].name[k] == name[k]) return i;
+  }
+  return -1;
+}
+template <int ROW>
+static constexpr int known_opt() {
+  static_assert(ROW >= 0, "optv: the option is not in OPT_TABLE");
+  return ROW;
+}
+// an option of a handle: as set by name, else its default in the table
+static double opt_value(const oh_handle* h, const OptDoc& d) {
+  const auto it = h->opt.find(d.name);
+  return it == h->opt.end() ? d.dflt : it->second;
+}
+// optv(h, "name"): a map-backed option of a handle; a name that is not in OPT_TABLE does not compile
+#define optv(h, name) opt_value(h, OPT_TABLE[known_opt<opt_row(name)>()])
+// option batch_invariant: kept in the map but outside the table (set_option_impl parks the scheduling fields it overrides); 0 until set
+static double batch_invariant(const oh_handle* h) {
+  const auto it = h->opt.find("batch_invariant");
+  return it == h->opt.end() ? 0.0 : it->second;
+}
 // field-backed options: the one list of name -> field of Sched that oh_set_option and oh_get_option read (a flag stores v != 0)
 struct FieldOpt {
   const char* name;
@@ -235,7 +255,7 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     // (the price: 1.3 x the device time of a 262 144 batch -- 3.0 x before the moving compaction --, and small batches pay launches)
     // (the scheduling fields the option overrides are parked and come back when it is switched off: a threshold the user set earlier is not replaced
     //  by the default -- ADVICE r5)
-    const bool was = optv(h, "batch_invariant", 0.0) != 0.0;
+    const bool was = batch_invariant(h) != 0.0;
     h->opt[name] = v;
     if (v != 0.0 && !was) {
       sc.inv_saved = {sc.compaction ? 1.0 : 0.0, (double)sc.tail_threshold, (double)sc.tail_vel, h->opt.count("free_persist") ? h->opt["free_persist"] : -2.0};
@@ -261,11 +281,11 @@ extern "C" int oh_set_option(oh_handle* h, const char* name, double value) {
 extern "C" int oh_get_option(oh_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_option: null argument");
   const std::string n(name);
-  if (n == "batch_invariant") *value = optv(h, "batch_invariant", 0.0);
+  if (n == "batch_invariant") *value = batch_invariant(h);
   else if (const FieldOpt* f = field_opt(n)) *value = f->get(h->sch);
   else {
     for (const OptDoc& d : OPT_TABLE)
-      if (n == d.name) { *value = optv(h, d.name, d.dflt); return OH_OK; }
+      if (n == d.name) { *value = opt_value(h, d); return OH_OK; }
     return fail(OH_ERR_INVALID, "oh_get_option: unknown option '" + n + "'");
   }
   return OH_OK;
@@ -291,19 +311,6 @@ static int apply_debug_options(oh_handle* h) {
     if (const int rc = set_option_impl(h, item.substr(0, eq), v)) return rc;
   }
   return OH_OK;
-}
-// the launchers' share of the options, for the call that is starting
-static void load_launch_opts(const oh_handle* h) {
-  OhLaunchOpts& o = g_launch_opts;
-  o = OhLaunchOpts{};
-  o.free_bb = (int)optv(h, "free_bb", o.free_bb);
-  o.free_cp_max = (int)optv(h, "free_cp_max", o.free_cp_max);
-  o.pm_wave_max = (int)optv(h, "pm_wave_max", o.pm_wave_max);
-  o.qp_mode = (int)optv(h, "qp_mode", o.qp_mode);
-  o.tape_lds_max = (int)optv(h, "tape_lds_max", o.tape_lds_max);
-  o.tape_wave_nt = (int)optv(h, "tape_wave_nt", o.tape_wave_nt);
-  o.tape_wave_regs = (int)optv(h, "tape_wave_regs", o.tape_wave_regs);
-  o.tape_wave_hist = (int)optv(h, "tape_wave_hist", o.tape_wave_hist);
 }
 // every oh_create*: a fresh handle with the debug options applied (nullptr: a bad OH_DEBUG_OPTIONS, oh_last_error says which)
 static oh_handle* new_handle() {
@@ -511,9 +518,8 @@ extern "C" int oh_tape_compile(const oh_tape_desc* d, size_t* code_bytes, char* 
 static int tape_configure(oh_handle* h) {
   oh_tape_desc d = h->t_desc;
   d.op = h->t_op.data(); d.a = h->t_a.data(); d.b = h->t_b.data(); d.c = h->t_c.data(); d.rows = h->t_rows.empty() ? nullptr : h->t_rows.data();
-  h->TP = tape_params(&d, (int)optv(h, "tape_lbfgs", -1.0));
+  h->TP = tape_params(&d, (int)optv(h, "tape_lbfgs"));
   h->TP.h0 = h->d_tape_h0;  // (a metric handed over before an option rebuilt the evaluator stays)
-  load_launch_opts(h);  // oh_tape_wave_build reads tape_wave_nt / _regs / _hist
   oh_tape_wave_release(&h->tape_wave);
   h->tape_wave = TapeWave{};
   if (h->tape_cap) {  // the work arrays were sized for the other evaluator
@@ -523,9 +529,11 @@ static int tape_configure(oh_handle* h) {
     h->tape_cap = 0;
   }
   int lds_limit = 0;
-  if (optv(h, "tape_wave", 1.0) != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
+  if (optv(h, "tape_wave") != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
     std::string err;
-    if (oh_tape_wave_build(h->TP, d.op, d.a, d.b, d.c, d.rows, (size_t)lds_limit, &h->tape_wave, &err)) return fail(OH_ERR_HIP, ("oh_create_tape: " + err).c_str());
+    if (oh_tape_wave_build(h->TP, d.op, d.a, d.b, d.c, d.rows, (size_t)lds_limit, (int)optv(h, "tape_wave_nt"), (int)optv(h, "tape_wave_regs"),
+                           (int)optv(h, "tape_wave_hist"), &h->tape_wave, &err))
+      return fail(OH_ERR_HIP, ("oh_create_tape: " + err).c_str());
   }
   if (d.jit && !h->tape_wave.ready && !h->tape_jit.fn) {
     std::vector<char> code;
@@ -670,7 +678,7 @@ static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* 
                                (int*)d_status, h->d_tape_mult));
   else if (h->tape_jit.fn)
     HIPCHK(oh_launch_tape_jit(h->stream, h->tape_jit, h->TP, B, h->tape_cap, (const double*)d_x0, (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f,
-                              (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult));
+                              (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult, (int)optv(h, "tape_lds_max")));
   else
     oh_launch_tape_solve(h->stream, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap, (const double*)d_x0,
                          (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult);
@@ -814,7 +822,7 @@ static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     d_p = h->d_qp_rows;
   }
   oh_launch_qp_solve(h->stream, Q, B, h->qp_cap, (const double*)d_x0, (const double*)d_p, h->d_qp_work, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                     (int*)d_iters, (int*)d_status, h->d_qp_mult);
+                     (int*)d_iters, (int*)d_status, h->d_qp_mult, (int)optv(h, "qp_mode"));
   if (h->qp_tape && d_f) oh_launch_qp_add_constant(h->stream, B, (double*)d_f, h->d_qp_f0);
   return finish_solve(h, 1);
 }
@@ -906,21 +914,21 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   P.dt = h->tq.dt; P.w_path = h->tq.w_path; P.w_vel = h->tq.w_vel; P.w_tau = h->tq.w_tau;
   P.tol = h->tq.tol; P.tol_compl = h->tq.tol_compl; P.mu_b0 = mu_b0_warm > 0.0 ? mu_b0_warm : h->tq.mu_barrier0; P.mu0 = h->tq.mu0;
   // interior point: relaxed barrier below theta mu_b; monotone barrier update of Waechter & Biegler (2006, eq. 7) -- IPOPT's constants except theta_mu (1.35 for 1.5: the hardest of 8192 instances needs 127 steps instead of 198) and, round 5, kappa_mu (0.4 for 0.2: tools/gpu_tq_param_sweep.py); exact
-  // curvature of the Lagrangian once the reduced gradient is below curv_from (oracle/torque_ipm.py:solve_torque_ipm has the same defaults)
-  P.theta = 0.01; P.kappa_eps = 10.0; P.kappa_mu = 0.4; P.theta_mu = 1.35; P.curv_from = 0.1; P.curv_late = 1.0; P.curv_after = 3; P.tau_ftb = 0.995; P.max_back = 3; P.stall_max = 25;
-  P.stall_max = (int)optv(h, "tq_stall", P.stall_max);  // options (oh_set_option)
-  P.curv_after = (int)optv(h, "tq_curv_after", P.curv_after);
-  P.tau_ftb = optv(h, "tq_ftb", P.tau_ftb);
-  P.theta_mu = optv(h, "tq_theta_mu", P.theta_mu);
-  P.kappa_mu = optv(h, "tq_kappa_mu", P.kappa_mu);
-  P.curv_from = optv(h, "tq_curv_from", P.curv_from);  // 0: Gauss-Newton blocks throughout (A/B)
-  P.curv_late = optv(h, "tq_curv_late", P.curv_late);
-  P.kappa_eps = optv(h, "tq_kappa_eps", P.kappa_eps);
+  // curvature of the Lagrangian once the reduced gradient is below curv_from (oracle/torque_ipm.py:solve_torque_ipm has the same defaults: OPT_TABLE's)
+  P.theta = 0.01;
+  P.stall_max = (int)optv(h, "tq_stall");
+  P.curv_after = (int)optv(h, "tq_curv_after");
+  P.tau_ftb = optv(h, "tq_ftb");
+  P.theta_mu = optv(h, "tq_theta_mu");
+  P.kappa_mu = optv(h, "tq_kappa_mu");
+  P.curv_from = optv(h, "tq_curv_from");  // 0: Gauss-Newton blocks throughout (A/B)
+  P.curv_late = optv(h, "tq_curv_late");
+  P.kappa_eps = optv(h, "tq_kappa_eps");
   // (a warm-started tick of oh_tq_rollout starts next to its optimum: there the damping comes down faster)
-  P.mu_dec = mu_b0_warm > 0.0 ? optv(h, "tq_mu_dec_warm", 0.1) : optv(h, "tq_mu_dec", 1.0 / 3.0);
-  P.ls_curv = (int)optv(h, "tq_ls_curv", 1);
-  P.curv_lag = (int)optv(h, "tq_curv_lag", 3);
-  P.max_back = (int)optv(h, "tq_max_back", P.max_back);
+  P.mu_dec = mu_b0_warm > 0.0 ? optv(h, "tq_mu_dec_warm") : optv(h, "tq_mu_dec");
+  P.ls_curv = (int)optv(h, "tq_ls_curv");
+  P.curv_lag = (int)optv(h, "tq_curv_lag");
+  P.max_back = (int)optv(h, "tq_max_back");
   P.vel = h->tq.vel_limits ? 1 : 0;
   // d tau / dz in closed form needs the tables to describe a rigid-body chain: unit joint axes that the joint-origin rotation leaves in place (then
   // the angular velocity the reference adds, iRp @ axis, is the axis its rotation turns about; models.py:1821-1823).  Otherwise: dual numbers.
@@ -932,7 +940,7 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     for (int k = 0; k < 3; ++k) dev = fmax(dev, fabs(R[k] * a[0] + R[3 + k] * a[1] + R[6 + k] * a[2] - a[k]));
     if (!(dev <= 1e-12)) P.jac_closed_form = 0;
   }
-  if (optv(h, "tq_jac_dual", 0.0) != 0.0) P.jac_closed_form = 0;  // the dual-number path whatever the tables (A/B, tests)
+  if (optv(h, "tq_jac_dual") != 0.0) P.jac_closed_form = 0;  // the dual-number path whatever the tables (A/B, tests)
   for (int i = 0; i < N; ++i) {
     P.tau_lo[i] = h->tq.tau_lo[i];
     P.tau_up[i] = h->tq.tau_up[i];
@@ -1022,7 +1030,7 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
       HIPCHK(hipStreamSynchronize(s));
       running = *h->h_flag;
       if (running == 0) break;
-      const double rebuild = optv(h, "tq_rebuild", 0.9);
+      const double rebuild = optv(h, "tq_rebuild");
       if (running <= rebuild * D.n_run) {  // rebuild the list of running instances: grids shrink with the batch
         HIPCHK(hipMemsetAsync(D.n_list, 0, sizeof(int), s));
         oh_launch_tq_list(s, D);
@@ -1114,7 +1122,7 @@ static int pm_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   if (rc) return rc;
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   oh_launch_pm_solve(h->stream, h->PmP, h->PmD, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                     (int*)d_iters, (int*)d_status);
+                     (int*)d_iters, (int*)d_status, (int)optv(h, "pm_wave_max"));
   return finish_solve(h, 1);
 }
 
@@ -1184,7 +1192,7 @@ static bool solver_chain_ok(const oh_chain& c) {
 // row stride of the SoA stage arrays for a batch of B (see ensure_capacity)
 static int row_stride(const oh_handle* h, int B) {
   int Bp = (B + 63) / 64 * 64;
-  if (Bp >= 4096) Bp += 64 * (int)optv(h, "row_pad", 13);
+  if (Bp >= 4096) Bp += 64 * (int)optv(h, "row_pad");
   return Bp;
 }
 static bool stage_fits(const oh_handle* h, int B) {
@@ -1431,31 +1439,27 @@ static void fill_params(oh_handle* h) {
   P.dt = d.dt;
   P.w_path = d.w_path;
   P.kappa = d.w_vel / (d.dt * d.dt);
-  P.tol = optv(h, "tol", 0.0) > 0.0 ? optv(h, "tol", 0.0) : d.tol;  // (option "tol": the stopping tolerance of an existing trajectory handle, bench.py's second pass)
+  P.tol = optv(h, "tol") > 0.0 ? optv(h, "tol") : d.tol;  // (option "tol": the stopping tolerance of an existing trajectory handle, bench.py's second pass)
   P.tol_feas = d.tol_feas;
   P.tol_retract = fmin(1e-10, d.tol_feas);
   // (every handle since the end of round 3.  First built for handles with inequality rows; a tolerance sweep then showed the plain family in the
   //  same retraction-noise end game below tol = 1e-7 -- a tenth of a batch sitting at 1.5 x tol until the cap at 1e-9 -- and at the default 1e-6
   //  the rules cut the rejected steps from 1.7 % to 0.4 % and the median instance from 13 to 10 steps: 2.92 -> 3.0-3.1 M solves/s)
-  P.tol_retract_min = fmin(1e-13, P.tol_retract);
-  P.tol_retract_min = fmin(optv(h, "retract_min", 1e-13), P.tol_retract);  // (option: experiments)
+  P.tol_retract_min = fmin(optv(h, "retract_min"), P.tol_retract);  // (option: experiments)
   P.feas_accept = fmax(1e-8, 10.0 * d.tol_feas);
   P.max_retract = 4;
   P.max_iter = d.max_iter;
   P.hessian = d.hessian;
-  P.hyb_switch = 1e-5 * d.w_path;
   // (The same switch for handles with limit rows.  Switching those earlier was measured and dropped: at 3e-5 x w_path 16 384 velocity-limited
   // instances take 20.4 instead of 22.0 steps on average with 99.95 % of them at the same optimum, at 1e-4 19.6 steps with 0.8 % forking -- but the
   // tail of the distribution moves about: of 24 576 instances one sits at the 600-step cap at 3e-5, takes 565 steps at 2e-5 and 166 at 5e-5, where
   // 1e-5 finishes every instance of every batch measured, 16 384 to 262 144, in at most 508; tools/gpu_vel_switch_quality.py, gpu_vel_24576_probe.py.)
-  P.hyb_switch = optv(h, "hyb_switch", 1e-5) * d.w_path;  // (option: experiments)
+  P.hyb_switch = optv(h, "hyb_switch") * d.w_path;  // (option: experiments)
   P.mu0 = d.mu0;
-  P.relax = 1.5;
-  P.relax_from = 4;
-  P.relax = optv(h, "relax", P.relax);
-  P.relax_from = (int)optv(h, "relax_from", P.relax_from);
-  P.settle_k = optv(h, "settle_k", 1.0);
-  P.al_fuse = (int)optv(h, "al_fuse", 1.0);
+  P.relax = optv(h, "relax");
+  P.relax_from = (int)optv(h, "relax_from");
+  P.settle_k = optv(h, "settle_k");
+  P.al_fuse = (int)optv(h, "al_fuse");
   P.local_path = h->d_local_path;
   P.np = (int)shape_of(h).npar;
   // coupling folded into evaluation and sweep (no k_couple launch): the plain orientation-locked handles, i.e. the batched path of config 2
@@ -1481,13 +1485,13 @@ static int move_everything(oh_handle* h, hipStream_t s, int Bnew) {
   // What a handle's kernels never carry from one launch to the next stays behind: the folded-coupling family (P.zc) keeps no coupling blocks, reduced
   // gradients or per-knot tracking cost of its own (E, gt, phi: oh_figure8_units.h writes merit[] instead and the sweep rebuilds the rest), the Riccati gains
   // are written by the backward pass of a sweep and read by the forward pass of the same launch, and a chain without a lead joint has no lead[].
-  const bool zc = h->P.zc != 0, slim = optv(h, "invariant_move_slim", 1.0) != 0.0;
+  const bool zc = h->P.zc != 0, slim = optv(h, "invariant_move_slim") != 0.0;
   // invariant_move_live (plain folded-coupling family only): of the per-slot stage data only the slot of the accepted point travels -- the other slot is the
   // trial the sweep has just judged: accepted, it IS the accepted slot by now; rejected, it is rewritten by the next evaluation before anything reads it.
   // The knots themselves travel in both slots (the pinned end knots of a slot are written once, by k_setup).
   struct Pair { double* a0; double* a1; int rows; };
   std::vector<Pair> live;
-  const bool live_only = zc && !h->have_guards && optv(h, "invariant_move_live", 1.0) != 0.0;
+  const bool live_only = zc && !h->have_guards && optv(h, "invariant_move_live") != 0.0;
   if (live_only) {
     live.push_back({D.Z[0], D.Z[1], T * (3 * N - 3)}); live.push_back({D.Dr[0], D.Dr[1], T * (NZ * (NZ + 1) / 2)}); live.push_back({D.g[0], D.g[1], T * N});
     live.push_back({D.cv[0], D.cv[1], T}); live.push_back({D.Gfull[0], D.Gfull[1], T * N}); live.push_back({D.mdl[0], D.mdl[1], T * (3 + 3 * NZ)});
@@ -1638,74 +1642,127 @@ static int solve_split(oh_handle* h, const int S, int B, const void* d_x0, const
   return OH_OK;
 }
 
-// The solve of every entry point and every lane: without may_fan_out the batch is never split.  rec (may be null): where the results live, on success.
-static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
-                        const bool may_fan_out, LastSolve* rec) {
-  if (B < 1) return fail(OH_ERR_INVALID, "oh_solve_device: B must be >= 1");
-  if (!d_x0 || !d_p) return fail(OH_ERR_INVALID, "oh_solve_device: x0 and p are required");
-  if (rec) *rec = LastSolve{B, {{h, B}}, false};
-  load_launch_opts(h);
-  if (h->desc.kind == OH_PROBLEM_POINT_MASS_MPC) return pm_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-  if (h->desc.kind == OH_PROBLEM_IK) return ik_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-  if (h->desc.kind == OH_PROBLEM_QP) return qp_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-  if (h->desc.kind == OH_PROBLEM_TAPE) return tape_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-  if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) {
-    const int S = std::min(8, (int)optv(h, "streams", 2.0));
-    if (may_fan_out && !h->profiling && S >= 2 && B >= (int)optv(h, "tq_split_min", 1024.0) && B / S >= 64 && h->have_chain && h->have_dyn)
-      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
-    return tq_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+// ---- trajectory solve: a prologue, one loop per family (orientation-locked, position-tracking), an epilogue ----------------------------------
+// A loop chooses its launches from the facts below, fixed before it, and re-tests only what a solve changes: D.B, a pending carried compaction,
+// the cadence of the host's look at the running count, and that count.
+struct Traj {
+  int B, N, NV, check_every, hard_cap;  // batch, joints, velocity rows per knot, ...
+  bool guarded, lead, prof, invariant;  // inequality rows, lead joint, profiling events, batch_invariant
+  const FigSpec* spec;  // kernels compiled for the chain (plain orientation-locked handles), else nullptr
+  FreeSweep sweep;      // position-tracking family: the sweep of the first launch
+  const double* p;
+  double *x, *f, *kkt;
+  int *iters, *status;
+  int launched, compactions;
+  size_t ne;  // profiling events recorded
+};
+// The one place that chooses the sweep of a position-tracking launch of nb instances (the launchers in oh_free.hip take the choice).  start: nb is
+// the batch of a solve that is starting; the choice then also fixes the stage layout of the whole solve -- instance-major when every launch takes
+// the twisted factorisation, which holds to the end once it holds for the whole batch -- and may give the whole solve to one launch.
+static FreeSweep free_sweep(oh_handle* h, const int nb, const bool start = false) {
+  const int N = h->desc.ndof, nK = h->desc.T - h->P.t0;
+  FreeSweep sw = FREE_SERIAL;
+  // a block per instance for 6 and 7 joints, at most free_pcr_max instances and 128 knots (batch_invariant: the serial sweep whatever the batch --
+  // the block-per-instance factorisations chosen by size round differently)
+  if (!h->P.lock && batch_invariant(h) == 0.0 && nb <= h->sch.free_pcr_max && nK <= 128 && (N == 6 || N == 7)) {
+    if (N == 7 && (int)optv(h, "free_bb") != 0) sw = FREE_BB;  // (free_bb = 0: the cyclic-reduction kernels of rounds 2-3; A/B, tests)
+    // eight lanes per knot up to free_cp_max instances, and only up to 64 knots: 128 knots x 8 lanes are 1024 threads, which leaves 128 registers
+    // per lane -- the kernel then spills and takes 147 us against k_step_free_pcr's 111 at T = 100; at T = 50 it is 61 against 87 us
+    else sw = (nb <= (int)optv(h, "free_cp_max") && nK <= 64) ? FREE_CP : FREE_PCR;
   }
-  if (h->desc.kind != OH_PROBLEM_FIGURE_EIGHT) return fail(OH_ERR_STATE, "oh_solve_device: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
-  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
-  if (!solver_chain_ok(h->chain_host))
-    return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
-  HIPCHK(hipSetDevice(h->device));
-  // (batch_invariant handles take part in the split too since their compaction moves everything: an instance's answer does not depend on its part)
-  if (may_fan_out && !h->profiling && spec_applies(h) && (optv(h, "batch_invariant", 0.0) == 0.0 || optv(h, "invariant_split", 1.0) != 0.0)) {
-    const int S = std::min(8, (int)optv(h, "streams", 2.0));
-    if (S >= 2 && B >= (int)optv(h, "split_min", 65536.0) && B / S >= 4096 && stage_fits(h, B)) {  // (a batch beyond oh_max_batch is refused below, as ever)
-      // (the kernels compiled for the chain are shared: make sure they exist before the parts look for them)
-      if (!h->spec && !h->spec_failed && h->sch.specialize != OH_SPECIALIZE_NEVER && oh_specialize(h) != OH_OK) h->spec_failed = true;
-      return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
-    }
+  if (!start) return sw;
+  h->P.inst_major = sw == FREE_BB ? 1 : 0;
+  // limit / sphere rows: the whole solve in one launch (k_free_persist).  Measured (HISTORY): same time per iteration as the launch pair (the
+  // iteration is memory round trips inside the phases, not launch gaps), so it only wins where the host's sparse looks at the running count cost
+  // idle launches and every block is resident: horizons up to 64 free knots, at most 512 instances (option free_persist = 1: always, 0: never)
+  const int fp = (int)optv(h, "free_persist");
+  const bool fits = (nK <= 64 && nb <= 512) || fp == 1;
+  return (sw == FREE_BB && h->have_guards && !h->GP.vel && h->P.zc_free && !h->profiling && fits && fp != 0) ? FREE_PERSIST : sw;
+}
+// oh_set_profiling(1): an event, tagged 0 (a new base: nothing is billed for the gap before it), 1 after an evaluation, 2 after a sweep, 3 after a
+// coupling, 4 after the evaluation before a carried compaction; none once fewer than `room` events are left
+static int mark(oh_handle* h, Traj& r, const int tag, const size_t room = 2) {
+  if (!r.prof || r.ne + room >= h->prof_events.size()) return OH_OK;
+  size_t& ne = r.ne;
+  hipStream_t s = h->stream;
+  HIPCHK(hipEventRecord(h->prof_events[ne++], s));
+  h->prof_tags.push_back(tag);
+  return OH_OK;
+}
+// After iteration it the host looks at the running count (a copy + stream synchronisation, 20-30 us of a ~150 us iteration): every check_every-th
+// iteration, or -- handles without a persistent tail kernel, whose last launches of a few hundred instances are pure latency -- every 8th (the
+// price: up to 7 idle iterations of finished instances at the very end)
+static bool check_after(const oh_handle* h, const Traj& r, const int it, const bool tail_ok) {
+  return (it + 1) % ((!tail_ok && r.check_every == 1 && h->D.B <= h->sch.sparse_check_below) ? 8 : r.check_every) == 0;
+}
+// the running count the last sweep left, when the host looks (check); -1 otherwise
+static int look(oh_handle* h, const bool check, int* nrun) {
+  *nrun = -1;
+  if (!check) return OH_OK;
+  hipStream_t s = h->stream;
+  HIPCHK(hipMemcpyAsync(h->h_flag, h->D.n_running, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *nrun = *h->h_flag;
+  return OH_OK;
+}
+// results of finished instances (only_done) or of all: x through the library's LDS transpose, scalars and multipliers through the kernel compiled
+// for the chain where there is one
+static void finalize(oh_handle* h, const Traj& r, const int only_done) {
+  hipStream_t s = h->stream;
+  if (r.spec && r.spec->finalize) {
+    oh_launch_finalize(s, r.N, h->P, h->D, only_done, r.x, r.f, r.kkt, r.iters, r.status, 1);
+    if (oh_spec_launch_finalize(*r.spec, s, h->P, h->D, only_done, r.f, r.kkt, r.iters, r.status) == hipSuccess) return;
+    (void)hipGetLastError();
+    oh_launch_finalize(s, r.N, h->P, h->D, only_done, r.x, r.f, r.kkt, r.iters, r.status, 2);
+    return;
   }
-  if (may_fan_out && !h->profiling && !h->desc.lock_orientation && !h->chain_host.has_lead && optv(h, "batch_invariant", 0.0) == 0.0) {
-    // position-tracking family (every launch latency-bound, the machine far from full): two halves side by side -- 1024 arms 9.5 -> 7.3 ms
-    const int S = std::min(8, (int)optv(h, "streams", 2.0));
-    if (S >= 2 && B >= (int)optv(h, "free_split_min", 256.0) && B / S >= 64) return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
+  oh_launch_finalize(s, r.N, h->P, h->D, only_done, r.x, r.f, r.kkt, r.iters, r.status);
+}
+// The batch down to its nrun survivors: finished instances' results (and multipliers) are written out, the survivors ordered (D.newidx); then they
+// move with everything they own (move: nothing restarts), or their accepted knots -- with inequality rows also their multipliers and outer-loop
+// state -- are laid down densely and re-evaluated from `slot`.
+static int compact_batch(oh_handle* h, Traj& r, const int nrun, const int slot, const bool move) {
+  hipStream_t s = h->stream;
+  finalize(h, r, 1);
+  if (r.guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, r.NV, 1);
+  oh_launch_scan_running(s, h->D, h->sch.compact_sort);
+  if (move) {
+    if (const int rc = move_everything(h, s, nrun)) return rc;
+  } else {
+    oh_launch_compact(s, r.N, h->P, h->D, 0, 0, 0);
+    if (r.guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, r.NV, 0, 0);
+    oh_launch_compact(s, r.N, h->P, h->D, 1, nrun, slot);
+    if (r.guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, r.NV, 1, nrun);
   }
-  int rc = ensure_capacity(h, B);
-  if (rc) return rc;
+  h->D.B = nrun;
+  ++r.compactions;
+  return OH_OK;
+}
+static int traj_prologue(oh_handle* h, Traj& r, const void* d_x0) {
+  if (const int rc = ensure_capacity(h, r.B)) return rc;
   fill_params(h);
   if ((spec_applies(h) || spec_tail_vel_applies(h)) && !h->spec && !h->spec_failed) {
-    bool want = h->sch.specialize == OH_SPECIALIZE_ALWAYS || (h->sch.specialize == OH_SPECIALIZE_AUTO && B >= h->specialize_min_B);
+    bool want = h->sch.specialize == OH_SPECIALIZE_ALWAYS || (h->sch.specialize == OH_SPECIALIZE_AUTO && r.B >= h->specialize_min_B);
     if (!want && h->sch.specialize == OH_SPECIALIZE_AUTO && !h->spec_cache_checked) {  // a compiled object is at hand: milliseconds, whatever the batch
       h->spec_cache_checked = true;
       want = oh_jit_figure8_cached(h->chain_host, h->desc.ndof);
     }
     if (want && oh_specialize(h) != OH_OK) h->spec_failed = true;
   }  // the generic kernels run (and no further attempt is made); oh_last_error keeps the reason
-  const bool guarded = h->have_guards;
-  const bool lead = h->chain_host.has_lead != 0;
-  {  // position-tracking family, 7 joints, every launch of this solve a block per instance (k_step_free_bb): stage blocks instance-major
-    // (batch_invariant: the size-independent path -- knot-major blocks, the serial sweep on one lane per instance -- whatever the batch: the block-per-instance
-    //  factorisations chosen by size round differently)
-    h->P.inst_major = (!h->desc.lock_orientation && h->desc.ndof == 7 && B <= h->sch.free_pcr_max && h->desc.T - (h->desc.fix_dq0 ? 2 : 1) <= 128 && optv(h, "free_bb", 1.0) != 0.0 &&
-                       optv(h, "batch_invariant", 0.0) == 0.0) ? 1 : 0;
-  }
-  if (lead && (guarded || !h->desc.lock_orientation || h->desc.ndof != 6))
+  if (r.lead && (r.guarded || !h->desc.lock_orientation || h->desc.ndof != 6))
     return fail(OH_ERR_INVALID, "oh_solve_device: a parameterised lead joint is lowered for the orientation-locked family with 6 optimised joints, "
                                 "without inequality rows");
-  if (guarded) {
-    rc = ensure_guards(h);
-    if (rc) return rc;
-  } else {
-    h->D.fpsi = nullptr;
-  }
-  const int N = h->desc.ndof;
+  if (!r.guarded) h->D.fpsi = nullptr;
+  else if (const int rc = ensure_guards(h)) return rc;
+  r.sweep = free_sweep(h, r.B, true);  // (and the stage layout, P.inst_major)
+  r.NV = (r.guarded && h->GP.vel) ? 2 * r.N : 0;
+  r.spec = spec_applies(h) ? h->spec : nullptr;
+  // one small D2H read per iteration: with the cheap compaction timely decisions beat the saved round trips (every 2nd: -1.5 %)
+  r.check_every = optv(h, "check_every") >= 1.0 ? (int)optv(h, "check_every") : 1;  // (option: experiments)
+  // every instance needs at most max_iter steps (accepted + rejected) plus its first evaluation: a rejected step costs two launches, a compaction one
+  r.hard_cap = 2 * h->desc.max_iter + 2 + 40 + 64;
   hipStream_t s = h->stream;
-  const bool prof = h->profiling;
-  if (prof) {
+  if (r.prof) {
     // events: [0] start, then per iteration (after eval, after step), last = end
     const size_t need = 4 * (size_t)(2 * h->desc.max_iter + 44) + 64;
     while (h->prof_events.size() < need) {
@@ -1716,195 +1773,155 @@ static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, 
   }
   HIPCHK(hipEventRecord(h->ev0, s));
   HIPCHK(hipMemsetAsync(h->D.work, 0, 4 * sizeof(unsigned long long), s));  // (work[0..2] and the two deferral counters)
-  if (!oh_launch_setup(s, N, h->P, h->D, (const double*)d_x0, (const double*)d_p))
-    return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
-  if (guarded) oh_launch_setup_guards(s, N, h->P, h->D, h->GP, h->GB, (const double*)d_p);
-  size_t ne = 0;
+  if (!oh_launch_setup(s, r.N, h->P, h->D, (const double*)d_x0, r.p)) return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
+  if (r.guarded) oh_launch_setup_guards(s, r.N, h->P, h->D, h->GP, h->GB, r.p);
   h->prof_tags.clear();
-  if (prof) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(0); }
-  int launched = 0;
-  int compactions = 0;
-  int check_every = 1;  // one small D2H read per iteration: with the cheap compaction timely decisions beat the saved round trips (every 2nd: -1.5 %)
-  if (optv(h, "check_every", 1.0) >= 1.0) check_every = (int)optv(h, "check_every", 1.0);  // (option: experiments)
-  double* ox = (double*)d_x; double* of = (double*)d_f; double* ok = (double*)d_kkt;
-  int* oi = (int*)d_iters; int* os = (int*)d_status;
-  // Every instance needs at most max_iter steps (accepted + rejected) plus its first evaluation; each
-  // plain compaction re-evaluates the survivors once.  The batch is compacted whenever 3 % of it have finished (compact_frac);
-  // the regular compactions carry the pending trial along and cost no evaluation (k_carry_*), the hand-over to the tail kernel
-  // restarts the survivors.
-  const int hard_cap = 2 * h->desc.max_iter + 2 + 40 + 64;  // a rejected step costs two launches, a compaction one
-  const int NV = (guarded && h->GP.vel) ? 2 * N : 0;  // velocity rows per knot
-  // persistent tail kernel: plain orientation-locked handles, and (round 3, k_tail_vel) those whose inequality rows are joint and / or joint-velocity limits (no sphere rows)
-  const bool tail_vel = guarded && (h->GP.vel || h->GP.limits) && h->GP.n_links == 0 && h->sch.tail_vel;
-  const bool tail_ok = (h->desc.T - h->P.t0 <= 64) && h->sch.tail_threshold > 0 && h->desc.lock_orientation && (!guarded || tail_vel) && !lead;
+  return mark(h, r, 0);
+}
+// the persistent one-wavefront-per-instance kernel (k_tail; k_tail_vel for limit rows), compiled for the chain where there is one
+static bool launch_tail(oh_handle* h, const Traj& r, const bool tail_vel, const int slot) {
+  hipStream_t s = h->stream;
+  if (tail_vel && h->spec && spec_tail_vel_applies(h)) return oh_spec_launch_tail_vel(*h->spec, s, h->P, h->D, h->GP, h->GB, slot) == hipSuccess;
+  if (tail_vel) return oh_launch_tail_vel(s, r.N, h->P, h->D, h->GP, h->GB, slot);
+  if (r.spec) return oh_spec_launch_tail(*r.spec, s, h->P, h->D, slot) == hipSuccess;
+  return oh_launch_tail(s, r.N, h->P, h->D, slot);
+}
+static void launch_eval(oh_handle* h, const Traj& r, const int slot, const int part) {
+  if (!r.spec) oh_launch_eval(h->stream, r.N, h->P, h->D, slot, part);
+  else oh_spec_launch_eval(*r.spec, h->stream, h->P, h->D, slot, part);
+}
+
+// The orientation-locked family (plain, with inequality rows or with a lead joint).  The batch is compacted whenever 3 % of it have finished
+// (compact_frac): the regular compactions carry the pending trial along and cost no evaluation (k_carry_*), the hand-over to the tail kernel restarts.
+static int locked_loop(oh_handle* h, Traj& r) {
+  FigParams& P = h->P; FigBuffers& D = h->D; const GuardParams& GP = h->GP; const GuardBuffers& GB = h->GB;
+  const hipStream_t s = h->stream;
+  const int N = r.N;
+  // persistent tail kernel: plain handles, and (round 3, k_tail_vel) those whose inequality rows are joint and / or joint-velocity limits (no sphere rows)
+  const bool tail_vel = r.guarded && (GP.vel || GP.limits) && GP.n_links == 0 && h->sch.tail_vel;
+  const bool tail_ok = (h->desc.T - P.t0 <= 64) && h->sch.tail_threshold > 0 && (!r.guarded || tail_vel) && !r.lead;
   // limit / velocity-limit handles: the batched launches (evaluation, velocity coupling in a launch of its own, sweep: 1.45 ms per iteration of
   // 40 000 instances) lose against the persistent kernel at every size measured -- 65 536 instances: 87.5 ms with the hand-over at 16 384,
   // 80.5 at 32 768, 76.3 when the whole batch starts there -- so these handles go to it whatever the batch (OH_TAIL_VEL_THRESHOLD overrides)
   const int tail_threshold = tail_vel ? h->sch.tail_vel_threshold : h->sch.tail_threshold;
-  const FigSpec* const spec = spec_applies(h) ? h->spec : nullptr;
-  // evaluation / tail launches: the kernels compiled for this handle's chain when they are loaded, the generic ones otherwise
-  auto launch_eval = [&](int slot, int part) {
-    if (spec) return oh_spec_launch_eval(*spec, s, h->P, h->D, slot, part) == hipSuccess;
-    return oh_launch_eval(s, N, h->P, h->D, slot, part);
-  };
-  auto launch_tail = [&](int slot) {
-    if (tail_vel && h->spec && spec_tail_vel_applies(h)) return oh_spec_launch_tail_vel(*h->spec, s, h->P, h->D, h->GP, h->GB, slot) == hipSuccess;
-    if (tail_vel) return oh_launch_tail_vel(s, N, h->P, h->D, h->GP, h->GB, slot);
-    if (spec) return oh_spec_launch_tail(*spec, s, h->P, h->D, slot) == hipSuccess;
-    return oh_launch_tail(s, N, h->P, h->D, slot);
-  };
-  // results of finished instances: x through the library's LDS transpose, scalars and multipliers through the kernel compiled for the chain where there is one
-  auto finalize = [&](const int only_done) {
-    if (spec && spec->finalize) {
-      oh_launch_finalize(s, N, h->P, h->D, only_done, ox, of, ok, oi, os, 1);
-      if (oh_spec_launch_finalize(*spec, s, h->P, h->D, only_done, of, ok, oi, os) == hipSuccess) return;
-      (void)hipGetLastError();
-      oh_launch_finalize(s, N, h->P, h->D, only_done, ox, of, ok, oi, os, 2);
-      return;
-    }
-    oh_launch_finalize(s, N, h->P, h->D, only_done, ox, of, ok, oi, os);
-  };
-  bool tail_done = false;
-  {  // position-tracking family with limit / sphere rows, every instance a block of its own: the whole solve in one launch (k_free_persist)
-    const int fp = (int)optv(h, "free_persist", -1.0);  // -1: where it pays, 1: always, 0: never
-    // measured (HISTORY): same time per iteration as the launch pair (the iteration is memory round trips inside the phases, not launch gaps), so it
-    // only wins where the host's sparse looks at the running count cost idle launches and every block is resident: horizons up to 64 free knots,
-    // at most 512 instances (option free_persist = 1: always, 0: never)
-    const bool fits = (h->desc.T - h->P.t0 <= 64 && B <= 512) || fp == 1;
-    if (!h->P.lock && guarded && !h->GP.vel && h->P.inst_major && h->P.zc_free && !prof && !lead && fits && fp != 0) {
-      if (oh_launch_free_persist(s, N, h->P, h->D, h->GP, h->GB)) {
-        tail_done = true;
-        launched = 1;
-      }
-    }
+  if (tail_ok && r.B <= tail_threshold) {  // small batch: the whole solve is one persistent launch
+    if (!launch_tail(h, r, tail_vel, 0)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
+    return OH_OK;
   }
-  if (!tail_done && tail_ok && B <= tail_threshold) {  // small batch: the whole solve is one persistent launch
-    if (!launch_tail(0)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
-    tail_done = true;
-  }
-  bool rebase = false;
-  const bool invariant = optv(h, "batch_invariant", 0.0) != 0.0;
-  const double inv_frac = optv(h, "invariant_compact_frac", 0.65);
-  int carry_pending = 0;  // > 0: survivors to compact the batch to, between k_retract and k_evalb of the next iteration
-  for (int it = 0; it < hard_cap && !tail_done; ++it) {
-    if (prof && rebase && ne + 3 < h->prof_events.size()) {  // host synced: do not bill the idle gap to the eval kernel
-      HIPCHK(hipEventRecord(h->prof_events[ne++], s));
-      h->prof_tags.push_back(0);
-    }
-    rebase = false;
+  // limit rows without sphere rows: retraction and evaluation as two launches like the plain family (k_evalb_lg in oh_kernels.hip)
+  const bool lg_split = r.guarded && h->sch.lg_split && GP.n_links == 0, lg_spec = lg_split && h->spec && spec_tail_vel_applies(h);
+  // coupling: folded into evaluation and sweep (P.zc: k_evalb_zc / k_step_zc), with the velocity rows (k_couple_vel), or k_couple
+  const bool couple_vel = !P.zc && r.guarded && GP.vel, couple = !P.zc && !couple_vel;
+  // compactions: carried (plain handles; k_carry_* park 22 per-instance scalars in the first rows of the spare Dr slot: T x NZ(NZ+1)/2 rows must
+  // hold them), moving (batch_invariant), restarting -- with inequality rows moving too (round 5: the same iterates, bit for bit); a lead joint: none
+  const bool carry = h->sch.compaction && h->sch.compact_carry && (size_t)h->desc.T * ((N - 3) * (N - 2) / 2) >= 22 && !r.guarded && !r.lead;
+  const double inv_frac = optv(h, "invariant_compact_frac");
+  const bool inv_move = r.invariant && !r.lead && inv_frac > 0.0, restart = h->sch.compaction && !r.lead, restart_moves = r.guarded && optv(h, "compact_move_all") != 0.0;
+  int nrun = -1, carry_pending = 0;  // the running count at the last look (-1: none after the last iteration); > 0: a carried compaction to this many
+  for (int it = 0; it < r.hard_cap; ++it) {
+    if (nrun >= 0)  // host synced: do not bill the idle gap to the eval kernel
+      if (const int rc = mark(h, r, 0, 3)) return rc;
     const int slot = it & 1;
-    if (h->P.lock && guarded) {
-      if (h->sch.lg_split && h->GP.n_links == 0) {  // retraction and evaluation as two launches, like the plain family (k_evalb_lg in oh_kernels.hip)
-        if (!(h->spec && spec_tail_vel_applies(h) && oh_spec_launch_eval(*h->spec, s, h->P, h->D, slot, 1) == hipSuccess))
-          oh_launch_eval_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, 1);
-        oh_launch_eval_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, 2);
-      } else oh_launch_eval_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, 0);
-    } else if (lead) oh_launch_eval_lead(s, N, h->P, h->D, slot);
-    else if (h->P.lock && carry_pending > 0) {
+    if (lg_split) {
+      if (!(lg_spec && oh_spec_launch_eval(*h->spec, s, P, D, slot, 1) == hipSuccess)) oh_launch_eval_locked_guarded(s, N, P, D, GP, GB, slot, 1);
+      oh_launch_eval_locked_guarded(s, N, P, D, GP, GB, slot, 2);
+    } else if (r.guarded) oh_launch_eval_locked_guarded(s, N, P, D, GP, GB, slot, 0);
+    else if (r.lead) oh_launch_eval_lead(s, N, P, D, slot);
+    else if (carry_pending > 0) {
       // compaction with the trial carried along: retract on the old layout, move, evaluate on the dense one (k_carry_* in oh_kernels.hip)
-      launch_eval(slot, 1);
-      if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(4); }
-      finalize(1);
-      oh_launch_scan_running(s, h->D, h->sch.compact_sort);
-      oh_launch_carry(s, N, h->P, h->D, 0, 0, slot);
-      oh_launch_carry(s, N, h->P, h->D, 1, carry_pending, slot);
+      launch_eval(h, r, slot, 1);
+      if (const int rc = mark(h, r, 4)) return rc;
+      finalize(h, r, 1);
+      oh_launch_scan_running(s, D, h->sch.compact_sort);
+      oh_launch_carry(s, N, P, D, 0, 0, slot);
+      oh_launch_carry(s, N, P, D, 1, carry_pending, slot);
       // the knots were laid down densely in the spare arrays: they become q[] / Gfull[] for the launches that follow (no copy back)
-      std::swap(h->D.q[slot], h->D.q_spare[0]);
-      std::swap(h->D.q[1 - slot], h->D.q_spare[1]);
-      if (h->P.hessian != OH_HESSIAN_GAUSS_NEWTON || h->P.zc) std::swap(h->D.Gfull[1 - slot], h->D.G_spare);
-      h->D.B = carry_pending;
+      std::swap(D.q[slot], D.q_spare[0]);
+      std::swap(D.q[1 - slot], D.q_spare[1]);
+      if (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc) std::swap(D.Gfull[1 - slot], D.G_spare);
+      D.B = carry_pending;
       carry_pending = 0;
-      ++compactions;
-      if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(0); }
-      launch_eval(slot, 2);
-    } else if (h->P.lock) launch_eval(slot, 0);
-    else if (guarded) oh_launch_eval_guarded(s, N, h->P, h->D, h->GP, h->GB, slot);
-    else oh_launch_eval_free(s, N, h->P, h->D, slot);
-    if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(1); }
-    if (h->P.zc || h->P.zc_free) {}  // folded into k_evalb_zc / k_step_zc (position tracking: into the evaluation)
-    else if (h->P.lock && guarded && h->GP.vel) oh_launch_couple_vel(s, N, h->P, h->D, h->GP, h->GB, slot);
-    else if (h->P.lock) oh_launch_couple(s, N, h->P, h->D, slot);
-    else if (guarded && h->GP.vel) oh_launch_couple_free_vel(s, N, h->P, h->D, h->GP, h->GB, slot);
-    else oh_launch_couple_free(s, N, h->P, h->D, slot);
-    // handles without a persistent tail kernel (inequality rows, position-only tracking, lead joint) end in launches of a few hundred instances that
-    // are pure latency: there the host looks at the running count every 8th iteration only (a look is a copy + stream synchronisation, 20-30 us
-    // of a ~150 us iteration; the price is up to 7 idle iterations of finished instances at the very end)
-    const int ce = (!tail_ok && check_every == 1 && h->D.B <= h->sch.sparse_check_below) ? 8 : check_every;
-    const bool check = ((it + 1) % ce == 0);
-    if (check && !h->P.lock) HIPCHK(hipMemsetAsync(h->D.n_running, 0, sizeof(int), s));  // the locked family's k_couple resets it
-    if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(3); }
-    if (h->P.lock && guarded) oh_launch_step_locked_guarded(s, N, h->P, h->D, h->GP, h->GB, slot);
-    else if (h->P.lock) oh_launch_step(s, N, h->P, h->D, slot);
-    else if (guarded) oh_launch_step_guarded(s, N, h->P, h->D, h->GP, h->GB, slot, !invariant && h->D.B <= h->sch.free_pcr_max);
-    else oh_launch_step_free(s, N, h->P, h->D, slot, !invariant && h->D.B <= h->sch.free_pcr_max);
-    if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(2); }
-    ++launched;
-    if (check) {
-      HIPCHK(hipMemcpyAsync(h->h_flag, h->D.n_running, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      const int nrun = *h->h_flag;
-      rebase = true;
-      if (nrun == 0) break;
-      if (tail_ok && nrun <= tail_threshold) {
-        // drain: compact the survivors and let one wavefront per instance finish them without further launches
-        finalize(1);
-        if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
-        oh_launch_compact(s, N, h->P, h->D, 0, 0, 0);
-        if (guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, NV, 0, 0);
-        oh_launch_compact(s, N, h->P, h->D, 1, nrun, (it + 1) & 1);
-        if (guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, NV, 1, nrun);
-        h->D.B = nrun;
-        ++compactions;
-        if (!launch_tail((it + 1) & 1)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
-        tail_done = true;
-        break;
-      }
-      // (k_carry_* park 22 per-instance scalars in the first rows of the spare Dr slot: T x NZ(NZ+1)/2 rows must hold them)
-      const bool carry_fits = (size_t)h->desc.T * ((N - 3) * (N - 2) / 2) >= 22;
-      if (h->sch.compaction && h->sch.compact_carry && carry_fits && h->P.lock && !guarded && !lead && h->D.B >= 512 && (double)nrun <= h->sch.compact_frac * (double)h->D.B) {
-        carry_pending = nrun;  // done after the next k_retract
-      } else if (invariant && h->P.lock && !lead && inv_frac > 0.0 && h->D.B >= 512 && (double)nrun <= inv_frac * (double)h->D.B) {
-        // batch_invariant handles: the survivors move with everything they own (both slots' stage data, the pending step, every scalar and flag), so
-        // the compaction is invisible to the state machine -- same iterates, bit for bit, as without it -- and is done on a coarse schedule (when
-        // a third of the batch has finished, by default: a move costs an instance a few iterations' worth of bandwidth; tools/gpu_invariant_compaction.py)
-        finalize(1);
-        if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
-        const int mrc = move_everything(h, s, nrun);
-        if (mrc) return mrc;
-        h->D.B = nrun;
-        ++compactions;
-        if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(0); }
-      } else if (h->sch.compaction && !lead && h->D.B >= 512 && (double)nrun <= h->sch.compact_frac_restart * (double)h->D.B) {
-        // restart compaction: the survivors' accepted knots (and, with inequality rows, their multipliers and outer-loop state) are laid
-        // down densely and re-evaluated
-        finalize(1);
-        if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 1);
-        oh_launch_scan_running(s, h->D, h->sch.compact_sort);
-        if (h->P.lock && guarded && optv(h, "compact_move_all", 1.0) != 0.0) {
-          // orientation-locked handles with inequality rows (horizons beyond the persistent kernel): the instance moves with everything it owns,
-          // nothing restarts -- the same iterates, bit for bit, as without compaction (round 5)
-          const int mrc = move_everything(h, s, nrun);
-          if (mrc) return mrc;
-        } else {
-          oh_launch_compact(s, N, h->P, h->D, 0, 0, 0);
-          if (guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, NV, 0, 0);
-          oh_launch_compact(s, N, h->P, h->D, 1, nrun, (it + 1) & 1);
-          if (guarded) oh_launch_guard_compact(s, h->P, h->D, h->GP, h->GB, NV, 1, nrun);
-        }
-        h->D.B = nrun;
-        ++compactions;
-        // the compaction kernels are accounted to neither eval nor step: restart the event pair
-        if (prof && ne + 2 < h->prof_events.size()) { HIPCHK(hipEventRecord(h->prof_events[ne++], s)); h->prof_tags.push_back(0); }
-      }
+      ++r.compactions;
+      if (const int rc = mark(h, r, 0)) return rc;
+      launch_eval(h, r, slot, 2);
+    } else launch_eval(h, r, slot, 0);
+    if (const int rc = mark(h, r, 1)) return rc;
+    if (couple_vel) oh_launch_couple_vel(s, N, P, D, GP, GB, slot);
+    else if (couple) oh_launch_couple(s, N, P, D, slot);
+    const bool check = check_after(h, r, it, tail_ok);  // (k_couple resets the running count)
+    if (const int rc = mark(h, r, 3)) return rc;
+    if (r.guarded) oh_launch_step_locked_guarded(s, N, P, D, GP, GB, slot);
+    else oh_launch_step(s, N, P, D, slot);
+    if (const int rc = mark(h, r, 2)) return rc;
+    ++r.launched;
+    if (const int rc = look(h, check, &nrun)) return rc;
+    if (nrun == 0) break;
+    if (tail_ok && nrun > 0 && nrun <= tail_threshold) {
+      // drain: compact the survivors and let one wavefront per instance finish them without further launches
+      if (const int rc = compact_batch(h, r, nrun, (it + 1) & 1, false)) return rc;
+      if (!launch_tail(h, r, tail_vel, (it + 1) & 1)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
+      break;
+    }
+    if (nrun < 0 || D.B < 512) continue;
+    if (carry && (double)nrun <= h->sch.compact_frac * (double)D.B) {
+      carry_pending = nrun;  // done after the next k_retract
+    } else if (inv_move && (double)nrun <= inv_frac * (double)D.B) {  // (a coarse schedule: a move costs a few iterations' bandwidth)
+      if (const int rc = compact_batch(h, r, nrun, 0, true)) return rc;
+      if (const int rc = mark(h, r, 0)) return rc;
+    } else if (restart && (double)nrun <= h->sch.compact_frac_restart * (double)D.B) {
+      if (const int rc = compact_batch(h, r, nrun, (it + 1) & 1, restart_moves)) return rc;
+      if (const int rc = mark(h, r, 0)) return rc;  // (the compaction kernels are accounted to neither eval nor step: restart the event pair)
     }
   }
-  finalize(0);
-  if (guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, NV, 0);
-  h->D.B = B;
-  if (guarded) oh_launch_guard_infeasible(s, N, h->P, h->D, h->GP, (const double*)d_p, B, ok, os);  // constant rows of the pinned knots
-  if (const int frc = finish_solve(h, launched)) return frc;
+  return OH_OK;
+}
+// The position-tracking family (oh_free.hip): restarting compactions (compact_frac_restart); the sweep follows the live batch (free_sweep).
+static int free_loop(oh_handle* h, Traj& r) {
+  FigParams& P = h->P; FigBuffers& D = h->D; const GuardParams& GP = h->GP; const GuardBuffers& GB = h->GB;
+  const hipStream_t s = h->stream;
+  const int N = r.N;
+  FreeSweep sweep = r.sweep;  // (changes with D.B)
+  if (sweep == FREE_PERSIST) {
+    if (!oh_launch_free_persist(s, N, P, D, GP, GB)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
+    r.launched = 1;
+    return OH_OK;
+  }
+  // coupling: folded into the evaluation (P.zc_free), with the velocity rows (k_couple_free_vel), or k_couple_free
+  const bool couple_vel = !P.zc_free && r.guarded && GP.vel, couple = !P.zc_free && !couple_vel;
+  int nrun = -1;
+  for (int it = 0; it < r.hard_cap; ++it) {
+    if (nrun >= 0)  // host synced: do not bill the idle gap to the eval kernel
+      if (const int rc = mark(h, r, 0, 3)) return rc;
+    const int slot = it & 1;
+    if (r.guarded) oh_launch_eval_guarded(s, N, P, D, GP, GB, slot);
+    else oh_launch_eval_free(s, N, P, D, slot);
+    if (const int rc = mark(h, r, 1)) return rc;
+    if (couple_vel) oh_launch_couple_free_vel(s, N, P, D, GP, GB, slot);
+    else if (couple) oh_launch_couple_free(s, N, P, D, slot);
+    const bool check = check_after(h, r, it, false);
+    if (check) HIPCHK(hipMemsetAsync(h->D.n_running, 0, sizeof(int), s));  // (the sweep counts the instances still running)
+    if (const int rc = mark(h, r, 3)) return rc;
+    if (r.guarded) oh_launch_step_guarded(s, N, P, D, GP, GB, slot, sweep);
+    else oh_launch_step_free(s, N, P, D, slot, sweep);
+    if (const int rc = mark(h, r, 2)) return rc;
+    ++r.launched;
+    if (const int rc = look(h, check, &nrun)) return rc;
+    if (nrun == 0) break;
+    if (nrun > 0 && h->sch.compaction && D.B >= 512 && (double)nrun <= h->sch.compact_frac_restart * (double)D.B) {
+      if (const int rc = compact_batch(h, r, nrun, (it + 1) & 1, false)) return rc;
+      sweep = free_sweep(h, D.B);
+      if (const int rc = mark(h, r, 0)) return rc;  // (the compaction kernels are accounted to neither eval nor step: restart the event pair)
+    }
+  }
+  return OH_OK;
+}
+static int traj_epilogue(oh_handle* h, Traj& r) {
+  hipStream_t s = h->stream;
+  finalize(h, r, 0);
+  if (r.guarded) oh_launch_guard_emit(s, h->P, h->D, h->GP, h->GB, r.NV, 0);
+  h->D.B = r.B;
+  if (r.guarded) oh_launch_guard_infeasible(s, r.N, h->P, h->D, h->GP, r.p, r.B, r.kkt, r.status);  // constant rows of the pinned knots
+  if (const int frc = finish_solve(h, r.launched)) return frc;
   unsigned long long work[3] = {0, 0, 0};
   // (on the handle's own stream: a hipMemcpy is an operation of the legacy null stream and waits for the kernels of every other handle's stream -- the other
   //  part of a split solve, the other lane of a pipelined one)
@@ -1913,27 +1930,72 @@ static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, 
   h->timing[6] = (double)work[0];
   h->rejects = (double)work[1];
   h->tail_iters = (double)work[2];
-  if (prof) {
-    double te = 0, tsx = 0, tc = 0;
-    int n_e = 0, n_s = 0;
-    for (size_t i = 1; i < ne; ++i) {
+  if (r.prof) {  // device time by tag (mark): evaluation (1 and 4), sweep, coupling; launches: evaluations (1), sweeps
+    double ms[4] = {0, 0, 0, 0};
+    int n[5] = {0, 0, 0, 0, 0};
+    for (size_t i = 1; i < r.ne; ++i) {
       const int tag = h->prof_tags[i];
-      if (tag == 0) continue;
-      float ms2 = 0.f;
-      hipEventElapsedTime(&ms2, h->prof_events[i - 1], h->prof_events[i]);
-      if (tag == 1) { te += ms2; ++n_e; }
-      else if (tag == 4) { te += ms2; }
-      else if (tag == 3) { tc += ms2; }
-      else { tsx += ms2; ++n_s; }
+      float m = 0.f;
+      if (tag) hipEventElapsedTime(&m, h->prof_events[i - 1], h->prof_events[i]);
+      ms[tag == 4 ? 1 : tag] += m;
+      ++n[tag];
     }
-    h->timing[0] = te;
-    h->timing[1] = n_e;
-    h->timing[2] = tsx;
-    h->timing[3] = n_s;
-    h->timing_couple = tc;
+    h->timing[0] = ms[1]; h->timing[1] = n[1]; h->timing[2] = ms[2]; h->timing[3] = n[2]; h->timing_couple = ms[3];
   }
-  h->timing[7] = compactions;
+  h->timing[7] = r.compactions;
   return OH_OK;
+}
+static int traj_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
+  Traj r{};
+  r.B = B; r.N = h->desc.ndof;
+  r.guarded = h->have_guards; r.lead = h->chain_host.has_lead != 0; r.prof = h->profiling; r.invariant = batch_invariant(h) != 0.0;
+  r.p = (const double*)d_p; r.x = (double*)d_x; r.f = (double*)d_f; r.kkt = (double*)d_kkt; r.iters = (int*)d_iters; r.status = (int*)d_status;
+  if (const int rc = traj_prologue(h, r, d_x0)) return rc;
+  if (const int rc = h->P.lock ? locked_loop(h, r) : free_loop(h, r)) return rc;
+  return traj_epilogue(h, r);
+}
+
+// Parts a batch of the torque, orientation-locked or position-tracking family is solved in (solve_split; 1: this handle alone).  A lane (may_fan_out
+// false) and a profiled handle never split.
+static int split_parts(const oh_handle* h, const int B, const bool may_fan_out) {
+  const int S = std::min(8, (int)optv(h, "streams"));
+  if (!may_fan_out || h->profiling || S < 2) return 1;
+  if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) return (B >= (int)optv(h, "tq_split_min") && B / S >= 64 && h->have_chain && h->have_dyn) ? S : 1;
+  // (batch_invariant handles take part in the split too since their compaction moves everything: an instance's answer does not depend on its part;
+  //  a batch beyond oh_max_batch is refused by ensure_capacity, as ever)
+  if (spec_applies(h) && (batch_invariant(h) == 0.0 || optv(h, "invariant_split") != 0.0) && B >= (int)optv(h, "split_min") && B / S >= 4096 && stage_fits(h, B))
+    return S;
+  // position-tracking family (every launch latency-bound, the machine far from full): two halves side by side -- 1024 arms 9.5 -> 7.3 ms
+  return (!h->desc.lock_orientation && !h->chain_host.has_lead && batch_invariant(h) == 0.0 && B >= (int)optv(h, "free_split_min") && B / S >= 64) ? S : 1;
+}
+
+// The solve of every entry point and every lane, by problem kind: without may_fan_out the batch is never split.  rec (may be null): where the
+// results live, on success.
+static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
+                        const bool may_fan_out, LastSolve* rec) {
+  if (B < 1) return fail(OH_ERR_INVALID, "oh_solve_device: B must be >= 1");
+  if (!d_x0 || !d_p) return fail(OH_ERR_INVALID, "oh_solve_device: x0 and p are required");
+  if (rec) *rec = LastSolve{B, {{h, B}}, false};
+  switch (h->desc.kind) {
+    case OH_PROBLEM_POINT_MASS_MPC: return pm_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    case OH_PROBLEM_IK: return ik_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    case OH_PROBLEM_QP: return qp_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    case OH_PROBLEM_TAPE: return tape_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    case OH_PROBLEM_TORQUE_MPC: break;
+    case OH_PROBLEM_FIGURE_EIGHT:
+      if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
+      if (!solver_chain_ok(h->chain_host)) return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
+      HIPCHK(hipSetDevice(h->device));
+      break;
+    default: return fail(OH_ERR_STATE, "oh_solve_device: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
+  }
+  if (const int S = split_parts(h, B, may_fan_out); S > 1) {
+    // (the kernels compiled for the chain are shared: make sure they exist before the parts look for them)
+    if (spec_applies(h) && !h->spec && !h->spec_failed && h->sch.specialize != OH_SPECIALIZE_NEVER && oh_specialize(h) != OH_OK) h->spec_failed = true;
+    return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
+  }
+  if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) return tq_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+  return traj_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
 }
 
 extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt,
@@ -2062,8 +2124,8 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
   // PCIe run under the other lane's kernels (round 6; until then: upload everything, solve, download everything -- 38 % of the resident rate).  Such a
   // call stages chunks only: the whole batch is never staged.
   const bool tqk = h->desc.kind == OH_PROBLEM_TORQUE_MPC;
-  const int chunk = std::max(1024, (int)optv(h, "pipe_chunk", 32768.0));
-  if ((h->desc.kind == OH_PROBLEM_FIGURE_EIGHT || tqk) && !h->is_peer && !h->profiling && optv(h, "pipe", 1.0) != 0.0 && h->have_chain && !h->have_guards &&
+  const int chunk = std::max(1024, (int)optv(h, "pipe_chunk"));
+  if ((h->desc.kind == OH_PROBLEM_FIGURE_EIGHT || tqk) && !h->is_peer && !h->profiling && optv(h, "pipe") != 0.0 && h->have_chain && !h->have_guards &&
       !h->chain_host.has_lead && B >= 2 * chunk && (!tqk || h->have_dyn)) {
     const int rc = solve_pipelined(h, B, chunk, x0, p, x, f, kkt, iters, status);
     if (rc == OH_OK) h->last = LastSolve{B, {}, true};
@@ -2146,7 +2208,8 @@ extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
     oh_launch_pm_tick_params(s, B, T, k, advance, ramp, st_k, d_obs, d_p);
     double* x_seed = (k & 1) ? d_xb : d_xa;  // previous solution = warm start of this tick
     double* x_sol = (k & 1) ? d_xa : d_xb;
-    oh_launch_pm_solve(s, h->PmP, h->PmD, x_seed, d_p, x_sol, d_f + (size_t)B * k, nullptr, d_it + (size_t)B * k, d_st + (size_t)B * k);
+    oh_launch_pm_solve(s, h->PmP, h->PmD, x_seed, d_p, x_sol, d_f + (size_t)B * k, nullptr, d_it + (size_t)B * k, d_st + (size_t)B * k,
+                       (int)optv(h, "pm_wave_max"));
     oh_launch_pm_advance(s, B, T, advance, x_sol, st_k + 4 * (size_t)B);
   }
   if ((rc = finish_solve(h, n_ticks))) return rc;

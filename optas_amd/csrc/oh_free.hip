@@ -5,7 +5,7 @@
 // simplifies to   S_t = H_t - (2k)^2 S_{t+1}^{-1},  r_t = g_t + 2k S_{t+1}^{-1} r_{t+1},
 //                 z_{t+1} = -S_{t+1}^{-1} r_{t+1} + 2k S_{t+1}^{-1} z_t.
 #include "oh_figure8.h"
-#include "oh_kernels.h"  // OhLaunchOpts
+#include "oh_kernels.h"  // FreeSweep
 
 #define IDX(t, K, k) (((size_t)(t) * (K) + (k)) * Bp + b)
 // Stage blocks W_t (packed, NP) and reduced gradients (N) of this family: knot-major like everything else (a thread per instance reads coalesced), or
@@ -1724,34 +1724,31 @@ bool oh_launch_couple_free(hipStream_t s, int n, const FigParams& P, const FigBu
 #undef C
   return true;
 }
-// pcr: one block per instance (k_step_free_pcr, or k_step_free_cp with eight lanes per knot while the launch has at most free_cp_max instances;
-// the knots must fit 128 lanes)
+// the block-per-instance sweeps (FREE_PCR, FREE_CP, FREE_BB; the knots fit 128 lanes, 64 for FREE_CP: the host's choice)
 template <int N, bool GUARD, bool VEL = false>
-static void launch_step_free_pcr(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, int slot) {
-  const int free_cp_max = oh_launch_opts().free_cp_max;  // (per call: the handle's option "free_cp_max"; a local: the parts of a split solve launch from threads of their own)
+static void launch_step_free_block(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, int slot, FreeSweep sweep) {
   const dim3 g(8 * ((D.B + 7) / 8));
   if constexpr (N == 7) {
-    if (oh_launch_opts().free_bb != 0) {  // option "free_bb" = 0: the cyclic-reduction kernels of rounds 2-3 (A/B, tests)
+    if (sweep == FREE_BB) {
       const int nK = P.T - P.t0, KH = nK - nK / 2;
       hipLaunchKernelGGL((k_step_free_bb<N, GUARD, VEL>), g, dim3(128), sizeof(double) * 2 * (size_t)KH * 72, s, P, D, GB, slot, KH);
       return;
     }
   }
-  // (only up to 64 knots: 128 knots x 8 lanes are 1024 threads, which leaves 128 registers per lane -- the kernel then spills and takes 147 us
-  //  against k_step_free_pcr's 111 at T = 100; at T = 50 it is 61 against 87 us)
-  if (D.B <= free_cp_max && P.T - P.t0 <= 64) {
+  if (sweep == FREE_CP) {
     hipLaunchKernelGGL((k_step_free_cp<N, GUARD, 64, VEL>), g, dim3(512), 0, s, P, D, GB, slot);
     return;
   }
   if (P.T - P.t0 <= 64) hipLaunchKernelGGL((k_step_free_pcr<N, GUARD, 64, VEL>), g, dim3(64), 0, s, P, D, GB, slot);
   else hipLaunchKernelGGL((k_step_free_pcr<N, GUARD, 128, VEL>), g, dim3(128), 0, s, P, D, GB, slot);
 }
-bool oh_launch_step_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool pcr) {
+bool oh_launch_step_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, FreeSweep sweep) {
   const dim3 g((D.B + 63) / 64), b(64);
   const GuardBuffers none{};
-  if (pcr && P.T - P.t0 <= 128 && (n == 7 || n == 6)) {
-    if (n == 7) launch_step_free_pcr<7, false>(s, P, D, none, slot);
-    else launch_step_free_pcr<6, false>(s, P, D, none, slot);
+  if (sweep != FREE_SERIAL) {
+    if (n == 7) launch_step_free_block<7, false>(s, P, D, none, slot, sweep);
+    else if (n == 6) launch_step_free_block<6, false>(s, P, D, none, slot, sweep);
+    else return false;
     return true;
   }
 #define C(NN) hipLaunchKernelGGL((k_step_free<NN, false>), g, b, 0, s, P, D, none, slot)
@@ -1764,9 +1761,8 @@ bool oh_launch_setup_guards(hipStream_t s, int n, const FigParams& P, const FigB
   return true;
 }
 bool oh_launch_free_persist(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB) {
-  if (n != 7) return false;
   const int nK = P.T - P.t0, KH = nK - nK / 2;
-  if (nK > 128) return false;
+  if (n != 7 || nK > 128) return false;  // (instantiated for 7 joints; the LDS holds up to 128 knots)
   hipLaunchKernelGGL(k_free_persist<7>, dim3(8 * ((D.B + 7) / 8)), dim3(128), sizeof(double) * 2 * (size_t)KH * 72, s, P, D, GP, GB, KH, 2 * P.max_iter + 8);
   return true;
 }
@@ -1778,23 +1774,26 @@ bool oh_launch_eval_guarded(hipStream_t s, int n, const FigParams& P, const FigB
   return true;
 }
 template <int N>
-static void launch_step_guarded_t(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot, bool pcr) {
+static bool launch_step_guarded_t(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot, FreeSweep sweep) {
   const dim3 g((D.B + 63) / 64), b(64);
-  if constexpr (N == 6 || N == 7) {  // (the block-per-instance sweeps are written for these lane layouts)
-    if (pcr && P.T - P.t0 <= 128) {
-      if (GP.vel) launch_step_free_pcr<N, true, true>(s, P, D, GB, slot);
-      else launch_step_free_pcr<N, true>(s, P, D, GB, slot);
-      return;
+  if (sweep != FREE_SERIAL) {
+    if constexpr (N == 6 || N == 7) {  // (the block-per-instance sweeps are written for these lane layouts)
+      if (GP.vel) launch_step_free_block<N, true, true>(s, P, D, GB, slot, sweep);
+      else launch_step_free_block<N, true>(s, P, D, GB, slot, sweep);
+      return true;
     }
+    return false;
   }
   if (GP.vel) hipLaunchKernelGGL((k_step_free<N, true, true>), g, b, 0, s, P, D, GB, slot);
   else hipLaunchKernelGGL((k_step_free<N, true>), g, b, 0, s, P, D, GB, slot);
+  return true;
 }
-bool oh_launch_step_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot, bool pcr) {
-#define C(NN) launch_step_guarded_t<NN>(s, P, D, GP, GB, slot, pcr)
+bool oh_launch_step_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot, FreeSweep sweep) {
+  bool ok = false;
+#define C(NN) ok = launch_step_guarded_t<NN>(s, P, D, GP, GB, slot, sweep)
   OH_FREE_DISPATCH_N(n, C)
 #undef C
-  return true;
+  return ok;
 }
 // position-tracking family with joint-velocity rows: multiplier refresh of those rows (outer updates only), then the coupling
 bool oh_launch_couple_free_vel(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot) {

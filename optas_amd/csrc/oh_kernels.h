@@ -27,20 +27,11 @@ bool oh_launch_step(hipStream_t s, int n, const FigParams& P, const FigBuffers& 
 bool oh_launch_eval_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple_free_vel(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot);
-bool oh_launch_step_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool pcr = false);  // pcr: one block per instance
-// Scheduling choices of the launchers that are not part of a kernel's parameter block.  oh_api.hip fills this from the handle's options
-// (oh_set_option) at the start of every call; until round 4 the launchers read OH_* environment variables themselves.
-struct OhLaunchOpts {
-  int free_bb = 1;         // position-tracking family, 7 joints, <= free_pcr_max instances: twisted factorisation (k_step_free_bb); 0: the cyclic-reduction kernels
-  int free_cp_max = 512;   // ... cyclic reduction with eight lanes per knot up to this many instances (horizons <= 64 knots)
-  int pm_wave_max = 20480; // point mass: a wavefront per plant up to this many plants
-  int qp_mode = -1;        // dense QP: -1 automatic, 0 / 1 / 2 force a work-set placement
-  int tape_lds_max = 1 << 30;  // generated tape evaluators: the solver's work set in LDS up to this many instances (0: never)
-  int tape_wave_nt = 256;  // wavefront tape evaluator: threads per instance (256 or 64)
-  int tape_wave_regs = -1; // ... register file: -1 chosen per launch, 0 global memory, 1 LDS
-  int tape_wave_hist = -1; // ... quasi-Newton pairs: -1 in LDS when they fit, 0 global memory
-};
-OhLaunchOpts& oh_launch_opts();  // of the calling thread (a handle is not thread-safe; the options of the handle in the call)
+// Sweep of a position-tracking launch, chosen by the host (oh_api.hip: free_sweep): one lane per instance (k_step_free), or a block per instance
+// by cyclic reduction (k_step_free_pcr), by cyclic reduction with eight lanes per knot (k_step_free_cp), by the twisted factorisation
+// (k_step_free_bb, 7 joints); or the whole solve in one launch (k_free_persist).  The block-per-instance sweeps are instantiated for 6 and 7 joints.
+enum FreeSweep { FREE_SERIAL, FREE_PCR, FREE_CP, FREE_BB, FREE_PERSIST };
+bool oh_launch_step_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, FreeSweep sweep);
 void oh_launch_move_rows(hipStream_t s, void* arr, void* scr, int rows, int Bp, int B, int Bnew, const int* newidx, bool is_int);
 void oh_launch_move_rows_live(hipStream_t s, double* a0, double* a1, double* scr, int rows, int Bp, int B, int Bnew, const int* newidx, const int* cur, const int* curn);
 bool oh_launch_setup_guards(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, const double* p);
@@ -48,7 +39,7 @@ void oh_launch_guard_infeasible(hipStream_t s, int n, const FigParams& P, const 
 bool oh_launch_eval_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot);
 bool oh_launch_free_persist(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB);  // whole solve, one block per instance
 bool oh_launch_step_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot,
-                            bool pcr = false);
+                            FreeSweep sweep);
 bool oh_launch_eval_locked_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot, int part);
 bool oh_launch_step_locked_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot);
 void oh_launch_guard_emit(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int NV, int only_done);
@@ -74,7 +65,7 @@ struct PmBuffers {
   double *a, *X, *s, *lam, *K, *kk, *dX, *da;  // [rows][Bp], rows: 2(T-1), 4T, 9T, 9T, 8(T-1), 2(T-1), 4T, 2(T-1)
 };
 void oh_launch_pm_solve(hipStream_t s, const PmParams& P, const PmBuffers& D, const double* x0, const double* p, double* x, double* f, double* kkt,
-                        int* iters, int* status);
+                        int* iters, int* status, int wave_max);  // wave_max: a wavefront per plant up to this many plants (option pm_wave_max)
 
 void oh_launch_pm_tick_params(hipStream_t s, int B, int T, int tick, int advance, double ramp, const double* state, const double* obs_table, double* p);
 void oh_launch_pm_advance(hipStream_t s, int B, int T, int advance, const double* x, double* state_next);
@@ -156,7 +147,8 @@ struct QpParams {
   double tol;
 };
 void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
-                        int* iters, int* status, double* mult);  // work: [Q.nwork][Bp] (used when the work set of a block does not fit LDS)
+                        int* iters, int* status, double* mult, int mode);  // work: [Q.nwork][Bp] (used when the work set of a block does not fit LDS)
+                                                                           // mode: -1 automatic, 0 / 1 / 2 force a work-set placement (option qp_mode)
 
 // ---- OH_PROBLEM_TAPE ---------------------------------------------------------------------------------------
 #define OH_TAPE_ST_CONVERGED OH_STATUS_CONVERGED
@@ -186,8 +178,10 @@ struct TapeWave {
   double *d_cst_val = nullptr, *d_hist = nullptr, *d_regs = nullptr;
   int hist_cap = 0, regs_cap = 0;
 };
-int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, size_t lds_limit, TapeWave* out,
-                       std::string* err);
+// nt: threads per instance (256 or 64; option tape_wave_nt), regs: register file -1 chosen per launch, 0 global memory, 1 LDS (tape_wave_regs),
+// hist: quasi-Newton pairs -1 in LDS when they fit, 0 global memory (tape_wave_hist)
+int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, size_t lds_limit, int nt, int regs,
+                       int hist, TapeWave* out, std::string* err);
 void oh_tape_wave_release(TapeWave* w);
 hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
                                int* iters, int* status, double* mult);
@@ -202,4 +196,4 @@ int oh_tape_jit_load(const std::vector<char>& code, TapeJit* out, std::string* e
 void oh_tape_jit_forget(const std::string& src);  // drop a cached object that did not load (disk and memory)
 void oh_tape_jit_release(TapeJit* j);
 hipError_t oh_launch_tape_jit(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f,
-                              double* kkt, int* iters, int* status, double* mult);
+                              double* kkt, int* iters, int* status, double* mult, int lds_max);  // lds_max: the work set in LDS up to this many instances (option tape_lds_max)

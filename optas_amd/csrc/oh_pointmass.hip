@@ -664,10 +664,10 @@ __global__ __launch_bounds__(64) void k_pm_infeasible(PmParams P, int B, const d
 }
 
 void oh_launch_pm_solve(hipStream_t s, const PmParams& P, const PmBuffers& D, const double* x0, const double* p, double* x, double* f, double* kkt,
-                        int* iters, int* status) {
+                        int* iters, int* status, const int wave_max) {
   // a wavefront per instance while that leaves the chip room (the thread kernel issues ~8x fewer instructions per instance, but needs ~10^5
-  // instances to fill the SIMDs: 1024 plants take 3.5 ms with it and 0.7 ms here)
-  const int wave_max = oh_launch_opts().pm_wave_max;  // option "pm_wave_max", default 20480  // (tools/gpu_pm_sweep.py: 16 384 plants 6.8 / 5.8 ms thread / wave kernel, 32 768 9.8 / 11.3 ms)
+  // instances to fill the SIMDs: 1024 plants take 3.5 ms with it and 0.7 ms here); wave_max: option "pm_wave_max", default 20480
+  // (tools/gpu_pm_sweep.py: 16 384 plants 6.8 / 5.8 ms thread / wave kernel, 32 768 9.8 / 11.3 ms)
   if (P.T <= 64 && D.B <= wave_max) hipLaunchKernelGGL(k_pm_solve_wave, dim3(D.B), dim3(64), 0, s, P, D.B, x0, p, x, f, kkt, iters, status);
   else hipLaunchKernelGGL(k_pm_solve, dim3((D.B + 63) / 64), dim3(64), 0, s, P, D, x0, p, x, f, kkt, iters, status);
   if (status || kkt) hipLaunchKernelGGL(k_pm_infeasible, dim3((D.B + 63) / 64), dim3(64), 0, s, P, D.B, p, kkt, status);

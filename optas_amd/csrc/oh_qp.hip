@@ -618,21 +618,20 @@ void oh_launch_qp_add_constant(hipStream_t s, int B, double* f, const double* f0
 }
 
 void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
-                        int* iters, int* status, double* mult) {
+                        int* iters, int* status, double* mult, const int forced) {
   // the work set of a block in LDS when it fits 48 KB at 64, 32 or 16 instances per block; for a few instances the problem row as well
   auto fit = [](const size_t doubles) {
     for (int c : {64, 32, 16})
       if (sizeof(double) * doubles * c <= 48 * 1024) return c;
     return 0;
   };
-  const int forced = oh_launch_opts().qp_mode;  // option "qp_mode" (experiments)
   const int bs2 = fit((size_t)Q.nwork + Q.np), bs1 = fit((size_t)Q.nwork);
   const size_t wave_bytes = sizeof(double) * ((size_t)Q.nwork + Q.np);
   if (forced != 0 && forced != 1 && forced != 2 && B <= 64 && wave_bytes <= 48 * 1024) {  // a few instances: one wavefront each
     hipLaunchKernelGGL(k_qp_solve_wave, dim3(B), dim3(64), wave_bytes, s, Q, B, x0, p, x, f, kkt, iters, status, mult);
     return;
   }
-  int mode = bs2 ? 2 : (bs1 ? 1 : 0);  // (velocity-IK QP, n = 7, m = 16: B = 1 in 1.77 / 1.49 / 1.15 ms wall, 65 536 in 13.0 / 12.7 / 11.5 ms for modes 0 / 1 / 2)
+  int mode = bs2 ? 2 : (bs1 ? 1 : 0);  // forced: option "qp_mode" (experiments)  // (velocity-IK QP, n = 7, m = 16: B = 1 in 1.77 / 1.49 / 1.15 ms wall, 65 536 in 13.0 / 12.7 / 11.5 ms for modes 0 / 1 / 2)
   if (forced == 0 || (forced == 1 && bs1) || (forced == 2 && bs2)) mode = forced;
   if (mode == 2)
     hipLaunchKernelGGL(k_qp_solve<2>, dim3((B + bs2 - 1) / bs2), dim3(bs2), sizeof(double) * ((size_t)Q.nwork + Q.np) * bs2, s, Q, B, Bp, x0, p, work, x, f, kkt, iters,

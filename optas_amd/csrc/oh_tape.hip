@@ -449,13 +449,12 @@ void oh_tape_jit_release(TapeJit* j) {
 }
 
 hipError_t oh_launch_tape_jit(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f,
-                              double* kkt, int* iters, int* status, double* mult) {
+                              double* kkt, int* iters, int* status, double* mult, const int lds_max) {
   void* args[] = {&T, &B, &Bp, &x0, &p, &work, &x, &f, &kkt, &iters, &status, &mult};
   // the solver's work set in LDS when it fits 48 KB at 64, 32 or 16 instances per block (tools/gpu_tape_sweep.py, the 7-joint IK problem: one
-  // instance 5.0 -> 3.4 ms, 2048 14.3 -> 10.9 ms, 32 768 25.8 -> 21.0 ms; option tape_lds_max = 0 switches it off)
+  // instance 5.0 -> 3.4 ms, 2048 14.3 -> 10.9 ms, 32 768 25.8 -> 21.0 ms; lds_max: option tape_lds_max, 0 switches it off)
   // (round 2: level above 32 768 instances -- 65 536: 30.2 / 33.5 ms, 131 072: 47.5 / 44.9 ms global / LDS; with the solver of round 3's end, which
   // spends 65 evaluations instead of 266 on the median instance, the LDS set wins at every size: 65 536: 9.8 / 7.7 ms, 131 072: 17.5 / 13.2 ms)
-  const int lds_max = oh_launch_opts().tape_lds_max;  // option "tape_lds_max"
   if (j.fn_lds && B <= lds_max) {
     const size_t per = sizeof(double) * tape_solver_rows(T);
     for (int bs : {64, 32, 16})

@@ -536,13 +536,13 @@ size_t oh_tape_wave_lds_bytes(const TapeParams& T, const TapeWave& W, bool hist_
 
 // Schedule of a tape for the wavefront-per-instance evaluator.  Returns 0 and leaves out->ready false when the path does not apply (dense BFGS
 // regime, or the register file does not fit lds_limit); 1 on an allocation failure.
-int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, size_t lds_limit, TapeWave* out,
-                       std::string* err) {
+int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, size_t lds_limit, const int nt,
+                       const int regs, const int hist, TapeWave* out, std::string* err) {
   *out = TapeWave{};
   if (T.lbfgs <= 0) return 0;
   // threads per instance: four wavefronts (the register file allows one block per CU: one wavefront would leave three SIMDs idle, and the wide
   // first levels of a trajectory tape are 400-800 instructions); option tape_wave_nt = 64: one
-  const int NT = oh_launch_opts().tape_wave_nt == 64 ? 64 : 256;  // option "tape_wave_nt"
+  const int NT = nt == 64 ? 64 : 256;  // option "tape_wave_nt"
   out->nt = NT;
   const int L = T.len, nrows = T.n_ineq + T.n_eq;
   auto is_binary = [](int o) { return (o >= 3 && o <= 6) || o == 10 || (o >= 15 && o <= 20) || (o >= 22 && o <= 24); };
@@ -709,13 +709,13 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   // Placement of the register file, decided per launch: in LDS (one block per CU: the lowest latency) for small batches, in global memory
   // (the block's own lines; the LDS then holds the vectors and the pairs only: two or more blocks per CU) for large ones and for tapes whose
   // registers do not fit -- the planner: 4 instances 96 / 125 ms, 4096 instances 1.99 / 1.60 s.  Same arithmetic, same bits either way.
-  out->reg_choice = oh_launch_opts().tape_wave_regs;  // option "tape_wave_regs": 0 global / 1 LDS forces one placement
+  out->reg_choice = regs;  // option "tape_wave_regs": 0 global / 1 LDS forces one placement
   out->reg_lds_fits = oh_tape_wave_lds_bytes(T, *out, false, true) <= lds_limit;
   const bool global_ok = NT == 256 && oh_tape_wave_lds_bytes(T, *out, false, false) <= lds_limit;  // (the global-memory placement is built for four wavefronts)
   if (!out->reg_lds_fits && !global_ok) return 0;  // not even the vectors fit: the thread-per-instance path stays
   if (!global_ok) out->reg_choice = 1;
   if (!out->reg_lds_fits) out->reg_choice = 0;
-  const bool hist_global = oh_launch_opts().tape_wave_hist == 0;  // option "tape_wave_hist" = 0: keep the (s, y) pairs out of the LDS even when they fit (the path big problems take)
+  const bool hist_global = hist == 0;  // option "tape_wave_hist" = 0: keep the (s, y) pairs out of the LDS even when they fit (the path big problems take)
   for (int rl = 0; rl < 2; ++rl) {
     out->hist_lds_by[rl] = oh_tape_wave_lds_bytes(T, *out, true, rl == 1) <= lds_limit && !hist_global;
     out->lds_bytes_by[rl] = oh_tape_wave_lds_bytes(T, *out, out->hist_lds_by[rl], rl == 1);
