@@ -31,8 +31,9 @@ extern "C" {
    built with, and a host binding refuses a library that answers otherwise (a binding that misreads a descriptor fails silently).
    5: round 5 -- OH_STATUS_INFEASIBLE / OH_STATUS_ACCEPTABLE, oh_set_option / oh_get_option, oh_tq_rollout, tape opcodes 25-26.
    6: round 5 -- oh_tape_set_metric.
-   7: round 6 -- OH_MAX_T 256, oh_comm_allgather, options tol / pipe / pipe_chunk, OH_STATUS_INFEASIBLE from the point-mass iteration, oh_solve in chunks on two lanes. */
-#define OH_ABI_VERSION 7
+   7: round 6 -- OH_MAX_T 256, oh_comm_allgather, options tol / pipe / pipe_chunk, OH_STATUS_INFEASIBLE from the point-mass iteration, oh_solve in chunks on two lanes.
+   8: oh_tape_phi. */
+#define OH_ABI_VERSION 8
 
 #define OH_MAX_CHAIN 16 /* actuated joints on one root->link chain */
 #define OH_MAX_T 256    /* horizon knots (128 until round 6; the persistent kernels take horizons of up to 64 / 128 free knots, longer ones run in batched launches) */
@@ -333,6 +334,19 @@ int oh_create_tape(const oh_tape_desc* desc, oh_handle** out);
 int oh_tape_probe(oh_handle* h, int B, const double* x, const double* p, int n_regs, const int* regs, double* val, const double* seeds, double* adj,
                   double* grad);
 
+/* ONE evaluation of the augmented-Lagrangian merit of an OH_PROBLEM_TAPE handle per instance, by the evaluator oh_solve would launch for this handle and
+   this B (the interpreter, the generated code with its work set in global memory or in LDS, the wavefront-per-instance evaluator with the register placement
+   of that batch size), at given points x [B][nx], parameters p [B][np], multipliers lam [B][n_ineq] (>= 0), mu [B][n_eq] and penalty rho > 0:
+     merit [B] = f + sum_i (max(0, lam_i - rho g_i)^2 - lam_i^2) / (2 rho) + sum_j (-mu_j c_j + rho c_j^2 / 2),   grad [B][nx] its gradient in x,
+     f [B], rows [B][n_ineq + n_eq] = (g, c), cmax [B] = max(max_i max(0, -g_i), max_j |c_j|), meas [B] = max(max_i |min(g_i, lam_i / rho)|, max_j |c_j|).
+   Host buffers; arrays of a length that is zero may be NULL.  The generated code's single-evaluation kernels are compiled by the first call, not with the
+   handle.  Convention of the gradient (this entry, the solver's evaluations and oracle/tape_ref.py alike): the reverse sweep multiplies every
+   instruction's adjoint through in IEEE arithmetic, also an adjoint that is exactly 0.  0 * (a non-finite partial derivative) is NaN: sqrt at 0, or
+   sqrt(x) at x < 0 behind IFZ(x > 0, .), makes the gradient NaN whatever the weight of that term.  Only IFZ, FMIN and FMAX cut a path: they hand
+   their adjoint to one operand and add nothing to the other. */
+int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, double* merit, double* f, double* rows,
+                double* grad, double* cmax, double* meas);
+
 /* Initial metric of an OH_PROBLEM_TAPE handle's limited-memory quasi-Newton iteration: H0 [nx][nx], symmetric positive definite, host memory (copied);
    NULL takes it away again.  The two-loop recursion then starts from r = H0 q instead of the identity scaled by the newest pair.  The reference hands
    IPOPT the exact Hessian of the Lagrangian (optimization.py:8-24, solver.py:355-384); this is the part of it that is known before the first solve:
@@ -401,7 +415,8 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    k_retract + k_evalb_zc + k_step_zc, the neighbour coupling folded in; 0: k_couple runs as a launch of its own), "tail_threshold",
    "specialized"; OH_PROBLEM_TAPE handles: "tape_wave" (0: one thread per instance; 1 / 2: one block of wavefronts per instance, the quasi-Newton
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
-   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation). */
+   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_jit_lds" (1: the last oh_tape_phi ran
+   the generated code's entry with its work set in LDS). */
 int oh_get_flag(oh_handle* h, const char* name, int* value);
 
 /*

@@ -237,8 +237,25 @@ class TapeBackend(_SolveMixin):
                                              _lib._ptr(seeds), _lib._ptr(adj) if (adj is not None and len(regs)) else None, _lib._ptr(grad)), "oh_tape_probe")
         return val, adj, grad
 
+    def phi(self, x, p, lam, mu, rho):
+        """oh_tape_phi: ONE evaluation of the augmented-Lagrangian merit per instance by the evaluator solve() would launch for this handle and this batch
+        size, at x (B, nx), p (B, np) with multipliers lam (B, n_ineq), mu (B, n_eq) and penalty rho.  Returns a dict: merit (B,), f (B,), rows (B, n_ineq + n_eq),
+        grad (B, nx), cmax (B,), meas (B,)."""
+        x = _lib.as_f64(x).reshape(-1, self.nx)
+        B = x.shape[0]
+        ni, ne = int(self.tape.n_ineq), int(self.tape.n_eq)
+        p = _lib.as_f64(p).reshape(B, -1) if self._np_real else np.zeros((B, 1))
+        assert p.shape == (B, self.np_), f"p must be (B, {self.np_})"
+        lam = _lib.as_f64(np.zeros((B, 0)) if lam is None else lam).reshape(B, ni)
+        mu = _lib.as_f64(np.zeros((B, 0)) if mu is None else mu).reshape(B, ne)
+        out = {"merit": np.empty(B), "f": np.empty(B), "rows": np.empty((B, ni + ne)), "grad": np.empty((B, self.nx)), "cmax": np.empty(B), "meas": np.empty(B)}
+        ptr = lambda a: _lib._ptr(a) if a.size else None
+        _lib.check(_lib.load().oh_tape_phi(self._h, B, _lib._ptr(x), _lib._ptr(p), ptr(lam), ptr(mu), float(rho), _lib._ptr(out["merit"]), _lib._ptr(out["f"]),
+                                           ptr(out["rows"]), _lib._ptr(out["grad"]), _lib._ptr(out["cmax"]), _lib._ptr(out["meas"])), "oh_tape_phi")
+        return out
+
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric'."""
+        """oh_get_flag: 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric'."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)

@@ -105,6 +105,8 @@ struct oh_handle {
   double* d_tape_h0 = nullptr;  // oh_tape_set_metric: initial metric of the limited-memory form [nx][nx]
   int tape_cap = 0;
   TapeJit tape_jit;
+  TapeJit tape_jit_phi;       // the single-evaluation kernels of the same generated evaluator: compiled by the first oh_tape_phi, not with the handle
+  int tape_phi_lds = 0;       // whether the last oh_tape_phi ran the generated code's entry with the work set in LDS
   TapeWave tape_wave;  // trajectory-sized tapes: one wavefront per instance (oh_tape_wave.hip)
   // dense QP family
   oh_qp_desc qp{};
@@ -584,7 +586,22 @@ extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
     oh_destroy(h);  // (releases the wavefront schedule / the generated module built above as well)
     return fail(OH_ERR_HIP, "oh_create_tape: stream/event/allocation failed");
   }
-  hipMemcpy(h->d_tape_op, d->op, li, hipMemcpyHostToDevice);
+  // the interpreter's copy of the opcodes carries bit 5 on every instruction that neither the cost nor a row depends on: its reverse sweep passes them by
+  // (oh_tape.hip:InterpEval::reverse), as the generated code and the wavefront schedule do
+  std::vector<int> op_dev(d->op, d->op + d->len);
+  {
+    std::vector<char> live(d->len, 0);
+    live[d->out_cost] = 1;
+    for (int i = 0; i < d->n_ineq + d->n_eq; ++i) live[d->rows[i]] = 1;
+    for (int i = d->len - 1; i >= 0; --i) {
+      if (!live[i]) { op_dev[i] |= 32; continue; }
+      if (d->op[i] >= 3) {
+        live[d->a[i]] = 1;
+        if (tape_op_arity(d->op[i]) == 2) live[d->b[i]] = 1;
+      }
+    }
+  }
+  hipMemcpy(h->d_tape_op, op_dev.data(), li, hipMemcpyHostToDevice);
   hipMemcpy(h->d_tape_a, d->a, li, hipMemcpyHostToDevice);
   hipMemcpy(h->d_tape_b, d->b, li, hipMemcpyHostToDevice);
   hipMemcpy(h->d_tape_c, d->c, ld, hipMemcpyHostToDevice);
@@ -660,9 +677,8 @@ extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
   return OH_OK;
 }
 
-static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
-  HIPCHK(hipSetDevice(h->device));
-  const int Bp = (B + 63) / 64 * 64;
+// work arrays of the thread-per-instance evaluators and the multipliers' buffer for batches of up to Bp instances
+static int tape_ensure_work(oh_handle* h, const int Bp) {
   if (Bp > h->tape_cap) {
     if (h->d_tape_work) hipFree(h->d_tape_work);
     if (h->d_tape_mult) hipFree(h->d_tape_mult);
@@ -672,6 +688,65 @@ static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* 
     HIPCHK(hipMalloc((void**)&h->d_tape_mult, sizeof(double) * (size_t)(h->TP.n_ineq + h->TP.n_eq + 1) * Bp));
     h->tape_cap = Bp;
   }
+  return OH_OK;
+}
+
+extern "C" int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, double* merit, double* f,
+                           double* rows, double* grad, double* cmax, double* meas) {
+  if (!h || !x || !merit || !f || !grad || !cmax || !meas) return fail(OH_ERR_INVALID, "oh_tape_phi: null argument");
+  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_phi: handle is not an OH_PROBLEM_TAPE problem");
+  const TapeParams& T = h->TP;
+  const int nrow = T.n_ineq + T.n_eq;
+  if (B < 1 || (T.np > 0 && !p) || (T.n_ineq > 0 && !lam) || (T.n_eq > 0 && !mu) || (nrow > 0 && !rows)) return fail(OH_ERR_INVALID, "oh_tape_phi: bad sizes");
+  if (!(rho > 0.0)) return fail(OH_ERR_INVALID, "oh_tape_phi: the penalty must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  const int Bp = (B + 63) / 64 * 64;
+  if (h->tape_jit.fn && !h->tape_wave.ready && !h->tape_jit_phi.fn) {
+    std::vector<char> code;
+    std::string err;
+    const std::string src = oh_tape_jit_source(T, h->t_op.data(), h->t_a.data(), h->t_b.data(), h->t_c.data(), h->t_rows.empty() ? nullptr : h->t_rows.data(), false);
+    if (oh_tape_jit_compile(src, &code, &err) || oh_tape_jit_load(code, &h->tape_jit_phi, &err, false)) return fail(OH_ERR_HIP, ("oh_tape_phi: " + err).c_str());
+  }
+  if (const int rc = tape_ensure_work(h, Bp)) return rc;
+  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t b_x = al(sizeof(double) * (size_t)T.nx * B), b_p = al(sizeof(double) * (size_t)(T.np > 0 ? T.np : 1) * B),
+               b_l = al(sizeof(double) * (size_t)(T.n_ineq > 0 ? T.n_ineq : 1) * B), b_m = al(sizeof(double) * (size_t)(T.n_eq > 0 ? T.n_eq : 1) * B),
+               b_r = al(sizeof(double) * (size_t)(nrow > 0 ? nrow : 1) * B), b_1 = al(sizeof(double) * (size_t)B);
+  if (const int rc = ensure_stage(h, 2 * b_x + b_p + b_l + b_m + b_r + 4 * b_1)) return rc;
+  char* base = (char*)h->stage;
+  auto take = [&](size_t bytes) { double* o = (double*)base; base += bytes; return o; };
+  double *d_x = take(b_x), *d_g = take(b_x), *d_p = take(b_p), *d_l = take(b_l), *d_m = take(b_m), *d_r = take(b_r), *d_v = take(b_1), *d_f = take(b_1),
+         *d_c = take(b_1), *d_s = take(b_1);
+  hipStream_t s = h->stream;
+  HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T.nx * B, hipMemcpyHostToDevice, s));
+  if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * B, hipMemcpyHostToDevice, s));
+  if (T.n_ineq > 0) HIPCHK(hipMemcpyAsync(d_l, lam, sizeof(double) * (size_t)T.n_ineq * B, hipMemcpyHostToDevice, s));
+  if (T.n_eq > 0) HIPCHK(hipMemcpyAsync(d_m, mu, sizeof(double) * (size_t)T.n_eq * B, hipMemcpyHostToDevice, s));
+  h->tape_phi_lds = 0;
+  // the evaluator oh_solve launches for this handle and this B (tape_solve_device)
+  if (h->tape_wave.ready)
+    HIPCHK(oh_launch_tape_wave_phi(s, h->tape_wave, T, B, d_x, d_p, d_l, d_m, rho, d_v, d_f, d_r, d_g, d_c, d_s));
+  else if (h->tape_jit.fn)
+    HIPCHK(oh_launch_tape_jit_phi(s, h->tape_jit_phi, T, B, h->tape_cap, d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f, d_r, d_g, d_c, d_s,
+                                  (int)optv(h, "tape_lds_max"), &h->tape_phi_lds));
+  else
+    oh_launch_tape_phi(s, T, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap, d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f,
+                       d_r, d_g, d_c, d_s);
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(merit, d_v, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(f, d_f, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cmax, d_c, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(meas, d_s, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(grad, d_g, sizeof(double) * (size_t)T.nx * B, hipMemcpyDeviceToHost));
+  if (nrow > 0) HIPCHK(hipMemcpy(rows, d_r, sizeof(double) * (size_t)nrow * B, hipMemcpyDeviceToHost));
+  return OH_OK;
+}
+
+static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
+  HIPCHK(hipSetDevice(h->device));
+  const int Bp = (B + 63) / 64 * 64;
+  if (const int rc = tape_ensure_work(h, Bp)) return rc;
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   if (h->tape_wave.ready)
     HIPCHK(oh_launch_tape_wave(h->stream, h->tape_wave, h->TP, B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters,
@@ -2484,6 +2559,7 @@ extern "C" void oh_destroy(oh_handle* h) {
   if (h->evt0) hipEventDestroy(h->evt0);
   if (h->evt1) hipEventDestroy(h->evt1);
   oh_tape_jit_release(&h->tape_jit);
+  oh_tape_jit_release(&h->tape_jit_phi);
   oh_tape_wave_release(&h->tape_wave);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -2738,7 +2814,8 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 }
 // How the handle's last solve was (or its next one will be) scheduled, by name: "fuse_couple" (1: coupling folded into evaluation and sweep, no
 // k_couple launch), "tail_threshold", "specialized"; tape handles: "tape_wave" (0: thread per instance, 1 / 2: wavefront per instance with the (s, y)
-// pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation).
+// pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
+// oh_tape_phi ran the generated code's entry with the work set in LDS).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
   const std::string n(name);
@@ -2749,6 +2826,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "specialized") *value = h->spec ? 1 : 0;
   else if (n == "tape_wave") *value = h->tape_wave.ready ? (h->tape_wave.hist_lds ? 2 : 1) : 0;
   else if (n == "tape_regs_lds") *value = h->tape_wave.ready && h->tape_wave.reg_lds ? 1 : 0;
+  else if (n == "tape_jit_lds") *value = h->tape_phi_lds;
   else if (n == "tape_metric") *value = (h->TP.h0 && h->TP.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape_wave.n_levels;
   else if (n == "tape_passes") *value = h->tape_wave.n_fw_pass + h->tape_wave.n_rv_pass;

@@ -185,15 +185,26 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
 void oh_tape_wave_release(TapeWave* w);
 hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
                                int* iters, int* status, double* mult);
+// one WaveEval::phi per instance (oh_tape_phi): the register placement oh_launch_tape_wave would choose for this B
+hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x, const double* p, const double* lam, const double* mu,
+                                   double rho, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas);
 size_t oh_tape_work_rows(const TapeParams& T, bool jit);
+// one InterpEval::phi per instance (oh_tape_phi); work as for oh_launch_tape_solve
+void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                        const double* x, const double* p, const double* lam, const double* mu, double rho, double* work, double* merit, double* f, double* rowv,
+                        double* grad, double* cmax, double* meas);
 void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
                           const double* x, const double* p, double* work, int n_regs, const int* regs, double* val, const double* seeds, double* adj, double* grad);
 void oh_launch_tape_solve(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
                           const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status, double* mult);
-std::string oh_tape_jit_source(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows);
+// solve = false: the program of the single-evaluation kernels (k_tape_jit_phi, k_tape_jit_phi_lds) around the same evaluator text
+std::string oh_tape_jit_source(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, bool solve = true);
 int oh_tape_jit_compile(const std::string& src, std::vector<char>* code, std::string* err);  // hiprtc for gfx950; needs no device
-int oh_tape_jit_load(const std::vector<char>& code, TapeJit* out, std::string* err);
+int oh_tape_jit_load(const std::vector<char>& code, TapeJit* out, std::string* err, bool solve = true);
 void oh_tape_jit_forget(const std::string& src);  // drop a cached object that did not load (disk and memory)
 void oh_tape_jit_release(TapeJit* j);
+hipError_t oh_launch_tape_jit_phi(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x, const double* p, const double* lam, const double* mu,
+                                  double rho, double* work, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas, int lds_max,
+                                  int* used_lds);  // used_lds: whether the launch took the entry with the work set in LDS
 hipError_t oh_launch_tape_jit(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f,
                               double* kkt, int* iters, int* status, double* mult, int lds_max);  // lds_max: the work set in LDS up to this many instances (option tape_lds_max)

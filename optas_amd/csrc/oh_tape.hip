@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -50,7 +51,7 @@ struct InterpEval {
   __device__ void forward(const double* __restrict__ xs) {
 #pragma clang fp contract(off)
     for (int i = 0; i < T.len; ++i) {
-      const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
+      const int o = tv.op[i] & 31, ia = tv.a[i], ib = tv.bb[i];  // (bit 5: dead, see reverse)
       double v;
       switch (o) {
         case 0: v = tv.c[i]; break;
@@ -94,6 +95,9 @@ struct InterpEval {
     for (int i = T.len - 1; i >= 0; --i) {
       const double w = adj[TIDX(i)];
       const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
+      // An instruction neither the cost nor a row depends on (marked by the host, oh_create_tape) has no part in the gradient: the generated code and the
+      // wavefront schedule leave it out, and so does this sweep -- its adjoint is 0, but 0 times a non-finite partial derivative (a dead x / 0) is not.
+      if (o & 32) continue;
       switch (o) {
         case 0: case 2: break;
         case 1: grad[TIDX(ia)] += w; break;
@@ -107,7 +111,8 @@ struct InterpEval {
         case 10: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)], d = va * va + vb * vb; adj[TIDX(ia)] += w * vb / d; adj[TIDX(ib)] -= w * va / d; } break;
         case 11: adj[TIDX(ia)] += w * 0.5 / val[TIDX(i)]; break;
         case 12: adj[TIDX(ia)] += w * 2.0 * val[TIDX(ia)]; break;
-        case 13: { const double va = val[TIDX(ia)]; adj[TIDX(ia)] += w / sqrt(1.0 - va * va); } break;
+        // (1 - a)(1 + a), not 1 - a a: both factors are exact near |a| = 1, where a a rounds by as much as is left of 1 - a a (half the digits of the slope at 1 - 1e-8, all of them at 1 - 1e-16)
+        case 13: { const double va = val[TIDX(ia)]; adj[TIDX(ia)] += w / sqrt((1.0 - va) * (1.0 + va)); } break;
         case 14: { const double va = val[TIDX(ia)]; adj[TIDX(ia)] += w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); } break;
         case 15: if (val[TIDX(ia)] <= val[TIDX(ib)]) adj[TIDX(ia)] += w; else adj[TIDX(ib)] += w; break;  // casadi: d fmin = (x <= y, !(x <= y))
         case 16: if (val[TIDX(ia)] >= val[TIDX(ib)]) adj[TIDX(ia)] += w; else adj[TIDX(ib)] += w; break;
@@ -186,6 +191,18 @@ __global__ __launch_bounds__(64) void k_tape_probe(TapeParams T, TapeView tv, in
     for (int k = 0; k < T.nx; ++k) grad_out[(size_t)b * T.nx + k] = gr[TIDX(k)];
 }
 
+// One InterpEval::phi per instance at given points, multipliers and penalty (oh_tape_phi).  work: the solve kernel's layout.
+__global__ __launch_bounds__(64) void k_tape_phi(TapeParams T, TapeView tv, int B, int Bp, const double* __restrict__ x, const double* __restrict__ par,
+                                                 const double* __restrict__ lam, const double* __restrict__ mu, double rho, double* __restrict__ work,
+                                                 double* __restrict__ merit, double* __restrict__ fo, double* __restrict__ rows, double* __restrict__ grad,
+                                                 double* __restrict__ cmax, double* __restrict__ meas) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const TapeWork W = tape_carve(T, work + 2 * (size_t)T.len * Bp, Bp);
+  InterpEval ev{T, tv, W, work, work + (size_t)T.len * Bp, par + (size_t)b * T.np, Bp, b};
+  tape_phi_instance(T, ev, W, Bp, b, b, x, lam, mu, rho, merit, fo, rows, grad, cmax, meas);
+}
+
 // ---- code generation ------------------------------------------------------------------------------------------------------------------
 void emit(std::string& s, const char* fmt, ...) {
   char buf[512];
@@ -196,7 +213,20 @@ void emit(std::string& s, const char* fmt, ...) {
   s += buf;
 }
 
-std::string generate(const TapeParams& T, const int* op, const int* a, const int* bb, const double* c, const int* rows) {
+// A double as a C++ expression: hexadecimal floating literal; the non-finite values, which have no literal, through the compiler's builtins
+// (fmin(x, inf) is a legal casadi graph)
+std::string literal(const double v) {
+  if (v != v) return "__builtin_nan(\"\")";
+  if (v == HUGE_VAL) return "__builtin_inf()";
+  if (v == -HUGE_VAL) return "(-__builtin_inf())";
+  char buf[64];
+  snprintf(buf, sizeof buf, "%a", v);
+  return buf;
+}
+
+// solve: the two solver kernels behind the evaluator (what a handle is created with); otherwise the two single-evaluation kernels of oh_tape_phi,
+// a program of its own compiled when first asked for
+std::string generate(const TapeParams& T, const int* op, const int* a, const int* bb, const double* c, const int* rows, const bool solve = true) {
   std::string s;
   s.reserve(64 * (size_t)T.len + sizeof(OH_TAPE_SOLVER_SRC) + 4096);
   emit(s, "#define OH_TAPE_ST_CONVERGED %d\n#define OH_TAPE_ST_MAX_ITER %d\n#define OH_TAPE_ST_NUMERICAL %d\n", (int)OH_STATUS_CONVERGED, (int)OH_STATUS_MAX_ITER,
@@ -218,7 +248,7 @@ std::string generate(const TapeParams& T, const int* op, const int* a, const int
   for (int i = 0; i < T.len; ++i) {
     if (!live[i]) continue;
     switch (op[i]) {
-      case 0: emit(s, "    const double v%d = %a;\n", i, c[i]); break;
+      case 0: emit(s, "    const double v%d = %s;\n", i, literal(c[i]).c_str()); break;
       case 1: emit(s, "    const double v%d = xs[TIDX(%d)];\n", i, a[i]); break;
       case 2: emit(s, "    const double v%d = pb[%d];\n", i, a[i]); break;
       case 3: emit(s, "    const double v%d = v%d + v%d;\n", i, a[i], bb[i]); break;
@@ -310,7 +340,7 @@ std::string generate(const TapeParams& T, const int* op, const int* a, const int
         if (da) emit(s, "    a%d += a%d * 2.0 * v%d;\n", ia, i, ia);
         break;
       case 13:
-        if (da) emit(s, "    a%d += a%d / sqrt(1.0 - v%d * v%d);\n", ia, i, ia, ia);
+        if (da) emit(s, "    a%d += a%d / sqrt((1.0 - v%d) * (1.0 + v%d));\n", ia, i, ia, ia);
         break;
       case 14:
         if (da) emit(s, "    a%d += a%d * (v%d > 0.0 ? 1.0 : (v%d < 0.0 ? -1.0 : 0.0));\n", ia, i, ia, ia);
@@ -337,6 +367,23 @@ std::string generate(const TapeParams& T, const int* op, const int* a, const int
   }
   for (int k = 0; k < T.nx; ++k) emit(s, "    gout[TIDX(%d)] = g%d;\n", k, k);
   emit(s, "    *fout = v%d; *cmax = cm; *meas = ms;\n    return val;\n  }\n};\n", T.out_cost);
+  if (!solve) {
+    s += "extern \"C\" __global__ __launch_bounds__(64) void k_tape_jit_phi(TapeParams T, int B, int Bp, const double* __restrict__ x, const double* __restrict__ par,\n"
+         "    const double* __restrict__ lam, const double* __restrict__ mu, double rho, double* __restrict__ work, double* __restrict__ merit, double* __restrict__ fo,\n"
+         "    double* __restrict__ rows, double* __restrict__ grad, double* __restrict__ cmax, double* __restrict__ meas) {\n"
+         "  const int b = blockIdx.x * blockDim.x + threadIdx.x;\n  if (b >= B) return;\n"
+         "  const TapeWork W = tape_carve(T, work, Bp);\n  JitEval ev{W, par + (size_t)b * T.np, Bp, b};\n"
+         "  tape_phi_instance(T, ev, W, Bp, b, b, x, lam, mu, rho, merit, fo, rows, grad, cmax, meas);\n}\n";
+    s += "extern \"C\" __global__ __launch_bounds__(64) void k_tape_jit_phi_lds(TapeParams T, int B, int Bp_unused, const double* __restrict__ x, const double* __restrict__ par,\n"
+         "    const double* __restrict__ lam, const double* __restrict__ mu, double rho, double* __restrict__ work_unused, double* __restrict__ merit, double* __restrict__ fo,\n"
+         "    double* __restrict__ rows, double* __restrict__ grad, double* __restrict__ cmax, double* __restrict__ meas) {\n"
+         "  extern __shared__ double tape_lds[];\n"
+         "  const int gb = blockIdx.x * blockDim.x + threadIdx.x;\n  if (gb >= B) return;\n"
+         "  const int Bp = blockDim.x, b = threadIdx.x;\n"
+         "  const TapeWork W = tape_carve(T, tape_lds, Bp);\n  JitEval ev{W, par + (size_t)gb * T.np, Bp, b};\n"
+         "  tape_phi_instance(T, ev, W, Bp, b, gb, x, lam, mu, rho, merit, fo, rows, grad, cmax, meas);\n}\n";
+    return s;
+  }
   s += "extern \"C\" __global__ __launch_bounds__(64) void k_tape_jit(TapeParams T, int B, int Bp, const double* __restrict__ x0, const double* __restrict__ par,\n"
        "    double* __restrict__ work, double* __restrict__ xo, double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters,\n"
        "    int* __restrict__ status, double* __restrict__ mult) {\n"
@@ -375,8 +422,15 @@ void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, con
   hipLaunchKernelGGL(k_tape_probe, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, x, p, work, n_regs, regs, val, seeds, adj, grad);
 }
 
-std::string oh_tape_jit_source(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows) {
-  return generate(T, op, a, b, c, rows);
+void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                        const double* x, const double* p, const double* lam, const double* mu, double rho, double* work, double* merit, double* f, double* rowv,
+                        double* grad, double* cmax, double* meas) {
+  TapeView tv{op, a, b, c, rows};
+  hipLaunchKernelGGL(k_tape_phi, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, x, p, lam, mu, rho, work, merit, f, rowv, grad, cmax, meas);
+}
+
+std::string oh_tape_jit_source(const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, const bool solve) {
+  return generate(T, op, a, b, c, rows, solve);
 }
 
 int oh_tape_jit_compile(const std::string& src, std::vector<char>* code, std::string* err) {
@@ -425,19 +479,21 @@ void oh_tape_jit_forget(const std::string& src) {
   g_code_cache.erase(src);
 }
 
-int oh_tape_jit_load(const std::vector<char>& code, TapeJit* out, std::string* err) {
+int oh_tape_jit_load(const std::vector<char>& code, TapeJit* out, std::string* err, const bool solve) {
+  const char* name = solve ? "k_tape_jit" : "k_tape_jit_phi";
+  const char* name_lds = solve ? "k_tape_jit_lds" : "k_tape_jit_phi_lds";
   if (hipModuleLoadData(&out->mod, code.data()) != hipSuccess) {
     (void)hipGetLastError();
     *err = "hipModuleLoadData failed for the generated tape kernel";
     return 1;
   }
-  if (hipModuleGetFunction(&out->fn, out->mod, "k_tape_jit") != hipSuccess) {
+  if (hipModuleGetFunction(&out->fn, out->mod, name) != hipSuccess) {
     hipModuleUnload(out->mod);
     out->mod = nullptr;
-    *err = "hipModuleGetFunction(k_tape_jit) failed";
+    *err = std::string("hipModuleGetFunction(") + name + ") failed";
     return 1;
   }
-  if (hipModuleGetFunction(&out->fn_lds, out->mod, "k_tape_jit_lds") != hipSuccess) out->fn_lds = nullptr;
+  if (hipModuleGetFunction(&out->fn_lds, out->mod, name_lds) != hipSuccess) out->fn_lds = nullptr;
   return 0;
 }
 
@@ -448,9 +504,24 @@ void oh_tape_jit_release(TapeJit* j) {
   j->fn_lds = nullptr;
 }
 
+// the launch of either program of a generated evaluator (solve kernels / single-evaluation kernels): the same choice of entry and block size
+static hipError_t launch_jit(hipStream_t s, const TapeJit& j, const TapeParams& T, int B, void** args, int lds_max);
+
+hipError_t oh_launch_tape_jit_phi(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x, const double* p, const double* lam, const double* mu,
+                                  double rho, double* work, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas, const int lds_max,
+                                  int* used_lds) {
+  void* args[] = {&T, &B, &Bp, &x, &p, &lam, &mu, &rho, &work, &merit, &f, &rowv, &grad, &cmax, &meas};
+  if (used_lds) *used_lds = (j.fn_lds && B <= lds_max && sizeof(double) * tape_solver_rows(T) * 16 <= 48 * 1024) ? 1 : 0;
+  return launch_jit(s, j, T, B, args, lds_max);
+}
+
 hipError_t oh_launch_tape_jit(hipStream_t s, const TapeJit& j, TapeParams T, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f,
                               double* kkt, int* iters, int* status, double* mult, const int lds_max) {
   void* args[] = {&T, &B, &Bp, &x0, &p, &work, &x, &f, &kkt, &iters, &status, &mult};
+  return launch_jit(s, j, T, B, args, lds_max);
+}
+
+static hipError_t launch_jit(hipStream_t s, const TapeJit& j, const TapeParams& T, int B, void** args, const int lds_max) {
   // the solver's work set in LDS when it fits 48 KB at 64, 32 or 16 instances per block (tools/gpu_tape_sweep.py, the 7-joint IK problem: one
   // instance 5.0 -> 3.4 ms, 2048 14.3 -> 10.9 ms, 32 768 25.8 -> 21.0 ms; lds_max: option tape_lds_max, 0 switches it off)
   // (round 2: level above 32 768 instances -- 65 536: 30.2 / 33.5 ms, 131 072: 47.5 / 44.9 ms global / LDS; with the solver of round 3's end, which

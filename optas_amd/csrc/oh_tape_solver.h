@@ -317,4 +317,25 @@ __device__ inline void tape_solve_instance(const TapeParams& T, E& ev, const Tap
   }
 }
 
+// ONE E::phi at a given point with given multipliers and penalty (oh_tape_phi): what the solver above calls, handed out as it is, so that a test can
+// compare the evaluators instruction by instruction with each other and with a high-precision reference.  Same work arrays, same addressing.
+template <class E>
+__device__ inline void tape_phi_instance(const TapeParams& T, E& ev, const TapeWork& W, const int Bp, const int b, const int gb, const double* __restrict__ x,
+                                         const double* __restrict__ lam, const double* __restrict__ mu, const double rho, double* __restrict__ merit,
+                                         double* __restrict__ fo, double* __restrict__ rows, double* __restrict__ grad, double* __restrict__ cmax,
+                                         double* __restrict__ meas) {
+  const int n = T.nx, nr = T.n_ineq + T.n_eq;
+  for (int k = 0; k < n; ++k) W.x[TIDX(k)] = x[(size_t)gb * n + k];
+  for (int i = 0; i < T.n_ineq; ++i) W.lam[TIDX(i)] = lam[(size_t)gb * T.n_ineq + i];
+  for (int i = 0; i < T.n_eq; ++i) W.mu[TIDX(i)] = mu[(size_t)gb * T.n_eq + i];
+  double fv, cm, ms;
+  const double v = ev.phi(W.x, W.g, rho, &fv, &cm, &ms);
+  merit[gb] = v;
+  fo[gb] = fv;
+  cmax[gb] = cm;
+  meas[gb] = ms;
+  for (int i = 0; i < nr; ++i) rows[(size_t)gb * nr + i] = W.rowv[TIDX(i)];
+  for (int k = 0; k < n; ++k) grad[(size_t)gb * n + k] = W.g[TIDX(k)];
+}
+
 #endif  // OH_TAPE_SOLVER_H

@@ -65,7 +65,7 @@ __device__ inline double wmax(double v) { return wreduce<true>(v); }
 // Selector bits of the five operations that make up nine tenths of a trajectory tape, decoded on the host into the entry (a pass is bound by
 // the number of instructions one wavefront issues -- DESIGN 2.6 -- and compares / selects on the opcode, which the compiler turns back into
 // masked branches, were two thirds of them):
-//   value    = MUL ? va * (SQR ? va : vb) : (+-va) + (ZB ? 0 : +-vb)        add: 0 | sub: NEGB | mul: MUL | sqr: MUL SQR | neg: NEGA ZB
+//   value    = MUL ? va * (SQR ? va : vb) : (+-va) + (ZB ? 0 : +-vb)        add: 0 | sub: NEGB | mul: MUL | sqr: MUL SQR | (NEGA ZB: -a + 0, no longer scheduled -- NEG is a product with -1)
 //   adjoints = MUL ? (w * (SQR ? 2 va : vb), SQR ? 0 : w * va) : (+-w, ZB ? 0 : +-w)
 // applied with bit masks (v_bfi / v_xor), never with control flow.  RARE: every other operation, behind one wavefront-uniform test.
 constexpr int F_MUL = 1, F_SQR = 2, F_NEGA = 4, F_NEGB = 8, F_ZB = 16, F_RARE = 32;
@@ -227,7 +227,7 @@ struct WaveEval {
               case 9: ca = -(w * sin(va)); break;
               case 10: { const double d = va * va + vb * vb; ca = w * vb / d; cb = -(w * va / d); } break;
               case 11: ca = w * 0.5 / val[i]; break;
-              case 13: ca = w / sqrt(1.0 - va * va); break;
+              case 13: ca = w / sqrt((1.0 - va) * (1.0 + va)); break;  // (as InterpEval::reverse writes it)
               case 14: ca = w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); break;
               case 15: if (va <= vb) ca = w; else cb = w; break;
               case 16: if (va >= vb) ca = w; else cb = w; break;
@@ -516,6 +516,57 @@ __global__ __launch_bounds__(NT) void k_tape_wave(TapeParams T, WaveSchedDev S, 
   }
 }
 
+// ONE WaveEval::phi per instance at given points, multipliers and penalty (oh_tape_phi): the set-up of k_tape_wave (same LDS layout, the quasi-Newton
+// pairs left out), one evaluation, the results written out.
+template <int NT, bool REG_LDS>
+__global__ __launch_bounds__(NT) void k_tape_wave_phi(TapeParams T, WaveSchedDev S, int B, const double* __restrict__ x, const double* __restrict__ par,
+                                                      const double* __restrict__ lam_in, const double* __restrict__ mu_in, double rho, double* regs_g,
+                                                      double* __restrict__ merit, double* __restrict__ fo, double* __restrict__ rows, double* __restrict__ grad,
+                                                      double* __restrict__ cmax, double* __restrict__ meas) {
+  extern __shared__ double lds[];
+  const int gb = blockIdx.x, lane = threadIdx.x;
+  if (gb >= B) return;
+  const int n = T.nx, m = T.lbfgs, ni = T.n_ineq, ne = T.n_eq;
+  double *val, *adj, *X;
+  if constexpr (REG_LDS) {
+    val = lds;
+    adj = val + S.n_reg;
+    X = adj + S.n_reg;
+  } else {
+    val = regs_g + (size_t)gb * 2 * S.n_reg;
+    adj = val + S.n_reg;
+    X = lds;
+  }
+  double* G = X + 2 * n;
+  double* lam = X + 5 * n;
+  double* mu = lam + (ni > 0 ? ni : 1);
+  double* rowv = mu + (ne > 0 ? ne : 1);
+  double* roww = rowv + (S.nrows > 0 ? S.nrows : 1);
+  double* redbuf = roww + (S.nrows > 0 ? S.nrows : 1) + 2 * m;
+  int* small = reinterpret_cast<int*>(redbuf + 8);
+  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
+  const int* row_reg = small;
+  const int* seed_reg = row_reg + S.nrows;
+  const int* seed_off = seed_reg + S.n_seed;
+  const int* seed_rows = seed_off + S.n_seed + 1;
+  const double* pb = par + (size_t)gb * T.np;
+  if (lane == 0) { val[ZREG] = 0.0; adj[ZREG] = 0.0; val[TRASH] = 0.0; adj[TRASH] = 0.0; }
+  for (int k = lane; k < S.n_cst; k += NT) val[S.cst_reg[k]] = S.cst_val[k];
+  for (int k = lane; k < S.n_par; k += NT) val[S.par_reg[k]] = pb[S.par_k[k]];
+  for (int k = lane; k < n; k += NT) X[k] = x[(size_t)gb * n + k];
+  for (int i = lane; i < ni; i += NT) lam[i] = lam_in[(size_t)gb * ni + i];
+  for (int i = lane; i < ne; i += NT) mu[i] = mu_in[(size_t)gb * ne + i];
+  __syncthreads();
+  Red<NT> red{redbuf};
+  WaveEval<NT, REG_LDS> ev{T, S, val, adj, lam, mu, rowv, roww, row_reg, seed_reg, seed_off, seed_rows, lane, red};
+  double f_, c_, m_;
+  const double v_ = ev.phi(X, G, rho, &f_, &c_, &m_);
+  __syncthreads();
+  if (lane == 0) { merit[gb] = v_; fo[gb] = f_; cmax[gb] = c_; meas[gb] = m_; }
+  for (int r = lane; r < S.nrows; r += NT) rows[(size_t)gb * S.nrows + r] = rowv[r];
+  for (int k = lane; k < n; k += NT) grad[(size_t)gb * n + k] = G[k];
+}
+
 template <class V>
 int upload(V** dst, const std::vector<V>& src) {
   *dst = nullptr;
@@ -568,6 +619,11 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
     }
     if (op[i] >= 3) level[i] = 1 + std::max(level[a[i]], is_binary(op[i]) ? level[b[i]] : 0);
   }
+  // NEG runs as a product with a register that holds -1 (exact, and -1 * +0 = -0 as IEEE negation gives it); the selector form (-a) + (+0) of the
+  // entry turned -(+0) into +0, which atan2(-x, c < 0) and 1 / (-x) then showed as 2 pi and as the other infinity at x = 0
+  int neg_one = -1;
+  for (int i = 0; i < L && neg_one < 0; ++i)
+    if (live[i] && op[i] == 7) neg_one = n_reg++;
   if (n_reg >= (1 << 18)) return 0;
   out->n_reg = n_reg;
   int n_lvl = 0;
@@ -624,7 +680,9 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   for (int l = 1; l <= n_lvl; ++l) {
     slots_of[l] = arrange(by_level[l]);
     for (int i : slots_of[l])
-      fw.push_back(i < 0 ? idle_entry : int4{reg[i] | (op[i] << OPSH), reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0, flags_of(op[i])});
+      fw.push_back(i < 0          ? idle_entry
+                   : op[i] == 7 ? int4{reg[i] | (5 << OPSH), reg[a[i]], neg_one, F_MUL}
+                                : int4{reg[i] | (op[i] << OPSH), reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0, flags_of(op[i])});
   }
   // ---- consumers of every register that carries an adjoint, in the order the serial reverse sweep adds them (descending instruction index)
   std::vector<std::vector<int>> cons(n_reg);
@@ -663,7 +721,8 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   for (int l = n_lvl; l >= 1; --l)
     for (int i : slots_of[l]) {
       if (i >= 0) {
-        rv_entry(reg[i], op[i], reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0);
+        if (op[i] == 7) rv_entry(reg[i], 5, reg[a[i]], neg_one);  // (its share for the -1 register lands in a slot nobody gathers)
+        else rv_entry(reg[i], op[i], reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0);
       } else {
         rv.push_back(idle_entry);
         rv.push_back(int4{0, 0, 0, 0});
@@ -684,6 +743,7 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
     if (op[i] == 0) { cst_reg.push_back(reg[i]); cst_val.push_back(c[i]); }
     if (op[i] == 2) { par_reg.push_back(reg[i]); par_k.push_back(a[i]); }
   }
+  if (neg_one >= 0) { cst_reg.push_back(neg_one); cst_val.push_back(-1.0); }
   for (int r = 0; r < nrows; ++r) small.push_back(reg[rows[r]]);
   for (int r : seed_reg) small.push_back(r);
   int off = 0;
@@ -752,10 +812,8 @@ void oh_tape_wave_release(TapeWave* w) {
   *w = TapeWave{};
 }
 
-hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
-                               int* iters, int* status, double* mult) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+// Placement of the register file for a launch of B instances, and the global buffer when that is where they go
+static hipError_t wave_place_registers(TapeWave& W, const int B) {
   // registers in LDS up to two instances per CU's worth of batch, in global memory beyond (OH_TAPE_WAVE_REGS forces one)
   W.reg_lds = W.reg_choice >= 0 ? W.reg_choice == 1 : B <= 512;
   W.hist_lds = W.hist_lds_by[W.reg_lds ? 1 : 0];
@@ -768,6 +826,14 @@ hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, 
     if (e != hipSuccess) return e;
     W.regs_cap = B;
   }
+  return hipSuccess;
+}
+
+hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
+                               int* iters, int* status, double* mult) {
+  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  if (const hipError_t e = wave_place_registers(W, B)) return e;
   if (!W.hist_lds && B > W.hist_cap) {
     if (W.d_hist) hipFree(W.d_hist);
     W.d_hist = nullptr;
@@ -783,5 +849,25 @@ hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, 
   else if (W.nt == 64) { if (W.hist_lds) OH_TW_LAUNCH(64, true, true); else OH_TW_LAUNCH(64, false, true); }
   else { if (W.hist_lds) OH_TW_LAUNCH(256, true, true); else OH_TW_LAUNCH(256, false, true); }
 #undef OH_TW_LAUNCH
+  return hipGetLastError();
+}
+
+hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x, const double* p, const double* lam, const double* mu,
+                                   double rho, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas) {
+  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  if (const hipError_t e = wave_place_registers(W, B)) return e;
+  const size_t bytes = oh_tape_wave_lds_bytes(T, W, false, W.reg_lds);  // the solve kernel's layout without the quasi-Newton pairs
+  double* rg = W.reg_lds ? nullptr : W.d_regs;
+#define OH_TW_PHI(NTv, Rv)                                                                                                                       \
+  do {                                                                                                                                            \
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_phi<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
+    if (e != hipSuccess) return e;                                                                                                                \
+    hipLaunchKernelGGL((k_tape_wave_phi<NTv, Rv>), dim3(B), dim3(NTv), bytes, s, T, S, B, x, p, lam, mu, rho, rg, merit, f, rowv, grad, cmax, meas);      \
+  } while (0)
+  if (!W.reg_lds) OH_TW_PHI(256, false);
+  else if (W.nt == 64) OH_TW_PHI(64, true);
+  else OH_TW_PHI(256, true);
+#undef OH_TW_PHI
   return hipGetLastError();
 }

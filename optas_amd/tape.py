@@ -177,6 +177,8 @@ class TapeBuilder:
 
     # ---- round 5: exp and log as instructions; the other elementary functions casadi offers (`from casadi import *`, optas/__init__.py:2)
     # composed from the instruction set, so that every evaluator, the reverse sweeps included, has two cases more and not twelve ---------------
+    # These compositions are accurate in absolute terms (error relative to max(1, |result|)), not relative to a small result: expm1, log1p, sinh, tanh, atanh and
+    # asinh keep half their digits relative to a result near 0, where casadi's own log1p / expm1 keep all of them (tests/test_tape_mp_reference.py).
     def exp(self, a):
         return self._fold1(OP_EXP, a, lambda v: float(np.exp(v)))
 
@@ -210,8 +212,11 @@ class TapeBuilder:
         return self.exp(self.mul(b, self.log(a)))
 
     def tanh(self, a):
-        """1 - 2 / (exp(2x) + 1): exact limits -1 / +1 where exp under- / overflows."""
-        return self.sub(self.const(1.0), self.div(self.const(2.0), self.add(self.exp(self.add(a, a)), self.const(1.0))))
+        """s (1 - t) / (1 + t) with t = exp(-2 |x|), s = -1 for x < 0, else +1: t underflows to 0 for large |x|, value +-1 and slope 0.  (1 - 2 / (exp(2x) + 1) had
+        the same limits in the value, but its reverse sweep multiplies the adjoint 0 of the overflowed exp(2x) by its value inf: a NaN gradient from x = 355 on.)"""
+        s = self.sub(self.const(1.0), self.mul(self.const(2.0), self.lt(a, self.const(0.0))))
+        t = self.exp(self.mul(self.const(-2.0), self.mul(s, a)))
+        return self.mul(s, self.div(self.sub(self.const(1.0), t), self.add(self.const(1.0), t)))
 
     def sinh(self, a):
         return self.mul(self.const(0.5), self.sub(self.exp(a), self.exp(self.neg(a))))
@@ -229,10 +234,15 @@ class TapeBuilder:
         return self.div(self.sin(a), self.cos(a))
 
     def asinh(self, a):
-        return self.log(self.add(a, self.sqrt(self.add(self.sqr(a), self.const(1.0)))))
+        """s log(s x + sqrt(x^2 + 1)) with s = -1 for x < 0, else +1: the textbook log(x + sqrt(x^2 + 1)) cancels for negative arguments (asinh(-3e4) 1e-7 off in
+        the derivative, asinh(-1e9) = -inf).  s x = |x| with the slope s, also at 0, where FABS has the slope 0.  Holds while x^2 is finite (|x| < 1.3e154)."""
+        s = self.sub(self.const(1.0), self.mul(self.const(2.0), self.lt(a, self.const(0.0))))
+        return self.mul(s, self.log(self.add(self.mul(s, a), self.sqrt(self.add(self.sqr(a), self.const(1.0))))))
 
     def acosh(self, a):
-        return self.log(self.add(a, self.sqrt(self.sub(self.sqr(a), self.const(1.0)))))
+        """log(x + sqrt((x - 1)(x + 1))): x^2 - 1 cancels near the end x = 1 of the domain (slope 2e-11 off at 1 + 1e-6), the factors do not."""
+        one = self.const(1.0)
+        return self.log(self.add(a, self.sqrt(self.mul(self.sub(a, one), self.add(a, one)))))
 
     def atanh(self, a):
         return self.mul(self.const(0.5), self.log(self.div(self.add(self.const(1.0), a), self.sub(self.const(1.0), a))))

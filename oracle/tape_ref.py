@@ -6,6 +6,7 @@ import numpy as np
 OP_CONST, OP_X, OP_P, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_SIN, OP_COS, OP_ATAN2, OP_SQRT, OP_SQR = range(13)
 OP_ASIN, OP_FABS, OP_FMIN, OP_FMAX, OP_LT, OP_LE, OP_EQ, OP_NE, OP_NOT, OP_AND, OP_OR, OP_IFZ = range(13, 25)
 OP_EXP, OP_LOG = 25, 26
+_BINARY = frozenset([3, 4, 5, 6, 10, 15, 16, 17, 18, 19, 20, 22, 23, 24])
 
 
 def forward(tape, x, p):
@@ -44,9 +45,9 @@ def forward(tape, x, p):
         elif o == OP_FABS:
             v[i] = abs(v[a])
         elif o == OP_FMIN:
-            v[i] = min(v[a], v[b])
+            v[i] = np.fmin(v[a], v[b])  # C's fmin / fmax: the operand that is a number where the other is NaN
         elif o == OP_FMAX:
-            v[i] = max(v[a], v[b])
+            v[i] = np.fmax(v[a], v[b])
         elif o == OP_LT:
             v[i] = float(v[a] < v[b])
         elif o == OP_LE:
@@ -71,17 +72,24 @@ def forward(tape, x, p):
 
 
 def reverse(tape, v, seeds):
-    """Gradient wrt x of sum_r seeds[r] * register r  (seeds: dict register -> weight)."""
+    """Gradient wrt x of sum_r seeds[r] * register r  (seeds: dict register -> weight).  Like the device evaluators (include/optas_hip.h, oh_tape_phi) the sweep
+    multiplies every adjoint through, one that is exactly 0 included: 0 times a non-finite partial derivative is NaN here as it is there."""
     L = tape.op.shape[0]
     adj = np.zeros(L)
     for r, w in seeds.items():
         adj[r] += w
     g = np.zeros(tape.nx)
+    reach = np.zeros(L, dtype=bool)  # what the seeded registers depend on: the rest has no part in the gradient (a dead x / 0 must not put 0 * inf into it)
+    reach[list(seeds)] = True
     for i in range(L - 1, -1, -1):
-        w = adj[i]
-        if w == 0.0:
+        if not reach[i]:
             continue
+        w = adj[i]
         o, a, b = tape.op[i], tape.a[i], tape.b[i]
+        if o >= 3:
+            reach[a] = True
+            if o in _BINARY:
+                reach[b] = True
         if o == OP_X:
             g[a] += w
         elif o == OP_ADD:
@@ -111,9 +119,9 @@ def reverse(tape, v, seeds):
         elif o == OP_SQR:
             adj[a] += w * 2.0 * v[a]
         elif o == OP_ASIN:
-            adj[a] += w / np.sqrt(1.0 - v[a] * v[a])
+            adj[a] += w / np.sqrt((1.0 - v[a]) * (1.0 + v[a]))  # both factors exact near |a| = 1 (csrc/oh_tape.hip)
         elif o == OP_FABS:
-            adj[a] += w * np.sign(v[a])
+            adj[a] += w * (1.0 if v[a] > 0.0 else (-1.0 if v[a] < 0.0 else 0.0))  # 0 at 0 (and at NaN, as the kernels' two comparisons give it)
         elif o == OP_FMIN:  # casadi/core/calculus.hpp: d fmin = (x <= y, !(x <= y))
             if v[a] <= v[b]:
                 adj[a] += w
@@ -192,8 +200,7 @@ def solve_tape_al(tape, x0, p, tol=1e-6, tol_feas=1e-9, max_iter=2000, rho0=10.0
         val = v[tape.out_cost] + np.sum((s * s - lam * lam) / (2.0 * rho)) + np.sum(-mu * c + 0.5 * rho * c * c)
         seeds = {int(tape.out_cost): 1.0}
         for i in range(ni):
-            if s[i] > 0.0:
-                seeds[int(rows[i])] = seeds.get(int(rows[i]), 0.0) - s[i]
+            seeds[int(rows[i])] = seeds.get(int(rows[i]), 0.0) - s[i]
         for i in range(ne):
             seeds[int(rows[ni + i])] = seeds.get(int(rows[ni + i]), 0.0) + (-mu[i] + rho * c[i])
         return val, reverse(tape, v, seeds), g, c, v[tape.out_cost]

@@ -54,6 +54,7 @@ def test_invalid_arguments_are_rejected_without_a_device_call():
     assert lib.oh_create(C.byref(d), C.byref(h)) == 1 and b"T must be" in lib.oh_last_error()
     assert lib.oh_solve(None, 1, None, None, None, None, None, None, None) == 1
     assert lib.oh_fk_jac(None, 1, None, None, None) == 1
+    assert lib.oh_tape_phi(None, 1, None, None, None, None, 1.0, None, None, None, None, None, None) == 1 and b"oh_tape_phi" in lib.oh_last_error()
 
 
 @pytest.mark.skipif(_lib.device_count() > 0, reason="only meaningful on a box without a GPU")

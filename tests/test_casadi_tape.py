@@ -116,10 +116,16 @@ def test_elementary_functions_walk_to_exp_log_and_compositions():
         assert np.abs(grad - fd).max() < 2e-7 * max(1.0, np.abs(fd).max())
 
 
+# the wavefront evaluator forced onto a small problem (option tape_lbfgs > 0): one wavefront / four, registers in LDS / in global memory (four wavefronts only)
+WAVE_FORCED = ({"tape_wave_nt": 64, "tape_wave_regs": "lds"}, {"tape_wave_nt": 256, "tape_wave_regs": "lds"}, {"tape_wave_nt": 256, "tape_wave_regs": "global"})
+
+
 @pytest.mark.gpu
-def test_elementary_functions_solve_on_the_gpu(hip_lib):
-    """The same graph through all three evaluators of the tape family (interpreter, generated code; the wavefront evaluator runs it when forced):
+def test_elementary_functions_solve_on_the_gpu(hip_lib, monkeypatch):
+    """The same graph through all three evaluators of the tape family (interpreter, generated code, and the wavefront evaluator forced onto this
+    3-variable problem through the limited-memory regime, at both block widths and both register placements):
     each ends in a KKT point of the problem as the numpy restatement of the tape sees it, and in the same one."""
+    from conftest import oh_debug
     from optas_amd.backend import TapeBackend
 
     f, g = _elementary_functions()
@@ -129,9 +135,15 @@ def test_elementary_functions_solve_on_the_gpu(hip_lib):
     X0, P = rng.uniform(-0.3, 0.3, (B, 3)), rng.uniform(-1, 1, (B, 2))
     ref = tape_ref.solve_tape_al(tp, X0[0], P[0], tol=1e-7)
     results = []
-    for jit in (False, True):
+    for jit, wave in ((False, None), (True, None)) + tuple((False, w) for w in WAVE_FORCED):
+        oh_debug(monkeypatch, tape_lbfgs=None, tape_wave_nt=None, tape_wave_regs=None)
+        if wave is not None:
+            oh_debug(monkeypatch, tape_lbfgs=8, **wave)
         be = TapeBackend(tp, max_iter=3000, tol=1e-7, jit=jit)
+        assert (be.flag("tape_wave") >= 1) == (wave is not None)
         r = be.solve(X0, P)
+        if wave is not None:
+            assert be.flag("tape_wave") >= 1 and be.flag("tape_regs_lds") == (0 if wave["tape_wave_regs"] == "global" else 1)
         lam, _ = be.multipliers(B)
         be.close()
         assert (r.status == 0).all()
@@ -143,6 +155,8 @@ def test_elementary_functions_solve_on_the_gpu(hip_lib):
             gl = tape_ref.reverse(tp, v, {int(tp.out_cost): 1.0, **{int(rr): -float(l) for rr, l in zip(tp.out_rows, lam[b])}})
             assert np.abs(gl).max() <= 1e-6 and (lam[b] >= 0).all() and np.abs(lam[b] * rows).max() <= 1e-7
     assert np.abs(results[0].x - results[1].x).max() <= 1e-6 and np.abs(results[0].x[0] - ref["x"]).max() <= 1e-5
+    for r in results[2:]:
+        assert np.abs(results[0].x - r.x).max() <= 1e-6
 
 
 @pytest.mark.gpu
@@ -391,8 +405,8 @@ def test_rpy_clip_and_logic_opcodes_walk_and_differentiate():
 
 
 @pytest.mark.gpu
-def test_rpy_term_through_the_literal_subclass_on_the_gpu(hip_lib):
-    """A problem with a roll / pitch term and a clipped variable solved through the literal Solver subclass (interpreter and generated-HIP path) against
+def test_rpy_term_through_the_literal_subclass_on_the_gpu(hip_lib, monkeypatch):
+    """A problem with a roll / pitch term and a clipped variable solved through the literal Solver subclass (interpreter, generated-HIP path and the forced wavefront evaluator) against
     scipy SLSQP on the same functions -- the round-3 verdict's `get_global_link_rpy` case, at the level of the opcodes it consists of."""
 
     class Solver:
@@ -413,12 +427,19 @@ def test_rpy_term_through_the_literal_subclass_on_the_gpu(hip_lib):
     goal = np.array([0.3, -0.2])
     x0 = np.array([0.1, 0.2, 0.1, 0.9])
     results = []
-    for jit in (True, False):
+    from conftest import oh_debug
+
+    for jit, wave in ((True, None), (False, None)) + tuple((False, w) for w in WAVE_FORCED):
+        oh_debug(monkeypatch, tape_lbfgs=None, tape_wave_nt=None, tape_wave_regs=None)
+        if wave is not None:
+            oh_debug(monkeypatch, tape_lbfgs=8, **wave)
         opt = FakeOptimization()
         opt.f, opt.g = _rpy_functions()
         opt.h = None
         opt.nx = 4
         solver = HIPSolver(opt).setup("hip_sqp", {"tol": 1e-8, "jit": jit})
+        backend = getattr(solver._backend, "inner", solver._backend)
+        assert (backend.flag("tape_wave") >= 1) == (wave is not None)
         solver.reset_initial_seed({"q": x0})
         solver.reset_parameters({"goal": goal})
         q = solver.solve()["q"]

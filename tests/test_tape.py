@@ -133,3 +133,16 @@ def test_tape_kernel_matches_port_and_goldens(hip_lib, jit):
     o = solver.opt
     x = o.decision_variables.dict2vec(sol)
     assert o.k(x, np.zeros(0)).min() > -1e-9 and o.g(x, np.zeros(0)).min() > -1e-9 and np.abs(o.h(x, np.zeros(0))).max() < 1e-8
+
+
+def test_generated_code_takes_non_finite_constants():
+    """fmin(x, inf) is a legal graph; printed with %a the constant came out as `inf`, no C++ literal, and hiprtc refused the handle.  Needs no GPU."""
+    from optas_amd.backend import TapeBackend
+    from optas_amd.tape import Tape
+
+    op = np.array([1, 0, 0, 0, 15, 16, 3, 12], dtype=np.int32)
+    a = np.array([0, 0, 0, 0, 0, 4, 5, 6], dtype=np.int32)
+    b = np.array([0, 0, 0, 0, 1, 2, 3, 0], dtype=np.int32)
+    c = np.array([0.0, np.inf, -np.inf, np.nan, 0.0, 0.0, 0.0, 0.0])
+    src, size = TapeBackend.generated_source(Tape(op, a, b, c, 7, np.zeros(0, dtype=np.int32), 0, 0, 1, 0))
+    assert size > 0 and "__builtin_inf()" in src and "(-__builtin_inf())" in src and "__builtin_nan" in src
