@@ -42,6 +42,8 @@ static int fail(int code, const std::string& msg) {
 struct Sched {
   int compaction = 1;
   int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
+  int compact_fused = 1;     // ... and the retraction compiled for the chain lays the knots down at their new index itself (oh_spec_retract_move;
+                             // 0: k_retract, then k_carry_gather moves them)
   int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see locked_loop)
   int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
   int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
@@ -161,6 +163,7 @@ struct oh_handle {
   int specialize_min_B = 4096;
   const FigSpec* spec = nullptr;
   bool spec_failed = false;
+  bool spec_move_failed = false;  // the moving retraction did not launch once: this handle's carried compactions gather as before
   bool spec_cache_checked = false;  // automatic mode has looked for a cached code object once (reset with the constants)
   const FkSpec* fk_spec = nullptr;  // K1 for this chain (any handle with constants)
   bool fk_spec_failed = false;
@@ -236,6 +239,7 @@ struct FieldOpt {
 static const FieldOpt FIELD_OPTS[] = {
     {"tail_threshold", &Sched::tail_threshold}, {"free_pcr_max", &Sched::free_pcr_max}, {"compaction", &Sched::compaction, nullptr, true},
     {"compact_frac", nullptr, &Sched::compact_frac}, {"compact_sort", &Sched::compact_sort}, {"compact_carry", &Sched::compact_carry},
+    {"compact_fused", &Sched::compact_fused, nullptr, true},
     {"tail_vel", &Sched::tail_vel}, {"lg_split", &Sched::lg_split}, {"tail_vel_threshold", &Sched::tail_vel_threshold},
     {"fuse_couple", &Sched::fuse_couple, nullptr, true}, {"sparse_check_below", &Sched::sparse_check_below}, {"specialize", &Sched::specialize},
     {"tq_check", &Sched::tq_check},
@@ -1231,6 +1235,7 @@ static void adopt_chain(oh_handle* h, const oh_chain& c) {
   h->have_chain = true;
   h->spec = nullptr;
   h->spec_failed = false;
+  h->spec_move_failed = false;
   h->spec_cache_checked = false;
   h->fk_spec = nullptr;
   h->fk_spec_failed = false;
@@ -1904,11 +1909,32 @@ static int locked_loop(oh_handle* h, Traj& r) {
     else if (r.lead) oh_launch_eval_lead(s, N, P, D, slot);
     else if (carry_pending > 0) {
       // compaction with the trial carried along: retract on the old layout, move, evaluate on the dense one (k_carry_* in oh_kernels.hip)
-      launch_eval(h, r, slot, 1);
-      if (const int rc = mark(h, r, 4)) return rc;
-      finalize(h, r, 1);
-      oh_launch_scan_running(s, D, h->sch.compact_sort);
-      oh_launch_carry(s, N, P, D, 0, 0, slot);
+      bool moved = false, scanned = false;
+      if (r.spec && r.spec->retract_move && h->sch.compact_fused && !h->spec_move_failed) {
+        // the new indices first (the scan reads status and stat, final since the last sweep; the retraction writes neither): the retraction compiled
+        // for the chain then lays the free knots down where they go, and what is left to gather are the pinned knots and the scalars
+        finalize(h, r, 1);
+        oh_launch_scan_running(s, D, h->sch.compact_sort);
+        scanned = true;
+        if (const int rc = mark(h, r, 0)) return rc;
+        moved = oh_spec_launch_eval(*r.spec, s, P, D, slot, 3) == hipSuccess;
+        if (moved) {
+          if (const int rc = mark(h, r, 4)) return rc;
+          oh_launch_carry(s, N, P, D, 2, 0, slot);
+        } else {
+          (void)hipGetLastError();
+          h->spec_move_failed = true;
+        }
+      }
+      if (!moved) {
+        launch_eval(h, r, slot, 1);
+        if (const int rc = mark(h, r, 4)) return rc;
+        if (!scanned) {  // (after a failed launch of the moving retraction the results are out and the scan is done already)
+          finalize(h, r, 1);
+          oh_launch_scan_running(s, D, h->sch.compact_sort);
+        }
+        oh_launch_carry(s, N, P, D, 0, 0, slot);
+      }
       oh_launch_carry(s, N, P, D, 1, carry_pending, slot);
       // the knots were laid down densely in the spare arrays: they become q[] / Gfull[] for the launches that follow (no copy back)
       std::swap(D.q[slot], D.q_spare[0]);

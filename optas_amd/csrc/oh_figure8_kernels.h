@@ -7,9 +7,10 @@
 
 // The same knot in two launches, each at two waves per SIMD (see EVAL_RETRACT_ONLY / EVAL_ONLY in oh_figure8.h): the first leaves the
 // retracted trial knot in the slot, the second evaluates it.  Grid: (instance block, knot), instance block fastest.
-template <int N>
+// MOVE: the retraction before a carried compaction, which lays the knots down at D.newidx in the spare arrays (eval_unit).
+template <int N, bool MOVE = false>
 __device__ void retract_block(const FigParams& P, const FigBuffers& D, const int slot) {
-  eval_unit<N, false, false, EVAL_RETRACT_ONLY>(P, D, slot, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y + P.t0);
+  eval_unit<N, false, false, EVAL_RETRACT_ONLY, false, true, MOVE>(P, D, slot, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y + P.t0);
 }
 // scalars of knot 0 and the multipliers of the quaternion rows (every knot) of the instances that have finished: grid (instance block, knot | 1)
 template <int N>

@@ -14,6 +14,8 @@
 // knot t of an array with K rows per knot; row k of that knot
 #define KNOT(arr, t, K) rowbuf((arr) + (size_t)(t) * (K) * (size_t)Bp)
 #define RB(k) ((unsigned)(k) * rowB)
+// row k of this lane's knot t in a compaction's spare array, at the instance's new index nb
+#define SPARE(k) (((size_t)t * N + (k)) * Bp + nb)
 
 
 // ---------------------------------------------------------------------------------------------
@@ -118,10 +120,15 @@ OH_DEV void load_householder(const double* __restrict__ Vs, const int Bp, const 
 // ||q_t - q_{t-1}||^2, from the neighbours' retracted knots (in HBM since k_retract) -- and stores G where it stored g, the merit where it
 // stored phi: same bytes out, 2N doubles more in, and the sweep (step_instance_zc) rebuilds E_t and gt_t from V and G on the fly.
 // SPH = false (GUARD only): the handle has no sphere rows -- their walk over the links is compiled out (86 registers of a kernel at the limit)
-template <int N, bool GUARD = false, bool LEAD = false, int MODE = EVAL_FUSED, bool ZC = false, bool SPH = true>
+// MOVE (EVAL_RETRACT_ONLY of plain handles; the kernels compiled for a chain only -- the generic k_retract spills with it): the retraction before a
+// carried compaction.  D.newidx is final (the scan reads status and stat, which the previous sweep left), and the lane lays its knot down where
+// k_carry_gather would have moved it: the trial at newidx in q_spare[0], the accepted knot in q_spare[1], the Lagrangian gradient of the accepted
+// point in G_spare.  Nothing goes to q[slot]; the arithmetic is that of the plain retraction, so the values are k_carry_gather's bit for bit.
+template <int N, bool GUARD = false, bool LEAD = false, int MODE = EVAL_FUSED, bool ZC = false, bool SPH = true, bool MOVE = false>
 OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, const int b, const int t, const GuardParams* GPp = nullptr,
                       const GuardBuffers* GBp = nullptr) {
   static_assert(!ZC || (MODE == EVAL_ONLY && !GUARD && !LEAD), "the folded coupling belongs to the plain batched evaluation");
+  static_assert(!MOVE || (MODE == EVAL_RETRACT_ONLY && !GUARD && !LEAD), "the moving retraction belongs to the plain batched retraction");
   constexpr int NZ = N - 3;
   constexpr int NP = NZ * (NZ + 1) / 2;
   const int Bp = D.Bp;
@@ -140,6 +147,11 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
   // point down as the trial AS IT IS (no step, no retraction), the evaluation rebuilds its stage data bit for bit and the next sweep runs at the raised damping
   const bool asis = (MODE == EVAL_RETRACT_ONLY && !GUARD) ? D.polish[b] == 2 : false;
   const double stat_b = D.stat[b], pred_b = D.pred[b];
+  // MOVE: the knot's place in the dense batch (-1: finished), and whether the Lagrangian gradient travels (k_carry_gather's condition)
+  int nb = 0;
+  if constexpr (MOVE) nb = D.newidx[b];
+  const bool move_G = MOVE && (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc);
+  double Gmv[N];  // MOVE: Gfull[cur] of the knot, requested with the other inputs and stored before the arithmetic starts
   constexpr bool EARLY = MODE == EVAL_ONLY || OH_RETRACT_PREFETCH;  // the generic retraction kernel sits at the register limit: it fetches
                                                                     // its knot data after the branch, as before
   double Rc[9], pc[3];
@@ -171,6 +183,12 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
     for (int j = 0; j < N; ++j) q[j] = D.q[cur][IDX(t, N, j)];
 #pragma unroll
     for (int i = 0; i < 3 + 3 * NZ; ++i) mdlc[i] = D.mdl[cur][IDX(t, MDL_ROWS(N), i)];
+    if constexpr (MOVE) {
+      if (move_G) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) Gmv[k] = D.Gfull[cur][IDX(t, N, k)];
+      }
+    }
   }
   double cpl_zc[N];  // ZC, OH_ZC_EARLY: 2 kappa ((q_t - q_{t-1}) - (q_{t+1} - q_t))
   if constexpr (ZC && OH_ZC_EARLY) {
@@ -198,13 +216,36 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
     oh_fence(q[N - 1]);
     oh_fence(Rc[8]);
   }
-  if (status_b >= 0 || skip_b) return;
+  if constexpr (MOVE) {
+    if (status_b >= 0 || nb < 0) return;
+    if (skip_b) {  // no trial: the accepted point sits in the slot and restarts on the dense batch (k_carry_gather's restart lanes)
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const double v = D.q[slot][IDX(t, N, j)];
+        D.q_spare[0][SPARE(j)] = v;
+        D.q_spare[1][SPARE(j)] = v;
+      }
+      if (move_G) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) D.G_spare[SPARE(k)] = D.Gfull[slot][IDX(t, N, k)];
+      }
+      return;
+    }
+  } else {
+    if (status_b >= 0 || skip_b) return;
+  }
   const bool first = first_b != 0;
   // trial knot: the seed on the first evaluation, otherwise q_cur + Z_cur z (roll-out of the step k_step solved for)
   if constexpr (MODE != EVAL_ONLY) {
     if (first) {
 #pragma unroll
       for (int j = 0; j < N; ++j) q[j] = D.q[slot][IDX(t, N, j)];
+      if constexpr (MOVE) {  // a restart lane as well: the retracted knot goes to both spare arrays (q_final), the gradient comes from the slot
+        if (move_G) {
+#pragma unroll
+          for (int k = 0; k < N; ++k) D.G_spare[SPARE(k)] = D.Gfull[slot][IDX(t, N, k)];
+        }
+      }
     } else {
       if constexpr (!OH_RETRACT_PREFETCH) {  // the generic kernels sit at the register limit: their knot data is fetched after the branch
 #pragma unroll
@@ -214,6 +255,20 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
         for (int j = 0; j < N; ++j) q[j] = D.q[cur][IDX(t, N, j)];
 #pragma unroll
         for (int i = 0; i < 3 + 3 * NZ; ++i) mdlc[i] = D.mdl[cur][IDX(t, MDL_ROWS(N), i)];
+        if constexpr (MOVE) {
+          if (move_G) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) Gmv[k] = D.Gfull[cur][IDX(t, N, k)];
+          }
+        }
+      }
+      if constexpr (MOVE) {  // the accepted knot before the step is added to it, and its gradient: out of the registers before the arithmetic starts
+#pragma unroll
+        for (int j = 0; j < N; ++j) D.q_spare[1][SPARE(j)] = q[j];
+        if (move_G) {
+#pragma unroll
+          for (int k = 0; k < N; ++k) D.G_spare[SPARE(k)] = Gmv[k];
+        }
       }
       double Zc[N][NZ];
       z_from_householder<N>(Vc, Zc);
@@ -261,7 +316,14 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
     const double* __restrict__ Gc;
     int Bp, b, t;
     OH_DEV void q_final(const double (&qv)[N]) const {
-      if constexpr (!GUARD && MODE != EVAL_ONLY) {
+      if constexpr (MOVE) {  // the trial at its new index (qo: q_spare[0]); a first evaluation has no other accepted point: both arrays
+#pragma unroll
+        for (int j = 0; j < N; ++j) qo[SPARE(j)] = qv[j];
+        if (qo2) {
+#pragma unroll
+          for (int j = 0; j < N; ++j) qo2[SPARE(j)] = qv[j];
+        }
+      } else if constexpr (!GUARD && MODE != EVAL_ONLY) {
 #pragma unroll
         for (int j = 0; j < N; ++j) qo[IDX(t, N, j)] = qv[j];
       }
@@ -307,8 +369,12 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
     double kap2;
     bool last;
     const double* cpl;
+    // MOVE
+    double* __restrict__ qo2;
+    int nb;
   };
-  const Hooks hooks{D.q[slot], D.g[slot], D.Z[slot], D.Gfull[cur], Bp, b, t, Gpre, D.q[slot], q, D.Gfull[slot], &sm_zc, 2.0 * P.kappa, t == P.T - 1, cpl_zc};
+  const Hooks hooks{MOVE ? D.q_spare[0] : D.q[slot], D.g[slot], D.Z[slot], D.Gfull[cur], Bp, b, t, Gpre, D.q[slot], q, D.Gfull[slot], &sm_zc, 2.0 * P.kappa, t == P.T - 1, cpl_zc,
+                    (MOVE && first) ? D.q_spare[1] : nullptr, nb};
   double e_new[3], JZ_new[3][NZ];
   // A restart after a compaction (first_b == 2) evaluates the accepted point AS IT IS: its knots are the retracted
   // knots the instance accepted, and retracting them again (to the floor tolerance, as a seed would be) moved them by ~1e-10 -- enough to send an

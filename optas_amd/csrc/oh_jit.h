@@ -7,7 +7,7 @@
 
 struct FigSpec {
   hipModule_t mod = nullptr;
-  hipFunction_t retract = nullptr, evalb = nullptr, evalb_zc = nullptr, tail = nullptr, tail_vel = nullptr, finalize = nullptr;
+  hipFunction_t retract = nullptr, retract_move = nullptr, evalb = nullptr, evalb_zc = nullptr, tail = nullptr, tail_vel = nullptr, finalize = nullptr;
   int n = 0;               // chain length the kernels were instantiated for
   bool from_disk = false;  // code object came from the disk cache
   double seconds = 0.0;    // wall time of source generation + compilation (or cache read) + module load
@@ -18,6 +18,7 @@ int oh_jit_compile_cached(const std::string& src, std::vector<char>* code, bool*
 // compile (or find) and load the kernels for this chain; *out stays owned by the process-wide cache
 int oh_jit_figure8(const oh_chain& chain, int N, const FigSpec** out, std::string* err);
 bool oh_jit_figure8_cached(const oh_chain& chain, int N);  // loaded in this process or present in the disk cache
+// part 0: the whole evaluation; 1: the retraction; 2: the evaluation of the retracted knots; 3: the retraction that moves the knots to D.newidx
 hipError_t oh_spec_launch_eval(const FigSpec& sp, hipStream_t s, const FigParams& P, const FigBuffers& D, int slot, int part);
 hipError_t oh_spec_launch_tail(const FigSpec& sp, hipStream_t s, const FigParams& P, const FigBuffers& D, int slot);
 hipError_t oh_spec_launch_finalize(const FigSpec& sp, hipStream_t s, FigParams P, FigBuffers D, int only_done, double* f, double* kkt, int* iters, int* status);

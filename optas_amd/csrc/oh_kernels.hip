@@ -389,7 +389,9 @@ __global__ __launch_bounds__(256) void k_compact_scatter(FigParams P, FigBuffers
 // Instances that sit the launch out (skip) or are at a restart point (first) have no trial: q[slot] is their accepted point, they restart.
 // (Writing the leaving instances out from here instead of from a k_finalize launch before the scan was tried in round 3: the gather then
 // carries the kinematics walk of the multiplier map, 128 registers instead of 20, and a bench step takes 96.5 instead of 89.5 ms.)
-template <int N>
+// REST: what the retraction compiled for the chain has not moved already (oh_spec_retract_move lays the free knots down at newidx itself): the
+// pinned knots t < t0 and the per-instance scalars, on a grid of (instance block, max(t0, 1)).
+template <int N, bool REST = false>
 __global__ __launch_bounds__(256) void k_carry_gather(FigParams P, FigBuffers D, const int slot) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   const int t = blockIdx.y;
@@ -403,11 +405,13 @@ __global__ __launch_bounds__(256) void k_carry_gather(FigParams P, FigBuffers D,
   double* __restrict__ t_cur = D.q_spare[1];
   double* __restrict__ t_G = D.G_spare;
   double* __restrict__ ts = D.Dr[1];
+  if (!REST || t < P.t0) {
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    t_trial[((size_t)t * N + j) * Bp + nb] = D.q[slot][IDX(t, N, j)];
-    t_cur[((size_t)t * N + j) * Bp + nb] = D.q[cur][IDX(t, N, j)];
-    if (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc) t_G[((size_t)t * N + j) * Bp + nb] = D.Gfull[cur][IDX(t, N, j)];
+    for (int j = 0; j < N; ++j) {
+      t_trial[((size_t)t * N + j) * Bp + nb] = D.q[slot][IDX(t, N, j)];
+      t_cur[((size_t)t * N + j) * Bp + nb] = D.q[cur][IDX(t, N, j)];
+      if (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc) t_G[((size_t)t * N + j) * Bp + nb] = D.Gfull[cur][IDX(t, N, j)];
+    }
   }
   if (t == 0) {
 #pragma unroll
@@ -474,7 +478,9 @@ static void launch_eval_t(hipStream_t s, const FigParams& P, const FigBuffers& D
 }
 template <int N>
 static void launch_carry_t(hipStream_t s, const FigParams& P, const FigBuffers& D, int phase, int Bnew, int slot) {
+  // phase 0: the gather of everything; 2: its rest after a moving retraction (pinned knots and scalars); 1: the scatter of the scalars
   if (phase == 0) hipLaunchKernelGGL(k_carry_gather<N>, dim3((D.B + 255) / 256, P.T), dim3(256), 0, s, P, D, slot);
+  else if (phase == 2) hipLaunchKernelGGL((k_carry_gather<N, true>), dim3((D.B + 255) / 256, P.t0 > 1 ? P.t0 : 1), dim3(256), 0, s, P, D, slot);
   else hipLaunchKernelGGL(k_carry_scatter<N>, dim3((Bnew + 255) / 256), dim3(256), 0, s, P, D, Bnew, slot);
 }
 template <int N>
