@@ -513,6 +513,32 @@ int oh_rnea_hess(oh_handle* h, int N, const double* q, const double* qd, const d
    q [ndof][N], pose [7][N], J [6*ndof][N] (unit index fastest => fully coalesced). */
 int oh_fk_jac_soa_device(oh_handle* h, int N, const void* d_q, void* d_pose, void* d_J);
 
+/* Kinematics of one link in the frame of another link of the same model, batched: replaces RobotModel.get_link_{transform,position,rotation,
+   quaternion,rpy,geometric_jacobian,analytical_jacobian,axis}_function(link, base_link, n=N) and, with the root as base, their get_global_* forms
+   (models.py:884-1197, 1283-1409, 1517-1729).  With T_L = (R_L, p_L), T_B = (R_B, p_B) the global transforms and quat_L, quat_B the reference-signed
+   global quaternions (what oh_fk_jac returns) of link and base:
+     pos  [3], rot [9] row-major : T_L invt(T_B): rot = R_L R_B^T, pos = p_L - rot p_B              (models.py:884-898)
+     quat [4] xyzw               : quat_L * inv(quat_B) in the reference's reversed product          (models.py:1108-1122, spatialmath.py:298-328)
+     rpy  [3]                    : getrpy(quat), with its pitch = pi/2 branch at |sinp| >= 1         (spatialmath.py:384-404)
+     axis [3]                    : rot a / |a| for the vector a = axis3 of the call                  (models.py:1637-1670)
+     Jg   [6][ndof] row-major    : blkdiag(R_B^T, R_B^T) J_L, J_L the global geometric Jacobian      (models.py:1320-1344)
+     Ja   [6][ndof] row-major    : rows 0-2 of Jg, then d rpy / d q in closed form (the reference: AD of rpy; models.py:1370-1385, 1590-1611);
+                                   it includes the base chain's joints, and its pitch row is zero on the |sinp| >= 1 branch.
+   Any member of oh_link_out may be NULL: that output is not computed or stored. */
+typedef struct oh_link_out {
+  double *pos, *rot, *quat, *rpy, *axis, *Jg, *Ja;
+} oh_link_out;
+/* OH_PROBLEM_KINEMATICS handles.  link and base are the chains root->link and root->base (RobotModel.kinematic_chain) of one model: same ndof (that
+   of the handle), n_chain of either 0 ... OH_MAX_CHAIN (0: the root, or a link rigidly attached to it; the constant transform is in the tool fields).
+   base == NULL: the root frame.  Independent of oh_set_constants / oh_fk_jac*.  A joint past the chains' common prefix must not be on both chains
+   (it cannot be, in a kinematic tree). */
+int oh_set_link_frames(oh_handle* h, const oh_chain* link, const oh_chain* base);
+/* Host buffers in the reference layout: q [N][ndof], every output [N][...].  axis3: 3 doubles on the host, NULL unless out->axis. */
+int oh_link_kin(oh_handle* h, int N, const double* q, const double* axis3, const oh_link_out* out);
+/* Device buffers, structure of arrays: q [ndof][N], every output [components][N] (unit index fastest: coalesced).  axis3 and the oh_link_out
+   struct itself are host memory; the pointers in it are device pointers.  One launch of the same kernel as oh_link_kin: the same bits. */
+int oh_link_kin_device(oh_handle* h, int N, const void* d_q, const double* axis3, const oh_link_out* d_out_soa);
+
 /* Timing of the last oh_solve*: HIP-event milliseconds accumulated per kernel on the handle's stream.
    out[0]=eval kernel total ms, out[1]=eval launches, out[2]=step kernel total ms, out[3]=step launches,
    out[4]=whole solve ms, out[5]=SQP iterations launched (pairs), out[6]=sum over launches of the number
@@ -556,7 +582,7 @@ int oh_event_timer_start(oh_handle* h);
 int oh_event_timer_stop(oh_handle* h, double* ms);
 
 /* Code-object facts of a kernel of this library, read from the loaded module (hipFuncGetAttributes, occupancy query): name in
-   {k_retract, k_evalb, k_couple, k_step, k_tail, k_fk_jac, k_tq_eval, k_tq_step} (the ndof-7 instantiations);
+   {k_retract, k_evalb, k_couple, k_step, k_tail, k_fk_jac, k_link_kin, k_tq_eval, k_tq_step} (the ndof-7 instantiations);
    out5 = {registers per lane (VGPR + AGPR), scratch bytes per lane, LDS bytes per block, block size, resident blocks per CU}.
    Waves per SIMD = blocks per CU x block size / 64 / 4.  What bench.py reports as roofline.occupancy. */
 int oh_kernel_info(const char* kernel, int* out5);

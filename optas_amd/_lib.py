@@ -86,6 +86,12 @@ class oh_dynamics(C.Structure):
     ]
 
 
+class oh_link_out(C.Structure):
+    """Output pointers of oh_link_kin*: a null member is not computed."""
+
+    _fields_ = [(name, C.c_void_p) for name in ("pos", "rot", "quat", "rpy", "axis", "Jg", "Ja")]
+
+
 class oh_problem_desc(C.Structure):
     _fields_ = [
         ("kind", C.c_int),
@@ -246,6 +252,9 @@ SYMBOLS = [
     "oh_fk_jac",
     "oh_fk_jac_device",
     "oh_fk_jac_soa_device",
+    "oh_set_link_frames",
+    "oh_link_kin",
+    "oh_link_kin_device",
     "oh_set_profiling",
     "oh_get_timing",
     "oh_device_count",
@@ -322,6 +331,9 @@ def load() -> C.CDLL:
     lib.oh_fk_jac.argtypes = [vp, i, vp, vp, vp]
     lib.oh_fk_jac_device.argtypes = [vp, i, vp, vp, vp]
     lib.oh_fk_jac_soa_device.argtypes = [vp, i, vp, vp, vp]
+    lib.oh_set_link_frames.argtypes = [vp, C.POINTER(oh_chain), C.POINTER(oh_chain)]
+    lib.oh_link_kin.argtypes = [vp, i, vp, vp, C.POINTER(oh_link_out)]
+    lib.oh_link_kin_device.argtypes = [vp, i, vp, vp, C.POINTER(oh_link_out)]
     lib.oh_set_profiling.argtypes = [vp, i]
     lib.oh_get_timing.argtypes = [vp, dp]
     lib.oh_device_count.argtypes = [ip]

@@ -81,6 +81,9 @@ struct oh_handle {
   bool have_chain = false;
   oh_chain chain_host;
   oh_chain* d_chain = nullptr;
+  bool have_frames = false;  // oh_set_link_frames: the two chains of oh_link_kin*, independent of the chain above
+  OhLinkFrames frames_host;
+  OhLinkFrames* d_frames = nullptr;
   bool have_dyn = false;
   oh_dynamics dyn_host;
   oh_dynamics* d_dyn = nullptr;
@@ -2524,6 +2527,117 @@ extern "C" int oh_fk_jac(oh_handle* h, int n, const double* q, double* pose, dou
   return OH_OK;
 }
 
+// ---- kinematics of a link in the frame of another link (k_link_kin, oh_linkkin.hip) ----------------------------------------------------------------
+static int validate_frame_chain(const oh_chain& c, const char* which) {
+  const std::string who = std::string("oh_set_link_frames: ") + which;
+  if (c.ndof < 1 || c.ndof > OH_MAX_CHAIN || c.n_chain < 0 || c.n_chain > OH_MAX_CHAIN || c.n_chain > c.ndof) return fail(OH_ERR_INVALID, who + " chain: bad n_chain/ndof");
+  for (int k = 0; k < c.n_chain; ++k) {
+    if (c.jtype[k] != 0 && c.jtype[k] != 1) return fail(OH_ERR_INVALID, who + " chain: joint type not supported");
+    if (c.qidx[k] < 0 || c.qidx[k] >= c.ndof) return fail(OH_ERR_INVALID, who + " chain: qidx out of range");
+  }
+  return OH_OK;
+}
+
+extern "C" int oh_set_link_frames(oh_handle* h, const oh_chain* link, const oh_chain* base) {
+  if (!h || !link) return fail(OH_ERR_INVALID, "oh_set_link_frames: null argument");
+  if (h->desc.kind != OH_PROBLEM_KINEMATICS) return fail(OH_ERR_INVALID, "oh_set_link_frames: the handle is not an OH_PROBLEM_KINEMATICS handle");
+  OhLinkFrames f{};
+  f.link = *link;
+  if (base) {
+    f.base = *base;
+  } else {  // the root frame: no joints, identity tool transform
+    f.base.ndof = link->ndof;
+    f.base.R_tool[0] = f.base.R_tool[4] = f.base.R_tool[8] = 1.0;
+    f.base.quat_tool[3] = 1.0;
+  }
+  int rc = validate_frame_chain(f.link, "link");
+  if (!rc) rc = validate_frame_chain(f.base, "base");
+  if (rc) return rc;
+  if (f.link.ndof != f.base.ndof) return fail(OH_ERR_INVALID, "oh_set_link_frames: link.ndof != base.ndof");
+  if (f.link.ndof != h->desc.ndof) return fail(OH_ERR_INVALID, "oh_set_link_frames: chain.ndof != desc.ndof");
+  // common prefix: the same joint with the same folded constants on both chains (the kernel gives such a joint an exactly zero d rpy / d q)
+  const oh_chain &a = f.link, &b = f.base;
+  int ns = 0;
+  while (ns < a.n_chain && ns < b.n_chain && a.qidx[ns] == b.qidx[ns] && a.jtype[ns] == b.jtype[ns] && !memcmp(a.R0[ns], b.R0[ns], sizeof a.R0[ns]) &&
+         !memcmp(a.p0[ns], b.p0[ns], sizeof a.p0[ns]) && !memcmp(a.axis[ns], b.axis[ns], sizeof a.axis[ns]))
+    ++ns;
+  for (int k = ns; k < a.n_chain; ++k)
+    for (int m = ns; m < b.n_chain; ++m)
+      if (a.qidx[k] == b.qidx[m]) return fail(OH_ERR_INVALID, "oh_set_link_frames: a joint past the chains' common prefix is on both chains");
+  f.n_shared = ns;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->d_frames) HIPCHK(hipMalloc((void**)&h->d_frames, sizeof(OhLinkFrames)));
+  HIPCHK(hipMemcpy(h->d_frames, &f, sizeof f, hipMemcpyHostToDevice));
+  h->frames_host = f;
+  h->have_frames = true;
+  return OH_OK;
+}
+
+// argument checks of both entry points (no device call before they pass); a3 <- axis3 / |axis3|
+static int link_kin_check(const char* who, oh_handle* h, int n, const void* q, const double* axis3, const oh_link_out* out, double (&a3)[3]) {
+  const std::string w(who);
+  if (!h) return fail(OH_ERR_INVALID, w + ": null handle");
+  if (!out) return fail(OH_ERR_INVALID, w + ": null out");
+  if (n < 1 || !q) return fail(OH_ERR_INVALID, w + ": bad arguments");
+  a3[0] = a3[1] = a3[2] = 0.0;
+  if (out->axis) {
+    if (!axis3) return fail(OH_ERR_INVALID, w + ": out->axis needs axis3");
+    const double nrm = std::sqrt(axis3[0] * axis3[0] + axis3[1] * axis3[1] + axis3[2] * axis3[2]);
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(OH_ERR_INVALID, w + ": axis3 must be a nonzero finite vector");
+    for (int i = 0; i < 3; ++i) a3[i] = axis3[i] / nrm;
+  }
+  if (!h->have_frames) return fail(OH_ERR_STATE, w + ": call oh_set_link_frames first");
+  return OH_OK;
+}
+
+static int link_kin_launch(oh_handle* h, int n, bool soa, const double* d_q, const double (&a3)[3], const oh_link_out& d_out) {
+  oh_launch_link_kin(h->stream, soa, h->d_frames, h->frames_host.link.n_chain, n, d_q, a3, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return OH_OK;
+}
+
+extern "C" int oh_link_kin_device(oh_handle* h, int n, const void* d_q, const double* axis3, const oh_link_out* d_out_soa) {
+  double a3[3];
+  int rc = link_kin_check("oh_link_kin_device", h, n, d_q, axis3, d_out_soa, a3);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  return link_kin_launch(h, n, true, (const double*)d_q, a3, *d_out_soa);
+}
+
+extern "C" int oh_link_kin(oh_handle* h, int n, const double* q, const double* axis3, const oh_link_out* out) {
+  double a3[3];
+  int rc = link_kin_check("oh_link_kin", h, n, q, axis3, out, a3);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const int ndof = h->frames_host.link.ndof;
+  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+  double* const host[7] = {out->pos, out->rot, out->quat, out->rpy, out->axis, out->Jg, out->Ja};
+  const size_t comps[7] = {3, 9, 4, 3, 3, 6 * (size_t)ndof, 6 * (size_t)ndof};
+  const size_t b_q = sizeof(double) * ndof * (size_t)n;
+  size_t total = al(b_q);
+  for (int i = 0; i < 7; ++i)
+    if (host[i]) total += al(sizeof(double) * comps[i] * (size_t)n);
+  rc = ensure_stage(h, total);
+  if (rc) return rc;
+  char* base = (char*)h->stage;
+  double* d_q = (double*)base;
+  base += al(b_q);
+  double* dev[7] = {};
+  for (int i = 0; i < 7; ++i)
+    if (host[i]) {
+      dev[i] = (double*)base;
+      base += al(sizeof(double) * comps[i] * (size_t)n);
+    }
+  HIPCHK(hipMemcpy(d_q, q, b_q, hipMemcpyHostToDevice));
+  const oh_link_out d_out{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
+  rc = link_kin_launch(h, n, false, d_q, a3, d_out);
+  if (rc) return rc;
+  for (int i = 0; i < 7; ++i)
+    if (host[i]) HIPCHK(hipMemcpy(host[i], dev[i], sizeof(double) * comps[i] * (size_t)n, hipMemcpyDeviceToHost));
+  return OH_OK;
+}
+
 extern "C" int oh_set_profiling(oh_handle* h, int enable) {
   if (!h) return fail(OH_ERR_INVALID, "oh_set_profiling: null handle");
   h->profiling = enable != 0;
@@ -2576,6 +2690,7 @@ extern "C" void oh_destroy(oh_handle* h) {
     if (q) hipFree(q);
   if (h->stage) hipFree(h->stage);
   if (h->d_chain) hipFree(h->d_chain);
+  if (h->d_frames) hipFree(h->d_frames);
   if (h->d_dyn) hipFree(h->d_dyn);
   if (h->d_local_path) hipFree(h->d_local_path);
   if (h->h_flag) hipHostFree(h->h_flag);
@@ -2876,7 +2991,7 @@ extern "C" int oh_kernel_info(const char* kernel, int* out5) {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_kernel_info: no HIP device available (this library has no CPU path)");
   OhKernelInfo k{};
-  if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_torque(kernel, &k))
+  if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_linkkin(kernel, &k) && !oh_kernel_info_torque(kernel, &k))
     return fail(OH_ERR_INVALID, std::string("oh_kernel_info: unknown kernel or attribute query failed: ") + kernel);
   out5[0] = k.vgprs; out5[1] = k.scratch_bytes; out5[2] = k.lds_bytes; out5[3] = k.block; out5[4] = k.blocks_per_cu;
   return OH_OK;

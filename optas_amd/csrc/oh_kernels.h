@@ -15,8 +15,17 @@ struct OhKernelInfo {
 bool oh_kernel_info_figure8(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_fkjac(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_torque(const char* name, OhKernelInfo* out);
+bool oh_kernel_info_linkkin(const char* name, OhKernelInfo* out);
 
 void oh_launch_fk_jac(hipStream_t s, bool soa, const oh_chain* d_chain, int n_chain, int ndof, int n, const double* q, double* pose, double* J);
+// What oh_set_link_frames keeps on the device for k_link_kin (oh_linkkin.hip): the chains root->link and root->base, and the number of leading
+// actuated joints the two have in common (same joint, same folded constants).
+struct OhLinkFrames {
+  oh_chain link, base;
+  int n_shared;
+};
+// a3: the unit vector of the axis output (read only with out.axis); out: device pointers, any of them null
+void oh_launch_link_kin(hipStream_t s, bool soa, const OhLinkFrames* d_frames, int n_link, int n, const double* q, const double* a3, const oh_link_out& out);
 bool oh_launch_setup(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const double* x0, const double* p);
 bool oh_launch_eval(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, int part = 0);
 bool oh_launch_carry(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int phase, int Bnew, int slot);  // phase 0: gather, 1: scatter, 2: the gather's rest after a moving retraction

@@ -126,6 +126,7 @@ class RobotModel(Model):
             name = self.urdf.name
         super().__init__(name, self.ndof, time_derivs, "q", dlim, T)
         self._fk_handles: Dict[str, "KinematicsHandle"] = {}
+        self._link_handles: Dict[Tuple[str, str], "LinkFrameHandle"] = {}
 
     @staticmethod
     def from_description(description: RobotDescription, **kwargs) -> "RobotModel":
@@ -248,6 +249,7 @@ class RobotModel(Model):
         self.urdf.add_link(Link(name=base_link))
         self.urdf.add_joint(Joint(name=joint_name, type="fixed", parent=base_link, child=child_link, xyz=xyz, rpy=rpy))
         self._fk_handles.clear()
+        self._link_handles.clear()
 
     def get_root_link(self) -> str:
         return self.urdf.get_root()
@@ -547,8 +549,7 @@ class RobotModel(Model):
         J = self.get_global_link_geometric_jacobian(link, q)
         return J[3:] if isinstance(J, np.ndarray) else [j[3:] for j in J]
 
-    # ---- 4x4 transforms and base-frame variants (models.py:826-868, 884-898, 949-960, 1011-1023, 1108-1122, 1320-1344, 1425-1443,
-    # 1496-1516): host compositions of the oh_fk_jac outputs, one configuration at a time ---------------------------------
+    # ---- 4x4 transforms ------------------------------------------------------------------------------------------------
     def get_global_link_transform(self, link: str, q) -> np.ndarray:
         """models.py:826-868: homogeneous transform of the link in the root frame."""
         T = np.eye(4)
@@ -556,43 +557,174 @@ class RobotModel(Model):
         T[:3, 3] = self.get_global_link_position(link, np.asarray(q, dtype=np.float64).reshape(-1))
         return T
 
-    def get_link_transform(self, link: str, q, base_link: str) -> np.ndarray:
+    # ---- kinematics in the frame of a base link (models.py:884-898, 949-960, 1011-1023, 1108-1122, 1148-1197, 1283-1409, 1517-1729): one oh_link_kin
+    # launch per call, whatever the number of configurations.  q is ndof or ndof-by-n like everywhere here: a 1-D q gives one vector or matrix, an
+    # ndof-by-n q gives 3-by-n / 4-by-n arrays for position, rpy, axis and quaternion and a list of n matrices for the rest. ---------------------------
+    def _frames(self, link: str, base_link: str) -> "LinkFrameHandle":
+        h = self._link_handles.get((link, base_link))
+        if h is None:
+            h = LinkFrameHandle(self.kinematic_chain(link), self.kinematic_chain(base_link))
+            self._link_handles[(link, base_link)] = h
+        return h
+
+    def _link_kin(self, link: str, q, base_link: str, want, axis=None):
+        """The outputs named in `want` (LinkFrameHandle.OUTPUTS) as n-by-components arrays, and whether q was a single configuration."""
+        if isinstance(q, Expr):
+            raise NotImplementedError("kinematics in a base frame (get_link_* and the rpy / analytical-Jacobian / axis methods) take numeric joint states only: a symbolic q is not lowered")
+        Q = self._q_cols(q)
+        return self._frames(link, base_link).link_kin(Q.T, want, axis), np.asarray(q).ndim == 1
+
+    @staticmethod
+    def _columns(a: np.ndarray, single: bool) -> np.ndarray:
+        return a[0] if single else a.T
+
+    @staticmethod
+    def _matrices(a: np.ndarray, single: bool):
+        return a[0] if single else [a[i] for i in range(a.shape[0])]
+
+    @staticmethod
+    def _axis3(axis) -> np.ndarray:
+        """models.py:1652-1668: 'x', 'y', 'z' or a 3-array (normalised by the library)."""
+        if isinstance(axis, str):
+            if axis in ("x", "y", "z"):
+                return np.eye(3)[("x", "y", "z").index(axis)]
+        elif not isinstance(axis, Expr):
+            a = np.asarray(axis, dtype=np.float64).reshape(-1)
+            if a.shape[0] == 3:
+                return a
+        raise ValueError(f"did not recognize input for axis: {axis}")
+
+    def get_link_transform(self, link: str, q, base_link: str):
         """models.py:884-898: T_L invt(T_B) -- the reference's convention (not invt(T_B) T_L), pinned by its tests."""
-        TB = self.get_global_link_transform(base_link, q)
-        inv = np.eye(4)
-        inv[:3, :3] = TB[:3, :3].T
-        inv[:3, 3] = -TB[:3, :3].T @ TB[:3, 3]
-        return self.get_global_link_transform(link, q) @ inv
+        out, single = self._link_kin(link, q, base_link, ("pos", "rot"))
+        T = np.zeros((out["pos"].shape[0], 4, 4))
+        T[:, :3, :3] = out["rot"]
+        T[:, :3, 3] = out["pos"]
+        T[:, 3, 3] = 1.0
+        return self._matrices(T, single)
 
     def get_link_position(self, link: str, q, base_link: str) -> np.ndarray:
-        return self.get_link_transform(link, q, base_link)[:3, 3].copy()
+        out, single = self._link_kin(link, q, base_link, ("pos",))
+        return self._columns(out["pos"], single)
 
-    def get_link_rotation(self, link: str, q, base_link: str) -> np.ndarray:
-        return self.get_link_transform(link, q, base_link)[:3, :3].copy()
+    def get_link_rotation(self, link: str, q, base_link: str):
+        out, single = self._link_kin(link, q, base_link, ("rot",))
+        return self._matrices(out["rot"], single)
 
     def get_link_quaternion(self, link: str, q, base_link: str) -> np.ndarray:
         """models.py:1108-1122: quat_L * quat_B^{-1} with the reference's reversed product (spatialmath.py:298-312)."""
-        qv = np.asarray(q, dtype=np.float64).reshape(-1)
-        ql = Quaternion.fromvec(self.get_global_link_quaternion(link, qv))
-        qb = Quaternion.fromvec(self.get_global_link_quaternion(base_link, qv))
-        return (ql * qb.inv()).getquat()
+        out, single = self._link_kin(link, q, base_link, ("quat",))
+        return self._columns(out["quat"], single)
 
-    def get_link_geometric_jacobian(self, link: str, q, base_link: str) -> np.ndarray:
+    def get_link_rpy(self, link: str, q, base_link: str) -> np.ndarray:
+        """models.py:1167-1177: getrpy of get_link_quaternion (spatialmath.py:384-404)."""
+        out, single = self._link_kin(link, q, base_link, ("rpy",))
+        return self._columns(out["rpy"], single)
+
+    def get_global_link_rpy(self, link: str, q) -> np.ndarray:
+        """models.py:1148-1157."""
+        return self.get_link_rpy(link, q, self.get_root_link())
+
+    def get_link_geometric_jacobian(self, link: str, q, base_link: str):
         """models.py:1320-1344: blkdiag(R_B^T, R_B^T) J."""
-        qv = np.asarray(q, dtype=np.float64).reshape(-1)
-        J = self.get_global_link_geometric_jacobian(link, qv)
-        RT = self.get_global_link_rotation(base_link, qv).T
-        return np.vstack([RT @ J[:3], RT @ J[3:]])
+        out, single = self._link_kin(link, q, base_link, ("Jg",))
+        return self._matrices(out["Jg"], single)
 
-    def get_link_linear_jacobian(self, link: str, q, base_link: str) -> np.ndarray:
-        return self.get_link_geometric_jacobian(link, q, base_link)[:3]
+    def get_link_linear_jacobian(self, link: str, q, base_link: str):
+        out, single = self._link_kin(link, q, base_link, ("Jg",))
+        return self._matrices(out["Jg"][:, :3], single)
 
-    def get_link_angular_geometric_jacobian(self, link: str, q, base_link: str) -> np.ndarray:
-        return self.get_link_geometric_jacobian(link, q, base_link)[3:]
+    def get_link_angular_geometric_jacobian(self, link: str, q, base_link: str):
+        out, single = self._link_kin(link, q, base_link, ("Jg",))
+        return self._matrices(out["Jg"][:, 3:], single)
+
+    def get_link_analytical_jacobian(self, link: str, q, base_link: str):
+        """models.py:1370-1385: the linear Jacobian over d rpy / d q."""
+        out, single = self._link_kin(link, q, base_link, ("Ja",))
+        return self._matrices(out["Ja"], single)
+
+    def get_link_angular_analytical_jacobian(self, link: str, q, base_link: str):
+        """models.py:1590-1611: d rpy / d q, in closed form where the reference differentiates the graph of get_link_rpy."""
+        out, single = self._link_kin(link, q, base_link, ("Ja",))
+        return self._matrices(out["Ja"][:, 3:], single)
+
+    def get_global_link_analytical_jacobian(self, link: str, q):
+        """models.py:1283-1297."""
+        return self.get_link_analytical_jacobian(link, q, self.get_root_link())
+
+    def get_global_link_angular_analytical_jacobian(self, link: str, q):
+        """models.py:1517-1528."""
+        return self.get_link_angular_analytical_jacobian(link, q, self.get_root_link())
+
+    def get_link_axis(self, link: str, q, axis, base_link: str) -> np.ndarray:
+        """models.py:1637-1670: the direction `axis` of the link frame ('x', 'y', 'z' or a 3-array, normalised) in the base frame."""
+        out, single = self._link_kin(link, q, base_link, ("axis",), self._axis3(axis))
+        return self._columns(out["axis"], single)
+
+    def get_global_link_axis(self, link: str, q, axis) -> np.ndarray:
+        """models.py:1698-1710."""
+        return self.get_link_axis(link, q, axis, self.get_root_link())
+
+    def _knots(self, method):
+        """The *_function(link, ..., n) forms: a callable on an ndof-by-n array (a single ndof vector gives the single-configuration result)."""
+
+        def call(Q):
+            if not isinstance(Q, Expr):
+                Q = np.asarray(Q, dtype=np.float64)
+                Q = Q.reshape(-1) if Q.size == self.ndof else Q.reshape(self.ndof, -1)
+            return method(Q)
+
+        return call
+
+    def get_link_transform_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_transform(link, Q, base_link))
 
     def get_link_position_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
         """models.py:962-984 (what sphere_collision_avoidance_constraints maps over the knots)."""
-        return lambda q: self.get_link_position(link, q, base_link)
+        return self._knots(lambda Q: self.get_link_position(link, Q, base_link))
+
+    def get_link_rotation_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_rotation(link, Q, base_link))
+
+    def get_link_quaternion_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_quaternion(link, Q, base_link))
+
+    def get_link_rpy_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_rpy(link, Q, base_link))
+
+    def get_global_link_rpy_function(self, link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_global_link_rpy(link, Q))
+
+    def get_link_geometric_jacobian_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_geometric_jacobian(link, Q, base_link))
+
+    def get_link_linear_jacobian_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_linear_jacobian(link, Q, base_link))
+
+    def get_link_angular_geometric_jacobian_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_angular_geometric_jacobian(link, Q, base_link))
+
+    def get_link_analytical_jacobian_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_analytical_jacobian(link, Q, base_link))
+
+    def get_global_link_analytical_jacobian_function(self, link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_global_link_analytical_jacobian(link, Q))
+
+    def get_link_angular_analytical_jacobian_function(self, link: str, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_angular_analytical_jacobian(link, Q, base_link))
+
+    def get_global_link_angular_analytical_jacobian_function(self, link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_global_link_angular_analytical_jacobian(link, Q))
+
+    def get_link_axis_function(self, link: str, axis, base_link: str, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_link_axis(link, Q, axis, base_link))
+
+    def get_global_link_axis_function(self, link: str, axis, n: int = 1, numpy_output: bool = True):
+        return self._knots(lambda Q: self.get_global_link_axis(link, Q, axis))
+
+    def get_global_link_rotation_function(self, link: str, n: int = 1, numpy_output: bool = True):
+        """models.py:997-1009."""
+        return lambda Q: self.get_global_link_rotation(link, Q if isinstance(Q, Expr) else np.asarray(Q, dtype=np.float64).reshape(self.ndof, -1))
 
     def get_global_link_transform_function(self, link: str, n: int = 1, numpy_output: bool = True):
         return lambda q: self.get_global_link_transform(link, q)
@@ -646,6 +778,44 @@ class KinematicsHandle:
             return pose, J
         _lib.check(lib.oh_fk_jac(self._h, n, _lib._ptr(Q), _lib._ptr(pose), _lib._ptr(J)), "oh_fk_jac")
         return pose, J
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.load().oh_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class LinkFrameHandle:
+    """A liboptas_hip handle that serves oh_link_kin for one (link, base link) pair: the chains root->link and root->base."""
+
+    OUTPUTS = {"pos": 3, "rot": 9, "quat": 4, "rpy": 3, "axis": 3, "Jg": 6, "Ja": 6}  # components per configuration (Jg, Ja: rows of ndof)
+
+    def __init__(self, link_chain: _lib.oh_chain, base_chain: _lib.oh_chain):
+        import ctypes as C
+
+        lib = _lib.load()
+        self.ndof = link_chain.ndof
+        self._h = C.c_void_p()
+        desc = _lib.oh_problem_desc(kind=_lib.OH_PROBLEM_KINEMATICS, ndof=self.ndof)
+        _lib.check(lib.oh_create(C.byref(desc), C.byref(self._h)), "oh_create")
+        _lib.check(lib.oh_set_link_frames(self._h, C.byref(link_chain), C.byref(base_chain)), "oh_set_link_frames")
+
+    def link_kin(self, Q: np.ndarray, want, axis3=None) -> Dict[str, np.ndarray]:
+        """Q: n-by-ndof (row = one joint state, the ABI layout); want: names out of OUTPUTS; axis3: the vector of the "axis" output.
+        One oh_link_kin call; returns n-by-3 / n-by-4 arrays, rot as n-by-3-by-3 and the Jacobians as n-by-6-by-ndof."""
+        import ctypes as C
+
+        Q = _lib.as_f64(Q)
+        n = Q.shape[0]
+        shapes = {"rot": (n, 3, 3), "Jg": (n, 6, self.ndof), "Ja": (n, 6, self.ndof)}
+        res = {name: np.empty(shapes.get(name, (n, self.OUTPUTS[name]))) for name in want}
+        out = _lib.oh_link_out(**{name: _lib._ptr(a) for name, a in res.items()})
+        a3 = None if axis3 is None else _lib.as_f64(axis3, (3,))
+        _lib.check(_lib.load().oh_link_kin(self._h, n, _lib._ptr(Q), _lib._ptr(a3), C.byref(out)), "oh_link_kin")
+        return res
 
     def __del__(self):
         try:
