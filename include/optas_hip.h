@@ -263,6 +263,8 @@ typedef struct oh_torque_desc {
 #define OH_QP_MAX_N 32
 #define OH_QP_MAX_M 256
 #define OH_QP_MAX_ME 32
+/* min x^T P x + q^T x  s.t.  M x + c >= 0,  A x + b = 0, one [P | q | M | c | A | b] row per instance.  P need not be symmetric: only its
+   symmetric part enters (the gradient is (P + P^T) x); that part must be positive semidefinite. */
 typedef struct oh_qp_desc {
   int n;        /* decision variables, <= OH_QP_MAX_N */
   int m;        /* rows of M x + c >= 0, <= OH_QP_MAX_M */

@@ -4,7 +4,7 @@
 //     min_x  x^T P x + q^T x      s.t.  M x + c >= 0,   A x + b = 0           (optimization.py:219-260: no factor 1/2)
 //
 // One thread owns one instance: infeasible-start primal-dual interior point with slacks s = Mx + c, Newton system reduced to
-// H = 2P + M^T (lam/s) M (dense Cholesky, n <= OH_QP_MAX_N) and the Schur complement A H^{-1} A^T for the equality rows.
+// H = P + P^T + M^T (lam/s) M (dense Cholesky, n <= OH_QP_MAX_N) and the Schur complement A H^{-1} A^T for the equality rows.
 // The matrices differ per instance (P, M, A may depend on the parameters: the Booth test has a * y in its cost), so every
 // instance brings its own [P | q | M | c | A | b] row; work arrays are thread-private slices of one global buffer.
 // numpy restatement of the same iteration: oracle/qp_ipm.py.
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64) void k_qp_solve(QpParams Q, int B, int Bp, cons
     bool finite = true;
     for (int i = 0; i < n; ++i) {
       double v = q[i];
-      for (int j = 0; j < n; ++j) v += 2.0 * P[i * n + j] * x[j];
+      for (int j = 0; j < n; ++j) v += (P[i * n + j] + P[j * n + i]) * x[j];  // gradient of x^T P x: P need not be symmetric
       for (int k = 0; k < m; ++k) v -= M[k * n + i] * lam[k];
       for (int k = 0; k < me; ++k) v -= A[k * n + i] * nu[k];
       rd[i] = v;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(64) void k_qp_solve(QpParams Q, int B, int Bp, cons
     if (!finite || !(feas == feas)) { st = OH_STATUS_NUMERICAL; break; }
     if (stat <= Q.tol && feas <= Q.tol && gap <= Q.tol) { st = OH_STATUS_CONVERGED; break; }
     if (it == Q.max_iter) break;
-    // H = 2P + M^T diag(lam/s) M (+ tiny shift), rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
+    // H = P + P^T + M^T diag(lam/s) M (+ tiny shift), rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
     double dmax = 0.0;
     for (int k = 0; k < m; ++k) dl[k] = lam[k] / s[k];  // (dl is free until the step: one division per row instead of one per use)
     for (int i = 0; i < n; ++i) {
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(64) void k_qp_solve_wave(QpParams Q, int B, const d
     bool finite = true;
     for (int i = lane; i < n; i += 64) {
       double v = q[i];
-      for (int j = 0; j < n; ++j) v += 2.0 * P[i * n + j] * x[j];
+      for (int j = 0; j < n; ++j) v += (P[i * n + j] + P[j * n + i]) * x[j];  // gradient of x^T P x: P need not be symmetric
       for (int k = 0; k < m; ++k) v -= M[k * n + i] * lam[k];
       for (int k = 0; k < me; ++k) v -= A[k * n + i] * nu[k];
       rd[i] = v;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(64) void k_qp_solve_wave(QpParams Q, int B, const d
     if (!finite || feas_nan) { st = OH_STATUS_NUMERICAL; break; }
     if (stat <= Q.tol && feas <= Q.tol && gap <= Q.tol) { st = OH_STATUS_CONVERGED; break; }
     if (it == Q.max_iter) break;
-    // H = 2P + M^T diag(lam/s) M, entry (i, j <= i) per lane; rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
+    // H = P + P^T + M^T diag(lam/s) M, entry (i, j <= i) per lane; rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
     const int nh = n * (n + 1) / 2;
     auto build = [&]() {
       for (int e = lane; e < nh; e += 64) {

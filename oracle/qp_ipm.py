@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure, not product code) -- numpy port of the state machine the HIP path runs for the dense QP
 family (optas_amd/csrc/oh_qp.hip):   min x^T P x + q^T x   s.t.  M x + c >= 0,  A x + b = 0   (optimization.py:219-260).
-Infeasible-start primal-dual interior point, slacks s = Mx + c, reduced Newton system H = 2P + M^T (lam/s) M, Schur
+Infeasible-start primal-dual interior point, slacks s = Mx + c, reduced Newton system H = P + P^T + M^T (lam/s) M, Schur
 complement on the equality rows.  Independent cross-checks: scipy SLSQP in the reference's wiring and, for the Booth
 function of the reference's own solver test (tests/test_solver.py:22-54), the known answer (1, 3).
 
@@ -23,7 +23,7 @@ def solve_qp_ipm(P, q, M, c, A, b, x0=None, tol=1e-9, max_iter=100):
     nu = np.zeros(me)
     status, it = 1, 0
     while True:
-        rd = 2.0 * P @ x + q - M.T @ lam - A.T @ nu
+        rd = (P + P.T) @ x + q - M.T @ lam - A.T @ nu  # gradient of x^T P x: P need not be symmetric
         rp = M @ x + c - s
         re = A @ x + b
         stat = np.abs(rd).max()
