@@ -260,11 +260,13 @@ typedef struct oh_torque_desc {
   double dq_up[OH_MAX_CHAIN];
 } oh_torque_desc;
 
-#define OH_QP_MAX_N 32
-#define OH_QP_MAX_M 256
-#define OH_QP_MAX_ME 32
+#define OH_QP_MAX_N 128
+#define OH_QP_MAX_M 1024
+#define OH_QP_MAX_ME 128
 /* min x^T P x + q^T x  s.t.  M x + c >= 0,  A x + b = 0, one [P | q | M | c | A | b] row per instance.  P need not be symmetric: only its
-   symmetric part enters (the gradient is (P + P^T) x); that part must be positive semidefinite. */
+   symmetric part enters (the gradient is (P + P^T) x); that part must be positive semidefinite.
+   Up to n = 32, m = 256, me = 32 an instance is solved by one thread, or by one wavefront when there are few of them; a handle beyond any of
+   these ("large") by one workgroup of 256 threads per instance (k_qp_solve_block), whatever the batch is.  me <= n always. */
 typedef struct oh_qp_desc {
   int n;        /* decision variables, <= OH_QP_MAX_N */
   int m;        /* rows of M x + c >= 0, <= OH_QP_MAX_M */
@@ -321,7 +323,8 @@ int oh_create_qp(const oh_qp_desc* desc, oh_handle** out);
    instruction tape (cost register quadratic in x; n_ineq = m rows affine in x that must be >= 0, then n_eq = me rows that must vanish;
    max_iter / tol / jit of the descriptor are ignored).  From then on the p of oh_solve / oh_solve_device is [B][tape.np] parameter
    vectors: one thread per instance reads [P | q | M | c | A | b] off the tape on the device (values at 0, +-e_i, e_i + e_j: exact for
-   these classes) before the solve, and f includes the cost's constant term f(0, p). */
+   these classes) before the solve, and f includes the cost's constant term f(0, p).  Large handles (beyond n = 32, m = 256, me = 32): a block
+   per instance, a lane per probe point, instances launched in chunks so the interpreter's register file stays under 256 MB for any B. */
 int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* tape);
 
 /* Same for OH_PROBLEM_TAPE: the tape is copied to the device.  oh_get_multipliers returns [B][n_ineq + n_eq] (lam >= 0 of the >= rows, signed mu
@@ -418,7 +421,8 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    "specialized"; OH_PROBLEM_TAPE handles: "tape_wave" (0: one thread per instance; 1 / 2: one block of wavefronts per instance, the quasi-Newton
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
    not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_jit_lds" (1: the last oh_tape_phi ran
-   the generated code's entry with its work set in LDS). */
+   the generated code's entry with its work set in LDS); OH_PROBLEM_QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance
+   kernel k_qp_solve_block). */
 int oh_get_flag(oh_handle* h, const char* name, int* value);
 
 /*
@@ -444,6 +448,8 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *   hyb_switch (1e-5, x w_path), relax (1.5), relax_from (4), retract_min (1e-13), settle_k (1)          -- algorithm constants (change the iterates)
  *   tol (0 = the descriptor's): stopping tolerance on the reduced gradient of a trajectory handle, changeable between solves
  *   pm_wave_max (20480), qp_mode (-1), tape_lds_max                                                     -- point-mass / QP / tape launch shapes
+ *       (qp_mode: -1 automatic; 0 / 1 / 2 force where the thread-per-instance kernel keeps its work set, falling back when it does not fit;
+ *        3 forces the workgroup-per-instance kernel on any handle; large handles take that kernel under every value)
  *   tape_wave (1), tape_lbfgs (-1 = by size), tape_wave_nt (256), tape_wave_regs (-1), tape_wave_hist (-1) -- tape evaluator (rebuilt when set)
  *   tq_check (4), tq_rebuild (0.9), tq_stall (25), tq_curv_after (3), tq_curv_from (0.1), tq_ftb (0.995), tq_theta_mu (1.35), tq_kappa_mu (0.4),
  *   tq_kappa_eps (10), tq_curv_late (1), tq_max_back (3), tq_mu_dec (1/3; warm ticks of oh_tq_rollout: tq_mu_dec_warm, 0.1), tq_ls_curv (1), tq_curv_lag (3: the exact-curvature term is computed at every 4th evaluation of an instance and reused in between; 0: always),

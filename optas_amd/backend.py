@@ -383,7 +383,9 @@ def tape_backend(tape, eliminate=True, rho0=None, **kw):
 
 
 class QPBackend(_SolveMixin):
-    """OH_PROBLEM_QP handle: x (B, n); p (B, n*n + n + m*n + m + me*n + me) = [P | q | M | c | A | b] per instance."""
+    """OH_PROBLEM_QP handle: x (B, n); p (B, n*n + n + m*n + m + me*n + me) = [P | q | M | c | A | b] per instance.
+    n <= 128, m <= 1024, me <= min(128, n).  Up to (32, 256, 32) a thread or a wavefront solves an instance (option qp_mode: -1 automatic,
+    0 / 1 / 2 the thread kernel's work-set placement); beyond, or with qp_mode 3, one workgroup of 256 threads does (k_qp_solve_block)."""
 
     def __init__(self, n: int, m: int, me: int, max_iter=100, tol=1e-9, tape=None):
         """tape (optas_amd.tape.Tape of the problem, rows k then a): p of a solve is then (B, np of the problem) and the QP data is read off
@@ -409,6 +411,12 @@ class QPBackend(_SolveMixin):
         if self.tape is not None and int(self.tape.np_) == 0:  # a problem without parameters: the ABI still wants one column
             p = np.zeros((len(np.atleast_2d(x0)), 1))
         return super().solve(x0, p)
+
+    def flag(self, name: str) -> int:
+        """oh_get_flag: 'qp_block' (1: the last solve ran k_qp_solve_block, a workgroup per instance)."""
+        v = C.c_int(0)
+        _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
+        return int(v.value)
 
     @staticmethod
     def pack(P, q, M, c, A, b) -> np.ndarray:

@@ -119,6 +119,11 @@ struct oh_handle {
   double* d_qp_work = nullptr;
   double* d_qp_mult = nullptr;
   int qp_cap = 0;
+  double* d_qp_blk = nullptr;  // k_qp_solve_block: [B][me n + me^2] (oh_qp_block_work_doubles), a contiguous slice per instance
+  int qp_blk_cap = 0;
+  int qp_last_block = 0;       // the last solve ran k_qp_solve_block (oh_get_flag "qp_block")
+  int qp_mult_cap = 0;
+  int qp_val_cap = 0;          // large handles: instances per launch of k_qp_assemble_block the register file d_qp_val holds
   bool qp_tape = false;       // oh_qp_set_tape: p of a solve is the problem's parameter vector, the QP data is read off the tape (h->TP, d_tape_*) on the device
   double* d_qp_rows = nullptr;  // [B][qp_np] assembled [P | q | M | c | A | b]
   double* d_qp_val = nullptr;   // [TP.len][Bp] registers of the tape interpreter
@@ -771,7 +776,7 @@ extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
   if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_qp: null argument");
   *out = nullptr;
   if (desc->n < 1 || desc->n > OH_QP_MAX_N || desc->m < 0 || desc->m > OH_QP_MAX_M || desc->me < 0 || desc->me > OH_QP_MAX_ME || desc->me > desc->n)
-    return fail(OH_ERR_INVALID, "oh_create_qp: sizes out of range (n <= 32, m <= 256, me <= min(32, n))");
+    return fail(OH_ERR_INVALID, "oh_create_qp: sizes out of range (1 <= n <= 128, 0 <= m <= 1024, 0 <= me <= min(128, n))");
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_create_qp: no HIP device available (this library has no CPU path)");
   oh_handle* h = new_handle();
@@ -862,7 +867,7 @@ extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
       if (*q2) hipFree(*q2);
       *q2 = nullptr;
     }
-    h->qp_tape_cap = 0;
+    h->qp_tape_cap = h->qp_val_cap = 0;
   }
   h->qp_tape = true;
   return OH_OK;
@@ -875,36 +880,63 @@ static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   Q.n = q.n; Q.m = q.m; Q.me = q.me; Q.np = (int)qp_np(q); Q.max_iter = q.max_iter; Q.tol = q.tol;
   Q.nwork = q.n + 2 * q.m + q.me + q.n * q.n + 2 * q.n + 2 * q.m + q.me * q.n + q.me * q.me + q.me + q.n;
   const int Bp = (B + 63) / 64 * 64;
-  if (Bp > h->qp_cap) {
-    if (h->d_qp_work) hipFree(h->d_qp_work);
+  const int mode = (int)optv(h, "qp_mode");
+  const bool large = oh_qp_is_large(Q), block = oh_qp_takes_block(Q, mode);
+  if (Bp > h->qp_mult_cap) {
     if (h->d_qp_mult) hipFree(h->d_qp_mult);
-    h->d_qp_work = h->d_qp_mult = nullptr;
+    h->d_qp_mult = nullptr;
+    h->qp_mult_cap = 0;
+    HIPCHK(hipMalloc((void**)&h->d_qp_mult, sizeof(double) * (size_t)(q.m + q.me + 1) * Bp));
+    h->qp_mult_cap = Bp;
+  }
+  if (block) {  // what k_qp_solve_block keeps in global memory: a slice per instance (its vectors and H live in LDS)
+    if (B > h->qp_blk_cap) {
+      if (h->d_qp_blk) hipFree(h->d_qp_blk);
+      h->d_qp_blk = nullptr;
+      h->qp_blk_cap = 0;
+      HIPCHK(hipMalloc((void**)&h->d_qp_blk, sizeof(double) * (oh_qp_block_work_doubles(Q) * (size_t)B + 1)));
+      h->qp_blk_cap = B;
+    }
+  } else if (Bp > h->qp_cap) {
+    if (h->d_qp_work) hipFree(h->d_qp_work);
+    h->d_qp_work = nullptr;
     h->qp_cap = 0;
     HIPCHK(hipMalloc((void**)&h->d_qp_work, sizeof(double) * (size_t)Q.nwork * Bp));
-    HIPCHK(hipMalloc((void**)&h->d_qp_mult, sizeof(double) * (size_t)(q.m + q.me + 1) * Bp));
     h->qp_cap = Bp;
   }
-  // register file of the tape interpreter: a lane per instance, or (a few instances: B <= 64) a lane per probe point of every instance
-  const int Bv = B <= 64 ? (B * 64 > Bp ? B * 64 : Bp) : Bp;
-  if (h->qp_tape && Bv > h->qp_tape_cap) {
+  // register file of the tape interpreter: a lane per instance, or (a few instances: B <= 64) a lane per probe point of every instance;
+  // large handles: rows and f(0, p) by instance, the register file by the instances of one launch (64 lanes each)
+  const int Bv = large ? B : (B <= 64 ? (B * 64 > Bp ? B * 64 : Bp) : Bp);
+  const int chunk = (large && h->qp_tape) ? oh_qp_assemble_block_chunk(h->TP, B) : 0;
+  if (h->qp_tape && (Bv > h->qp_tape_cap || chunk > h->qp_val_cap)) {
     for (double** q2 : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) {
       if (*q2) hipFree(*q2);
       *q2 = nullptr;
     }
-    h->qp_tape_cap = 0;
+    h->qp_tape_cap = h->qp_val_cap = 0;
     HIPCHK(hipMalloc((void**)&h->d_qp_rows, sizeof(double) * (size_t)Q.np * Bv));
-    HIPCHK(hipMalloc((void**)&h->d_qp_val, sizeof(double) * (size_t)h->TP.len * Bv));
+    HIPCHK(hipMalloc((void**)&h->d_qp_val, sizeof(double) * (size_t)h->TP.len * (large ? (size_t)chunk * 64 : (size_t)Bv)));
     HIPCHK(hipMalloc((void**)&h->d_qp_f0, sizeof(double) * (size_t)Bv));
     h->qp_tape_cap = Bv;
+    h->qp_val_cap = chunk;
   }
   HIPCHK(hipEventRecord(h->ev0, h->stream));
+  std::string err;
+  h->qp_last_block = block ? 1 : 0;
   if (h->qp_tape) {
-    oh_launch_qp_assemble(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, B <= 64 ? B * 64 : h->qp_tape_cap, (const double*)d_p,
-                          h->d_qp_val, h->d_qp_rows, h->d_qp_f0);
+    if (large) {
+      if (oh_launch_qp_assemble_block(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, chunk,
+                                      (const double*)d_p, h->d_qp_val, h->d_qp_rows, h->d_qp_f0, &err))
+        return fail(OH_ERR_HIP, "oh_solve: " + err);
+    } else {
+      oh_launch_qp_assemble(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, B <= 64 ? B * 64 : h->qp_tape_cap, (const double*)d_p,
+                            h->d_qp_val, h->d_qp_rows, h->d_qp_f0);
+    }
     d_p = h->d_qp_rows;
   }
-  oh_launch_qp_solve(h->stream, Q, B, h->qp_cap, (const double*)d_x0, (const double*)d_p, h->d_qp_work, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                     (int*)d_iters, (int*)d_status, h->d_qp_mult, (int)optv(h, "qp_mode"));
+  if (oh_launch_qp_solve(h->stream, Q, B, h->qp_cap, (const double*)d_x0, (const double*)d_p, block ? h->d_qp_blk : h->d_qp_work, (double*)d_x, (double*)d_f, (double*)d_kkt,
+                         (int*)d_iters, (int*)d_status, h->d_qp_mult, mode, &err))
+    return fail(OH_ERR_HIP, "oh_solve: " + err);
   if (h->qp_tape && d_f) oh_launch_qp_add_constant(h->stream, B, (double*)d_f, h->d_qp_f0);
   return finish_solve(h, 1);
 }
@@ -2682,6 +2714,7 @@ extern "C" void oh_destroy(oh_handle* h) {
   if (h->move_scr) hipFree(h->move_scr);
   if (h->d_pipe_mult) hipFree(h->d_pipe_mult);
   if (h->d_qp_work) hipFree(h->d_qp_work);
+  if (h->d_qp_blk) hipFree(h->d_qp_blk);
   for (void* q : {(void*)h->d_tape_op, (void*)h->d_tape_a, (void*)h->d_tape_b, (void*)h->d_tape_rows, (void*)h->d_tape_c, (void*)h->d_tape_work, (void*)h->d_tape_mult,
                   (void*)h->d_tape_h0})
     if (q) hipFree(q);
@@ -2956,7 +2989,7 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 // How the handle's last solve was (or its next one will be) scheduled, by name: "fuse_couple" (1: coupling folded into evaluation and sweep, no
 // k_couple launch), "tail_threshold", "specialized"; tape handles: "tape_wave" (0: thread per instance, 1 / 2: wavefront per instance with the (s, y)
 // pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
-// oh_tape_phi ran the generated code's entry with the work set in LDS).
+// oh_tape_phi ran the generated code's entry with the work set in LDS); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
   const std::string n(name);
@@ -2971,6 +3004,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_metric") *value = (h->TP.h0 && h->TP.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape_wave.n_levels;
   else if (n == "tape_passes") *value = h->tape_wave.n_fw_pass + h->tape_wave.n_rv_pass;
+  else if (n == "qp_block") *value = h->qp_last_block;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);
   return OH_OK;
 }
@@ -2991,7 +3025,8 @@ extern "C" int oh_kernel_info(const char* kernel, int* out5) {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_kernel_info: no HIP device available (this library has no CPU path)");
   OhKernelInfo k{};
-  if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_linkkin(kernel, &k) && !oh_kernel_info_torque(kernel, &k))
+  if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_linkkin(kernel, &k) && !oh_kernel_info_torque(kernel, &k) &&
+      !oh_kernel_info_qp_block(kernel, &k))
     return fail(OH_ERR_INVALID, std::string("oh_kernel_info: unknown kernel or attribute query failed: ") + kernel);
   out5[0] = k.vgprs; out5[1] = k.scratch_bytes; out5[2] = k.lds_bytes; out5[3] = k.block; out5[4] = k.blocks_per_cu;
   return OH_OK;

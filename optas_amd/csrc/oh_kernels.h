@@ -16,6 +16,7 @@ bool oh_kernel_info_figure8(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_fkjac(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_torque(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_linkkin(const char* name, OhKernelInfo* out);
+bool oh_kernel_info_qp_block(const char* name, OhKernelInfo* out);
 
 void oh_launch_fk_jac(hipStream_t s, bool soa, const oh_chain* d_chain, int n_chain, int ndof, int n, const double* q, double* pose, double* J);
 // What oh_set_link_frames keeps on the device for k_link_kin (oh_linkkin.hip): the chains root->link and root->base, and the number of leading
@@ -155,9 +156,15 @@ struct QpParams {
   int n, m, me, np, nwork, max_iter;
   double tol;
 };
-void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
-                        int* iters, int* status, double* mult, int mode);  // work: [Q.nwork][Bp] (used when the work set of a block does not fit LDS)
-                                                                           // mode: -1 automatic, 0 / 1 / 2 force a work-set placement (option qp_mode)
+// work: [Q.nwork][Bp] (used when the work set of a block does not fit LDS), or B slices of oh_qp_block_work_doubles when oh_qp_takes_block
+// mode: -1 automatic, 0 / 1 / 2 force a work-set placement, 3 forces the block-per-instance kernel (option qp_mode).  Non-zero: *err says why.
+int oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
+                       int* iters, int* status, double* mult, int mode, std::string* err);
+bool oh_qp_is_large(const QpParams& Q);                  // beyond n = 32, m = 256, me = 32: block-per-instance kernels only
+bool oh_qp_takes_block(const QpParams& Q, int mode);     // the solve runs k_qp_solve_block (oh_qp_block.hip)
+size_t oh_qp_block_work_doubles(const QpParams& Q);      // per instance: W^T [n][me] and the Schur complement
+int oh_launch_qp_solve_block(hipStream_t s, const QpParams& Q, int B, const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters,
+                             int* status, double* mult, std::string* err);
 
 // ---- OH_PROBLEM_TAPE ---------------------------------------------------------------------------------------
 #define OH_TAPE_ST_CONVERGED OH_STATUS_CONVERGED
@@ -168,6 +175,10 @@ void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const d
 void oh_launch_qp_assemble(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
                            const int* xdep, int n_xdep, int B, int Bp, const double* p_raw, double* val, double* rows_out, double* f0);  // xdep: x-dependent instructions
 void oh_launch_qp_add_constant(hipStream_t s, int B, double* f, const double* f0);
+// the same for handles beyond the old limits: `chunk` (oh_qp_assemble_block_chunk) instances per launch, val = [T.len][chunk * 64]
+int oh_qp_assemble_block_chunk(const TapeParams& T, int B);
+int oh_launch_qp_assemble_block(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
+                                const int* xdep, int n_xdep, int B, int chunk, const double* p_raw, double* val, double* rows_out, double* f0, std::string* err);
 struct TapeJit {
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;

@@ -4,13 +4,16 @@
 //     min_x  x^T P x + q^T x      s.t.  M x + c >= 0,   A x + b = 0           (optimization.py:219-260: no factor 1/2)
 //
 // One thread owns one instance: infeasible-start primal-dual interior point with slacks s = Mx + c, Newton system reduced to
-// H = P + P^T + M^T (lam/s) M (dense Cholesky, n <= OH_QP_MAX_N) and the Schur complement A H^{-1} A^T for the equality rows.
+// H = P + P^T + M^T (lam/s) M (dense Cholesky, n <= 32, m <= 256, me <= 32; larger handles, up to OH_QP_MAX_N / _M / _ME, are solved by one workgroup per
+// instance: oh_qp_block.hip) and the Schur complement A H^{-1} A^T for the equality rows.
 // The matrices differ per instance (P, M, A may depend on the parameters: the Booth test has a * y in its cost), so every
 // instance brings its own [P | q | M | c | A | b] row; work arrays are thread-private slices of one global buffer.
 // numpy restatement of the same iteration: oracle/qp_ipm.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <mutex>
+#include <string>
 
 #include "oh_kernels.h"
 
@@ -475,6 +478,7 @@ struct QpTape {
   int n_xdep;                     // instructions whose value depends on x (the kinematics of a velocity-IK problem depend on p only:
   const int* __restrict__ xdep;   // 139 of its 474 instructions are left), in tape order
 };
+constexpr int QP_SMALL_N = 32;  // n of the handles these two kernels serve (their per-lane and static LDS arrays); larger ones: k_qp_assemble_block
 #define QIDX(i) ((size_t)(i) * Bp + b)
 // FULL: every instruction; else only the x-dependent ones (the others keep the values of an earlier full sweep at the same p)
 template <bool FULL>
@@ -510,7 +514,7 @@ __global__ __launch_bounds__(64) void k_qp_assemble(QpParams Q, QpTape tp, int n
   double* c = M + m * n;
   double* A = c + m;
   double* bv = A + me * n;
-  double x[OH_QP_MAX_N], f1[OH_QP_MAX_N];
+  double x[QP_SMALL_N], f1[QP_SMALL_N];
   for (int i = 0; i < n; ++i) x[i] = 0.0;
   const double f0 = qp_tape_forward<true>(tp, x, pb, val, Bp, b);
   for (int r = 0; r < m; ++r) c[r] = val[QIDX(tp.rows[r])];
@@ -553,7 +557,7 @@ __device__ void qp_probe_point(const int pid, const int n, double* x, int* pi, i
 }
 __global__ __launch_bounds__(64) void k_qp_assemble_par(QpParams Q, QpTape tp, int np_raw, int B, const double* __restrict__ par, double* __restrict__ val,
                                                         double* __restrict__ rows_out, double* __restrict__ f0_out) {
-  __shared__ double fs[1 + 2 * OH_QP_MAX_N + OH_QP_MAX_N * (OH_QP_MAX_N - 1) / 2];
+  __shared__ double fs[1 + 2 * QP_SMALL_N + QP_SMALL_N * (QP_SMALL_N - 1) / 2];
   const int inst = blockIdx.x, lane = threadIdx.x;
   const int n = Q.n, m = Q.m, me = Q.me;
   const int n_probe = 1 + 2 * n + n * (n - 1) / 2;
@@ -565,7 +569,7 @@ __global__ __launch_bounds__(64) void k_qp_assemble_par(QpParams Q, QpTape tp, i
   double* A = c + m;
   double* bv = A + me * n;
   const int Bp = B * 64, b = inst * 64 + lane;  // QIDX(i) = (i * B + inst) * 64 + lane
-  double x[OH_QP_MAX_N];
+  double x[QP_SMALL_N];
   for (int base = 0; base < n_probe; base += 64) {
     const int pid = base + lane;
     const bool live = pid < n_probe;
@@ -600,6 +604,88 @@ __global__ __launch_bounds__(64) void k_qp_assemble_par(QpParams Q, QpTape tp, i
   }
   if (lane == 0) f0_out[inst] = f0;
 }
+// Handles beyond n = 32, m = 256, me = 32 (oh_qp_block.hip solves them): the mapping of k_qp_assemble_par for every B -- a block per instance,
+// a lane per probe point, 64 at a time -- without a per-lane x: the value of an `X a` instruction follows from the probe's (i, j, sign).  The
+// probes' values sit in dynamic LDS (8385 doubles at n = 128).  nb instances per launch: registers of lane l of instance b at
+// val[(i * nb + b) * 64 + l]; the host loop (oh_launch_qp_assemble_block) keeps nb * len * 64 doubles under a fixed budget.
+__global__ __launch_bounds__(64) void k_qp_assemble_block(QpParams Q, QpTape tp, int np_raw, int nb, const double* __restrict__ par, double* __restrict__ val,
+                                                          double* __restrict__ rows_out, double* __restrict__ f0_out) {
+#pragma clang fp contract(off)
+  extern __shared__ double qa_fs[];
+  double* fs = qa_fs;
+  const int inst = blockIdx.x, lane = threadIdx.x;
+  const int n = Q.n, m = Q.m, me = Q.me;
+  const int n_probe = 1 + 2 * n + n * (n - 1) / 2;
+  const double* pb = par + (size_t)inst * np_raw;
+  double* P = rows_out + (size_t)inst * Q.np;
+  double* q = P + n * n;
+  double* M = q + n;
+  double* c = M + (size_t)m * n;
+  double* A = c + m;
+  double* bv = A + me * n;
+  const int Bp = nb * 64, b = inst * 64 + lane;  // QIDX(i) = (i * nb + inst) * 64 + lane
+  for (int base = 0; base < n_probe; base += 64) {
+    const int pid = base + lane;
+    const bool live = pid < n_probe;
+    // probe pid: 0 at x = 0; 1 .. n at e_i; n + 1 .. 2 n at -e_i; then the pairs e_i + e_j, j < i
+    int pi = -1, pj = -1;
+    double sign = 1.0;
+    if (live && pid >= 1) {
+      if (pid <= n) pi = pid - 1;
+      else if (pid <= 2 * n) { pi = pid - 1 - n; sign = -1.0; }
+      else {
+        int k = pid - 1 - 2 * n, i = 1;
+        while (k >= i) { k -= i; ++i; }
+        pi = i;
+        pj = k;
+      }
+    }
+    for (int i = 0; i < tp.len; ++i) {  // full sweep on the first pass (the p-only instructions), the x-dependent ones afterwards
+      if (base > 0) {
+        if (i >= tp.n_xdep) break;
+      }
+      const int k = base > 0 ? tp.xdep[i] : i;
+      const int o = tp.op[k], ia = tp.a[k], ib = tp.bb[k];
+      double v;
+      switch (o) {
+        case 0: v = tp.c[k]; break;
+        case 1: v = (ia == pi || ia == pj) ? sign : 0.0; break;
+        case 2: v = pb[ia]; break;
+        case 3: v = val[QIDX(ia)] + val[QIDX(ib)]; break;
+        case 4: v = val[QIDX(ia)] - val[QIDX(ib)]; break;
+        case 5: v = val[QIDX(ia)] * val[QIDX(ib)]; break;
+        default: v = tape_op_value(o, val[QIDX(ia)], tape_op_arity(o) == 2 ? val[QIDX(ib)] : 0.0); break;
+      }
+      val[QIDX(k)] = v;
+    }
+    if (live) fs[pid] = val[QIDX(tp.out_cost)];
+    if (base == 0) {  // the rows at 0 first, then the columns of M and A relative to them
+      if (lane == 0) {
+        for (int r = 0; r < m; ++r) c[r] = val[QIDX(tp.rows[r])];
+        for (int r = 0; r < me; ++r) bv[r] = val[QIDX(tp.rows[m + r])];
+      }
+      __syncthreads();
+    }
+    if (live && pid >= 1 && pid <= n) {
+      const int i = pid - 1;
+      for (int r = 0; r < m; ++r) M[(size_t)r * n + i] = val[QIDX(tp.rows[r])] - c[r];
+      for (int r = 0; r < me; ++r) A[r * n + i] = val[QIDX(tp.rows[m + r])] - bv[r];
+    }
+  }
+  __syncthreads();
+  const double f0 = fs[0];
+  for (int i = lane; i < n; i += 64) {
+    const double qi = 0.5 * (fs[1 + i] - fs[1 + n + i]);
+    q[i] = qi;
+    P[i * n + i] = fs[1 + i] - f0 - qi;
+  }
+  for (int k = lane; k < n * (n - 1) / 2; k += 64) {
+    int kk = k, i = 1;
+    while (kk >= i) { kk -= i; ++i; }
+    P[i * n + kk] = P[kk * n + i] = 0.5 * (fs[1 + 2 * n + k] - fs[1 + i] - fs[1 + kk] + f0);
+  }
+  if (lane == 0) f0_out[inst] = f0;
+}
 __global__ __launch_bounds__(256) void k_qp_add_constant(int B, double* __restrict__ f, const double* __restrict__ f0) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) f[b] += f0[b];
@@ -613,12 +699,58 @@ void oh_launch_qp_assemble(hipStream_t s, const QpParams& Q, const TapeParams& T
   if ((size_t)B * 64 <= (size_t)Bp) hipLaunchKernelGGL(k_qp_assemble_par, dim3(B), dim3(64), 0, s, Q, tp, T.np, B, p_raw, val, rows_out, f0);  // room for a lane per probe
   else hipLaunchKernelGGL(k_qp_assemble, dim3((B + 63) / 64), dim3(64), 0, s, Q, tp, T.np, B, Bp, p_raw, val, rows_out, f0);
 }
+namespace {
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device and sticky: ask only when a launch needs more than this device has been granted
+bool grant_dynamic_lds(const void* fn, const size_t bytes, size_t* granted /* [64], by device */) {
+  static std::mutex mtx;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  std::lock_guard<std::mutex> lock(mtx);
+  if (bytes <= granted[dev]) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+  granted[dev] = bytes;
+  return true;
+}
+size_t g_assemble_lds[64];
+}  // namespace
+
+int oh_qp_assemble_block_chunk(const TapeParams& T, int B) {
+  // instances per launch: the register file (len * 64 doubles per instance in flight) stays under 256 MB whatever B is
+  const size_t per = sizeof(double) * 64 * (size_t)(T.len > 0 ? T.len : 1);
+  size_t nb = ((size_t)256 << 20) / per;
+  if (nb < 1) nb = 1;
+  return (int)(nb < (size_t)B ? nb : (size_t)B);
+}
+int oh_launch_qp_assemble_block(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
+                                const int* xdep, int n_xdep, int B, int chunk, const double* p_raw, double* val, double* rows_out, double* f0, std::string* err) {
+  const QpTape tp{T.len, T.out_cost, op, a, b, c, rows, n_xdep, xdep};
+  const size_t lds = sizeof(double) * (size_t)(1 + 2 * Q.n + Q.n * (Q.n - 1) / 2);
+  if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_qp_assemble_block), lds, g_assemble_lds)) {
+    (void)hipGetLastError();
+    *err = "k_qp_assemble_block: " + std::to_string(lds) + " bytes of LDS per block were refused";
+    return 1;
+  }
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = B - b0 < chunk ? B - b0 : chunk;
+    hipLaunchKernelGGL(k_qp_assemble_block, dim3(nb), dim3(64), lds, s, Q, tp, T.np, nb, p_raw + (size_t)b0 * T.np, val, rows_out + (size_t)b0 * Q.np, f0 + b0);
+  }
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+    *err = std::string("k_qp_assemble_block: launch failed: ") + hipGetErrorString(e);
+    return 1;
+  }
+  return 0;
+}
 void oh_launch_qp_add_constant(hipStream_t s, int B, double* f, const double* f0) {
   hipLaunchKernelGGL(k_qp_add_constant, dim3((B + 255) / 256), dim3(256), 0, s, B, f, f0);
 }
 
-void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
-                        int* iters, int* status, double* mult, const int forced) {
+bool oh_qp_is_large(const QpParams& Q) { return Q.n > QP_SMALL_N || Q.m > 256 || Q.me > 32; }
+bool oh_qp_takes_block(const QpParams& Q, const int forced) { return forced == 3 || oh_qp_is_large(Q); }
+
+int oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const double* x0, const double* p, double* work, double* x, double* f, double* kkt,
+                       int* iters, int* status, double* mult, const int forced, std::string* err) {
+  // beyond n = 32, m = 256, me = 32 a workgroup per instance for every B (a forced 0 / 1 / 2 does not fit there and falls back to it); forced == 3: on any handle
+  if (oh_qp_takes_block(Q, forced)) return oh_launch_qp_solve_block(s, Q, B, x0, p, work, x, f, kkt, iters, status, mult, err);
   // the work set of a block in LDS when it fits 48 KB at 64, 32 or 16 instances per block; for a few instances the problem row as well
   auto fit = [](const size_t doubles) {
     for (int c : {64, 32, 16})
@@ -629,7 +761,7 @@ void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const d
   const size_t wave_bytes = sizeof(double) * ((size_t)Q.nwork + Q.np);
   if (forced != 0 && forced != 1 && forced != 2 && B <= 64 && wave_bytes <= 48 * 1024) {  // a few instances: one wavefront each
     hipLaunchKernelGGL(k_qp_solve_wave, dim3(B), dim3(64), wave_bytes, s, Q, B, x0, p, x, f, kkt, iters, status, mult);
-    return;
+    return 0;
   }
   int mode = bs2 ? 2 : (bs1 ? 1 : 0);  // forced: option "qp_mode" (experiments)  // (velocity-IK QP, n = 7, m = 16: B = 1 in 1.77 / 1.49 / 1.15 ms wall, 65 536 in 13.0 / 12.7 / 11.5 ms for modes 0 / 1 / 2)
   if (forced == 0 || (forced == 1 && bs1) || (forced == 2 && bs2)) mode = forced;
@@ -639,4 +771,5 @@ void oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const d
   else if (mode == 1)
     hipLaunchKernelGGL(k_qp_solve<1>, dim3((B + bs1 - 1) / bs1), dim3(bs1), sizeof(double) * (size_t)Q.nwork * bs1, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
   else hipLaunchKernelGGL(k_qp_solve<0>, dim3((B + 63) / 64), dim3(64), 0, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
+  return 0;
 }

@@ -702,11 +702,16 @@ def _band_rows(opt: Optimization):
     return out
 
 
-def match_qp(opt: Optimization) -> QpSpec:
+QP_LIMITS = (32, 256, 32)  # n, m, me up to which match_qp takes a problem by default
+QP_LIMITS_LARGE = (128, 1024, 128)  # what the library takes (OH_QP_MAX_N / _M / _ME): HIPSolver option "dense_qp"
+
+
+def match_qp(opt: Optimization, limits=QP_LIMITS) -> QpSpec:
     """QuadraticCostUnconstrained / QuadraticCostLinearConstraints (optimization.py:312-388) with small dense data: what the
     reference's OSQP / CVXOPT / qpOASES back-ends take (solver.py:421-584).  QuadraticCostNonlinearConstraints (optimization.py:391-460)
     whose only nonlinear rows are squares of affine expressions under a constant bound (`_band_rows`) are handed over as the equivalent
-    linearly constrained QP.  Last resort: the dedicated families come first."""
+    linearly constrained QP.  Last resort: the dedicated families come first.  limits: largest (nx, nk, na) taken; beyond the default the
+    library solves an instance with one workgroup (k_qp_solve_block)."""
     from .optimization import QuadraticCostLinearConstraints, QuadraticCostNonlinearConstraints, QuadraticCostUnconstrained
     from .sx_container import SXContainer
 
@@ -730,8 +735,9 @@ def match_qp(opt: Optimization) -> QpSpec:
     if opt.has_discrete_variables():
         raise LoweringError("dense-QP lowering: discrete variables are not supported")
     n, m, me = opt.nx, opt.nk, opt.na
-    if not (1 <= n <= 32 and m <= 256 and me <= min(32, n)):
-        raise LoweringError(f"dense-QP lowering: sizes nx={n}, nk={m}, na={me} exceed the dense kernel's limits (32, 256, 32)")
+    ln, lm, lme = (int(v) for v in limits)
+    if not (1 <= n <= ln and m <= lm and me <= min(lme, n)):
+        raise LoweringError(f"dense-QP lowering: sizes nx={n}, nk={m}, na={me} exceed the dense kernel's limits ({ln}, {lm}, {lme})")
     return QpSpec(n, m, me, problem, bands)
 
 
@@ -873,12 +879,12 @@ def match_torque_mpc(opt: Optimization) -> TorqueSpec:
                       None if vlo is None else np.asarray(vlo, float), None if vup is None else np.asarray(vup, float))
 
 
-def lower(opt: Optimization):
-    """Return (kind, spec).  Raises LoweringError if no kernel family matches."""
+def lower(opt: Optimization, qp_limits=QP_LIMITS):
+    """Return (kind, spec).  Raises LoweringError if no kernel family matches.  qp_limits: see match_qp."""
     errors = []
     for kind, fn in ((_lib.OH_PROBLEM_FIGURE_EIGHT, match_figure_eight), (_lib.OH_PROBLEM_TORQUE_MPC, match_torque_mpc), (_lib.OH_PROBLEM_POINT_MASS_MPC, match_point_mass), (_lib.OH_PROBLEM_POINT_MASS_MPC, match_point_mass_planner),
                      (OH_KIND_MULTI_ARM, match_multi_arm),
-                     (_lib.OH_PROBLEM_IK, match_ik), (_lib.OH_PROBLEM_QP, match_qp), (_lib.OH_PROBLEM_TAPE, match_tape)):
+                     (_lib.OH_PROBLEM_IK, match_ik), (_lib.OH_PROBLEM_QP, lambda o: match_qp(o, qp_limits)), (_lib.OH_PROBLEM_TAPE, match_tape)):
         try:
             return kind, fn(opt)
         except LoweringError as e:

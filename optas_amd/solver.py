@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .backend import BatchResult, FigureEightBackend, IKBackend, MultiArmBackend, PointMassBackend, QPBackend, TapeBackend, TorqueBackend, tape_backend, tape_default_max_iter
-from .lowering import FigureEightSpec, IkSpec, MultiArmSpec, PointMassSpec, QpSpec, TapeSpec, TorqueSpec, lower
+from .lowering import QP_LIMITS, QP_LIMITS_LARGE, FigureEightSpec, IkSpec, MultiArmSpec, PointMassSpec, QpSpec, TapeSpec, TorqueSpec, lower
 from .models import RobotModel
 from .optimization import Optimization
 
@@ -226,6 +226,9 @@ class _QpAdapter:
         r.f = r.f + np.asarray(f0)
         return r
 
+    def solve_ms(self) -> float:
+        return self.be.solve_ms()
+
     def close(self) -> None:
         self.be.close()
 
@@ -280,7 +283,8 @@ class HIPSolver(Solver):
         o = dict(solver_options or {})
         # options of the library handle(s) behind this solver (include/optas_hip.h: oh_set_option), e.g. {"batch_invariant": 1}
         handle_options = dict(o.pop("options", None) or {})
-        kind, spec = lower(self.opt)
+        # "dense_qp": quadratic programs up to (128, 1024, 128) go to the dense QP family (a workgroup per instance beyond (32, 256, 32)) instead of the tape family
+        kind, spec = lower(self.opt, QP_LIMITS_LARGE if bool(o.pop("dense_qp", False)) else QP_LIMITS)
         self._kind, self._spec = kind, spec
         hessian = {"gauss_newton": _lib.OH_HESSIAN_GAUSS_NEWTON, "exact": _lib.OH_HESSIAN_EXACT, "hybrid": _lib.OH_HESSIAN_HYBRID}[o.get("hessian", "hybrid")]
         if isinstance(spec, FigureEightSpec):
