@@ -422,7 +422,11 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
    not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_jit_lds" (1: the last oh_tape_phi ran
    the generated code's entry with its work set in LDS); OH_PROBLEM_QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance
-   kernel k_qp_solve_block). */
+   kernel k_qp_solve_block); position-tracking handles (lock_orientation = 0): "free_sweep", the kernel that solved the block-tridiagonal system
+   of the last oh_solve / oh_solve_device call's first launch -- 0 k_step_free (one lane per instance), 1 k_step_free_pcr, 2 k_step_free_cp,
+   3 k_step_free_bb, 4 k_free_persist (the whole solve in one launch); -1 before the first solve -- and "free_sweeps_used", the bit mask
+   (1 << value) of every sweep that solve launched, those chosen for the smaller batch after a compaction included.  Both describe the handle
+   that ran the loop: a batch solved in parts (option "streams") leaves them on the parts' handles, and the caller's keeps its last own solve. */
 int oh_get_flag(oh_handle* h, const char* name, int* value);
 
 /*

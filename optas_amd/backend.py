@@ -679,7 +679,8 @@ class FigureEightBackend(_OptionsMixin):
         _lib.check(_lib.load().oh_set_profiling(self._h, 1 if on else 0), "oh_set_profiling")
 
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'fuse_couple', 'tail_threshold', 'specialized'."""
+        """oh_get_flag: 'fuse_couple', 'tail_threshold', 'specialized'; position-tracking handles: 'free_sweep' (0 serial, 1 PCR, 2 CP, 3 BB,
+        4 persistent: the sweep the last solve started with), 'free_sweeps_used' (bit mask of every sweep it launched)."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return v.value

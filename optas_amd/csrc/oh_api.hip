@@ -122,6 +122,8 @@ struct oh_handle {
   double* d_qp_blk = nullptr;  // k_qp_solve_block: [B][me n + me^2] (oh_qp_block_work_doubles), a contiguous slice per instance
   int qp_blk_cap = 0;
   int qp_last_block = 0;       // the last solve ran k_qp_solve_block (oh_get_flag "qp_block")
+  int free_sweep_last = -1;    // position-tracking family: the FreeSweep the last solve started with (oh_get_flag "free_sweep"; -1: none yet)
+  int free_sweeps_used = 0;    // ... and bit (1 << FreeSweep) of every sweep its loop used, those chosen after compactions included ("free_sweeps_used")
   int qp_mult_cap = 0;
   int qp_val_cap = 0;          // large handles: instances per launch of k_qp_assemble_block the register file d_qp_val holds
   bool qp_tape = false;       // oh_qp_set_tape: p of a solve is the problem's parameter vector, the QP data is read off the tape (h->TP, d_tape_*) on the device
@@ -2017,6 +2019,8 @@ static int free_loop(oh_handle* h, Traj& r) {
   const hipStream_t s = h->stream;
   const int N = r.N;
   FreeSweep sweep = r.sweep;  // (changes with D.B)
+  h->free_sweep_last = (int)sweep;
+  h->free_sweeps_used = 1 << (int)sweep;
   if (sweep == FREE_PERSIST) {
     if (!oh_launch_free_persist(s, N, P, D, GP, GB)) return fail(OH_ERR_INVALID, "oh_solve_device: no persistent kernel for this handle (ndof / rows)");
     r.launched = 1;
@@ -2046,6 +2050,7 @@ static int free_loop(oh_handle* h, Traj& r) {
     if (nrun > 0 && h->sch.compaction && D.B >= 512 && (double)nrun <= h->sch.compact_frac_restart * (double)D.B) {
       if (const int rc = compact_batch(h, r, nrun, (it + 1) & 1, false)) return rc;
       sweep = free_sweep(h, D.B);
+      h->free_sweeps_used |= 1 << (int)sweep;
       if (const int rc = mark(h, r, 0)) return rc;  // (the compaction kernels are accounted to neither eval nor step: restart the event pair)
     }
   }
@@ -2989,7 +2994,8 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 // How the handle's last solve was (or its next one will be) scheduled, by name: "fuse_couple" (1: coupling folded into evaluation and sweep, no
 // k_couple launch), "tail_threshold", "specialized"; tape handles: "tape_wave" (0: thread per instance, 1 / 2: wavefront per instance with the (s, y)
 // pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
-// oh_tape_phi ran the generated code's entry with the work set in LDS); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel).
+// oh_tape_phi ran the generated code's entry with the work set in LDS); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
+// position-tracking handles: "free_sweep" (the FreeSweep the last solve started with, -1 before the first), "free_sweeps_used" (bit mask over its launches).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
   const std::string n(name);
@@ -3005,6 +3011,8 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_levels") *value = h->tape_wave.n_levels;
   else if (n == "tape_passes") *value = h->tape_wave.n_fw_pass + h->tape_wave.n_rv_pass;
   else if (n == "qp_block") *value = h->qp_last_block;
+  else if (n == "free_sweep") *value = h->free_sweep_last;
+  else if (n == "free_sweeps_used") *value = h->free_sweeps_used;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);
   return OH_OK;
 }

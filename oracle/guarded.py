@@ -89,12 +89,13 @@ def guard_values(chain: FoldedChain, Q, G: Guards, weights=None):
 
 
 def solve_free_al(chain: FoldedChain, T, dt, offsets, qc, guards: Guards, Q0=None, w_path=1.0, w_vel=0.01, fix_dq0=False, max_iter=400,
-                  tol=1e-6, tol_feas=1e-9, rho0=1e3, verbose=False, exact=True, vlimits=None, fuse=True):
+                  tol=1e-6, tol_feas=1e-9, rho0=1e3, verbose=False, exact=True, vlimits=None, fuse=True, on_system=None):
     """vlimits = (vlo, vup): joint-velocity rows dq_t - vlo >= 0, vup - dq_t >= 0 on dq_t = (q_{t+1} - q_t) / dt, t = 0 .. T-2
     (enforce_model_limits(name, time_deriv=1), builder.py:471-509; round 3: k_couple_free_vel in csrc/oh_free.hip).  Same treatment as in
     oracle/structured.py: penalty rho * vscale, the value of interval (t-1, t) is booked on knot t, its gradient enters both knots, its
     Gauss-Newton weight rho_v / dt^2 joins 2 kappa on the diagonal of both knots and in the coupling block between them (which stays
-    diagonal).  Adds "lam_v" (T-1, 2n) and "g_v"."""
+    diagonal).  Adds "lam_v" (T-1, 2n) and "g_v".
+    on_system(iteration, D, Er, rhs, mu, z): as in solve_free_lm, called after every linear solve; an observer."""
     n = chain.ndof
     t0 = 2 if fix_dq0 else 1
     kap = w_vel / dt**2
@@ -222,6 +223,8 @@ def solve_free_al(chain: FoldedChain, T, dt, offsets, qc, guards: Guards, Q0=Non
         Er = cur["Er"]
         while True:
             z, ok = block_tridiag_solve(cur["D"], Er, -cur["G"], mu)
+            if on_system is not None:
+                on_system(iters, cur["D"], Er, -cur["G"], mu, z)
             if ok:
                 break
             mu = max(4.0 * mu, 1e-2)

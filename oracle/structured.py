@@ -620,9 +620,12 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
 # ----------------------------------------------------------------------------------------------------
 # Position-only tracking (dual_arm.py per arm): port of k_eval_free / k_couple_free / k_step_free.
 # ----------------------------------------------------------------------------------------------------
-def solve_free_lm(chain: FoldedChain, T, dt, offsets, qc, Q0=None, w_path=1.0, w_vel=0.01, fix_dq0=False, max_iter=300, tol=1e-6, exact=False, verbose=False):
+def solve_free_lm(chain: FoldedChain, T, dt, offsets, qc, Q0=None, w_path=1.0, w_vel=0.01, fix_dq0=False, max_iter=300, tol=1e-6, exact=False, verbose=False,
+                  on_system=None):
     """min sum_t w_path ||p(q_t) - (p(qc) + offsets_t)||^2 + (w_vel/dt^2) sum_t ||q_{t+1}-q_t||^2, q_0 = qc (and q_1 = qc if fix_dq0).
-    offsets: (T,3).  Same LM ratio test / Nielsen update / Riccati recursion as the HIP kernels."""
+    offsets: (T,3).  Same LM ratio test / Nielsen update / Riccati recursion as the HIP kernels.
+    on_system(iteration, D, Er, rhs, mu, z): called after every linear solve (iteration = steps counted so far; z is None where the factorisation
+    broke down and the damping is raised); an observer, it changes nothing."""
     n = chain.ndof
     t0 = 2 if fix_dq0 else 1
     kap = w_vel / dt**2
@@ -680,6 +683,8 @@ def solve_free_lm(chain: FoldedChain, T, dt, offsets, qc, Q0=None, w_path=1.0, w
         Er = np.tile(-2 * kap * np.eye(n), (nf - 1, 1, 1))
         while True:
             z, ok = block_tridiag_solve(cur["D"], Er, -cur["G"], mu)
+            if on_system is not None:
+                on_system(iters, cur["D"], Er, -cur["G"], mu, z)
             if ok:
                 break
             mu = max(4.0 * mu, 1e-2)

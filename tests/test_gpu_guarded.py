@@ -354,6 +354,9 @@ def test_cyclic_reduction_step_equals_the_serial_sweep(hip_lib, monkeypatch, T, 
         mb = MultiArmBackend(spec, o, max_iter=400)
         res = mb.solve(X0, P)
         out[mode] = (res, [be.multipliers(B) for _, be in mb.arms] if guarded else [])
+        # the kernel each mode is meant to run (FreeSweep: 0 serial, 1 pcr, 2 cp, 3 bb, 4 persistent; automatic persistence up to 64 free knots)
+        want = {"0": 0, "4096": 4 if guarded and T - 1 <= 64 else 3, "4096/pair": 3, "4096/cr": 2 if T - 1 <= 64 else 1, "4096/lane": 1}[mode]
+        assert [be.flag("free_sweep") for _, be in mb.arms] == [want, want] and [be.flag("free_sweeps_used") for _, be in mb.arms] == [1 << want] * 2, (mode, want)
         mb.close()
     for mode in ("4096/pair", "4096/cr"):
         rv = out[mode][0]
