@@ -1,5 +1,7 @@
 // C ABI of liboptas_hip.so (see include/optas_hip.h).  Host-side orchestration only: buffer
 // ownership, the SQP launch loop (eval kernel + Riccati/step kernel per iteration), HIP-event timing.
+// Memory: every device or pinned allocation of a handle is a DevBuf member (grow-only, freed by the handle's destructor); what lives inside a pool
+// or the staging area is laid out by ONE list of Carver takes (oh_carve.h) that both measures and carves it.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is opened with dlopen when a communicator is first asked for
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "oh_kernels.h"
+#include "oh_carve.h"
 #include "oh_jit.h"
 #include "oh_rnea.h"
 
@@ -37,6 +40,37 @@ static int fail(int code, const std::string& msg) {
   } while (0)
 
 #define OH_PINNED_STAGE_BYTES (256 * 1024)
+
+// An owned device (or pinned host) array of `cap` elements: grows only, freed by release() and by the destructor.
+template <class T, bool PINNED = false>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  void release() {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  // room for n elements; *grew (may be null): the array was reallocated, its content is gone.  A failed allocation leaves {nullptr, 0}.
+  hipError_t reserve(const size_t n, bool* grew = nullptr) {
+    if (grew) *grew = false;
+    if (n <= cap) return hipSuccess;
+    release();
+    const hipError_t e = PINNED ? hipHostMalloc((void**)&p, n * sizeof(T)) : hipMalloc((void**)&p, n * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    cap = n;
+    if (grew) *grew = true;
+    return hipSuccess;
+  }
+};
 
 // Scheduling state of a handle, set by name through the field-backed options (FIELD_OPTS): a peer takes it over in one assignment.
 struct Sched {
@@ -80,14 +114,14 @@ struct oh_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evt0 = nullptr, evt1 = nullptr;
   bool have_chain = false;
   oh_chain chain_host;
-  oh_chain* d_chain = nullptr;
+  DevBuf<oh_chain> d_chain;
   bool have_frames = false;  // oh_set_link_frames: the two chains of oh_link_kin*, independent of the chain above
   OhLinkFrames frames_host;
-  OhLinkFrames* d_frames = nullptr;
+  DevBuf<OhLinkFrames> d_frames;
   bool have_dyn = false;
   oh_dynamics dyn_host;
-  oh_dynamics* d_dyn = nullptr;
-  double* d_local_path = nullptr;
+  DevBuf<oh_dynamics> d_dyn;
+  DevBuf<double> d_local_path;
   // point-mass family
   oh_pointmass_desc pm{};
   PmParams PmP{};
@@ -97,64 +131,54 @@ struct oh_handle {
   oh_guards guards{};
   GuardParams GP{};
   GuardBuffers GB{};
-  void* gpool = nullptr;
-  int gcap = 0;
-  void* move_scr = nullptr;  // scratch of the compaction that moves every array (move_everything)
-  size_t move_scr_bytes = 0;
+  DevBuf<char> gpool;
+  int gcap = 0;              // the row stride (D.Bp) the guard pool was carved for
+  DevBuf<char> move_scr;     // scratch of the compaction that moves every array (move_everything)
   // tape family
   TapeParams TP{};
-  int *d_tape_op = nullptr, *d_tape_a = nullptr, *d_tape_b = nullptr, *d_tape_rows = nullptr;
-  double* d_tape_c = nullptr;
-  double* d_tape_work = nullptr;
-  double* d_tape_mult = nullptr;
-  double* d_tape_h0 = nullptr;  // oh_tape_set_metric: initial metric of the limited-memory form [nx][nx]
-  int tape_cap = 0;
+  DevBuf<int> d_tape_op, d_tape_a, d_tape_b, d_tape_rows;
+  DevBuf<double> d_tape_c;
+  DevBuf<double> d_tape_work;   // [oh_tape_work_rows][tape_cap]; grows with d_tape_mult
+  DevBuf<double> d_tape_mult;   // [n_ineq + n_eq + 1][tape_cap]
+  DevBuf<double> d_tape_h0;     // oh_tape_set_metric: initial metric of the limited-memory form [nx][nx]
+  int tape_cap() const { return (int)(d_tape_mult.cap / (size_t)(TP.n_ineq + TP.n_eq + 1)); }  // instances the two work arrays hold: their row stride
   TapeJit tape_jit;
   TapeJit tape_jit_phi;       // the single-evaluation kernels of the same generated evaluator: compiled by the first oh_tape_phi, not with the handle
   int tape_phi_lds = 0;       // whether the last oh_tape_phi ran the generated code's entry with the work set in LDS
   TapeWave tape_wave;  // trajectory-sized tapes: one wavefront per instance (oh_tape_wave.hip)
   // dense QP family
   oh_qp_desc qp{};
-  void* h_stage = nullptr;  // pinned mirror of the staging area for small oh_solve calls (OH_PINNED_STAGE_BYTES)
-  double* d_qp_work = nullptr;
-  double* d_qp_mult = nullptr;
-  int qp_cap = 0;
-  double* d_qp_blk = nullptr;  // k_qp_solve_block: [B][me n + me^2] (oh_qp_block_work_doubles), a contiguous slice per instance
-  int qp_blk_cap = 0;
+  DevBuf<char, true> h_stage;  // pinned mirror of the staging area for small oh_solve calls (OH_PINNED_STAGE_BYTES)
+  DevBuf<double> d_qp_work;    // [Q.nwork][Bp]
+  DevBuf<double> d_qp_mult;    // [m + me + 1][Bp]
+  DevBuf<double> d_qp_blk;     // k_qp_solve_block: [B][me n + me^2] (oh_qp_block_work_doubles), a contiguous slice per instance
   int qp_last_block = 0;       // the last solve ran k_qp_solve_block (oh_get_flag "qp_block")
   int free_sweep_last = -1;    // position-tracking family: the FreeSweep the last solve started with (oh_get_flag "free_sweep"; -1: none yet)
   int free_sweeps_used = 0;    // ... and bit (1 << FreeSweep) of every sweep its loop used, those chosen after compactions included ("free_sweeps_used")
-  int qp_mult_cap = 0;
-  int qp_val_cap = 0;          // large handles: instances per launch of k_qp_assemble_block the register file d_qp_val holds
   bool qp_tape = false;       // oh_qp_set_tape: p of a solve is the problem's parameter vector, the QP data is read off the tape (h->TP, d_tape_*) on the device
-  double* d_qp_rows = nullptr;  // [B][qp_np] assembled [P | q | M | c | A | b]
-  double* d_qp_val = nullptr;   // [TP.len][Bp] registers of the tape interpreter
-  double* d_qp_f0 = nullptr;    // [B] f(0, p)
-  int* d_qp_xdep = nullptr;     // indices of the tape's x-dependent instructions
+  // the three grow together (qp_solve_device): [Bv][qp_np] assembled [P | q | M | c | A | b]; [TP.len][Bv] registers of the tape interpreter (large
+  // handles: [TP.len][64 x instances per launch of k_qp_assemble_block]); [Bv] f(0, p)
+  DevBuf<double> d_qp_rows, d_qp_val, d_qp_f0;
+  DevBuf<int> d_qp_xdep;        // indices of the tape's x-dependent instructions
   int qp_n_xdep = 0;
-  int qp_tape_cap = 0;
   // inverse-kinematics family
   oh_ik_desc ik{};
-  double* d_ik_mult = nullptr;
-  int ik_cap = 0;
+  DevBuf<double> d_ik_mult;  // [B][3 + 2 ndof]
   // torque-MPC family
   oh_torque_desc tq{};
   TqParams TqP{};
   TqBuffers TqD{};
-  void* tq_pool = nullptr;
-  double* d_tq_mult = nullptr;
-  double* d_tq_hc = nullptr;  // [tq_cap][T][TQ_HC] stored curvature terms (k_tq_curv)
-  int tq_cap = 0;
+  // the three grow together (tq_solve_device): the pool of layout_tq; [B][T][4 ndof] multipliers; [B][T][TQ_HC] stored curvature terms (k_tq_curv)
+  DevBuf<char> tq_pool;
+  DevBuf<double> d_tq_mult, d_tq_hc;
   // solver buffers
   int cap_B = 0;
   FigBuffers D{};
   FigParams P{};
-  void* pool = nullptr;
-  size_t pool_bytes = 0;
+  DevBuf<char> pool;  // layout_fig, or (point-mass handles) layout_pm, carved for a row stride of cap_B
   LastSolve last;  // where the results of the last successful solve live (oh_get_multipliers)
   // staging for the host-buffer entry points
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
+  DevBuf<char> stage;
   // profiling
   bool profiling = false;
   std::vector<hipEvent_t> prof_events;
@@ -162,11 +186,10 @@ struct oh_handle {
   double timing_couple = 0;
   double rejects = 0;
   double tail_iters = 0;
-  int* h_flag = nullptr;  // pinned
+  DevBuf<int, true> h_flag;  // pinned
   // a large batch of the plain orientation-locked family is solved in parts on handles (streams, host threads) of their own: solve_split
   std::vector<oh_handle*> peers;
-  double* d_pipe_mult = nullptr;  // multipliers of every chunk of a pipelined oh_solve, in instance order
-  size_t pipe_mult_cap = 0;      // doubles
+  DevBuf<double> d_pipe_mult;    // multipliers of every chunk of a pipelined oh_solve, in instance order
   bool is_peer = false;          // this handle is a lane of another one (fan_out): it never fans out itself
   Sched sch;
   // run-time specialised evaluation kernels of the orientation-locked figure-eight family (oh_jit.hip)
@@ -186,9 +209,21 @@ struct oh_handle {
   std::vector<int> t_op, t_a, t_b, t_rows;
   std::vector<double> t_c;
   oh_tape_desc t_desc{};
+  // the lanes first, then everything this handle launched has to be over before its events, modules, stream and (the DevBuf members) memory go
+  ~oh_handle() {
+    for (oh_handle* p : peers) delete p;
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    for (hipEvent_t e : prof_events) hipEventDestroy(e);
+    for (hipEvent_t e : {ev0, ev1, evt0, evt1})
+      if (e) hipEventDestroy(e);
+    oh_tape_jit_release(&tape_jit);
+    oh_tape_jit_release(&tape_jit_phi);
+    oh_tape_wave_release(&tape_wave);
+    if (stream) hipStreamDestroy(stream);
+  }
 };
 
-extern "C" void oh_destroy(oh_handle* h);
 extern "C" int oh_specialize(oh_handle* h);
 static bool spec_applies(const oh_handle* h);
 static bool spec_tail_vel_applies(const oh_handle* h);
@@ -338,6 +373,38 @@ static oh_handle* new_handle() {
   return h;
 }
 
+// What every oh_create* does once its description is checked: a device must be there; a fresh handle on the current device with a stream, the four
+// events and -- by `want` -- the device copy of the chain and the pinned flag.  nullptr: *rc is the code, oh_last_error says why.  (The peers of
+// ensure_peers come through oh_create / oh_create_torque and so through here: a peer wants the defaults those fill in.)
+enum { OPEN_CHAIN = 1, OPEN_FLAG = 2 };
+static oh_handle* open_handle(const std::string& who, const int kind, const int T, const int ndof, const int want, int* rc) {
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) {
+    *rc = fail(OH_ERR_HIP, who + ": no HIP device available (this library has no CPU path)");
+    return nullptr;
+  }
+  oh_handle* h = new_handle();
+  if (!h) {
+    *rc = OH_ERR_INVALID;
+    return nullptr;
+  }
+  h->desc = oh_problem_desc{};
+  h->desc.kind = kind;
+  h->desc.T = T;
+  h->desc.ndof = ndof;
+  hipGetDevice(&h->device);
+  bool ok = hipStreamCreate(&h->stream) == hipSuccess;
+  for (hipEvent_t* e : {&h->ev0, &h->ev1, &h->evt0, &h->evt1}) ok = ok && hipEventCreate(e) == hipSuccess;
+  if ((want & OPEN_CHAIN) && ok) ok = h->d_chain.reserve(1) == hipSuccess;
+  if ((want & OPEN_FLAG) && ok) ok = h->h_flag.reserve(1) == hipSuccess;
+  if (!ok) {
+    delete h;
+    *rc = fail(OH_ERR_HIP, who + (want ? ": stream/event/allocation failed" : ": stream/event creation failed"));
+    return nullptr;
+  }
+  return h;
+}
+
 // every solve reports counters of its own only (oh_get_timing)
 static void reset_counters(oh_handle* h) {
   for (double& t : h->timing) t = 0.0;
@@ -400,20 +467,11 @@ extern "C" int oh_create(const oh_problem_desc* desc, oh_handle** out) {
     return fail(OH_ERR_INVALID, "oh_create: unknown problem kind");
   if (desc->kind == OH_PROBLEM_KINEMATICS) {
     if (desc->ndof < 1 || desc->ndof > OH_MAX_CHAIN) return fail(OH_ERR_INVALID, "oh_create: ndof must be in [1, OH_MAX_CHAIN]");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1)
-      return fail(OH_ERR_HIP, "oh_create: no HIP device available (this library has no CPU path)");
-    oh_handle* hk = new_handle();
-    if (!hk) return OH_ERR_INVALID;
+    int rc = OH_OK;
+    oh_handle* hk = open_handle("oh_create", desc->kind, desc->T, desc->ndof, OPEN_CHAIN, &rc);
+    if (!hk) return rc;
     hk->desc = *desc;
     hk->desc.local_path = nullptr;
-    hipGetDevice(&hk->device);
-    if (hipStreamCreate(&hk->stream) != hipSuccess || hipEventCreate(&hk->ev0) != hipSuccess ||
-        hipEventCreate(&hk->ev1) != hipSuccess || hipEventCreate(&hk->evt0) != hipSuccess ||
-        hipEventCreate(&hk->evt1) != hipSuccess || hipMalloc((void**)&hk->d_chain, sizeof(oh_chain)) != hipSuccess) {
-      delete hk;
-      return fail(OH_ERR_HIP, "oh_create: stream/event/allocation failed");
-    }
     *out = hk;
     return OH_OK;
   }
@@ -425,12 +483,9 @@ extern "C" int oh_create(const oh_problem_desc* desc, oh_handle** out) {
   if (!desc->local_path) return fail(OH_ERR_INVALID, "oh_create: local_path is null");
   if (desc->hessian != OH_HESSIAN_GAUSS_NEWTON && desc->hessian != OH_HESSIAN_EXACT && desc->hessian != OH_HESSIAN_HYBRID)
     return fail(OH_ERR_INVALID, "oh_create: bad hessian mode");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev < 1)
-    return fail(OH_ERR_HIP, "oh_create: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create", desc->kind, desc->T, desc->ndof, OPEN_CHAIN | OPEN_FLAG, &rc);
+  if (!h) return rc;
   h->desc = *desc;
   h->local_path.assign(desc->local_path, desc->local_path + 3 * (size_t)desc->T);
   h->desc.local_path = nullptr;
@@ -438,16 +493,7 @@ extern "C" int oh_create(const oh_problem_desc* desc, oh_handle** out) {
   if (!(h->desc.tol > 0.0)) h->desc.tol = 1e-6;
   if (!(h->desc.tol_feas > 0.0)) h->desc.tol_feas = 1e-9;
   if (h->desc.mu0 < 0.0) h->desc.mu0 = 0.0;
-  hipGetDevice(&h->device);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
-      hipEventCreate(&h->ev1) != hipSuccess || hipEventCreate(&h->evt0) != hipSuccess ||
-      hipEventCreate(&h->evt1) != hipSuccess) {
-    delete h;
-    return fail(OH_ERR_HIP, "oh_create: stream/event creation failed");
-  }
-  if (hipMalloc((void**)&h->d_chain, sizeof(oh_chain)) != hipSuccess ||
-      hipMalloc((void**)&h->d_local_path, sizeof(double) * 3 * (size_t)desc->T) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_flag, sizeof(int)) != hipSuccess) {
+  if (h->d_local_path.reserve(3 * (size_t)desc->T) != hipSuccess) {
     delete h;
     return fail(OH_ERR_HIP, "oh_create: device allocation failed");
   }
@@ -463,24 +509,12 @@ extern "C" int oh_create_pointmass(const oh_pointmass_desc* desc, oh_handle** ou
   if (!(desc->dt > 0.0) || !(desc->w_acc > 0.0) || !(desc->ylim > 0.0) || !(desc->vlim > 0.0) || !(desc->safe >= 0.0) || !(desc->w_vel >= 0.0) ||
       (desc->fix_final_velocity && desc->T < 3))
     return fail(OH_ERR_INVALID, "oh_create_pointmass: dt, w_acc, ylim, vlim must be positive and safe non-negative");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1)
-    return fail(OH_ERR_HIP, "oh_create_pointmass: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
-  h->desc = oh_problem_desc{};
-  h->desc.kind = OH_PROBLEM_POINT_MASS_MPC;
-  h->desc.T = desc->T;
-  h->desc.ndof = 2;
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_pointmass", OH_PROBLEM_POINT_MASS_MPC, desc->T, 2, 0, &rc);
+  if (!h) return rc;
   h->pm = *desc;
   if (h->pm.max_iter <= 0) h->pm.max_iter = 100;
   if (!(h->pm.tol > 0.0)) h->pm.tol = 1e-8;
-  hipGetDevice(&h->device);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipEventCreate(&h->evt0) != hipSuccess || hipEventCreate(&h->evt1) != hipSuccess) {
-    delete h;
-    return fail(OH_ERR_HIP, "oh_create_pointmass: stream/event creation failed");
-  }
   *out = h;
   return OH_OK;
 }
@@ -538,12 +572,8 @@ static int tape_configure(oh_handle* h) {
   h->TP.h0 = h->d_tape_h0;  // (a metric handed over before an option rebuilt the evaluator stays)
   oh_tape_wave_release(&h->tape_wave);
   h->tape_wave = TapeWave{};
-  if (h->tape_cap) {  // the work arrays were sized for the other evaluator
-    if (h->d_tape_work) hipFree(h->d_tape_work);
-    if (h->d_tape_mult) hipFree(h->d_tape_mult);
-    h->d_tape_work = h->d_tape_mult = nullptr;
-    h->tape_cap = 0;
-  }
+  h->d_tape_work.release();  // the work arrays were sized for the other evaluator
+  h->d_tape_mult.release();
   int lds_limit = 0;
   if (optv(h, "tape_wave") != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
     std::string err;
@@ -566,19 +596,31 @@ static int tape_configure(oh_handle* h) {
   return OH_OK;
 }
 
+// the five device arrays of a tape (op_override: the opcodes to upload in place of d->op)
+static int upload_tape(oh_handle* h, const oh_tape_desc* d, const int* op_override) {
+  const size_t len = (size_t)d->len, nrow = (size_t)(d->n_ineq + d->n_eq);
+  for (DevBuf<int>* b : {&h->d_tape_op, &h->d_tape_a, &h->d_tape_b, &h->d_tape_rows}) b->release();  // (sized for this tape, not grown from the last one's)
+  h->d_tape_c.release();
+  HIPCHK(h->d_tape_op.reserve(len));
+  HIPCHK(h->d_tape_a.reserve(len));
+  HIPCHK(h->d_tape_b.reserve(len));
+  HIPCHK(h->d_tape_c.reserve(len));
+  HIPCHK(h->d_tape_rows.reserve(nrow + 1));
+  HIPCHK(hipMemcpy(h->d_tape_op, op_override ? op_override : d->op, sizeof(int) * len, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->d_tape_a, d->a, sizeof(int) * len, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->d_tape_b, d->b, sizeof(int) * len, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->d_tape_c, d->c, sizeof(double) * len, hipMemcpyHostToDevice));
+  if (nrow > 0) HIPCHK(hipMemcpy(h->d_tape_rows, d->rows, sizeof(int) * nrow, hipMemcpyHostToDevice));
+  return OH_OK;
+}
+
 extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
   if (!d || !out) return fail(OH_ERR_INVALID, "oh_create_tape: null argument");
   *out = nullptr;
   if (const int rc = tape_validate(d, "oh_create_tape")) return rc;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_create_tape: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
-  h->desc = oh_problem_desc{};
-  h->desc.kind = OH_PROBLEM_TAPE;
-  h->desc.T = 1;
-  h->desc.ndof = d->nx;
-  hipGetDevice(&h->device);
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_tape", OH_PROBLEM_TAPE, 1, d->nx, 0, &rc);
+  if (!h) return rc;
   // the tape stays with the handle: the evaluator is rebuilt when an option that shapes it changes
   h->t_op.assign(d->op, d->op + d->len);
   h->t_a.assign(d->a, d->a + d->len);
@@ -588,17 +630,9 @@ extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
   h->t_desc = *d;
   if (d->no_wave && !h->opt.count("tape_wave")) h->opt["tape_wave"] = 0.0;
   if (d->lbfgs != 0 && !h->opt.count("tape_lbfgs")) h->opt["tape_lbfgs"] = d->lbfgs > 0 ? (double)d->lbfgs : 0.0;
-  if (const int rc = tape_configure(h)) {
-    oh_destroy(h);
+  if ((rc = tape_configure(h))) {
+    delete h;  // (releases the wavefront schedule / the generated module as well)
     return rc;
-  }
-  const size_t li = sizeof(int) * (size_t)d->len, ld = sizeof(double) * (size_t)d->len, lr = sizeof(int) * (size_t)(d->n_ineq + d->n_eq + 1);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipEventCreate(&h->evt0) != hipSuccess || hipEventCreate(&h->evt1) != hipSuccess || hipMalloc((void**)&h->d_tape_op, li) != hipSuccess ||
-      hipMalloc((void**)&h->d_tape_a, li) != hipSuccess || hipMalloc((void**)&h->d_tape_b, li) != hipSuccess ||
-      hipMalloc((void**)&h->d_tape_c, ld) != hipSuccess || hipMalloc((void**)&h->d_tape_rows, lr) != hipSuccess) {
-    oh_destroy(h);  // (releases the wavefront schedule / the generated module built above as well)
-    return fail(OH_ERR_HIP, "oh_create_tape: stream/event/allocation failed");
   }
   // the interpreter's copy of the opcodes carries bit 5 on every instruction that neither the cost nor a row depends on: its reverse sweep passes them by
   // (oh_tape.hip:InterpEval::reverse), as the generated code and the wavefront schedule do
@@ -615,16 +649,23 @@ extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
       }
     }
   }
-  hipMemcpy(h->d_tape_op, op_dev.data(), li, hipMemcpyHostToDevice);
-  hipMemcpy(h->d_tape_a, d->a, li, hipMemcpyHostToDevice);
-  hipMemcpy(h->d_tape_b, d->b, li, hipMemcpyHostToDevice);
-  hipMemcpy(h->d_tape_c, d->c, ld, hipMemcpyHostToDevice);
-  if (d->n_ineq + d->n_eq > 0) hipMemcpy(h->d_tape_rows, d->rows, sizeof(int) * (size_t)(d->n_ineq + d->n_eq), hipMemcpyHostToDevice);
+  if ((rc = upload_tape(h, d, op_dev.data()))) {
+    delete h;
+    return rc;
+  }
   *out = h;
   return OH_OK;
 }
 
 static int ensure_stage(oh_handle* h, size_t bytes);
+// The staging area of a host-buffer entry point: layout(Carver) is its one list of takes, each a 256-byte slot, and returns the carver's bytes().
+// It runs on a null base to size the area, then on the area itself.
+template <class Layout>
+static int stage_carve(oh_handle* h, Layout&& layout) {
+  if (const int rc = ensure_stage(h, layout(Carver(nullptr, Carver::Slots)))) return rc;
+  layout(Carver(h->stage.p, Carver::Slots));
+  return OH_OK;
+}
 extern "C" int oh_tape_probe(oh_handle* h, int B, const double* x, const double* p, int n_regs, const int* regs, double* val, const double* seeds, double* adj,
                              double* grad) {
   if (!h || !x) return fail(OH_ERR_INVALID, "oh_tape_probe: null argument");
@@ -636,20 +677,21 @@ extern "C" int oh_tape_probe(oh_handle* h, int B, const double* x, const double*
   HIPCHK(hipSetDevice(h->device));
   const int Bp = (B + 63) / 64 * 64;
   const int nrow = T.n_ineq + T.n_eq;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t b_x = sizeof(double) * (size_t)T.nx * B, b_p = sizeof(double) * (size_t)(T.np > 0 ? T.np : 1) * B, b_r = sizeof(int) * (size_t)(n_regs + 1),
-               b_v = sizeof(double) * (size_t)(n_regs + 1) * B, b_s = sizeof(double) * (size_t)(1 + nrow) * B, b_w = sizeof(double) * (2 * (size_t)T.len + 2 * (size_t)T.nx) * Bp;
-  int rc = ensure_stage(h, al(b_x) * 2 + al(b_p) + al(b_r) + 2 * al(b_v) + al(b_s) + al(b_w));
-  if (rc) return rc;
-  char* base = (char*)h->stage;
-  double* d_x = (double*)base; base += al(b_x);
-  double* d_g = (double*)base; base += al(b_x);
-  double* d_p = (double*)base; base += al(b_p);
-  int* d_r = (int*)base; base += al(b_r);
-  double* d_v = (double*)base; base += al(b_v);
-  double* d_a = (double*)base; base += al(b_v);
-  double* d_s = (double*)base; base += al(b_s);
-  double* d_w = (double*)base;
+  const size_t nB = (size_t)B, b_x = sizeof(double) * (size_t)T.nx * nB, b_s = sizeof(double) * (size_t)(1 + nrow) * nB;
+  double *d_x, *d_g, *d_p, *d_v, *d_a, *d_s, *d_w;
+  int* d_r;
+  auto layout = [&](Carver c) {
+    d_x = c.take<double>((size_t)T.nx * nB);
+    d_g = c.take<double>((size_t)T.nx * nB);
+    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
+    d_r = c.take<int>((size_t)n_regs + 1);
+    d_v = c.take<double>((size_t)(n_regs + 1) * nB);
+    d_a = c.take<double>((size_t)(n_regs + 1) * nB);
+    d_s = c.take<double>((size_t)(1 + nrow) * nB);
+    d_w = c.take<double>((2 * (size_t)T.len + 2 * (size_t)T.nx) * Bp);
+    return c.bytes();
+  };
+  if (const int rc = stage_carve(h, layout)) return rc;
   hipStream_t s = h->stream;
   HIPCHK(hipMemcpyAsync(d_x, x, b_x, hipMemcpyHostToDevice, s));
   if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * B, hipMemcpyHostToDevice, s));
@@ -671,8 +713,7 @@ extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
   HIPCHK(hipSetDevice(h->device));
   const size_t n = (size_t)h->TP.nx;
   if (!H0) {
-    if (h->d_tape_h0) hipFree(h->d_tape_h0);
-    h->d_tape_h0 = nullptr;
+    h->d_tape_h0.release();
     h->TP.h0 = nullptr;
     return OH_OK;
   }
@@ -685,7 +726,7 @@ extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
       if (!(fabs(a - b) <= 1e-10 * (fabs(a) + fabs(b)) + 1e-300)) return fail(OH_ERR_INVALID, "oh_tape_set_metric: matrix not symmetric");
     }
   }
-  if (!h->d_tape_h0) HIPCHK(hipMalloc((void**)&h->d_tape_h0, sizeof(double) * n * n));
+  HIPCHK(h->d_tape_h0.reserve(n * n));
   HIPCHK(hipMemcpy(h->d_tape_h0, H0, sizeof(double) * n * n, hipMemcpyHostToDevice));
   h->TP.h0 = h->d_tape_h0;
   return OH_OK;
@@ -693,14 +734,11 @@ extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
 
 // work arrays of the thread-per-instance evaluators and the multipliers' buffer for batches of up to Bp instances
 static int tape_ensure_work(oh_handle* h, const int Bp) {
-  if (Bp > h->tape_cap) {
-    if (h->d_tape_work) hipFree(h->d_tape_work);
-    if (h->d_tape_mult) hipFree(h->d_tape_mult);
-    h->d_tape_work = h->d_tape_mult = nullptr;
-    h->tape_cap = 0;
-    if (!h->tape_wave.ready) HIPCHK(hipMalloc((void**)&h->d_tape_work, sizeof(double) * oh_tape_work_rows(h->TP, h->tape_jit.fn != nullptr) * Bp));
-    HIPCHK(hipMalloc((void**)&h->d_tape_mult, sizeof(double) * (size_t)(h->TP.n_ineq + h->TP.n_eq + 1) * Bp));
-    h->tape_cap = Bp;
+  if (Bp > h->tape_cap()) {  // both at the new stride, or (an allocation failed) tape_cap() == 0
+    h->d_tape_work.release();
+    h->d_tape_mult.release();
+    if (!h->tape_wave.ready) HIPCHK(h->d_tape_work.reserve((size_t)oh_tape_work_rows(h->TP, h->tape_jit.fn != nullptr) * Bp));
+    HIPCHK(h->d_tape_mult.reserve((size_t)(h->TP.n_ineq + h->TP.n_eq + 1) * Bp));
   }
   return OH_OK;
 }
@@ -722,15 +760,19 @@ extern "C" int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p
     if (oh_tape_jit_compile(src, &code, &err) || oh_tape_jit_load(code, &h->tape_jit_phi, &err, false)) return fail(OH_ERR_HIP, ("oh_tape_phi: " + err).c_str());
   }
   if (const int rc = tape_ensure_work(h, Bp)) return rc;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t b_x = al(sizeof(double) * (size_t)T.nx * B), b_p = al(sizeof(double) * (size_t)(T.np > 0 ? T.np : 1) * B),
-               b_l = al(sizeof(double) * (size_t)(T.n_ineq > 0 ? T.n_ineq : 1) * B), b_m = al(sizeof(double) * (size_t)(T.n_eq > 0 ? T.n_eq : 1) * B),
-               b_r = al(sizeof(double) * (size_t)(nrow > 0 ? nrow : 1) * B), b_1 = al(sizeof(double) * (size_t)B);
-  if (const int rc = ensure_stage(h, 2 * b_x + b_p + b_l + b_m + b_r + 4 * b_1)) return rc;
-  char* base = (char*)h->stage;
-  auto take = [&](size_t bytes) { double* o = (double*)base; base += bytes; return o; };
-  double *d_x = take(b_x), *d_g = take(b_x), *d_p = take(b_p), *d_l = take(b_l), *d_m = take(b_m), *d_r = take(b_r), *d_v = take(b_1), *d_f = take(b_1),
-         *d_c = take(b_1), *d_s = take(b_1);
+  double *d_x, *d_g, *d_p, *d_l, *d_m, *d_r, *d_v, *d_f, *d_c, *d_s;
+  auto layout = [&](Carver c) {
+    const size_t nB = (size_t)B;
+    d_x = c.take<double>((size_t)T.nx * nB);
+    d_g = c.take<double>((size_t)T.nx * nB);
+    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
+    d_l = c.take<double>((size_t)(T.n_ineq > 0 ? T.n_ineq : 1) * nB);
+    d_m = c.take<double>((size_t)(T.n_eq > 0 ? T.n_eq : 1) * nB);
+    d_r = c.take<double>((size_t)(nrow > 0 ? nrow : 1) * nB);
+    for (double** q : {&d_v, &d_f, &d_c, &d_s}) *q = c.take<double>(nB);
+    return c.bytes();
+  };
+  if (const int rc = stage_carve(h, layout)) return rc;
   hipStream_t s = h->stream;
   HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T.nx * B, hipMemcpyHostToDevice, s));
   if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * B, hipMemcpyHostToDevice, s));
@@ -741,10 +783,10 @@ extern "C" int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p
   if (h->tape_wave.ready)
     HIPCHK(oh_launch_tape_wave_phi(s, h->tape_wave, T, B, d_x, d_p, d_l, d_m, rho, d_v, d_f, d_r, d_g, d_c, d_s));
   else if (h->tape_jit.fn)
-    HIPCHK(oh_launch_tape_jit_phi(s, h->tape_jit_phi, T, B, h->tape_cap, d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f, d_r, d_g, d_c, d_s,
+    HIPCHK(oh_launch_tape_jit_phi(s, h->tape_jit_phi, T, B, h->tape_cap(), d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f, d_r, d_g, d_c, d_s,
                                   (int)optv(h, "tape_lds_max"), &h->tape_phi_lds));
   else
-    oh_launch_tape_phi(s, T, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap, d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f,
+    oh_launch_tape_phi(s, T, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap(), d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f,
                        d_r, d_g, d_c, d_s);
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
@@ -766,10 +808,10 @@ static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* 
     HIPCHK(oh_launch_tape_wave(h->stream, h->tape_wave, h->TP, B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters,
                                (int*)d_status, h->d_tape_mult));
   else if (h->tape_jit.fn)
-    HIPCHK(oh_launch_tape_jit(h->stream, h->tape_jit, h->TP, B, h->tape_cap, (const double*)d_x0, (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f,
+    HIPCHK(oh_launch_tape_jit(h->stream, h->tape_jit, h->TP, B, h->tape_cap(), (const double*)d_x0, (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f,
                               (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult, (int)optv(h, "tape_lds_max")));
   else
-    oh_launch_tape_solve(h->stream, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap, (const double*)d_x0,
+    oh_launch_tape_solve(h->stream, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap(), (const double*)d_x0,
                          (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult);
   return finish_solve(h, 1);
 }
@@ -779,31 +821,19 @@ extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
   *out = nullptr;
   if (desc->n < 1 || desc->n > OH_QP_MAX_N || desc->m < 0 || desc->m > OH_QP_MAX_M || desc->me < 0 || desc->me > OH_QP_MAX_ME || desc->me > desc->n)
     return fail(OH_ERR_INVALID, "oh_create_qp: sizes out of range (1 <= n <= 128, 0 <= m <= 1024, 0 <= me <= min(128, n))");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_create_qp: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
-  h->desc = oh_problem_desc{};
-  h->desc.kind = OH_PROBLEM_QP;
-  h->desc.T = 1;
-  h->desc.ndof = desc->n;
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_qp", OH_PROBLEM_QP, 1, desc->n, 0, &rc);
+  if (!h) return rc;
   h->qp = *desc;
   if (h->qp.max_iter <= 0) h->qp.max_iter = 100;
   if (!(h->qp.tol > 0.0)) h->qp.tol = 1e-9;
-  hipGetDevice(&h->device);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipEventCreate(&h->evt0) != hipSuccess || hipEventCreate(&h->evt1) != hipSuccess) {
-    delete h;
-    return fail(OH_ERR_HIP, "oh_create_qp: stream/event creation failed");
-  }
   *out = h;
   return OH_OK;
 }
 
 static size_t qp_np(const oh_qp_desc& q) { return (size_t)q.n * q.n + q.n + (size_t)q.m * q.n + q.m + (size_t)q.me * q.n + q.me; }
 
-// Doubles per instance of a handle's problem: x, p, and the multipliers oh_get_multipliers returns (0: the problem has none).
-struct Shape { size_t nx, npar, mult; };
+// Shape (oh_carve.h) of a handle's problem
 static Shape shape_of(const oh_handle* h) {
   const size_t N = h->desc.ndof, T = h->desc.T;
   switch (h->desc.kind) {
@@ -831,22 +861,8 @@ extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
   if (d->nx != h->qp.n || d->n_ineq != h->qp.m || d->n_eq != h->qp.me)
     return fail(OH_ERR_INVALID, "oh_qp_set_tape: the tape's nx / n_ineq / n_eq differ from the handle's n / m / me");
   HIPCHK(hipSetDevice(h->device));
-  for (void** q2 : {(void**)&h->d_tape_op, (void**)&h->d_tape_a, (void**)&h->d_tape_b, (void**)&h->d_tape_c, (void**)&h->d_tape_rows}) {
-    if (*q2) hipFree(*q2);
-    *q2 = nullptr;
-  }
   h->qp_tape = false;
-  const size_t li = sizeof(int) * (size_t)d->len, ld = sizeof(double) * (size_t)d->len, lr = sizeof(int) * (size_t)(d->n_ineq + d->n_eq + 1);
-  HIPCHK(hipMalloc((void**)&h->d_tape_op, li));
-  HIPCHK(hipMalloc((void**)&h->d_tape_a, li));
-  HIPCHK(hipMalloc((void**)&h->d_tape_b, li));
-  HIPCHK(hipMalloc((void**)&h->d_tape_c, ld));
-  HIPCHK(hipMalloc((void**)&h->d_tape_rows, lr));
-  HIPCHK(hipMemcpy(h->d_tape_op, d->op, li, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_a, d->a, li, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_b, d->b, li, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_c, d->c, ld, hipMemcpyHostToDevice));
-  if (d->n_ineq + d->n_eq > 0) HIPCHK(hipMemcpy(h->d_tape_rows, d->rows, sizeof(int) * (size_t)(d->n_ineq + d->n_eq), hipMemcpyHostToDevice));
+  if (const int rc = upload_tape(h, d, nullptr)) return rc;
   h->TP = tape_params(d);
   {
     // instructions whose value depends on x: the probes after the first re-run only these
@@ -858,19 +874,12 @@ extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
       dep[i] = o == 1 || ((one || two) && dep[d->a[i]]) || (two && dep[d->b[i]]);
       if (dep[i]) list.push_back(i);
     }
-    if (h->d_qp_xdep) hipFree(h->d_qp_xdep);
-    h->d_qp_xdep = nullptr;
+    h->d_qp_xdep.release();
     h->qp_n_xdep = (int)list.size();
-    HIPCHK(hipMalloc((void**)&h->d_qp_xdep, sizeof(int) * (list.size() + 1)));
+    HIPCHK(h->d_qp_xdep.reserve(list.size() + 1));
     if (!list.empty()) HIPCHK(hipMemcpy(h->d_qp_xdep, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
   }
-  if (h->qp_tape_cap) {  // the register file of another tape: size it again at the next solve
-    for (double** q2 : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) {
-      if (*q2) hipFree(*q2);
-      *q2 = nullptr;
-    }
-    h->qp_tape_cap = h->qp_val_cap = 0;
-  }
+  for (DevBuf<double>* b : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) b->release();  // the register file of another tape: size it again at the next solve
   h->qp_tape = true;
   return OH_OK;
 }
@@ -884,43 +893,21 @@ static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   const int Bp = (B + 63) / 64 * 64;
   const int mode = (int)optv(h, "qp_mode");
   const bool large = oh_qp_is_large(Q), block = oh_qp_takes_block(Q, mode);
-  if (Bp > h->qp_mult_cap) {
-    if (h->d_qp_mult) hipFree(h->d_qp_mult);
-    h->d_qp_mult = nullptr;
-    h->qp_mult_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_qp_mult, sizeof(double) * (size_t)(q.m + q.me + 1) * Bp));
-    h->qp_mult_cap = Bp;
-  }
-  if (block) {  // what k_qp_solve_block keeps in global memory: a slice per instance (its vectors and H live in LDS)
-    if (B > h->qp_blk_cap) {
-      if (h->d_qp_blk) hipFree(h->d_qp_blk);
-      h->d_qp_blk = nullptr;
-      h->qp_blk_cap = 0;
-      HIPCHK(hipMalloc((void**)&h->d_qp_blk, sizeof(double) * (oh_qp_block_work_doubles(Q) * (size_t)B + 1)));
-      h->qp_blk_cap = B;
-    }
-  } else if (Bp > h->qp_cap) {
-    if (h->d_qp_work) hipFree(h->d_qp_work);
-    h->d_qp_work = nullptr;
-    h->qp_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_qp_work, sizeof(double) * (size_t)Q.nwork * Bp));
-    h->qp_cap = Bp;
-  }
+  HIPCHK(h->d_qp_mult.reserve((size_t)(q.m + q.me + 1) * Bp));
+  // what k_qp_solve_block keeps in global memory: a slice per instance (its vectors and H live in LDS); the other kernels: [Q.nwork][Bp]
+  if (block) HIPCHK(h->d_qp_blk.reserve(oh_qp_block_work_doubles(Q) * (size_t)B + 1));
+  else HIPCHK(h->d_qp_work.reserve((size_t)Q.nwork * Bp));
+  const int work_stride = (int)(h->d_qp_work.cap / (size_t)Q.nwork);  // the Bp d_qp_work was allocated for (0: never)
   // register file of the tape interpreter: a lane per instance, or (a few instances: B <= 64) a lane per probe point of every instance;
   // large handles: rows and f(0, p) by instance, the register file by the instances of one launch (64 lanes each)
   const int Bv = large ? B : (B <= 64 ? (B * 64 > Bp ? B * 64 : Bp) : Bp);
   const int chunk = (large && h->qp_tape) ? oh_qp_assemble_block_chunk(h->TP, B) : 0;
-  if (h->qp_tape && (Bv > h->qp_tape_cap || chunk > h->qp_val_cap)) {
-    for (double** q2 : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) {
-      if (*q2) hipFree(*q2);
-      *q2 = nullptr;
-    }
-    h->qp_tape_cap = h->qp_val_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_qp_rows, sizeof(double) * (size_t)Q.np * Bv));
-    HIPCHK(hipMalloc((void**)&h->d_qp_val, sizeof(double) * (size_t)h->TP.len * (large ? (size_t)chunk * 64 : (size_t)Bv)));
-    HIPCHK(hipMalloc((void**)&h->d_qp_f0, sizeof(double) * (size_t)Bv));
-    h->qp_tape_cap = Bv;
-    h->qp_val_cap = chunk;
+  // (d_qp_f0 is allocated last: its capacity is the Bv all three hold; large handles: d_qp_val holds 64 lanes for each of `chunk` instances)
+  if (h->qp_tape && ((size_t)Bv > h->d_qp_f0.cap || (size_t)h->TP.len * chunk * 64 > h->d_qp_val.cap)) {
+    for (DevBuf<double>* b : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) b->release();
+    HIPCHK(h->d_qp_rows.reserve((size_t)Q.np * Bv));
+    HIPCHK(h->d_qp_val.reserve((size_t)h->TP.len * (large ? (size_t)chunk * 64 : (size_t)Bv)));
+    HIPCHK(h->d_qp_f0.reserve((size_t)Bv));
   }
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   std::string err;
@@ -931,12 +918,12 @@ static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
                                       (const double*)d_p, h->d_qp_val, h->d_qp_rows, h->d_qp_f0, &err))
         return fail(OH_ERR_HIP, "oh_solve: " + err);
     } else {
-      oh_launch_qp_assemble(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, B <= 64 ? B * 64 : h->qp_tape_cap, (const double*)d_p,
+      oh_launch_qp_assemble(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, B <= 64 ? B * 64 : (int)h->d_qp_f0.cap, (const double*)d_p,
                             h->d_qp_val, h->d_qp_rows, h->d_qp_f0);
     }
     d_p = h->d_qp_rows;
   }
-  if (oh_launch_qp_solve(h->stream, Q, B, h->qp_cap, (const double*)d_x0, (const double*)d_p, block ? h->d_qp_blk : h->d_qp_work, (double*)d_x, (double*)d_f, (double*)d_kkt,
+  if (oh_launch_qp_solve(h->stream, Q, B, work_stride, (const double*)d_x0, (const double*)d_p, block ? h->d_qp_blk.p : h->d_qp_work.p, (double*)d_x, (double*)d_f, (double*)d_kkt,
                          (int*)d_iters, (int*)d_status, h->d_qp_mult, mode, &err))
     return fail(OH_ERR_HIP, "oh_solve: " + err);
   if (h->qp_tape && d_f) oh_launch_qp_add_constant(h->stream, B, (double*)d_f, h->d_qp_f0);
@@ -950,27 +937,14 @@ extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
   if (!(desc->w_nominal > 0.0)) return fail(OH_ERR_INVALID, "oh_create_ik: w_nominal must be positive");
   for (int i = 0; i < desc->ndof; ++i)
     if (!(desc->q_lo[i] <= desc->q_up[i])) return fail(OH_ERR_INVALID, "oh_create_ik: q_lo must not exceed q_up");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1)
-    return fail(OH_ERR_HIP, "oh_create_ik: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
-  h->desc = oh_problem_desc{};
-  h->desc.kind = OH_PROBLEM_IK;
-  h->desc.T = 1;
-  h->desc.ndof = desc->ndof;
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_ik", OH_PROBLEM_IK, 1, desc->ndof, OPEN_CHAIN, &rc);
+  if (!h) return rc;
   h->ik = *desc;
   if (h->ik.max_iter <= 0) h->ik.max_iter = 200;
   if (!(h->ik.tol > 0.0)) h->ik.tol = 1e-6;
   if (!(h->ik.tol_feas > 0.0)) h->ik.tol_feas = 1e-9;
   if (!(h->ik.rho0 > 0.0)) h->ik.rho0 = 100.0 * h->ik.w_nominal;
-  hipGetDevice(&h->device);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipEventCreate(&h->evt0) != hipSuccess || hipEventCreate(&h->evt1) != hipSuccess ||
-      hipMalloc((void**)&h->d_chain, sizeof(oh_chain)) != hipSuccess) {
-    delete h;
-    return fail(OH_ERR_HIP, "oh_create_ik: stream/event/allocation failed");
-  }
   *out = h;
   return OH_OK;
 }
@@ -989,28 +963,15 @@ extern "C" int oh_create_torque(const oh_torque_desc* desc, oh_handle** out) {
   if (desc->vel_limits)
     for (int i = 0; i < desc->ndof; ++i)
       if (!(desc->dq_lo[i] < desc->dq_up[i])) return fail(OH_ERR_INVALID, "oh_create_torque: dq_lo must be below dq_up");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1)
-    return fail(OH_ERR_HIP, "oh_create_torque: no HIP device available (this library has no CPU path)");
-  oh_handle* h = new_handle();
-  if (!h) return OH_ERR_INVALID;
-  h->desc = oh_problem_desc{};
-  h->desc.kind = OH_PROBLEM_TORQUE_MPC;
-  h->desc.T = desc->T;
-  h->desc.ndof = desc->ndof;
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_torque", OH_PROBLEM_TORQUE_MPC, desc->T, desc->ndof, OPEN_CHAIN | OPEN_FLAG, &rc);
+  if (!h) return rc;
   h->tq = *desc;
   if (h->tq.max_iter <= 0) h->tq.max_iter = 300;
   if (!(h->tq.tol > 0.0)) h->tq.tol = 1e-6;
   if (!(h->tq.tol_compl > 0.0)) h->tq.tol_compl = 1e-8;
   if (!(h->tq.mu_barrier0 > 0.0)) h->tq.mu_barrier0 = 0.1;
   if (!(h->tq.mu0 >= 0.0)) h->tq.mu0 = 0.0;
-  hipGetDevice(&h->device);
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipEventCreate(&h->evt0) != hipSuccess || hipEventCreate(&h->evt1) != hipSuccess ||
-      hipMalloc((void**)&h->d_chain, sizeof(oh_chain)) != hipSuccess || hipHostMalloc((void**)&h->h_flag, sizeof(int)) != hipSuccess) {
-    oh_destroy(h);
-    return fail(OH_ERR_HIP, "oh_create_torque: stream/event/allocation failed");
-  }
   *out = h;
   return OH_OK;
 }
@@ -1066,50 +1027,27 @@ static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
   P.nx = (int)shape_of(h).nx;
   P.np = (int)shape_of(h).npar;
   TqBuffers& D = h->TqD;
-  if (B > h->tq_cap) {
+  const size_t BT = (size_t)B * T;
+  if (BT * TQ_HC > h->d_tq_hc.cap) {  // the pool, the multipliers and the curvature terms grow together (d_tq_hc last: its capacity is the batch all three hold)
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->tq_pool) hipFree(h->tq_pool);
-    if (h->d_tq_mult) hipFree(h->d_tq_mult);
-    if (h->d_tq_hc) hipFree(h->d_tq_hc);
-    h->d_tq_hc = nullptr;
-    h->tq_pool = nullptr;
-    h->d_tq_mult = nullptr;
-    h->tq_cap = 0;
-    const size_t BT = (size_t)B * T;
-    const size_t nd = 2 * BT * TQ_XS + 2 * BT * TQ_SD + 2 * BT * TQ_LAM + BT * TQ_GN + BT * 4 + 11 * (size_t)B;
-    const size_t bytes = nd * sizeof(double) + (12 * (size_t)B + 16) * sizeof(int);
-    HIPCHK(hipMalloc(&h->tq_pool, bytes));
-    HIPCHK(hipMalloc((void**)&h->d_tq_mult, sizeof(double) * BT * 4 * N));  // effort rows, and room for the velocity rows
-    HIPCHK(hipMalloc((void**)&h->d_tq_hc, sizeof(double) * BT * TQ_HC));
+    h->tq_pool.release();
+    h->d_tq_mult.release();
+    h->d_tq_hc.release();
+    Carver measure(nullptr, Carver::Packed);
+    layout_tq(measure, D, B, T);
+    HIPCHK(h->tq_pool.reserve(measure.bytes()));
+    HIPCHK(h->d_tq_mult.reserve(BT * 4 * N));  // effort rows, and room for the velocity rows
+    HIPCHK(h->d_tq_hc.reserve(BT * TQ_HC));
     HIPCHK(hipMemsetAsync(h->d_tq_hc, 0, sizeof(double) * BT * TQ_HC, h->stream));  // entries the adjoint never writes stay zero
-    h->tq_cap = B;
   }
   {
-    // carve for the capacity the pool was allocated with; D.B is the live batch (strides of the [slot][B][T] arrays follow it)
-    const size_t BT = (size_t)B * T;
-    double* d = (double*)h->tq_pool;
-    auto take = [&](size_t n) { double* r = d; d += n; return r; };
+    // D.B is the live batch: the strides of the [slot][B][T] arrays follow it, inside a pool that holds the largest batch so far
+    Carver carve(h->tq_pool.p, Carver::Packed);
+    layout_tq(carve, D, B, T);
     D.B = B;
     D.chain = h->d_chain;
     D.dyn = h->d_dyn;
-    D.xs = take(2 * BT * TQ_XS);
-    D.st = take(2 * BT * TQ_SD);
-    D.lam = take(2 * BT * TQ_LAM);
-    D.gains = take(BT * TQ_GN);
-    D.goal = take(BT * 4);
     D.hc = h->d_tq_hc;
-    D.f_cur = take(B); D.f_true = take(B); D.bsum = take(B); D.mu = take(B); D.nun = take(B); D.mub = take(B); D.stat = take(B);
-    D.alpha = take(B); D.qk = take(B); D.ndx = take(B); D.viol = take(B);
-    int* ip = (int*)d;
-    D.cur = ip; ip += B; D.first = ip; ip += B; D.curv = ip; ip += B; D.status = ip; ip += B; D.iters = ip; ip += B; D.rejected = ip; ip += B;
-    D.n_barrier = ip; ip += B;
-    D.nrel = ip; ip += B;
-    D.n_back = ip; ip += B;
-    D.stall = ip; ip += B;
-    D.curv_age = ip; ip += B;
-    D.list = ip; ip += B;
-    D.n_running = ip;
-    D.n_list = ip + 1;
     D.n_run = B;
   }
   hipStream_t s = h->stream;
@@ -1177,13 +1115,7 @@ static int ik_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_
     return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
   HIPCHK(hipSetDevice(h->device));
   const int N = h->ik.ndof;
-  if (B > h->ik_cap) {
-    if (h->d_ik_mult) hipFree(h->d_ik_mult);
-    h->d_ik_mult = nullptr;
-    h->ik_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_ik_mult, sizeof(double) * (3 + 2 * (size_t)N) * B));
-    h->ik_cap = B;
-  }
+  HIPCHK(h->d_ik_mult.reserve((3 + 2 * (size_t)N) * B));
   IkParams P{};
   P.ndof = N;
   P.max_iter = h->ik.max_iter;
@@ -1206,25 +1138,16 @@ static int pm_prepare(oh_handle* h, int B) {
   HIPCHK(hipSetDevice(h->device));
   const int T = h->pm.T;
   const int Bp = (B + 63) / 64 * 64;  // (padding the row stride like the trajectory families do was measured: no effect, the solve is latency bound)
-  const size_t rows = 2 * (size_t)(T - 1) + 4 * (size_t)T + 9 * (size_t)T + 9 * (size_t)T + 8 * (size_t)(T - 1) + 2 * (size_t)(T - 1) +
-                      4 * (size_t)T + 2 * (size_t)(T - 1);
   if (Bp > h->cap_B || !h->pool) {
-    if (h->pool) hipFree(h->pool);
-    h->pool = nullptr;
-    hipError_t e = hipMalloc(&h->pool, rows * Bp * sizeof(double));
+    h->pool.release();
+    Carver measure(nullptr, Carver::Packed);
+    layout_pm(measure, h->PmD, T, Bp);
+    const hipError_t e = h->pool.reserve(measure.bytes());
     if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("device pool allocation failed: ") + hipGetErrorString(e));
     h->cap_B = Bp;
     h->PmD.Bp = Bp;
-    double* d = (double*)h->pool;
-    auto take = [&](size_t r) { double* o = d; d += r * Bp; return o; };
-    h->PmD.a = take(2 * (size_t)(T - 1));
-    h->PmD.X = take(4 * (size_t)T);
-    h->PmD.s = take(9 * (size_t)T);
-    h->PmD.lam = take(9 * (size_t)T);
-    h->PmD.K = take(8 * (size_t)(T - 1));
-    h->PmD.kk = take(2 * (size_t)(T - 1));
-    h->PmD.dX = take(4 * (size_t)T);
-    h->PmD.da = take(2 * (size_t)(T - 1));
+    Carver carve(h->pool.p, Carver::Packed);
+    layout_pm(carve, h->PmD, T, Bp);
   }
   h->PmD.B = B;
   h->PmP = PmParams{T, h->pm.dt, h->pm.w_acc, h->pm.ylim, h->pm.vlim, h->pm.safe * h->pm.safe, h->pm.tol, h->pm.max_iter,
@@ -1260,7 +1183,7 @@ static int validate_chain(const oh_handle* h, const oh_chain& c) {
 static void drop_peers(oh_handle* h) {
   h->last = LastSolve{};
   if (h->is_peer) return;
-  for (oh_handle* p : h->peers) oh_destroy(p);
+  for (oh_handle* p : h->peers) delete p;
   h->peers.clear();
 }
 
@@ -1342,7 +1265,7 @@ extern "C" int oh_max_batch(oh_handle* h, int* out) {
 
 // carve the handle's device pool for B instances
 static int ensure_capacity(oh_handle* h, int B) {
-  const int N = h->desc.ndof, NZ = h->desc.lock_orientation ? N - 3 : N, T = h->desc.T;
+  const int N = h->desc.ndof, T = h->desc.T;
   // Row stride of the SoA stage arrays: B rounded up to whole wavefronts, plus -- for large batches -- 13 x 512 B.  With a power-of-two batch
   // every row of every knot starts at a multiple of 2 MiB: the ~30 rows a sweep wave streams side by side then sit at the same offset of
   // their pages, and how the channel hash happens to spread them differed from process to process (k_couple 494 or 525 us per launch,
@@ -1357,89 +1280,20 @@ static int ensure_capacity(oh_handle* h, int B) {
     // keep the Bp the pool was carved with (stride), only the active count changes
     return OH_OK;
   }
-  if (h->pool) {
-    hipFree(h->pool);
-    h->pool = nullptr;
-  }
-  const size_t per_q = (size_t)T * N * Bp;
-  // Householder vectors of the null-space basis: 3N - 3 rows per knot (HV_ROWS).  (Until round 3 this was carved as N x NZ rows, the size of Z
-  // itself: at 393 216 instances the second slot then started 4.4 GB after the first and the sweep's 32-bit slot offset wrapped.)
-  const size_t per_Z = (size_t)T * (3 * N - 3) * Bp;
-  const size_t per_Dr = (size_t)T * (NZ * (NZ + 1) / 2) * Bp;
-  const size_t per_t = (size_t)T * Bp;
-  size_t nd = 0;  // doubles
-  nd += 2 * per_q + 2 * per_Z + 2 * per_Dr + 2 * per_q /*g*/ + 4 * per_t /*phi,cv*/;
-  nd += 3 * per_q;  // q_spare, G_spare
-  nd += 2 * per_q /*Gfull*/ + (size_t)T * NZ * NZ * Bp + (size_t)T * NZ * Bp;
-  nd += 2 * (size_t)T * (3 + 3 * NZ) * Bp;  // mdl
-  nd += 2 * (size_t)T * NZ * NZ * Bp + 2 * (size_t)T * NZ * Bp + 2 * per_t + (size_t)T * NZ * Bp;  // E, gt, merit, zstep
-  nd += (size_t)12 * Bp + 7 * (size_t)Bp;
-  nd += (size_t)4 * T * Bp;  // lam_h
-  nd += per_t;               // lead-joint angles
-  size_t ni = 11 * (size_t)Bp + 32 + 8 * 1024;  // + n_running, n_new, work (8-byte aligned), n_defer; defer_list [2][Bp]
-  size_t bytes = nd * sizeof(double) + ni * sizeof(int);
-  void* pool = nullptr;
-  hipError_t e = hipMalloc(&pool, bytes);
-  if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("device pool allocation failed: ") + hipGetErrorString(e));
-  hipMemsetAsync(pool, 0, bytes, h->stream);
-  h->pool = pool;
-  h->pool_bytes = bytes;
-  h->cap_B = Bp;
-  double* d = (double*)pool;
-  auto take = [&](size_t n) {
-    double* r = d;
-    d += n;
-    return r;
-  };
+  h->pool.release();
   FigBuffers& D = h->D;
+  Carver measure(nullptr, Carver::Packed);
+  layout_fig(measure, D, N, h->desc.lock_orientation, T, Bp);
+  const size_t bytes = measure.bytes();
+  const hipError_t e = h->pool.reserve(bytes);
+  if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("device pool allocation failed: ") + hipGetErrorString(e));
+  hipMemsetAsync(h->pool, 0, bytes, h->stream);
+  h->cap_B = Bp;
+  Carver carve(h->pool.p, Carver::Packed);
+  layout_fig(carve, D, N, h->desc.lock_orientation, T, Bp);
   D.B = B;
   D.Bp = Bp;
   D.chain = h->d_chain;
-  for (int s = 0; s < 2; ++s) D.q[s] = take(per_q);
-  for (int s = 0; s < 2; ++s) D.q_spare[s] = take(per_q);
-  for (int s = 0; s < 2; ++s) D.Z[s] = take(per_Z);
-  for (int s = 0; s < 2; ++s) D.Dr[s] = take(per_Dr);
-  for (int s = 0; s < 2; ++s) D.g[s] = take(per_q);
-  for (int s = 0; s < 2; ++s) D.phi[s] = take(per_t);
-  for (int s = 0; s < 2; ++s) D.cv[s] = take(per_t);
-  // (the sweep with the coupling folded in addresses G of either slot as a 32-bit offset from the lowest of these three: the carried
-  //  compaction swaps Gfull[] with the spare, so the three stay next to each other in the pool)
-  for (int s = 0; s < 2; ++s) D.Gfull[s] = take(per_q);
-  D.G_spare = take(per_q);
-  for (int s = 0; s < 2; ++s) D.mdl[s] = take((size_t)T * (3 + 3 * NZ) * Bp);
-  for (int s = 0; s < 2; ++s) D.E[s] = take((size_t)T * NZ * NZ * Bp);
-  for (int s = 0; s < 2; ++s) D.gt[s] = take((size_t)T * NZ * Bp);
-  for (int s = 0; s < 2; ++s) D.merit[s] = take(per_t);
-  D.zstep = take((size_t)T * NZ * Bp);
-  D.Kmat = take((size_t)T * NZ * NZ * Bp);
-  D.kvec = take((size_t)T * NZ * Bp);
-  D.ref = take((size_t)12 * Bp);
-  D.fconst = take(Bp);
-  D.f_cur = take(Bp);
-  D.pred = take(Bp);
-  D.mu = take(Bp);
-  D.nun = take(Bp);
-  D.stat = take(Bp);
-  D.feas = take(Bp);
-  D.lam_h = take((size_t)4 * T * Bp);
-  D.lead = take(per_t);
-  if (!h->desc.lock_orientation) D.lam_h = nullptr;  // no quaternion rows, no multipliers to report
-  int* ip = (int*)d;
-  D.cur = ip; ip += Bp;
-  D.first = ip; ip += Bp;
-  D.skip = ip; ip += Bp;
-  D.polish = ip; ip += Bp;
-  D.stale = ip; ip += Bp;
-  D.status = ip; ip += Bp;
-  D.iters = ip; ip += Bp;
-  D.orig = ip; ip += Bp;
-  D.newidx = ip; ip += Bp;
-  D.n_running = ip; ip += 1;
-  D.n_new = ip; ip += 1;
-  D.work = (unsigned long long*)ip; ip += 28;
-  D.n_defer = (int*)(D.work + 3);  // (two ints inside the spare part of the counter block: zeroed with it at the start of a solve)
-  D.scan_blk = ip; ip += 8 * 1024;
-  D.defer_list = ip;
   return OH_OK;
 }
 
@@ -1467,8 +1321,7 @@ extern "C" int oh_set_guards(oh_handle* h, const oh_guards* g) {
   if (h->gpool) {  // the pool was carved for the previous row count: rebuild it at the next solve
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(h->gpool);
-    h->gpool = nullptr;
+    h->gpool.release();
     h->gcap = 0;
   }
   h->guards = *g;
@@ -1502,46 +1355,19 @@ static int ensure_guards(oh_handle* h) {
   }
   GP.vscale = h->desc.dt * h->desc.dt / 40.0;
   const int Bp = h->D.Bp;
-  if (!h->gpool || h->gcap != Bp) {
-    if (h->gpool) hipFree(h->gpool);
-    h->gpool = nullptr;
-    const size_t npar = (size_t)g.n_links + 4 * (size_t)g.n_obstacles;
-    const size_t n_lam = (size_t)T * GP.NC * Bp, n_lamv = GP.vel ? (size_t)T * 2 * N * Bp : 0;
-    const size_t nd = 3 * (n_lam + n_lamv) + 2 * npar * Bp + 4 * (size_t)T * Bp + (6 + 8 + 2) * (size_t)Bp;  // lam, lam_out, the compaction scratch, ls_*
-    const size_t bytes = nd * sizeof(double) + 3 * (size_t)Bp * sizeof(int);
-    hipError_t e = hipMalloc(&h->gpool, bytes);
+  if (!h->gpool || h->gcap != Bp) {  // (not grow-only: the pool is rebuilt for the stride it is carved with)
+    h->gpool.release();
+    Carver measure(nullptr, Carver::Packed);
+    layout_guards(measure, h->GB, h->D.fpsi, GP, N, T, Bp);
+    const size_t bytes = measure.bytes();
+    const hipError_t e = h->gpool.reserve(bytes);
     if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("guard pool allocation failed: ") + hipGetErrorString(e));
     hipMemsetAsync(h->gpool, 0, bytes, h->stream);
     h->gcap = Bp;
-    double* d = (double*)h->gpool;
-    auto take = [&](size_t n) { double* r = d; d += n; return r; };
-    GuardBuffers& GB = h->GB;
-    GB.lam = take((size_t)T * GP.NC * Bp);
-    GB.par = take(npar * Bp);
-    GB.psi[0] = take((size_t)T * Bp);
-    GB.psi[1] = take((size_t)T * Bp);
-    GB.rho = take(Bp);
-    GB.rho_next = take(Bp);
-    GB.omega = take(Bp);
-    GB.meas_prev = take(Bp);
-    h->D.fpsi = take(Bp);
-    GB.mcv[0] = take((size_t)T * Bp);
-    GB.mcv[1] = take((size_t)T * Bp);
-    GB.meas = take(Bp);
-    GB.lamv = GP.vel ? take((size_t)T * 2 * N * Bp) : nullptr;
-    GB.lam_out = take(n_lam);
-    GB.lamv_out = GP.vel ? take(n_lamv) : nullptr;
-    GB.scr = take(n_lam + n_lamv + (npar + 8) * Bp);
-    GB.ls_gd = take(Bp);
-    GB.ls_q = take(Bp);
-    int* ip = (int*)d;
-    GB.outer = ip; ip += Bp;
-    GB.n_outer = ip; ip += Bp;
-    GB.ls_count = ip;
-  } else {
-    // D.fpsi lives in the guard pool; ensure_capacity may have rebuilt FigBuffers
-    h->D.fpsi = h->GB.meas_prev + Bp;
   }
+  // (every time: D.fpsi lives in the guard pool, and ensure_capacity may have rebuilt FigBuffers since)
+  Carver carve(h->gpool.p, Carver::Packed);
+  layout_guards(carve, h->GB, h->D.fpsi, GP, N, T, Bp);
   return OH_OK;
 }
 
@@ -1633,19 +1459,13 @@ static int move_everything(oh_handle* h, hipStream_t s, int Bnew) {
   for (const Item& it : items) max_rows = it.rows > max_rows ? it.rows : max_rows;
   for (const Pair& pr : live) max_rows = pr.rows > max_rows ? pr.rows : max_rows;
   const size_t need = sizeof(double) * ((size_t)max_rows + 1) * Bp;  // (+ one row: cur in the new order, for the live-slot moves)
-  if (need > h->move_scr_bytes) {
-    if (h->move_scr) hipFree(h->move_scr);
-    h->move_scr = nullptr;
-    h->move_scr_bytes = 0;
-    HIPCHK(hipMalloc(&h->move_scr, need));
-    h->move_scr_bytes = need;
-  }
+  HIPCHK(h->move_scr.reserve(need));
   if (!live.empty()) {
-    int* curn = (int*)((double*)h->move_scr + (size_t)max_rows * Bp);
+    int* curn = (int*)((double*)h->move_scr.p + (size_t)max_rows * Bp);
     hipLaunchKernelGGL(k_gather_int, dim3((B + 255) / 256), dim3(256), 0, s, (const int*)D.cur, curn, B, (const int*)D.newidx);
-    for (const Pair& pr : live) oh_launch_move_rows_live(s, pr.a0, pr.a1, (double*)h->move_scr, pr.rows, Bp, B, Bnew, D.newidx, D.cur, curn);
+    for (const Pair& pr : live) oh_launch_move_rows_live(s, pr.a0, pr.a1, (double*)h->move_scr.p, pr.rows, Bp, B, Bnew, D.newidx, D.cur, curn);
   }
-  for (const Item& it : items) oh_launch_move_rows(s, it.p, h->move_scr, it.rows, Bp, B, Bnew, D.newidx, it.is_int);
+  for (const Item& it : items) oh_launch_move_rows(s, it.p, h->move_scr.p, it.rows, Bp, B, Bnew, D.newidx, it.is_int);
   return OH_OK;
 }
 
@@ -1676,7 +1496,7 @@ static int ensure_peers(oh_handle* h, const int n) {
     rc = oh_set_constants(p, &h->chain_host);
     if (!rc && tqk) rc = oh_set_dynamics(p, &h->dyn_host);
     if (!rc && !tqk && h->have_guards) rc = oh_set_guards(p, &h->guards);
-    if (rc) { oh_destroy(p); return rc; }
+    if (rc) { delete p; return rc; }
     h->peers.push_back(p);
   }
   return OH_OK;
@@ -2150,27 +1970,17 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
 }
 
 static int ensure_stage(oh_handle* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return OH_OK;
-  if (h->stage) hipFree(h->stage);
-  h->stage = nullptr;
-  h->stage_bytes = 0;
-  hipError_t e = hipMalloc(&h->stage, bytes);
+  const hipError_t e = h->stage.reserve(bytes);
   if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("staging allocation failed: ") + hipGetErrorString(e));
-  h->stage_bytes = bytes;
   return OH_OK;
 }
-
-// Staging area of a host-buffer solve of B instances: inputs [x0 | p], then outputs [x | f | kkt | iters | status], every array 256-byte aligned.
-struct StageLayout {
-  size_t b_x, b_p, b_f, b_k, b_i;              // bytes of x0 / x, p, f, kkt, iters / status
-  size_t o_p, o_x, o_f, o_k, o_it, o_st, total;  // offsets (x0 at 0)
-  StageLayout(const Shape& sh, const size_t B) {
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    b_x = sizeof(double) * sh.nx * B; b_p = sizeof(double) * sh.npar * B; b_f = sizeof(double) * B; b_k = sizeof(double) * 3 * B; b_i = sizeof(int) * B;
-    o_p = al(b_x); o_x = o_p + al(b_p); o_f = o_x + al(b_x); o_k = o_f + al(b_f); o_it = o_k + al(b_k); o_st = o_it + al(b_i);
-    total = o_st + al(b_i);
-  }
-};
+// the staging area of a host-buffer solve of n instances on handle q (layout_stage), grown as needed
+static int stage_solve(oh_handle* q, const Shape& sh, const size_t n, StageLayout& L) {
+  return stage_carve(q, [&](Carver c) {
+    layout_stage(c, L, sh, n);
+    return c.bytes();
+  });
+}
 
 // device pointer of a handle's multipliers, [B][shape.mult] (nullptr: none, or the guarded SoA layout that copy_multipliers transposes)
 static const double* mult_ptr(const oh_handle* q) {
@@ -2217,33 +2027,26 @@ static int solve_pipelined(oh_handle* h, const int B, const int chunk, const dou
     h->spec_failed = true;
   // multipliers of every chunk, kept on the device in instance order for oh_get_multipliers (a handle only remembers its last solve)
   const Shape sh = shape_of(h);
-  if (sh.mult * B > h->pipe_mult_cap) {
-    if (h->d_pipe_mult) hipFree(h->d_pipe_mult);
-    h->d_pipe_mult = nullptr;
-    h->pipe_mult_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_pipe_mult, sizeof(double) * sh.mult * B));
-    h->pipe_mult_cap = sh.mult * B;
-  }
+  HIPCHK(h->d_pipe_mult.reserve(sh.mult * B));
   const int C = (B + chunk - 1) / chunk;
   return fan_out(h, 2, [&](const int l, oh_handle* q, Tally& t) {
     for (int c = l; c < C; c += 2) {
       const size_t lo = (size_t)c * chunk;
       const int n = (int)std::min((size_t)chunk, (size_t)B - lo);
-      const StageLayout L(sh, n);
-      if (const int rc = ensure_stage(q, L.total)) return rc;
-      char* base = (char*)q->stage;
+      StageLayout L{};
+      if (const int rc = stage_solve(q, sh, (size_t)n, L)) return rc;
       hipStream_t s = q->stream;
-      bool ok = hipMemcpyAsync(base, x0 + lo * sh.nx, L.b_x, hipMemcpyHostToDevice, s) == hipSuccess &&
-                hipMemcpyAsync(base + L.o_p, p + lo * sh.npar, L.b_p, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+      bool ok = hipMemcpyAsync(L.x0, x0 + lo * sh.nx, L.b_x, hipMemcpyHostToDevice, s) == hipSuccess &&
+                hipMemcpyAsync(L.p, p + lo * sh.npar, L.b_p, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
       if (!ok) return fail(OH_ERR_HIP, "oh_solve: upload failed");
-      if (const int rc = lane_solve(q, t, n, base, base + L.o_p, base + L.o_x, base + L.o_f, base + L.o_k, base + L.o_it, base + L.o_st)) return rc;
+      if (const int rc = lane_solve(q, t, n, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status)) return rc;
       const double* mult = mult_ptr(q);
-      if (sh.mult && mult) ok = ok && hipMemcpyAsync(h->d_pipe_mult + lo * sh.mult, mult, sizeof(double) * sh.mult * n, hipMemcpyDeviceToDevice, s) == hipSuccess;
-      if (x) ok = ok && hipMemcpyAsync(x + lo * sh.nx, base + L.o_x, L.b_x, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (f) ok = ok && hipMemcpyAsync(f + lo, base + L.o_f, L.b_f, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (kkt) ok = ok && hipMemcpyAsync(kkt + 3 * lo, base + L.o_k, L.b_k, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (iters) ok = ok && hipMemcpyAsync(iters + lo, base + L.o_it, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
-      if (status) ok = ok && hipMemcpyAsync(status + lo, base + L.o_st, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (sh.mult && mult) ok = ok && hipMemcpyAsync(h->d_pipe_mult.p + lo * sh.mult, mult, sizeof(double) * sh.mult * n, hipMemcpyDeviceToDevice, s) == hipSuccess;
+      if (x) ok = ok && hipMemcpyAsync(x + lo * sh.nx, L.x, L.b_x, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (f) ok = ok && hipMemcpyAsync(f + lo, L.f, L.b_f, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (kkt) ok = ok && hipMemcpyAsync(kkt + 3 * lo, L.kkt, L.b_k, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (iters) ok = ok && hipMemcpyAsync(iters + lo, L.iters, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
+      if (status) ok = ok && hipMemcpyAsync(status + lo, L.status, L.b_i, hipMemcpyDeviceToHost, s) == hipSuccess;
       ok = ok && hipStreamSynchronize(s) == hipSuccess;
       if (!ok) return fail(OH_ERR_HIP, "oh_solve: download failed");
     }
@@ -2272,44 +2075,41 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
     if (rc == OH_OK) h->last = LastSolve{B, {}, true};
     return rc;
   }
-  const StageLayout L(shape_of(h), B);
-  int rc = ensure_stage(h, L.total);
+  const Shape sh = shape_of(h);
+  StageLayout L{};
+  int rc = stage_solve(h, sh, (size_t)B, L);
   if (rc) return rc;
-  char* base = (char*)h->stage;
-  void* d_x0 = base; void* d_p = base + L.o_p; void* d_x = base + L.o_x; void* d_f = base + L.o_f; void* d_k = base + L.o_k;
-  void* d_it = base + L.o_it; void* d_st = base + L.o_st;
   LastSolve rec;
-  // a controller's tick moves a few hundred bytes in seven pieces: through one pinned mirror of the staging area that is two transfers (each
-  // hipMemcpy of pageable memory is ~10-15 us of driver work whatever its size)
-  const bool small = L.total <= OH_PINNED_STAGE_BYTES;
-  if (small && !h->h_stage) {
-    if (hipHostMalloc((void**)&h->h_stage, OH_PINNED_STAGE_BYTES) != hipSuccess) h->h_stage = nullptr;
+  // a controller's tick moves a few hundred bytes in seven pieces: through one pinned mirror of the staging area, carved like it, that is two
+  // transfers, [x0 | p] up and [x ... status] down (each hipMemcpy of pageable memory is ~10-15 us of driver work whatever its size)
+  const bool small = L.total <= OH_PINNED_STAGE_BYTES && (h->h_stage || h->h_stage.reserve(OH_PINNED_STAGE_BYTES) == hipSuccess);
+  StageLayout M = L;  // (small: the image of the staging area in the mirror)
+  if (small) {
+    Carver mirror(h->h_stage.p, Carver::Slots);
+    layout_stage(mirror, M, sh, (size_t)B);
+    memcpy(M.x0, x0, L.b_x);
+    memcpy(M.p, p, L.b_p);
+    HIPCHK(hipMemcpy(L.x0, M.x0, L.in_bytes(), hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(hipMemcpy(L.x0, x0, L.b_x, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(L.p, p, L.b_p, hipMemcpyHostToDevice));
   }
-  if (small && h->h_stage) {
-    char* hb = (char*)h->h_stage;
-    memcpy(hb, x0, L.b_x);
-    memcpy(hb + L.o_p, p, L.b_p);
-    HIPCHK(hipMemcpy(base, hb, L.o_p + L.b_p, hipMemcpyHostToDevice));
-    rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st, !h->is_peer, &rec);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(hb + L.o_x, base + L.o_x, L.o_st + L.b_i - L.o_x, hipMemcpyDeviceToHost));
-    if (x) memcpy(x, hb + L.o_x, L.b_x);
-    if (f) memcpy(f, hb + L.o_f, L.b_f);
-    if (kkt) memcpy(kkt, hb + L.o_k, L.b_k);
-    if (iters) memcpy(iters, hb + L.o_it, L.b_i);
-    if (status) memcpy(status, hb + L.o_st, L.b_i);
-    h->last = rec;
-    return OH_OK;
-  }
-  HIPCHK(hipMemcpy(d_x0, x0, L.b_x, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_p, p, L.b_p, hipMemcpyHostToDevice));
-  rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st, !h->is_peer, &rec);
+  rc = solve_device(h, B, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status, !h->is_peer, &rec);
   if (rc) return rc;
-  if (x) HIPCHK(hipMemcpy(x, d_x, L.b_x, hipMemcpyDeviceToHost));
-  if (f) HIPCHK(hipMemcpy(f, d_f, L.b_f, hipMemcpyDeviceToHost));
-  if (kkt) HIPCHK(hipMemcpy(kkt, d_k, L.b_k, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, d_it, L.b_i, hipMemcpyDeviceToHost));
-  if (status) HIPCHK(hipMemcpy(status, d_st, L.b_i, hipMemcpyDeviceToHost));
+  if (small) {
+    HIPCHK(hipMemcpy(M.x, L.x, L.out_bytes(), hipMemcpyDeviceToHost));
+    if (x) memcpy(x, M.x, L.b_x);
+    if (f) memcpy(f, M.f, L.b_f);
+    if (kkt) memcpy(kkt, M.kkt, L.b_k);
+    if (iters) memcpy(iters, M.iters, L.b_i);
+    if (status) memcpy(status, M.status, L.b_i);
+  } else {
+    if (x) HIPCHK(hipMemcpy(x, L.x, L.b_x, hipMemcpyDeviceToHost));
+    if (f) HIPCHK(hipMemcpy(f, L.f, L.b_f, hipMemcpyDeviceToHost));
+    if (kkt) HIPCHK(hipMemcpy(kkt, L.kkt, L.b_k, hipMemcpyDeviceToHost));
+    if (iters) HIPCHK(hipMemcpy(iters, L.iters, L.b_i, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, L.status, L.b_i, hipMemcpyDeviceToHost));
+  }
   h->last = rec;
   return OH_OK;
 }
@@ -2323,22 +2123,23 @@ extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
   h->last = LastSolve{};
   int rc = pm_prepare(h, B);
   if (rc) return rc;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t n_obs = (size_t)n_ticks * advance + T;
-  const size_t b_states = sizeof(double) * 4 * (size_t)B * (n_ticks + 1), b_obs = sizeof(double) * 2 * n_obs;
-  const size_t b_p = sizeof(double) * (4 + 4 * (size_t)T) * B, b_x = sizeof(double) * 4 * (size_t)T * B;
-  const size_t b_f = sizeof(double) * (size_t)B * n_ticks, b_i = sizeof(int) * (size_t)B * n_ticks;
-  rc = ensure_stage(h, al(b_states) + al(b_obs) + al(b_p) + 2 * al(b_x) + al(b_f) + 2 * al(b_i));
+  const size_t nB = (size_t)B, n_obs = (size_t)n_ticks * advance + T;
+  const size_t b_states = sizeof(double) * 4 * nB * (n_ticks + 1), b_obs = sizeof(double) * 2 * n_obs, b_x = sizeof(double) * 4 * (size_t)T * nB;
+  const size_t b_f = sizeof(double) * nB * n_ticks, b_i = sizeof(int) * nB * n_ticks;
+  double *d_states, *d_obs, *d_p, *d_xa, *d_xb, *d_f;
+  int *d_it, *d_st;
+  rc = stage_carve(h, [&](Carver c) {
+    d_states = c.take<double>(4 * nB * (n_ticks + 1));
+    d_obs = c.take<double>(2 * n_obs);
+    d_p = c.take<double>((4 + 4 * (size_t)T) * nB);
+    d_xa = c.take<double>(4 * (size_t)T * nB);
+    d_xb = c.take<double>(4 * (size_t)T * nB);
+    d_f = c.take<double>(nB * n_ticks);
+    d_it = c.take<int>(nB * n_ticks);
+    d_st = c.take<int>(nB * n_ticks);
+    return c.bytes();
+  });
   if (rc) return rc;
-  char* base = (char*)h->stage;
-  double* d_states = (double*)base; base += al(b_states);
-  double* d_obs = (double*)base; base += al(b_obs);
-  double* d_p = (double*)base; base += al(b_p);
-  double* d_xa = (double*)base; base += al(b_x);
-  double* d_xb = (double*)base; base += al(b_x);
-  double* d_f = (double*)base; base += al(b_f);
-  int* d_it = (int*)base; base += al(b_i);
-  int* d_st = (int*)base;
   hipStream_t s = h->stream;
   HIPCHK(hipMemcpyAsync(d_states, state0, sizeof(double) * 4 * (size_t)B, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(d_obs, obs_table, b_obs, hipMemcpyHostToDevice, s));
@@ -2371,24 +2172,25 @@ extern "C" int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, doub
   if (!(mu_warm > 0.0)) mu_warm = 1e-6;
   HIPCHK(hipSetDevice(h->device));
   h->last = LastSolve{};
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t n_rows = (size_t)n_ticks * advance + T;
+  const size_t nB = (size_t)B, n_rows = (size_t)n_ticks * advance + T;
   const size_t nx = shape_of(h).nx, np_ = shape_of(h).npar;
-  const size_t b_states = sizeof(double) * 2 * N * (size_t)B * (n_ticks + 1), b_goal = sizeof(double) * 3 * n_rows * B, b_p = sizeof(double) * np_ * B,
-               b_x = sizeof(double) * nx * B, b_tau = sizeof(double) * N * (size_t)B * n_ticks, b_f = sizeof(double) * (size_t)B * n_ticks,
-               b_i = sizeof(int) * (size_t)B * n_ticks;
-  int rc = ensure_stage(h, al(b_states) + al(b_goal) + al(b_p) + 2 * al(b_x) + al(b_tau) + al(b_f) + 2 * al(b_i));
+  const size_t b_states = sizeof(double) * 2 * N * nB * (n_ticks + 1), b_goal = sizeof(double) * 3 * n_rows * nB, b_x = sizeof(double) * nx * nB,
+               b_tau = sizeof(double) * N * nB * n_ticks, b_f = sizeof(double) * nB * n_ticks, b_i = sizeof(int) * nB * n_ticks;
+  double *d_states, *d_goal, *d_p, *d_xa, *d_xb, *d_tau, *d_f;
+  int *d_it, *d_st;
+  int rc = stage_carve(h, [&](Carver c) {
+    d_states = c.take<double>(2 * N * nB * (n_ticks + 1));
+    d_goal = c.take<double>(3 * n_rows * nB);
+    d_p = c.take<double>(np_ * nB);
+    d_xa = c.take<double>(nx * nB);
+    d_xb = c.take<double>(nx * nB);
+    d_tau = c.take<double>(N * nB * n_ticks);
+    d_f = c.take<double>(nB * n_ticks);
+    d_it = c.take<int>(nB * n_ticks);
+    d_st = c.take<int>(nB * n_ticks);
+    return c.bytes();
+  });
   if (rc) return rc;
-  char* base = (char*)h->stage;
-  double* d_states = (double*)base; base += al(b_states);
-  double* d_goal = (double*)base; base += al(b_goal);
-  double* d_p = (double*)base; base += al(b_p);
-  double* d_xa = (double*)base; base += al(b_x);
-  double* d_xb = (double*)base; base += al(b_x);
-  double* d_tau = (double*)base; base += al(b_tau);
-  double* d_f = (double*)base; base += al(b_f);
-  int* d_it = (int*)base; base += al(b_i);
-  int* d_st = (int*)base;
   hipStream_t s = h->stream;
   HIPCHK(hipMemcpyAsync(d_states, state0, sizeof(double) * 2 * N * (size_t)B, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(d_goal, goal_table, b_goal, hipMemcpyHostToDevice, s));
@@ -2449,7 +2251,7 @@ extern "C" int oh_set_dynamics(oh_handle* h, const oh_dynamics* dyn) {
   if (dyn->n < 2 || dyn->n > OH_MAX_BODIES - 1 || dyn->ndof != dyn->n - 1)
     return fail(OH_ERR_INVALID, "oh_set_dynamics: need 2 <= n <= 9 bodies and ndof == n - 1");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_dyn) HIPCHK(hipMalloc((void**)&h->d_dyn, sizeof(oh_dynamics)));
+  HIPCHK(h->d_dyn.reserve(1));
   HIPCHK(hipMemcpy(h->d_dyn, dyn, sizeof(oh_dynamics), hipMemcpyHostToDevice));
   h->dyn_host = *dyn;
   h->have_dyn = true;
@@ -2470,17 +2272,18 @@ template <size_t NIN, class Launch>
 static int run_dyn_staged(oh_handle* h, const int n, const std::array<const double*, NIN>& in, double* out, const size_t out_per_sample,
                           const char* unsupported, Launch&& launch) {
   HIPCHK(hipSetDevice(h->device));
-  const size_t b_in = sizeof(double) * h->dyn_host.ndof * (size_t)n, bq = (b_in + 255) / 256 * 256, b_out = sizeof(double) * out_per_sample * (size_t)n;
-  if (const int rc = ensure_stage(h, NIN * bq + b_out)) return rc;
-  char* base = (char*)h->stage;
+  const size_t n_in = h->dyn_host.ndof * (size_t)n, n_out = out_per_sample * (size_t)n;
   std::array<const double*, NIN> d_in;
-  for (size_t k = 0; k < NIN; ++k) {
-    HIPCHK(hipMemcpy(base + k * bq, in[k], b_in, hipMemcpyHostToDevice));
-    d_in[k] = (const double*)(base + k * bq);
-  }
-  double* d_out = (double*)(base + NIN * bq);
+  double* d_out;
+  const int src = stage_carve(h, [&](Carver c) {
+    for (size_t k = 0; k < NIN; ++k) d_in[k] = c.take<double>(n_in);
+    d_out = c.take<double>(n_out);
+    return c.bytes();
+  });
+  if (src) return src;
+  for (size_t k = 0; k < NIN; ++k) HIPCHK(hipMemcpy((void*)d_in[k], in[k], sizeof(double) * n_in, hipMemcpyHostToDevice));
   if (const int rc = run_dyn(h, unsupported, [&] { return launch(d_in, d_out); })) return rc;
-  HIPCHK(hipMemcpy(out, d_out, b_out, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost));
   return OH_OK;
 }
 
@@ -2547,15 +2350,16 @@ extern "C" int oh_fk_jac(oh_handle* h, int n, const double* q, double* pose, dou
   if (!h->have_chain) return fail(OH_ERR_STATE, "oh_fk_jac: call oh_set_constants first");
   HIPCHK(hipSetDevice(h->device));
   const int ndof = h->chain_host.ndof;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
   const size_t b_q = sizeof(double) * ndof * (size_t)n, b_p = sizeof(double) * 7 * (size_t)n,
                b_J = sizeof(double) * 6 * ndof * (size_t)n;
-  int rc = ensure_stage(h, al(b_q) + al(b_p) + al(b_J));
+  double *d_q, *d_pose, *d_J;
+  int rc = stage_carve(h, [&](Carver c) {
+    d_q = c.take<double>(ndof * (size_t)n);
+    d_pose = c.take<double>(7 * (size_t)n);
+    d_J = c.take<double>(6 * ndof * (size_t)n);
+    return c.bytes();
+  });
   if (rc) return rc;
-  char* base = (char*)h->stage;
-  void* d_q = base; base += al(b_q);
-  void* d_pose = base; base += al(b_p);
-  void* d_J = base;
   HIPCHK(hipMemcpy(d_q, q, b_q, hipMemcpyHostToDevice));
   rc = fk_common(h, n, false, d_q, pose ? d_pose : nullptr, J ? d_J : nullptr);
   if (rc) return rc;
@@ -2603,7 +2407,7 @@ extern "C" int oh_set_link_frames(oh_handle* h, const oh_chain* link, const oh_c
       if (a.qidx[k] == b.qidx[m]) return fail(OH_ERR_INVALID, "oh_set_link_frames: a joint past the chains' common prefix is on both chains");
   f.n_shared = ns;
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_frames) HIPCHK(hipMalloc((void**)&h->d_frames, sizeof(OhLinkFrames)));
+  HIPCHK(h->d_frames.reserve(1));
   HIPCHK(hipMemcpy(h->d_frames, &f, sizeof f, hipMemcpyHostToDevice));
   h->frames_host = f;
   h->have_frames = true;
@@ -2648,24 +2452,18 @@ extern "C" int oh_link_kin(oh_handle* h, int n, const double* q, const double* a
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
   const int ndof = h->frames_host.link.ndof;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
   double* const host[7] = {out->pos, out->rot, out->quat, out->rpy, out->axis, out->Jg, out->Ja};
   const size_t comps[7] = {3, 9, 4, 3, 3, 6 * (size_t)ndof, 6 * (size_t)ndof};
   const size_t b_q = sizeof(double) * ndof * (size_t)n;
-  size_t total = al(b_q);
-  for (int i = 0; i < 7; ++i)
-    if (host[i]) total += al(sizeof(double) * comps[i] * (size_t)n);
-  rc = ensure_stage(h, total);
-  if (rc) return rc;
-  char* base = (char*)h->stage;
-  double* d_q = (double*)base;
-  base += al(b_q);
+  double* d_q;
   double* dev[7] = {};
-  for (int i = 0; i < 7; ++i)
-    if (host[i]) {
-      dev[i] = (double*)base;
-      base += al(sizeof(double) * comps[i] * (size_t)n);
-    }
+  rc = stage_carve(h, [&](Carver c) {
+    d_q = c.take<double>(ndof * (size_t)n);
+    for (int i = 0; i < 7; ++i)
+      if (host[i]) dev[i] = c.take<double>(comps[i] * (size_t)n);
+    return c.bytes();
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpy(d_q, q, b_q, hipMemcpyHostToDevice));
   const oh_link_out d_out{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
   rc = link_kin_launch(h, n, false, d_q, a3, d_out);
@@ -2704,44 +2502,7 @@ extern "C" int oh_event_timer_stop(oh_handle* h, double* ms) {
 }
 
 extern "C" void oh_destroy(oh_handle* h) {
-  if (!h) return;
-  for (oh_handle* p : h->peers) oh_destroy(p);
-  h->peers.clear();
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (hipEvent_t e : h->prof_events) hipEventDestroy(e);
-  if (h->pool) hipFree(h->pool);
-  if (h->tq_pool) hipFree(h->tq_pool);
-  if (h->d_tq_mult) hipFree(h->d_tq_mult);
-  if (h->d_tq_hc) hipFree(h->d_tq_hc);
-  if (h->d_ik_mult) hipFree(h->d_ik_mult);
-  if (h->gpool) hipFree(h->gpool);
-  if (h->move_scr) hipFree(h->move_scr);
-  if (h->d_pipe_mult) hipFree(h->d_pipe_mult);
-  if (h->d_qp_work) hipFree(h->d_qp_work);
-  if (h->d_qp_blk) hipFree(h->d_qp_blk);
-  for (void* q : {(void*)h->d_tape_op, (void*)h->d_tape_a, (void*)h->d_tape_b, (void*)h->d_tape_rows, (void*)h->d_tape_c, (void*)h->d_tape_work, (void*)h->d_tape_mult,
-                  (void*)h->d_tape_h0})
-    if (q) hipFree(q);
-  if (h->d_qp_mult) hipFree(h->d_qp_mult);
-  for (void* q : {(void*)h->d_qp_rows, (void*)h->d_qp_val, (void*)h->d_qp_f0, (void*)h->d_qp_xdep})
-    if (q) hipFree(q);
-  if (h->stage) hipFree(h->stage);
-  if (h->d_chain) hipFree(h->d_chain);
-  if (h->d_frames) hipFree(h->d_frames);
-  if (h->d_dyn) hipFree(h->d_dyn);
-  if (h->d_local_path) hipFree(h->d_local_path);
-  if (h->h_flag) hipHostFree(h->h_flag);
-  if (h->h_stage) hipHostFree(h->h_stage);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
-  if (h->evt0) hipEventDestroy(h->evt0);
-  if (h->evt1) hipEventDestroy(h->evt1);
-  oh_tape_jit_release(&h->tape_jit);
-  oh_tape_jit_release(&h->tape_jit_phi);
-  oh_tape_wave_release(&h->tape_wave);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
+  if (h) delete h;  // ~oh_handle
 }
 
 
