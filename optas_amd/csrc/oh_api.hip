@@ -1,277 +1,36 @@
-// C ABI of liboptas_hip.so (see include/optas_hip.h).  Host-side orchestration only: buffer
-// ownership, the SQP launch loop (eval kernel + Riccati/step kernel per iteration), HIP-event timing.
+// C ABI of liboptas_hip.so (see include/optas_hip.h), host side: the handle's life cycle, the options, the chain constants, the one place that
+// switches on the problem kind (shape_of, mult_ptr, solve_device), the split and pipelined solves, and the whole trajectory solve (the SQP launch
+// loop: eval kernel + Riccati/step kernel per iteration).  Each self-contained family has a source of its own, oh_api_<family>.hip, and its state in
+// a struct of oh_handle.h; kinematics / dynamics entry points: oh_api_kin.hip; the RCCL communicator: oh_api_comm.hip.
 // Memory: every device or pinned allocation of a handle is a DevBuf member (grow-only, freed by the handle's destructor); what lives inside a pool
 // or the staging area is laid out by ONE list of Carver takes (oh_carve.h) that both measures and carves it.
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>  // types only: the library is opened with dlopen when a communicator is first asked for
-
+#include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <array>
-#include <map>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <utility>
 #include <vector>
 
-#include "oh_kernels.h"
-#include "oh_carve.h"
-#include "oh_jit.h"
-#include "oh_rnea.h"
+#include "oh_handle.h"
 
-static thread_local std::string g_err;
+static thread_local std::string g_err;  // per host thread: a lane of fan_out reads its own message
 
-static int fail(int code, const std::string& msg) {
+int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) {                                                                            \
-      return fail(OH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                     \
-    }                                                                                                  \
-  } while (0)
-
-#define OH_PINNED_STAGE_BYTES (256 * 1024)
-
-// An owned device (or pinned host) array of `cap` elements: grows only, freed by release() and by the destructor.
-template <class T, bool PINNED = false>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  operator T*() const { return p; }
-  void release() {
-    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
-    p = nullptr;
-    cap = 0;
-  }
-  // room for n elements; *grew (may be null): the array was reallocated, its content is gone.  A failed allocation leaves {nullptr, 0}.
-  hipError_t reserve(const size_t n, bool* grew = nullptr) {
-    if (grew) *grew = false;
-    if (n <= cap) return hipSuccess;
-    release();
-    const hipError_t e = PINNED ? hipHostMalloc((void**)&p, n * sizeof(T)) : hipMalloc((void**)&p, n * sizeof(T));
-    if (e != hipSuccess) {
-      p = nullptr;
-      return e;
-    }
-    cap = n;
-    if (grew) *grew = true;
-    return hipSuccess;
-  }
-};
-
-// Scheduling state of a handle, set by name through the field-backed options (FIELD_OPTS): a peer takes it over in one assignment.
-struct Sched {
-  int compaction = 1;
-  int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
-  int compact_fused = 1;     // ... and the retraction compiled for the chain lays the knots down at their new index itself (oh_spec_retract_move;
-                             // 0: k_retract, then k_carry_gather moves them)
-  int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see locked_loop)
-  int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
-  int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
-  int compact_sort = 1;      // order the survivors of a compaction by progress (k_scan_*)
-  double compact_frac = 0.97;  // compact the batch once this fraction of it (or less) is still running (0.9 until the carried compaction
-                               // stopped copying back: 0.95 ... 0.99 are +1 ... 2 % over 0.9 on two boxes, interleaved runs)
-  double compact_frac_restart = 0.9;  // the same for the compaction that restarts the survivors (guarded handles, free family): it costs an evaluation
-  int tail_threshold = 16384;  // hand the last instances to the persistent one-wave-per-instance kernel (round 2: with the kernel compiled for the
-                               // chain 8192 against 2048 was +1.3 ... 3 % at B = 262 144 and -21 % on a batch of 4096; with four of its blocks per CU
-                               // (two-pass exchange, 40 KB of LDS) 16 384 is level at B = 262 144 and -6 ... 13 % on batches of 16 ... 24 k)
-  int sparse_check_below = 2048;  // OH_SPARSE_CHECK_BELOW (0: look every iteration whatever the batch)
-  int fuse_couple = 1;        // OH_FUSE_COUPLE=0 restores the three-kernel iteration (k_couple between evaluation and sweep) for A/B runs
-  int free_pcr_max = 1536;    // position-tracking family: K3 by cyclic reduction, one block per instance, while at most this many are in the launch
-  int specialize = OH_SPECIALIZE_AUTO;  // option "specialize": 0 never, 1 at the first solve, 2 auto: at the first solve of >= specialize_min_B instances
-  int tq_check = 4;  // the host looks at the running count every tq_check iterations
-  std::array<double, 4> inv_saved{1.0, 16384.0, 1.0, -2.0};  // compaction, tail_threshold, tail_vel, free_persist (-2: unset) as they were before batch_invariant
-};
-
-// The last successful solve or rollout of a handle: B, and where each instance's multipliers live -- on the handles of `parts` (n instances
-// each, in instance order) or, after a pipelined oh_solve, in the handle's d_pipe_mult.  Cleared by every entry that solves and by drop_peers.
-struct oh_handle;
-struct LastSolve {
-  struct Part { const oh_handle* q; int n; };
-  int B = 0;
-  std::vector<Part> parts;
-  bool pipe_cache = false;
-};
-
-struct oh_handle {
-  oh_problem_desc desc;
-  std::vector<double> local_path;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, evt0 = nullptr, evt1 = nullptr;
-  bool have_chain = false;
-  oh_chain chain_host;
-  DevBuf<oh_chain> d_chain;
-  bool have_frames = false;  // oh_set_link_frames: the two chains of oh_link_kin*, independent of the chain above
-  OhLinkFrames frames_host;
-  DevBuf<OhLinkFrames> d_frames;
-  bool have_dyn = false;
-  oh_dynamics dyn_host;
-  DevBuf<oh_dynamics> d_dyn;
-  DevBuf<double> d_local_path;
-  // point-mass family
-  oh_pointmass_desc pm{};
-  PmParams PmP{};
-  PmBuffers PmD{};
-  // inequality rows of the position-tracking family
-  bool have_guards = false;
-  oh_guards guards{};
-  GuardParams GP{};
-  GuardBuffers GB{};
-  DevBuf<char> gpool;
-  int gcap = 0;              // the row stride (D.Bp) the guard pool was carved for
-  DevBuf<char> move_scr;     // scratch of the compaction that moves every array (move_everything)
-  // tape family
-  TapeParams TP{};
-  DevBuf<int> d_tape_op, d_tape_a, d_tape_b, d_tape_rows;
-  DevBuf<double> d_tape_c;
-  DevBuf<double> d_tape_work;   // [oh_tape_work_rows][tape_cap]; grows with d_tape_mult
-  DevBuf<double> d_tape_mult;   // [n_ineq + n_eq + 1][tape_cap]
-  DevBuf<double> d_tape_h0;     // oh_tape_set_metric: initial metric of the limited-memory form [nx][nx]
-  int tape_cap() const { return (int)(d_tape_mult.cap / (size_t)(TP.n_ineq + TP.n_eq + 1)); }  // instances the two work arrays hold: their row stride
-  TapeJit tape_jit;
-  TapeJit tape_jit_phi;       // the single-evaluation kernels of the same generated evaluator: compiled by the first oh_tape_phi, not with the handle
-  int tape_phi_lds = 0;       // whether the last oh_tape_phi ran the generated code's entry with the work set in LDS
-  TapeWave tape_wave;  // trajectory-sized tapes: one wavefront per instance (oh_tape_wave.hip)
-  // dense QP family
-  oh_qp_desc qp{};
-  DevBuf<char, true> h_stage;  // pinned mirror of the staging area for small oh_solve calls (OH_PINNED_STAGE_BYTES)
-  DevBuf<double> d_qp_work;    // [Q.nwork][Bp]
-  DevBuf<double> d_qp_mult;    // [m + me + 1][Bp]
-  DevBuf<double> d_qp_blk;     // k_qp_solve_block: [B][me n + me^2] (oh_qp_block_work_doubles), a contiguous slice per instance
-  int qp_last_block = 0;       // the last solve ran k_qp_solve_block (oh_get_flag "qp_block")
-  int free_sweep_last = -1;    // position-tracking family: the FreeSweep the last solve started with (oh_get_flag "free_sweep"; -1: none yet)
-  int free_sweeps_used = 0;    // ... and bit (1 << FreeSweep) of every sweep its loop used, those chosen after compactions included ("free_sweeps_used")
-  bool qp_tape = false;       // oh_qp_set_tape: p of a solve is the problem's parameter vector, the QP data is read off the tape (h->TP, d_tape_*) on the device
-  // the three grow together (qp_solve_device): [Bv][qp_np] assembled [P | q | M | c | A | b]; [TP.len][Bv] registers of the tape interpreter (large
-  // handles: [TP.len][64 x instances per launch of k_qp_assemble_block]); [Bv] f(0, p)
-  DevBuf<double> d_qp_rows, d_qp_val, d_qp_f0;
-  DevBuf<int> d_qp_xdep;        // indices of the tape's x-dependent instructions
-  int qp_n_xdep = 0;
-  // inverse-kinematics family
-  oh_ik_desc ik{};
-  DevBuf<double> d_ik_mult;  // [B][3 + 2 ndof]
-  // torque-MPC family
-  oh_torque_desc tq{};
-  TqParams TqP{};
-  TqBuffers TqD{};
-  // the three grow together (tq_solve_device): the pool of layout_tq; [B][T][4 ndof] multipliers; [B][T][TQ_HC] stored curvature terms (k_tq_curv)
-  DevBuf<char> tq_pool;
-  DevBuf<double> d_tq_mult, d_tq_hc;
-  // solver buffers
-  int cap_B = 0;
-  FigBuffers D{};
-  FigParams P{};
-  DevBuf<char> pool;  // layout_fig, or (point-mass handles) layout_pm, carved for a row stride of cap_B
-  LastSolve last;  // where the results of the last successful solve live (oh_get_multipliers)
-  // staging for the host-buffer entry points
-  DevBuf<char> stage;
-  // profiling
-  bool profiling = false;
-  std::vector<hipEvent_t> prof_events;
-  double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double timing_couple = 0;
-  double rejects = 0;
-  double tail_iters = 0;
-  DevBuf<int, true> h_flag;  // pinned
-  // a large batch of the plain orientation-locked family is solved in parts on handles (streams, host threads) of their own: solve_split
-  std::vector<oh_handle*> peers;
-  DevBuf<double> d_pipe_mult;    // multipliers of every chunk of a pipelined oh_solve, in instance order
-  bool is_peer = false;          // this handle is a lane of another one (fan_out): it never fans out itself
-  Sched sch;
-  // run-time specialised evaluation kernels of the orientation-locked figure-eight family (oh_jit.hip)
-  int specialize_min_B = 4096;
-  const FigSpec* spec = nullptr;
-  bool spec_failed = false;
-  bool spec_move_failed = false;  // the moving retraction did not launch once: this handle's carried compactions gather as before
-  bool spec_cache_checked = false;  // automatic mode has looked for a cached code object once (reset with the constants)
-  const FkSpec* fk_spec = nullptr;  // K1 for this chain (any handle with constants)
-  bool fk_spec_failed = false;
-  int specialize_min_units = 1 << 16;
-  double spec_seconds = 0.0;  // of the last oh_specialize
-  std::vector<int> prof_tags;  // per recorded event: 0 base marker, 1 after eval, 2 after step
-  // options set by name (oh_set_option; OH_DEBUG_OPTIONS at creation) that are not backed by a field above: read with optv() where they are used
-  std::map<std::string, double> opt;
-  // host copy of the tape of an OH_PROBLEM_TAPE handle: the evaluator is rebuilt when an option that shapes it changes (tape_wave, tape_lbfgs, ...)
-  std::vector<int> t_op, t_a, t_b, t_rows;
-  std::vector<double> t_c;
-  oh_tape_desc t_desc{};
-  // the lanes first, then everything this handle launched has to be over before its events, modules, stream and (the DevBuf members) memory go
-  ~oh_handle() {
-    for (oh_handle* p : peers) delete p;
-    hipSetDevice(device);
-    if (stream) hipStreamSynchronize(stream);
-    for (hipEvent_t e : prof_events) hipEventDestroy(e);
-    for (hipEvent_t e : {ev0, ev1, evt0, evt1})
-      if (e) hipEventDestroy(e);
-    oh_tape_jit_release(&tape_jit);
-    oh_tape_jit_release(&tape_jit_phi);
-    oh_tape_wave_release(&tape_wave);
-    if (stream) hipStreamDestroy(stream);
-  }
-};
-
 extern "C" int oh_specialize(oh_handle* h);
 static bool spec_applies(const oh_handle* h);
 static bool spec_tail_vel_applies(const oh_handle* h);
-static int specialize_fk(oh_handle* h);
 extern "C" const char* oh_last_error(void) { return g_err.c_str(); }
 extern "C" const char* oh_version(void) { return "optas_hip 0.2 (gfx950)"; }
 extern "C" int oh_abi_version(void) { return OH_ABI_VERSION; }
 
-// ---- per-handle options (round 5) ----------------------------------------------------------------------------------------------------
-// Until round 4 forty OH_* environment variables were read inside the library: two handles of one process could not differ and a result
-// depended on the caller's environment.  Now every knob is an option of ONE handle, set by name; the single environment hook left is
-// OH_DEBUG_OPTIONS ("name=value,name=value"), applied to every handle when it is created (tools/, A/B runs).
-struct OptDoc { const char* name; double dflt; };
-// map-backed options and their defaults, the one place a default is written (field-backed ones: FIELD_OPTS; batch_invariant: set_option_impl)
-static constexpr OptDoc OPT_TABLE[] = {
-    {"check_every", 1},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
-    {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30},
-    {"tape_wave", 1},          {"tape_lbfgs", -1},       {"tape_wave_nt", 256},  {"tape_wave_regs", -1}, {"tape_wave_hist", -1},  {"tq_stall", 25},
-    {"tq_curv_after", 3},      {"tq_ftb", 0.995},        {"tq_theta_mu", 1.35},  {"tq_kappa_mu", 0.4},   {"tq_curv_from", 0.1},   {"tq_jac_dual", 0},
-    {"tq_rebuild", 0.9},         {"compact_move_all", 1},  {"tq_curv_late", 1.0},  {"tq_kappa_eps", 10.0}, {"tq_max_back", 3},     {"tq_mu_dec", 1.0 / 3.0},     {"tq_ls_curv", 1},   {"tq_mu_dec_warm", 0.1}, {"tq_curv_lag", 3},
-    {"tol", 0},                {"pipe", 1},               {"pipe_chunk", 32768},                {"invariant_compact_frac", 0.65}, {"invariant_split", 1}, {"invariant_move_slim", 1}, {"invariant_move_live", 1},
-};
-// row of a map-backed option in OPT_TABLE (-1: none)
-static constexpr int opt_row(const char* name) {
-  for (int i = 0; i < (int)(sizeof(OPT_TABLE) / sizeof(OPT_TABLE[0])); ++i) {
-    int k = 0;
-    while (OPT_TABLE[i].name[k] && OPT_TABLE[i].name[k] == name[k]) ++k;
-    if (OPT_TABLE[i].name[k] == name[k]) return i;
-  }
-  return -1;
-}
-template <int ROW>
-static constexpr int known_opt() {
-  static_assert(ROW >= 0, "optv: the option is not in OPT_TABLE");
-  return ROW;
-}
-// an option of a handle: as set by name, else its default in the table
-static double opt_value(const oh_handle* h, const OptDoc& d) {
-  const auto it = h->opt.find(d.name);
-  return it == h->opt.end() ? d.dflt : it->second;
-}
-// optv(h, "name"): a map-backed option of a handle; a name that is not in OPT_TABLE does not compile
-#define optv(h, name) opt_value(h, OPT_TABLE[known_opt<opt_row(name)>()])
-// option batch_invariant: kept in the map but outside the table (set_option_impl parks the scheduling fields it overrides); 0 until set
-static double batch_invariant(const oh_handle* h) {
-  const auto it = h->opt.find("batch_invariant");
-  return it == h->opt.end() ? 0.0 : it->second;
-}
+// ---- per-handle options (OPT_TABLE, optv: oh_handle.h) -----------------------------------------------------------------------------------
 // field-backed options: the one list of name -> field of Sched that oh_set_option and oh_get_option read (a flag stores v != 0)
 struct FieldOpt {
   const char* name;
@@ -294,7 +53,6 @@ static const FieldOpt* field_opt(const std::string& name) {
     if (name == f.name) return &f;
   return nullptr;
 }
-static int tape_configure(oh_handle* h);
 static int set_option_impl(oh_handle* h, const std::string& name, double v) {
   Sched& sc = h->sch;
   if (name == "compact_frac") sc.compact_frac = sc.compact_frac_restart = v;
@@ -321,7 +79,7 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     for (const OptDoc& d : OPT_TABLE) known = known || name == d.name;
     if (!known) return fail(OH_ERR_INVALID, "oh_set_option: unknown option '" + name + "'");
     h->opt[name] = v;
-    if (h->desc.kind == OH_PROBLEM_TAPE && !h->t_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max") return tape_configure(h);
+    if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max") return tape_configure(h);
   }
   return OH_OK;
 }
@@ -376,8 +134,7 @@ static oh_handle* new_handle() {
 // What every oh_create* does once its description is checked: a device must be there; a fresh handle on the current device with a stream, the four
 // events and -- by `want` -- the device copy of the chain and the pinned flag.  nullptr: *rc is the code, oh_last_error says why.  (The peers of
 // ensure_peers come through oh_create / oh_create_torque and so through here: a peer wants the defaults those fill in.)
-enum { OPEN_CHAIN = 1, OPEN_FLAG = 2 };
-static oh_handle* open_handle(const std::string& who, const int kind, const int T, const int ndof, const int want, int* rc) {
+oh_handle* open_handle(const std::string& who, const int kind, const int T, const int ndof, const int want, int* rc) {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) {
     *rc = fail(OH_ERR_HIP, who + ": no HIP device available (this library has no CPU path)");
@@ -406,12 +163,12 @@ static oh_handle* open_handle(const std::string& who, const int kind, const int 
 }
 
 // every solve reports counters of its own only (oh_get_timing)
-static void reset_counters(oh_handle* h) {
+void reset_counters(oh_handle* h) {
   for (double& t : h->timing) t = 0.0;
   h->timing_couple = h->rejects = h->tail_iters = 0.0;
 }
 // the tail every solve shares: wait for the launches since ev0, report a launch error, time the solve ([4]) and count its launches ([5])
-static int finish_solve(oh_handle* h, const double launched) {
+int finish_solve(oh_handle* h, const double launched) {
   HIPCHK(hipEventRecord(h->ev1, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
@@ -502,344 +259,15 @@ extern "C" int oh_create(const oh_problem_desc* desc, oh_handle** out) {
   return OH_OK;
 }
 
-extern "C" int oh_create_pointmass(const oh_pointmass_desc* desc, oh_handle** out) {
-  if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_pointmass: null argument");
-  *out = nullptr;
-  if (desc->T < 2 || desc->T > OH_MAX_T) return fail(OH_ERR_INVALID, "oh_create_pointmass: T must be in [2, OH_MAX_T]");
-  if (!(desc->dt > 0.0) || !(desc->w_acc > 0.0) || !(desc->ylim > 0.0) || !(desc->vlim > 0.0) || !(desc->safe >= 0.0) || !(desc->w_vel >= 0.0) ||
-      (desc->fix_final_velocity && desc->T < 3))
-    return fail(OH_ERR_INVALID, "oh_create_pointmass: dt, w_acc, ylim, vlim must be positive and safe non-negative");
-  int rc = OH_OK;
-  oh_handle* h = open_handle("oh_create_pointmass", OH_PROBLEM_POINT_MASS_MPC, desc->T, 2, 0, &rc);
-  if (!h) return rc;
-  h->pm = *desc;
-  if (h->pm.max_iter <= 0) h->pm.max_iter = 100;
-  if (!(h->pm.tol > 0.0)) h->pm.tol = 1e-8;
-  *out = h;
-  return OH_OK;
-}
-
-static int tape_validate(const oh_tape_desc* d, const char* who) {
-  const std::string w(who);
-  if (d->nx < 1 || d->nx > OH_TAPE_MAX_N || d->np < 0 || d->len < 1 || d->len > OH_TAPE_MAX_LEN || d->n_ineq < 0 || d->n_eq < 0 || !d->op || !d->a ||
-      !d->b || !d->c || (d->n_ineq + d->n_eq > 0 && !d->rows) || d->out_cost < 0 || d->out_cost >= d->len)
-    return fail(OH_ERR_INVALID, (w + ": bad sizes or null arrays").c_str());
-  for (int i = 0; i < d->len; ++i) {
-    const int o = d->op[i];
-    const bool two = (o >= 3 && o <= 6) || o == 10 || (o >= 15 && o <= 20) || (o >= 22 && o <= 24);
-    const bool one = o == 7 || o == 8 || o == 9 || o == 11 || o == 12 || o == 13 || o == 14 || o == 21 || o == 25 || o == 26;
-    if (o < 0 || o > 26 || (o == 1 && (d->a[i] < 0 || d->a[i] >= d->nx)) || (o == 2 && (d->a[i] < 0 || d->a[i] >= d->np)) ||
-        ((one || two) && (d->a[i] < 0 || d->a[i] >= i)) || (two && (d->b[i] < 0 || d->b[i] >= i)))
-      return fail(OH_ERR_INVALID, (w + ": malformed instruction (operands must be earlier registers / valid indices)").c_str());
-  }
-  for (int i = 0; i < d->n_ineq + d->n_eq; ++i)
-    if (d->rows[i] < 0 || d->rows[i] >= d->len) return fail(OH_ERR_INVALID, (w + ": row register out of range").c_str());
-  return OH_OK;
-}
-
-static TapeParams tape_params(const oh_tape_desc* d, const int lbfgs_opt = -1) {
-  // dense inverse-Hessian BFGS up to 48 variables (n^2 doubles per instance), the limited-memory form with 12 pairs beyond (option tape_lbfgs overrides:
-  // 0 forces the dense matrix, m > 0 the m-pair form at any size)
-  int lb = d->nx > 48 ? 12 : 0;
-  if (lbfgs_opt >= 0) lb = lbfgs_opt > 64 ? 64 : lbfgs_opt;
-  return TapeParams{d->len, d->nx, d->np, d->n_ineq, d->n_eq, d->out_cost, d->max_iter > 0 ? d->max_iter : 2000, d->tol > 0.0 ? d->tol : 1e-6,
-                    d->tol_feas > 0.0 ? d->tol_feas : 1e-9, d->rho0 > 0.0 ? d->rho0 : 10.0, lb, nullptr};
-}
-
-extern "C" int oh_tape_compile(const oh_tape_desc* d, size_t* code_bytes, char* source, size_t source_cap, size_t* source_len) {
-  if (!d) return fail(OH_ERR_INVALID, "oh_tape_compile: null argument");
-  if (const int rc = tape_validate(d, "oh_tape_compile")) return rc;
-  const std::string src = oh_tape_jit_source(tape_params(d), d->op, d->a, d->b, d->c, d->rows);
-  if (source_len) *source_len = src.size();
-  if (source && source_cap > 0) {
-    const size_t k = src.size() < source_cap - 1 ? src.size() : source_cap - 1;
-    memcpy(source, src.data(), k);
-    source[k] = 0;
-  }
-  std::vector<char> code;
-  std::string err;
-  if (oh_tape_jit_compile(src, &code, &err)) return fail(OH_ERR_HIP, ("oh_tape_compile: " + err).c_str());
-  if (code_bytes) *code_bytes = code.size();
-  return OH_OK;
-}
-
-// (Re)build the evaluator of an OH_PROBLEM_TAPE handle from its host copy of the tape and its options: the wavefront-per-instance schedule where it
-// applies (tape_wave != 0, limited-memory regime, LDS fit), otherwise generated code (desc.jit) or the interpreter.
-static int tape_configure(oh_handle* h) {
-  oh_tape_desc d = h->t_desc;
-  d.op = h->t_op.data(); d.a = h->t_a.data(); d.b = h->t_b.data(); d.c = h->t_c.data(); d.rows = h->t_rows.empty() ? nullptr : h->t_rows.data();
-  h->TP = tape_params(&d, (int)optv(h, "tape_lbfgs"));
-  h->TP.h0 = h->d_tape_h0;  // (a metric handed over before an option rebuilt the evaluator stays)
-  oh_tape_wave_release(&h->tape_wave);
-  h->tape_wave = TapeWave{};
-  h->d_tape_work.release();  // the work arrays were sized for the other evaluator
-  h->d_tape_mult.release();
-  int lds_limit = 0;
-  if (optv(h, "tape_wave") != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
-    std::string err;
-    if (oh_tape_wave_build(h->TP, d.op, d.a, d.b, d.c, d.rows, (size_t)lds_limit, (int)optv(h, "tape_wave_nt"), (int)optv(h, "tape_wave_regs"),
-                           (int)optv(h, "tape_wave_hist"), &h->tape_wave, &err))
-      return fail(OH_ERR_HIP, ("oh_create_tape: " + err).c_str());
-  }
-  if (d.jit && !h->tape_wave.ready && !h->tape_jit.fn) {
-    std::vector<char> code;
-    std::string err;
-    const std::string src = oh_tape_jit_source(h->TP, d.op, d.a, d.b, d.c, d.rows);
-    bool ok = !oh_tape_jit_compile(src, &code, &err) && !oh_tape_jit_load(code, &h->tape_jit, &err);
-    if (!ok && !code.empty()) {  // an object that compiled (or came from the disk cache) and does not load: drop it, recompile once (as oh_jit_figure8 does)
-      oh_tape_jit_forget(src);
-      code.clear();
-      ok = !oh_tape_jit_compile(src, &code, &err) && !oh_tape_jit_load(code, &h->tape_jit, &err);
-    }
-    if (!ok) return fail(OH_ERR_HIP, ("oh_create_tape: " + err).c_str());
-  }
-  return OH_OK;
-}
-
-// the five device arrays of a tape (op_override: the opcodes to upload in place of d->op)
-static int upload_tape(oh_handle* h, const oh_tape_desc* d, const int* op_override) {
-  const size_t len = (size_t)d->len, nrow = (size_t)(d->n_ineq + d->n_eq);
-  for (DevBuf<int>* b : {&h->d_tape_op, &h->d_tape_a, &h->d_tape_b, &h->d_tape_rows}) b->release();  // (sized for this tape, not grown from the last one's)
-  h->d_tape_c.release();
-  HIPCHK(h->d_tape_op.reserve(len));
-  HIPCHK(h->d_tape_a.reserve(len));
-  HIPCHK(h->d_tape_b.reserve(len));
-  HIPCHK(h->d_tape_c.reserve(len));
-  HIPCHK(h->d_tape_rows.reserve(nrow + 1));
-  HIPCHK(hipMemcpy(h->d_tape_op, op_override ? op_override : d->op, sizeof(int) * len, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_a, d->a, sizeof(int) * len, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_b, d->b, sizeof(int) * len, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_tape_c, d->c, sizeof(double) * len, hipMemcpyHostToDevice));
-  if (nrow > 0) HIPCHK(hipMemcpy(h->d_tape_rows, d->rows, sizeof(int) * nrow, hipMemcpyHostToDevice));
-  return OH_OK;
-}
-
-extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
-  if (!d || !out) return fail(OH_ERR_INVALID, "oh_create_tape: null argument");
-  *out = nullptr;
-  if (const int rc = tape_validate(d, "oh_create_tape")) return rc;
-  int rc = OH_OK;
-  oh_handle* h = open_handle("oh_create_tape", OH_PROBLEM_TAPE, 1, d->nx, 0, &rc);
-  if (!h) return rc;
-  // the tape stays with the handle: the evaluator is rebuilt when an option that shapes it changes
-  h->t_op.assign(d->op, d->op + d->len);
-  h->t_a.assign(d->a, d->a + d->len);
-  h->t_b.assign(d->b, d->b + d->len);
-  h->t_c.assign(d->c, d->c + d->len);
-  h->t_rows.assign(d->rows ? d->rows : d->op, (d->rows ? d->rows : d->op) + (d->rows ? d->n_ineq + d->n_eq : 0));
-  h->t_desc = *d;
-  if (d->no_wave && !h->opt.count("tape_wave")) h->opt["tape_wave"] = 0.0;
-  if (d->lbfgs != 0 && !h->opt.count("tape_lbfgs")) h->opt["tape_lbfgs"] = d->lbfgs > 0 ? (double)d->lbfgs : 0.0;
-  if ((rc = tape_configure(h))) {
-    delete h;  // (releases the wavefront schedule / the generated module as well)
-    return rc;
-  }
-  // the interpreter's copy of the opcodes carries bit 5 on every instruction that neither the cost nor a row depends on: its reverse sweep passes them by
-  // (oh_tape.hip:InterpEval::reverse), as the generated code and the wavefront schedule do
-  std::vector<int> op_dev(d->op, d->op + d->len);
-  {
-    std::vector<char> live(d->len, 0);
-    live[d->out_cost] = 1;
-    for (int i = 0; i < d->n_ineq + d->n_eq; ++i) live[d->rows[i]] = 1;
-    for (int i = d->len - 1; i >= 0; --i) {
-      if (!live[i]) { op_dev[i] |= 32; continue; }
-      if (d->op[i] >= 3) {
-        live[d->a[i]] = 1;
-        if (tape_op_arity(d->op[i]) == 2) live[d->b[i]] = 1;
-      }
-    }
-  }
-  if ((rc = upload_tape(h, d, op_dev.data()))) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return OH_OK;
-}
-
-static int ensure_stage(oh_handle* h, size_t bytes);
-// The staging area of a host-buffer entry point: layout(Carver) is its one list of takes, each a 256-byte slot, and returns the carver's bytes().
-// It runs on a null base to size the area, then on the area itself.
-template <class Layout>
-static int stage_carve(oh_handle* h, Layout&& layout) {
-  if (const int rc = ensure_stage(h, layout(Carver(nullptr, Carver::Slots)))) return rc;
-  layout(Carver(h->stage.p, Carver::Slots));
-  return OH_OK;
-}
-extern "C" int oh_tape_probe(oh_handle* h, int B, const double* x, const double* p, int n_regs, const int* regs, double* val, const double* seeds, double* adj,
-                             double* grad) {
-  if (!h || !x) return fail(OH_ERR_INVALID, "oh_tape_probe: null argument");
-  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_probe: handle is not an OH_PROBLEM_TAPE problem");
-  const TapeParams& T = h->TP;
-  if (B < 1 || n_regs < 0 || (n_regs > 0 && !regs) || (T.np > 0 && !p)) return fail(OH_ERR_INVALID, "oh_tape_probe: bad sizes");
-  for (int i = 0; i < n_regs; ++i)
-    if (regs[i] < 0 || regs[i] >= T.len) return fail(OH_ERR_INVALID, "oh_tape_probe: register out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const int Bp = (B + 63) / 64 * 64;
-  const int nrow = T.n_ineq + T.n_eq;
-  const size_t nB = (size_t)B, b_x = sizeof(double) * (size_t)T.nx * nB, b_s = sizeof(double) * (size_t)(1 + nrow) * nB;
-  double *d_x, *d_g, *d_p, *d_v, *d_a, *d_s, *d_w;
-  int* d_r;
-  auto layout = [&](Carver c) {
-    d_x = c.take<double>((size_t)T.nx * nB);
-    d_g = c.take<double>((size_t)T.nx * nB);
-    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
-    d_r = c.take<int>((size_t)n_regs + 1);
-    d_v = c.take<double>((size_t)(n_regs + 1) * nB);
-    d_a = c.take<double>((size_t)(n_regs + 1) * nB);
-    d_s = c.take<double>((size_t)(1 + nrow) * nB);
-    d_w = c.take<double>((2 * (size_t)T.len + 2 * (size_t)T.nx) * Bp);
-    return c.bytes();
-  };
-  if (const int rc = stage_carve(h, layout)) return rc;
-  hipStream_t s = h->stream;
-  HIPCHK(hipMemcpyAsync(d_x, x, b_x, hipMemcpyHostToDevice, s));
-  if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * B, hipMemcpyHostToDevice, s));
-  if (n_regs > 0) HIPCHK(hipMemcpyAsync(d_r, regs, sizeof(int) * (size_t)n_regs, hipMemcpyHostToDevice, s));
-  if (seeds) HIPCHK(hipMemcpyAsync(d_s, seeds, b_s, hipMemcpyHostToDevice, s));
-  oh_launch_tape_probe(s, T, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, Bp, d_x, d_p, d_w, n_regs, d_r, val ? d_v : nullptr,
-                       seeds ? d_s : nullptr, (seeds && adj) ? d_a : nullptr, (seeds && grad) ? d_g : nullptr);
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  if (val && n_regs > 0) HIPCHK(hipMemcpy(val, d_v, sizeof(double) * (size_t)n_regs * B, hipMemcpyDeviceToHost));
-  if (seeds && adj && n_regs > 0) HIPCHK(hipMemcpy(adj, d_a, sizeof(double) * (size_t)n_regs * B, hipMemcpyDeviceToHost));
-  if (seeds && grad) HIPCHK(hipMemcpy(grad, d_g, b_x, hipMemcpyDeviceToHost));
-  return OH_OK;
-}
-
-extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_tape_set_metric: null argument");
-  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_INVALID, "oh_tape_set_metric: not an OH_PROBLEM_TAPE handle");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t n = (size_t)h->TP.nx;
-  if (!H0) {
-    h->d_tape_h0.release();
-    h->TP.h0 = nullptr;
-    return OH_OK;
-  }
-  // symmetric with a positive diagonal is what can be checked here without factorising; a matrix that is not positive definite costs the solver a
-  // reset to steepest descent whenever the direction it gives does not descend (oh_tape_solver.h), never a wrong answer
-  for (size_t i = 0; i < n; ++i) {
-    if (!(H0[i * n + i] > 0.0)) return fail(OH_ERR_INVALID, "oh_tape_set_metric: diagonal entry not positive");
-    for (size_t j = 0; j < i; ++j) {
-      const double a = H0[i * n + j], b = H0[j * n + i];
-      if (!(fabs(a - b) <= 1e-10 * (fabs(a) + fabs(b)) + 1e-300)) return fail(OH_ERR_INVALID, "oh_tape_set_metric: matrix not symmetric");
-    }
-  }
-  HIPCHK(h->d_tape_h0.reserve(n * n));
-  HIPCHK(hipMemcpy(h->d_tape_h0, H0, sizeof(double) * n * n, hipMemcpyHostToDevice));
-  h->TP.h0 = h->d_tape_h0;
-  return OH_OK;
-}
-
-// work arrays of the thread-per-instance evaluators and the multipliers' buffer for batches of up to Bp instances
-static int tape_ensure_work(oh_handle* h, const int Bp) {
-  if (Bp > h->tape_cap()) {  // both at the new stride, or (an allocation failed) tape_cap() == 0
-    h->d_tape_work.release();
-    h->d_tape_mult.release();
-    if (!h->tape_wave.ready) HIPCHK(h->d_tape_work.reserve((size_t)oh_tape_work_rows(h->TP, h->tape_jit.fn != nullptr) * Bp));
-    HIPCHK(h->d_tape_mult.reserve((size_t)(h->TP.n_ineq + h->TP.n_eq + 1) * Bp));
-  }
-  return OH_OK;
-}
-
-extern "C" int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, double* merit, double* f,
-                           double* rows, double* grad, double* cmax, double* meas) {
-  if (!h || !x || !merit || !f || !grad || !cmax || !meas) return fail(OH_ERR_INVALID, "oh_tape_phi: null argument");
-  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_phi: handle is not an OH_PROBLEM_TAPE problem");
-  const TapeParams& T = h->TP;
-  const int nrow = T.n_ineq + T.n_eq;
-  if (B < 1 || (T.np > 0 && !p) || (T.n_ineq > 0 && !lam) || (T.n_eq > 0 && !mu) || (nrow > 0 && !rows)) return fail(OH_ERR_INVALID, "oh_tape_phi: bad sizes");
-  if (!(rho > 0.0)) return fail(OH_ERR_INVALID, "oh_tape_phi: the penalty must be positive");
-  HIPCHK(hipSetDevice(h->device));
-  const int Bp = (B + 63) / 64 * 64;
-  if (h->tape_jit.fn && !h->tape_wave.ready && !h->tape_jit_phi.fn) {
-    std::vector<char> code;
-    std::string err;
-    const std::string src = oh_tape_jit_source(T, h->t_op.data(), h->t_a.data(), h->t_b.data(), h->t_c.data(), h->t_rows.empty() ? nullptr : h->t_rows.data(), false);
-    if (oh_tape_jit_compile(src, &code, &err) || oh_tape_jit_load(code, &h->tape_jit_phi, &err, false)) return fail(OH_ERR_HIP, ("oh_tape_phi: " + err).c_str());
-  }
-  if (const int rc = tape_ensure_work(h, Bp)) return rc;
-  double *d_x, *d_g, *d_p, *d_l, *d_m, *d_r, *d_v, *d_f, *d_c, *d_s;
-  auto layout = [&](Carver c) {
-    const size_t nB = (size_t)B;
-    d_x = c.take<double>((size_t)T.nx * nB);
-    d_g = c.take<double>((size_t)T.nx * nB);
-    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
-    d_l = c.take<double>((size_t)(T.n_ineq > 0 ? T.n_ineq : 1) * nB);
-    d_m = c.take<double>((size_t)(T.n_eq > 0 ? T.n_eq : 1) * nB);
-    d_r = c.take<double>((size_t)(nrow > 0 ? nrow : 1) * nB);
-    for (double** q : {&d_v, &d_f, &d_c, &d_s}) *q = c.take<double>(nB);
-    return c.bytes();
-  };
-  if (const int rc = stage_carve(h, layout)) return rc;
-  hipStream_t s = h->stream;
-  HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T.nx * B, hipMemcpyHostToDevice, s));
-  if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * B, hipMemcpyHostToDevice, s));
-  if (T.n_ineq > 0) HIPCHK(hipMemcpyAsync(d_l, lam, sizeof(double) * (size_t)T.n_ineq * B, hipMemcpyHostToDevice, s));
-  if (T.n_eq > 0) HIPCHK(hipMemcpyAsync(d_m, mu, sizeof(double) * (size_t)T.n_eq * B, hipMemcpyHostToDevice, s));
-  h->tape_phi_lds = 0;
-  // the evaluator oh_solve launches for this handle and this B (tape_solve_device)
-  if (h->tape_wave.ready)
-    HIPCHK(oh_launch_tape_wave_phi(s, h->tape_wave, T, B, d_x, d_p, d_l, d_m, rho, d_v, d_f, d_r, d_g, d_c, d_s));
-  else if (h->tape_jit.fn)
-    HIPCHK(oh_launch_tape_jit_phi(s, h->tape_jit_phi, T, B, h->tape_cap(), d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f, d_r, d_g, d_c, d_s,
-                                  (int)optv(h, "tape_lds_max"), &h->tape_phi_lds));
-  else
-    oh_launch_tape_phi(s, T, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap(), d_x, d_p, d_l, d_m, rho, h->d_tape_work, d_v, d_f,
-                       d_r, d_g, d_c, d_s);
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(merit, d_v, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(f, d_f, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cmax, d_c, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(meas, d_s, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(grad, d_g, sizeof(double) * (size_t)T.nx * B, hipMemcpyDeviceToHost));
-  if (nrow > 0) HIPCHK(hipMemcpy(rows, d_r, sizeof(double) * (size_t)nrow * B, hipMemcpyDeviceToHost));
-  return OH_OK;
-}
-
-static int tape_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
-  HIPCHK(hipSetDevice(h->device));
-  const int Bp = (B + 63) / 64 * 64;
-  if (const int rc = tape_ensure_work(h, Bp)) return rc;
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  if (h->tape_wave.ready)
-    HIPCHK(oh_launch_tape_wave(h->stream, h->tape_wave, h->TP, B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters,
-                               (int*)d_status, h->d_tape_mult));
-  else if (h->tape_jit.fn)
-    HIPCHK(oh_launch_tape_jit(h->stream, h->tape_jit, h->TP, B, h->tape_cap(), (const double*)d_x0, (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f,
-                              (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult, (int)optv(h, "tape_lds_max")));
-  else
-    oh_launch_tape_solve(h->stream, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, B, h->tape_cap(), (const double*)d_x0,
-                         (const double*)d_p, h->d_tape_work, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tape_mult);
-  return finish_solve(h, 1);
-}
-
-extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
-  if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_qp: null argument");
-  *out = nullptr;
-  if (desc->n < 1 || desc->n > OH_QP_MAX_N || desc->m < 0 || desc->m > OH_QP_MAX_M || desc->me < 0 || desc->me > OH_QP_MAX_ME || desc->me > desc->n)
-    return fail(OH_ERR_INVALID, "oh_create_qp: sizes out of range (1 <= n <= 128, 0 <= m <= 1024, 0 <= me <= min(128, n))");
-  int rc = OH_OK;
-  oh_handle* h = open_handle("oh_create_qp", OH_PROBLEM_QP, 1, desc->n, 0, &rc);
-  if (!h) return rc;
-  h->qp = *desc;
-  if (h->qp.max_iter <= 0) h->qp.max_iter = 100;
-  if (!(h->qp.tol > 0.0)) h->qp.tol = 1e-9;
-  *out = h;
-  return OH_OK;
-}
-
-static size_t qp_np(const oh_qp_desc& q) { return (size_t)q.n * q.n + q.n + (size_t)q.m * q.n + q.m + (size_t)q.me * q.n + q.me; }
-
 // Shape (oh_carve.h) of a handle's problem
-static Shape shape_of(const oh_handle* h) {
+Shape shape_of(const oh_handle* h) {
   const size_t N = h->desc.ndof, T = h->desc.T;
+  const TapeParams& tp = h->tape.P;
+  const oh_qp_desc& qp = h->qp.desc;
   switch (h->desc.kind) {
-    case OH_PROBLEM_TORQUE_MPC: return {4 * N * T, 2 * N + 3 * T, T * (h->tq.vel_limits ? 4 : 2) * N};
-    case OH_PROBLEM_TAPE: return {(size_t)h->TP.nx, (size_t)(h->TP.np > 0 ? h->TP.np : 1), (size_t)(h->TP.n_ineq + h->TP.n_eq)};
-    case OH_PROBLEM_QP: return {(size_t)h->qp.n, h->qp_tape ? (size_t)(h->TP.np > 0 ? h->TP.np : 1) : qp_np(h->qp), (size_t)(h->qp.m + h->qp.me)};
+    case OH_PROBLEM_TORQUE_MPC: return {4 * N * T, 2 * N + 3 * T, T * (h->tq.desc.vel_limits ? 4 : 2) * N};
+    case OH_PROBLEM_TAPE: return {(size_t)tp.nx, (size_t)(tp.np > 0 ? tp.np : 1), (size_t)(tp.n_ineq + tp.n_eq)};
+    case OH_PROBLEM_QP: return {(size_t)qp.n, h->qp.use_tape ? (size_t)(tp.np > 0 ? tp.np : 1) : qp_np(qp), (size_t)(qp.m + qp.me)};
     case OH_PROBLEM_POINT_MASS_MPC: return {4 * T, 4 + 4 * T, 0};
     case OH_PROBLEM_IK: return {N, N + 3, 3 + 2 * N};
     case OH_PROBLEM_FIGURE_EIGHT: {
@@ -854,318 +282,7 @@ static Shape shape_of(const oh_handle* h) {
   }
 }
 
-extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
-  if (!h || !d) return fail(OH_ERR_INVALID, "oh_qp_set_tape: null argument");
-  if (h->desc.kind != OH_PROBLEM_QP) return fail(OH_ERR_STATE, "oh_qp_set_tape: not an OH_PROBLEM_QP handle");
-  if (const int rc = tape_validate(d, "oh_qp_set_tape")) return rc;
-  if (d->nx != h->qp.n || d->n_ineq != h->qp.m || d->n_eq != h->qp.me)
-    return fail(OH_ERR_INVALID, "oh_qp_set_tape: the tape's nx / n_ineq / n_eq differ from the handle's n / m / me");
-  HIPCHK(hipSetDevice(h->device));
-  h->qp_tape = false;
-  if (const int rc = upload_tape(h, d, nullptr)) return rc;
-  h->TP = tape_params(d);
-  {
-    // instructions whose value depends on x: the probes after the first re-run only these
-    std::vector<char> dep((size_t)d->len, 0);
-    std::vector<int> list;
-    for (int i = 0; i < d->len; ++i) {
-      const int o = d->op[i];
-      const bool two = tape_op_arity(o) == 2, one = tape_op_arity(o) == 1;
-      dep[i] = o == 1 || ((one || two) && dep[d->a[i]]) || (two && dep[d->b[i]]);
-      if (dep[i]) list.push_back(i);
-    }
-    h->d_qp_xdep.release();
-    h->qp_n_xdep = (int)list.size();
-    HIPCHK(h->d_qp_xdep.reserve(list.size() + 1));
-    if (!list.empty()) HIPCHK(hipMemcpy(h->d_qp_xdep, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
-  }
-  for (DevBuf<double>* b : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) b->release();  // the register file of another tape: size it again at the next solve
-  h->qp_tape = true;
-  return OH_OK;
-}
-
-static int qp_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
-  HIPCHK(hipSetDevice(h->device));
-  const oh_qp_desc& q = h->qp;
-  QpParams Q{};
-  Q.n = q.n; Q.m = q.m; Q.me = q.me; Q.np = (int)qp_np(q); Q.max_iter = q.max_iter; Q.tol = q.tol;
-  Q.nwork = q.n + 2 * q.m + q.me + q.n * q.n + 2 * q.n + 2 * q.m + q.me * q.n + q.me * q.me + q.me + q.n;
-  const int Bp = (B + 63) / 64 * 64;
-  const int mode = (int)optv(h, "qp_mode");
-  const bool large = oh_qp_is_large(Q), block = oh_qp_takes_block(Q, mode);
-  HIPCHK(h->d_qp_mult.reserve((size_t)(q.m + q.me + 1) * Bp));
-  // what k_qp_solve_block keeps in global memory: a slice per instance (its vectors and H live in LDS); the other kernels: [Q.nwork][Bp]
-  if (block) HIPCHK(h->d_qp_blk.reserve(oh_qp_block_work_doubles(Q) * (size_t)B + 1));
-  else HIPCHK(h->d_qp_work.reserve((size_t)Q.nwork * Bp));
-  const int work_stride = (int)(h->d_qp_work.cap / (size_t)Q.nwork);  // the Bp d_qp_work was allocated for (0: never)
-  // register file of the tape interpreter: a lane per instance, or (a few instances: B <= 64) a lane per probe point of every instance;
-  // large handles: rows and f(0, p) by instance, the register file by the instances of one launch (64 lanes each)
-  const int Bv = large ? B : (B <= 64 ? (B * 64 > Bp ? B * 64 : Bp) : Bp);
-  const int chunk = (large && h->qp_tape) ? oh_qp_assemble_block_chunk(h->TP, B) : 0;
-  // (d_qp_f0 is allocated last: its capacity is the Bv all three hold; large handles: d_qp_val holds 64 lanes for each of `chunk` instances)
-  if (h->qp_tape && ((size_t)Bv > h->d_qp_f0.cap || (size_t)h->TP.len * chunk * 64 > h->d_qp_val.cap)) {
-    for (DevBuf<double>* b : {&h->d_qp_rows, &h->d_qp_val, &h->d_qp_f0}) b->release();
-    HIPCHK(h->d_qp_rows.reserve((size_t)Q.np * Bv));
-    HIPCHK(h->d_qp_val.reserve((size_t)h->TP.len * (large ? (size_t)chunk * 64 : (size_t)Bv)));
-    HIPCHK(h->d_qp_f0.reserve((size_t)Bv));
-  }
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  std::string err;
-  h->qp_last_block = block ? 1 : 0;
-  if (h->qp_tape) {
-    if (large) {
-      if (oh_launch_qp_assemble_block(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, chunk,
-                                      (const double*)d_p, h->d_qp_val, h->d_qp_rows, h->d_qp_f0, &err))
-        return fail(OH_ERR_HIP, "oh_solve: " + err);
-    } else {
-      oh_launch_qp_assemble(h->stream, Q, h->TP, h->d_tape_op, h->d_tape_a, h->d_tape_b, h->d_tape_c, h->d_tape_rows, h->d_qp_xdep, h->qp_n_xdep, B, B <= 64 ? B * 64 : (int)h->d_qp_f0.cap, (const double*)d_p,
-                            h->d_qp_val, h->d_qp_rows, h->d_qp_f0);
-    }
-    d_p = h->d_qp_rows;
-  }
-  if (oh_launch_qp_solve(h->stream, Q, B, work_stride, (const double*)d_x0, (const double*)d_p, block ? h->d_qp_blk.p : h->d_qp_work.p, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                         (int*)d_iters, (int*)d_status, h->d_qp_mult, mode, &err))
-    return fail(OH_ERR_HIP, "oh_solve: " + err);
-  if (h->qp_tape && d_f) oh_launch_qp_add_constant(h->stream, B, (double*)d_f, h->d_qp_f0);
-  return finish_solve(h, 1);
-}
-
-extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
-  if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_ik: null argument");
-  *out = nullptr;
-  if (desc->ndof < 2 || desc->ndof > 8) return fail(OH_ERR_INVALID, "oh_create_ik: kernels are instantiated for 2 ... 8 actuated joints");
-  if (!(desc->w_nominal > 0.0)) return fail(OH_ERR_INVALID, "oh_create_ik: w_nominal must be positive");
-  for (int i = 0; i < desc->ndof; ++i)
-    if (!(desc->q_lo[i] <= desc->q_up[i])) return fail(OH_ERR_INVALID, "oh_create_ik: q_lo must not exceed q_up");
-  int rc = OH_OK;
-  oh_handle* h = open_handle("oh_create_ik", OH_PROBLEM_IK, 1, desc->ndof, OPEN_CHAIN, &rc);
-  if (!h) return rc;
-  h->ik = *desc;
-  if (h->ik.max_iter <= 0) h->ik.max_iter = 200;
-  if (!(h->ik.tol > 0.0)) h->ik.tol = 1e-6;
-  if (!(h->ik.tol_feas > 0.0)) h->ik.tol_feas = 1e-9;
-  if (!(h->ik.rho0 > 0.0)) h->ik.rho0 = 100.0 * h->ik.w_nominal;
-  *out = h;
-  return OH_OK;
-}
-
-static bool solver_chain_ok(const oh_chain& c);
-
-extern "C" int oh_create_torque(const oh_torque_desc* desc, oh_handle** out) {
-  if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_torque: null argument");
-  *out = nullptr;
-  if (desc->ndof < 2 || desc->ndof > 7) return fail(OH_ERR_INVALID, "oh_create_torque: kernels are instantiated for ndof 2 .. 7");
-  if (desc->T < 2 || desc->T > OH_MAX_T) return fail(OH_ERR_INVALID, "oh_create_torque: T must be in [2, OH_MAX_T]");
-  if (!(desc->dt > 0.0) || !(desc->w_tau > 0.0) || !(desc->w_path >= 0.0) || !(desc->w_vel >= 0.0))
-    return fail(OH_ERR_INVALID, "oh_create_torque: dt and w_tau must be positive, w_path and w_vel non-negative");
-  for (int i = 0; i < desc->ndof; ++i)
-    if (!(desc->tau_lo[i] < desc->tau_up[i])) return fail(OH_ERR_INVALID, "oh_create_torque: tau_lo must be below tau_up");
-  if (desc->vel_limits)
-    for (int i = 0; i < desc->ndof; ++i)
-      if (!(desc->dq_lo[i] < desc->dq_up[i])) return fail(OH_ERR_INVALID, "oh_create_torque: dq_lo must be below dq_up");
-  int rc = OH_OK;
-  oh_handle* h = open_handle("oh_create_torque", OH_PROBLEM_TORQUE_MPC, desc->T, desc->ndof, OPEN_CHAIN | OPEN_FLAG, &rc);
-  if (!h) return rc;
-  h->tq = *desc;
-  if (h->tq.max_iter <= 0) h->tq.max_iter = 300;
-  if (!(h->tq.tol > 0.0)) h->tq.tol = 1e-6;
-  if (!(h->tq.tol_compl > 0.0)) h->tq.tol_compl = 1e-8;
-  if (!(h->tq.mu_barrier0 > 0.0)) h->tq.mu_barrier0 = 0.1;
-  if (!(h->tq.mu0 >= 0.0)) h->tq.mu0 = 0.0;
-  *out = h;
-  return OH_OK;
-}
-
-static int tq_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
-                           const double mu_b0_warm = 0.0) {
-  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
-  if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_dynamics first");
-  if (!solver_chain_ok(h->chain_host) || h->chain_host.has_lead)
-    return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
-  const int N = h->tq.ndof, T = h->tq.T;
-  if (h->dyn_host.ndof != N) return fail(OH_ERR_INVALID, "oh_solve_device: the inverse-dynamics tables must have ndof + 1 bodies");
-  HIPCHK(hipSetDevice(h->device));
-  TqParams& P = h->TqP;
-  P = TqParams{};
-  P.T = T; P.N = N; P.max_iter = h->tq.max_iter;
-  P.dt = h->tq.dt; P.w_path = h->tq.w_path; P.w_vel = h->tq.w_vel; P.w_tau = h->tq.w_tau;
-  P.tol = h->tq.tol; P.tol_compl = h->tq.tol_compl; P.mu_b0 = mu_b0_warm > 0.0 ? mu_b0_warm : h->tq.mu_barrier0; P.mu0 = h->tq.mu0;
-  // interior point: relaxed barrier below theta mu_b; monotone barrier update of Waechter & Biegler (2006, eq. 7) -- IPOPT's constants except theta_mu (1.35 for 1.5: the hardest of 8192 instances needs 127 steps instead of 198) and, round 5, kappa_mu (0.4 for 0.2: tools/gpu_tq_param_sweep.py); exact
-  // curvature of the Lagrangian once the reduced gradient is below curv_from (oracle/torque_ipm.py:solve_torque_ipm has the same defaults: OPT_TABLE's)
-  P.theta = 0.01;
-  P.stall_max = (int)optv(h, "tq_stall");
-  P.curv_after = (int)optv(h, "tq_curv_after");
-  P.tau_ftb = optv(h, "tq_ftb");
-  P.theta_mu = optv(h, "tq_theta_mu");
-  P.kappa_mu = optv(h, "tq_kappa_mu");
-  P.curv_from = optv(h, "tq_curv_from");  // 0: Gauss-Newton blocks throughout (A/B)
-  P.curv_late = optv(h, "tq_curv_late");
-  P.kappa_eps = optv(h, "tq_kappa_eps");
-  // (a warm-started tick of oh_tq_rollout starts next to its optimum: there the damping comes down faster)
-  P.mu_dec = mu_b0_warm > 0.0 ? optv(h, "tq_mu_dec_warm") : optv(h, "tq_mu_dec");
-  P.ls_curv = (int)optv(h, "tq_ls_curv");
-  P.curv_lag = (int)optv(h, "tq_curv_lag");
-  P.max_back = (int)optv(h, "tq_max_back");
-  P.vel = h->tq.vel_limits ? 1 : 0;
-  // d tau / dz in closed form needs the tables to describe a rigid-body chain: unit joint axes that the joint-origin rotation leaves in place (then
-  // the angular velocity the reference adds, iRp @ axis, is the axis its rotation turns about; models.py:1821-1823).  Otherwise: dual numbers.
-  P.jac_closed_form = 1;
-  for (int i = 0; i < N; ++i) {
-    const double* a = h->dyn_host.axis[i];
-    const double* R = h->dyn_host.R0[i];
-    double dev = fabs(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] - 1.0);
-    for (int k = 0; k < 3; ++k) dev = fmax(dev, fabs(R[k] * a[0] + R[3 + k] * a[1] + R[6 + k] * a[2] - a[k]));
-    if (!(dev <= 1e-12)) P.jac_closed_form = 0;
-  }
-  if (optv(h, "tq_jac_dual") != 0.0) P.jac_closed_form = 0;  // the dual-number path whatever the tables (A/B, tests)
-  for (int i = 0; i < N; ++i) {
-    P.tau_lo[i] = h->tq.tau_lo[i];
-    P.tau_up[i] = h->tq.tau_up[i];
-    P.dq_lo[i] = h->tq.dq_lo[i];
-    P.dq_up[i] = h->tq.dq_up[i];
-  }
-  P.nx = (int)shape_of(h).nx;
-  P.np = (int)shape_of(h).npar;
-  TqBuffers& D = h->TqD;
-  const size_t BT = (size_t)B * T;
-  if (BT * TQ_HC > h->d_tq_hc.cap) {  // the pool, the multipliers and the curvature terms grow together (d_tq_hc last: its capacity is the batch all three hold)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->tq_pool.release();
-    h->d_tq_mult.release();
-    h->d_tq_hc.release();
-    Carver measure(nullptr, Carver::Packed);
-    layout_tq(measure, D, B, T);
-    HIPCHK(h->tq_pool.reserve(measure.bytes()));
-    HIPCHK(h->d_tq_mult.reserve(BT * 4 * N));  // effort rows, and room for the velocity rows
-    HIPCHK(h->d_tq_hc.reserve(BT * TQ_HC));
-    HIPCHK(hipMemsetAsync(h->d_tq_hc, 0, sizeof(double) * BT * TQ_HC, h->stream));  // entries the adjoint never writes stay zero
-  }
-  {
-    // D.B is the live batch: the strides of the [slot][B][T] arrays follow it, inside a pool that holds the largest batch so far
-    Carver carve(h->tq_pool.p, Carver::Packed);
-    layout_tq(carve, D, B, T);
-    D.B = B;
-    D.chain = h->d_chain;
-    D.dyn = h->d_dyn;
-    D.hc = h->d_tq_hc;
-    D.n_run = B;
-  }
-  hipStream_t s = h->stream;
-  HIPCHK(hipEventRecord(h->ev0, s));
-  if (!oh_launch_tq_setup(s, P, D, (const double*)d_x0, (const double*)d_p)) return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
-  // iteration k: evaluate the pending trial of every running instance, then ratio test / Riccati sweep / next trial.  The host only looks at
-  // the running count every tq_check iterations (instances that finished in between cost nothing: their lanes exit at once).
-  int launched = 0;
-  double work = 0.0;
-  int running = B;
-  const int cap = P.max_iter + 2;
-  // oh_set_profiling(1): one event before the evaluation pair (k_tq_eval3 + k_tq_curv), one after it, one after k_tq_step, every iteration -- the
-  // per-kernel device times behind the family's roofline object (tools/bench_configs.py); such a solve runs on one stream
-  const bool prof = h->profiling;
-  size_t ne = 0;
-  if (prof) {
-    const size_t need = 3 * (size_t)cap + 4;
-    while (h->prof_events.size() < need) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      h->prof_events.push_back(e);
-    }
-  }
-  while (launched < cap) {
-    if (prof) HIPCHK(hipEventRecord(h->prof_events[ne++], s));
-    oh_launch_tq_eval(s, P, D);  // also resets the running count
-    if (prof) HIPCHK(hipEventRecord(h->prof_events[ne++], s));
-    oh_launch_tq_step(s, P, D);
-    if (prof) HIPCHK(hipEventRecord(h->prof_events[ne++], s));
-    ++launched;
-    work += running;
-    if (launched % h->sch.tq_check == 0 || launched == cap) {
-      HIPCHK(hipMemcpyAsync(h->h_flag, D.n_running, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      running = *h->h_flag;
-      if (running == 0) break;
-      const double rebuild = optv(h, "tq_rebuild");
-      if (running <= rebuild * D.n_run) {  // rebuild the list of running instances: grids shrink with the batch
-        HIPCHK(hipMemsetAsync(D.n_list, 0, sizeof(int), s));
-        oh_launch_tq_list(s, D);
-        D.n_run = running;
-      }
-    }
-  }
-  oh_launch_tq_finalize(s, P, D, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status, h->d_tq_mult);
-  if (const int rc = finish_solve(h, launched)) return rc;
-  if (prof) {
-    for (size_t i = 0; i + 3 <= ne; i += 3) {
-      float a = 0.f, b2 = 0.f;
-      hipEventElapsedTime(&a, h->prof_events[i], h->prof_events[i + 1]);
-      hipEventElapsedTime(&b2, h->prof_events[i + 1], h->prof_events[i + 2]);
-      h->timing[0] += a;
-      h->timing[2] += b2;
-    }
-    h->timing[1] = h->timing[3] = launched;
-  }
-  h->timing[6] = work;
-  return OH_OK;
-}
-
-static int ik_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters,
-                           void* d_status) {
-  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
-  if (!solver_chain_ok(h->chain_host))
-    return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
-  HIPCHK(hipSetDevice(h->device));
-  const int N = h->ik.ndof;
-  HIPCHK(h->d_ik_mult.reserve((3 + 2 * (size_t)N) * B));
-  IkParams P{};
-  P.ndof = N;
-  P.max_iter = h->ik.max_iter;
-  P.w = h->ik.w_nominal;
-  P.tol = h->ik.tol;
-  P.tol_feas = h->ik.tol_feas;
-  P.rho0 = h->ik.rho0;
-  for (int i = 0; i < N; ++i) {
-    P.lo[i] = h->ik.q_lo[i];
-    P.up[i] = h->ik.q_up[i];
-  }
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  if (!oh_launch_ik_solve(h->stream, h->d_chain, P, B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                          (int*)d_iters, (int*)d_status, h->d_ik_mult))
-    return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
-  return finish_solve(h, 1);
-}
-
-static int pm_prepare(oh_handle* h, int B) {
-  HIPCHK(hipSetDevice(h->device));
-  const int T = h->pm.T;
-  const int Bp = (B + 63) / 64 * 64;  // (padding the row stride like the trajectory families do was measured: no effect, the solve is latency bound)
-  if (Bp > h->cap_B || !h->pool) {
-    h->pool.release();
-    Carver measure(nullptr, Carver::Packed);
-    layout_pm(measure, h->PmD, T, Bp);
-    const hipError_t e = h->pool.reserve(measure.bytes());
-    if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("device pool allocation failed: ") + hipGetErrorString(e));
-    h->cap_B = Bp;
-    h->PmD.Bp = Bp;
-    Carver carve(h->pool.p, Carver::Packed);
-    layout_pm(carve, h->PmD, T, Bp);
-  }
-  h->PmD.B = B;
-  h->PmP = PmParams{T, h->pm.dt, h->pm.w_acc, h->pm.ylim, h->pm.vlim, h->pm.safe * h->pm.safe, h->pm.tol, h->pm.max_iter,
-                    h->pm.track_final_only ? 1 : 0, h->pm.w_vel, h->pm.fix_final_velocity ? 1 : 0};
-  return OH_OK;
-}
-
-static int pm_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters,
-                           void* d_status) {
-  int rc = pm_prepare(h, B);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  oh_launch_pm_solve(h->stream, h->PmP, h->PmD, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt,
-                     (int*)d_iters, (int*)d_status, (int)optv(h, "pm_wave_max"));
-  return finish_solve(h, 1);
-}
-
-static int validate_chain(const oh_handle* h, const oh_chain& c) {
+int validate_chain(const oh_handle* h, const oh_chain& c) {
   if (c.n_chain < 1 || c.n_chain > OH_MAX_CHAIN || c.ndof < c.n_chain || c.ndof > OH_MAX_CHAIN)
     return fail(OH_ERR_INVALID, "oh_set_constants: bad n_chain/ndof");
   for (int k = 0; k < c.n_chain; ++k) {
@@ -1180,7 +297,7 @@ static int validate_chain(const oh_handle* h, const oh_chain& c) {
 // (solve_split).  Any setter that changes one of those on the main handle destroys the peers: the next split solve builds them again from the new
 // data (parts 1.. used to go on solving with the old chain / limits / obstacles, and guards set after a first split solve left the peers
 // striding p by ndof only).  The record of the last solve goes with them: what it points at was computed with the old data.
-static void drop_peers(oh_handle* h) {
+void drop_peers(oh_handle* h) {
   h->last = LastSolve{};
   if (h->is_peer) return;
   for (oh_handle* p : h->peers) delete p;
@@ -1189,7 +306,7 @@ static void drop_peers(oh_handle* h) {
 
 // the handle has new constants: everything compiled for, or remembered about, the previous chain goes (one place for the three entry
 // points that set constants)
-static void adopt_chain(oh_handle* h, const oh_chain& c) {
+void adopt_chain(oh_handle* h, const oh_chain& c) {
   drop_peers(h);
   h->chain_host = c;
   h->have_chain = true;
@@ -1222,7 +339,7 @@ extern "C" int oh_set_constants_device(oh_handle* h, const void* d_chain, size_t
   return OH_OK;
 }
 
-static bool solver_chain_ok(const oh_chain& c) {
+bool solver_chain_ok(const oh_chain& c) {
   if (c.n_chain != c.ndof) return false;
   for (int k = 0; k < c.n_chain; ++k)
     if (c.qidx[k] != k) return false;
@@ -1484,7 +601,7 @@ static int ensure_peers(oh_handle* h, const int n) {
   while ((int)h->peers.size() < n) {
     oh_handle* p = nullptr;
     int rc;
-    if (tqk) rc = oh_create_torque(&h->tq, &p);
+    if (tqk) rc = oh_create_torque(&h->tq.desc, &p);
     else {
       oh_problem_desc d = h->desc;
       d.local_path = h->local_path.data();
@@ -1501,15 +618,14 @@ static int ensure_peers(oh_handle* h, const int n) {
   }
   return OH_OK;
 }
-static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
-                        bool may_fan_out, LastSolve* rec);
+static int solve_device(oh_handle* h, const Solve& a, bool may_fan_out, LastSolve* rec);
 // counters of the solves one lane ran, merged into the handle's timing by fan_out
 struct Tally {
   double launched = 0, work = 0, compactions = 0, rejects = 0, tails = 0;
 };
 // one solve of a lane: never fans out again (the lanes ARE the streams)
-static int lane_solve(oh_handle* q, Tally& t, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
-  if (const int rc = solve_device(q, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, false, nullptr)) return rc;
+static int lane_solve(oh_handle* q, Tally& t, const Solve& a) {
+  if (const int rc = solve_device(q, a, false, nullptr)) return rc;
   t.launched = std::max(t.launched, q->timing[5]);
   t.work += q->timing[6];
   t.compactions += q->timing[7];
@@ -1560,19 +676,15 @@ static int fan_out(oh_handle* h, const int n, Work&& work) {
   return OH_OK;
 }
 // a batch in S contiguous parts, one per lane (parts start on multiples of 64: whole wavefronts of the thread-per-instance kernels)
-static int solve_split(oh_handle* h, const int S, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
-                       LastSolve* rec) {
+static int solve_split(oh_handle* h, const int S, const Solve& a, LastSolve* rec) {
   const Shape sh = shape_of(h);
   std::vector<int> lo(S + 1, 0);
-  for (int i = 1; i <= S; ++i) lo[i] = (int)((long long)B * i / S / 64 * 64);
-  lo[S] = B;
+  for (int i = 1; i <= S; ++i) lo[i] = (int)((long long)a.B * i / S / 64 * 64);
+  lo[S] = a.B;
   std::vector<LastSolve::Part> parts(S);
   const int rc = fan_out(h, S, [&](const int i, oh_handle* q, Tally& t) {
-    const size_t o = (size_t)lo[i];
-    auto off = [&](const void* ptr, const size_t bytes_per) -> void* { return ptr ? (void*)((char*)ptr + o * bytes_per) : nullptr; };
     parts[i] = {q, lo[i + 1] - lo[i]};
-    return lane_solve(q, t, parts[i].n, off(d_x0, sh.nx * 8), off(d_p, sh.npar * 8), off(d_x, sh.nx * 8), off(d_f, 8), off(d_kkt, 24), off(d_iters, 4),
-                      off(d_status, 4));
+    return lane_solve(q, t, a.part((size_t)lo[i], parts[i].n, sh));
   });
   if (rc) return rc;
   rec->parts = parts;
@@ -1675,7 +787,7 @@ static int compact_batch(oh_handle* h, Traj& r, const int nrun, const int slot, 
   ++r.compactions;
   return OH_OK;
 }
-static int traj_prologue(oh_handle* h, Traj& r, const void* d_x0) {
+static int traj_prologue(oh_handle* h, Traj& r, const double* x0) {
   if (const int rc = ensure_capacity(h, r.B)) return rc;
   fill_params(h);
   if ((spec_applies(h) || spec_tail_vel_applies(h)) && !h->spec && !h->spec_failed) {
@@ -1710,7 +822,7 @@ static int traj_prologue(oh_handle* h, Traj& r, const void* d_x0) {
   }
   HIPCHK(hipEventRecord(h->ev0, s));
   HIPCHK(hipMemsetAsync(h->D.work, 0, 4 * sizeof(unsigned long long), s));  // (work[0..2] and the two deferral counters)
-  if (!oh_launch_setup(s, r.N, h->P, h->D, (const double*)d_x0, r.p)) return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
+  if (!oh_launch_setup(s, r.N, h->P, h->D, x0, r.p)) return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
   if (r.guarded) oh_launch_setup_guards(s, r.N, h->P, h->D, h->GP, h->GB, r.p);
   h->prof_tags.clear();
   return mark(h, r, 0);
@@ -1906,12 +1018,12 @@ static int traj_epilogue(oh_handle* h, Traj& r) {
   h->timing[7] = r.compactions;
   return OH_OK;
 }
-static int traj_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status) {
+static int traj_solve_device(oh_handle* h, const Solve& a) {
   Traj r{};
-  r.B = B; r.N = h->desc.ndof;
+  r.B = a.B; r.N = h->desc.ndof;
   r.guarded = h->have_guards; r.lead = h->chain_host.has_lead != 0; r.prof = h->profiling; r.invariant = batch_invariant(h) != 0.0;
-  r.p = (const double*)d_p; r.x = (double*)d_x; r.f = (double*)d_f; r.kkt = (double*)d_kkt; r.iters = (int*)d_iters; r.status = (int*)d_status;
-  if (const int rc = traj_prologue(h, r, d_x0)) return rc;
+  r.p = a.p; r.x = a.x; r.f = a.f; r.kkt = a.kkt; r.iters = a.iters; r.status = a.status;
+  if (const int rc = traj_prologue(h, r, a.x0)) return rc;
   if (const int rc = h->P.lock ? locked_loop(h, r) : free_loop(h, r)) return rc;
   return traj_epilogue(h, r);
 }
@@ -1932,16 +1044,16 @@ static int split_parts(const oh_handle* h, const int B, const bool may_fan_out) 
 
 // The solve of every entry point and every lane, by problem kind: without may_fan_out the batch is never split.  rec (may be null): where the
 // results live, on success.
-static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt, void* d_iters, void* d_status,
-                        const bool may_fan_out, LastSolve* rec) {
+static int solve_device(oh_handle* h, const Solve& a, const bool may_fan_out, LastSolve* rec) {
+  const int B = a.B;
   if (B < 1) return fail(OH_ERR_INVALID, "oh_solve_device: B must be >= 1");
-  if (!d_x0 || !d_p) return fail(OH_ERR_INVALID, "oh_solve_device: x0 and p are required");
+  if (!a.x0 || !a.p) return fail(OH_ERR_INVALID, "oh_solve_device: x0 and p are required");
   if (rec) *rec = LastSolve{B, {{h, B}}, false};
   switch (h->desc.kind) {
-    case OH_PROBLEM_POINT_MASS_MPC: return pm_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-    case OH_PROBLEM_IK: return ik_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-    case OH_PROBLEM_QP: return qp_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-    case OH_PROBLEM_TAPE: return tape_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+    case OH_PROBLEM_POINT_MASS_MPC: return pm_solve_device(h, a);
+    case OH_PROBLEM_IK: return ik_solve_device(h, a);
+    case OH_PROBLEM_QP: return qp_solve_device(h, a);
+    case OH_PROBLEM_TAPE: return tape_solve_device(h, a);
     case OH_PROBLEM_TORQUE_MPC: break;
     case OH_PROBLEM_FIGURE_EIGHT:
       if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
@@ -1953,10 +1065,9 @@ static int solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, 
   if (const int S = split_parts(h, B, may_fan_out); S > 1) {
     // (the kernels compiled for the chain are shared: make sure they exist before the parts look for them)
     if (spec_applies(h) && !h->spec && !h->spec_failed && h->sch.specialize != OH_SPECIALIZE_NEVER && oh_specialize(h) != OH_OK) h->spec_failed = true;
-    return solve_split(h, S, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, rec);
+    return solve_split(h, S, a, rec);
   }
-  if (h->desc.kind == OH_PROBLEM_TORQUE_MPC) return tq_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
-  return traj_solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status);
+  return h->desc.kind == OH_PROBLEM_TORQUE_MPC ? tq_solve_device(h, a) : traj_solve_device(h, a);
 }
 
 extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void* d_p, void* d_x, void* d_f, void* d_kkt,
@@ -1964,12 +1075,13 @@ extern "C" int oh_solve_device(oh_handle* h, int B, const void* d_x0, const void
   if (!h) return fail(OH_ERR_INVALID, "oh_solve_device: null handle");
   h->last = LastSolve{};
   LastSolve rec;
-  const int rc = solve_device(h, B, d_x0, d_p, d_x, d_f, d_kkt, d_iters, d_status, !h->is_peer, &rec);
+  const Solve a{B, (const double*)d_x0, (const double*)d_p, (double*)d_x, (double*)d_f, (double*)d_kkt, (int*)d_iters, (int*)d_status};
+  const int rc = solve_device(h, a, !h->is_peer, &rec);
   if (rc == OH_OK) h->last = rec;
   return rc;
 }
 
-static int ensure_stage(oh_handle* h, size_t bytes) {
+int ensure_stage(oh_handle* h, size_t bytes) {
   const hipError_t e = h->stage.reserve(bytes);
   if (e != hipSuccess) return fail(OH_ERR_HIP, std::string("staging allocation failed: ") + hipGetErrorString(e));
   return OH_OK;
@@ -1985,10 +1097,10 @@ static int stage_solve(oh_handle* q, const Shape& sh, const size_t n, StageLayou
 // device pointer of a handle's multipliers, [B][shape.mult] (nullptr: none, or the guarded SoA layout that copy_multipliers transposes)
 static const double* mult_ptr(const oh_handle* q) {
   switch (q->desc.kind) {
-    case OH_PROBLEM_TORQUE_MPC: return q->d_tq_mult;
-    case OH_PROBLEM_TAPE: return q->d_tape_mult;
-    case OH_PROBLEM_QP: return q->d_qp_mult;
-    case OH_PROBLEM_IK: return q->d_ik_mult;
+    case OH_PROBLEM_TORQUE_MPC: return q->tq.mult;
+    case OH_PROBLEM_TAPE: return q->tape.mult;
+    case OH_PROBLEM_QP: return q->qp.mult;
+    case OH_PROBLEM_IK: return q->ik.mult;
     case OH_PROBLEM_FIGURE_EIGHT: return q->have_guards ? nullptr : q->D.lam_h;
     default: return nullptr;
   }
@@ -2039,7 +1151,7 @@ static int solve_pipelined(oh_handle* h, const int B, const int chunk, const dou
       bool ok = hipMemcpyAsync(L.x0, x0 + lo * sh.nx, L.b_x, hipMemcpyHostToDevice, s) == hipSuccess &&
                 hipMemcpyAsync(L.p, p + lo * sh.npar, L.b_p, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
       if (!ok) return fail(OH_ERR_HIP, "oh_solve: upload failed");
-      if (const int rc = lane_solve(q, t, n, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status)) return rc;
+      if (const int rc = lane_solve(q, t, Solve{n, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status})) return rc;
       const double* mult = mult_ptr(q);
       if (sh.mult && mult) ok = ok && hipMemcpyAsync(h->d_pipe_mult.p + lo * sh.mult, mult, sizeof(double) * sh.mult * n, hipMemcpyDeviceToDevice, s) == hipSuccess;
       if (x) ok = ok && hipMemcpyAsync(x + lo * sh.nx, L.x, L.b_x, hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -2059,9 +1171,7 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
   if (!h) return fail(OH_ERR_INVALID, "oh_solve: null handle");
   if (B < 1) return fail(OH_ERR_INVALID, "oh_solve: B must be >= 1");
   if (!x0 || !p) return fail(OH_ERR_INVALID, "oh_solve: x0 and p are required");
-  if (h->desc.kind != OH_PROBLEM_FIGURE_EIGHT && h->desc.kind != OH_PROBLEM_POINT_MASS_MPC && h->desc.kind != OH_PROBLEM_IK &&
-      h->desc.kind != OH_PROBLEM_QP && h->desc.kind != OH_PROBLEM_TAPE && h->desc.kind != OH_PROBLEM_TORQUE_MPC)
-    return fail(OH_ERR_STATE, "oh_solve: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
+  if (!shape_of(h).nx) return fail(OH_ERR_STATE, "oh_solve: handle was created without a problem (OH_PROBLEM_KINEMATICS)");
   HIPCHK(hipSetDevice(h->device));
   h->last = LastSolve{};
   // large batches of the trajectory families from host buffers: chunks on two lanes (handles, streams, host threads), so that one lane's transfers over
@@ -2094,7 +1204,7 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
     HIPCHK(hipMemcpy(L.x0, x0, L.b_x, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(L.p, p, L.b_p, hipMemcpyHostToDevice));
   }
-  rc = solve_device(h, B, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status, !h->is_peer, &rec);
+  rc = solve_device(h, Solve{B, L.x0, L.p, L.x, L.f, L.kkt, L.iters, L.status}, !h->is_peer, &rec);
   if (rc) return rc;
   if (small) {
     HIPCHK(hipMemcpy(M.x, L.x, L.out_bytes(), hipMemcpyDeviceToHost));
@@ -2114,123 +1224,11 @@ extern "C" int oh_solve(oh_handle* h, int B, const double* x0, const double* p, 
   return OH_OK;
 }
 
-extern "C" int oh_pm_rollout(oh_handle* h, int B, int n_ticks, int advance, double ramp, const double* state0, const double* obs_table,
-                             double* states, double* f, int* iters, int* status) {
-  if (!h || !state0 || !obs_table) return fail(OH_ERR_INVALID, "oh_pm_rollout: null argument");
-  if (h->desc.kind != OH_PROBLEM_POINT_MASS_MPC) return fail(OH_ERR_STATE, "oh_pm_rollout: handle is not a point-mass MPC problem");
-  const int T = h->pm.T;
-  if (B < 1 || n_ticks < 1 || advance < 1 || advance >= T) return fail(OH_ERR_INVALID, "oh_pm_rollout: need B >= 1, n_ticks >= 1, 1 <= advance < T");
-  h->last = LastSolve{};
-  int rc = pm_prepare(h, B);
-  if (rc) return rc;
-  const size_t nB = (size_t)B, n_obs = (size_t)n_ticks * advance + T;
-  const size_t b_states = sizeof(double) * 4 * nB * (n_ticks + 1), b_obs = sizeof(double) * 2 * n_obs, b_x = sizeof(double) * 4 * (size_t)T * nB;
-  const size_t b_f = sizeof(double) * nB * n_ticks, b_i = sizeof(int) * nB * n_ticks;
-  double *d_states, *d_obs, *d_p, *d_xa, *d_xb, *d_f;
-  int *d_it, *d_st;
-  rc = stage_carve(h, [&](Carver c) {
-    d_states = c.take<double>(4 * nB * (n_ticks + 1));
-    d_obs = c.take<double>(2 * n_obs);
-    d_p = c.take<double>((4 + 4 * (size_t)T) * nB);
-    d_xa = c.take<double>(4 * (size_t)T * nB);
-    d_xb = c.take<double>(4 * (size_t)T * nB);
-    d_f = c.take<double>(nB * n_ticks);
-    d_it = c.take<int>(nB * n_ticks);
-    d_st = c.take<int>(nB * n_ticks);
-    return c.bytes();
-  });
-  if (rc) return rc;
-  hipStream_t s = h->stream;
-  HIPCHK(hipMemcpyAsync(d_states, state0, sizeof(double) * 4 * (size_t)B, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_obs, obs_table, b_obs, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(d_xa, 0, b_x, s));  // first tick: zero seed (solver.py:76)
-  HIPCHK(hipEventRecord(h->ev0, s));
-  for (int k = 0; k < n_ticks; ++k) {
-    double* st_k = d_states + 4 * (size_t)B * k;
-    oh_launch_pm_tick_params(s, B, T, k, advance, ramp, st_k, d_obs, d_p);
-    double* x_seed = (k & 1) ? d_xb : d_xa;  // previous solution = warm start of this tick
-    double* x_sol = (k & 1) ? d_xa : d_xb;
-    oh_launch_pm_solve(s, h->PmP, h->PmD, x_seed, d_p, x_sol, d_f + (size_t)B * k, nullptr, d_it + (size_t)B * k, d_st + (size_t)B * k,
-                       (int)optv(h, "pm_wave_max"));
-    oh_launch_pm_advance(s, B, T, advance, x_sol, st_k + 4 * (size_t)B);
-  }
-  if ((rc = finish_solve(h, n_ticks))) return rc;
-  if (states) HIPCHK(hipMemcpy(states, d_states, b_states, hipMemcpyDeviceToHost));
-  if (f) HIPCHK(hipMemcpy(f, d_f, b_f, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, d_it, b_i, hipMemcpyDeviceToHost));
-  if (status) HIPCHK(hipMemcpy(status, d_st, b_i, hipMemcpyDeviceToHost));
-  h->last = LastSolve{B, {{h, B}}, false};
-  return OH_OK;
-}
-
-extern "C" int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, double mu_warm, const double* state0, const double* goal_table, double* states,
-                             double* tau0, double* f, int* iters, int* status) {
-  if (!h || !state0 || !goal_table) return fail(OH_ERR_INVALID, "oh_tq_rollout: null argument");
-  if (h->desc.kind != OH_PROBLEM_TORQUE_MPC) return fail(OH_ERR_STATE, "oh_tq_rollout: handle is not a torque-MPC problem");
-  const int T = h->tq.T, N = h->tq.ndof;
-  if (B < 1 || n_ticks < 1 || advance < 1 || advance >= T) return fail(OH_ERR_INVALID, "oh_tq_rollout: need B >= 1, n_ticks >= 1, 1 <= advance < T");
-  if (!(mu_warm > 0.0)) mu_warm = 1e-6;
-  HIPCHK(hipSetDevice(h->device));
-  h->last = LastSolve{};
-  const size_t nB = (size_t)B, n_rows = (size_t)n_ticks * advance + T;
-  const size_t nx = shape_of(h).nx, np_ = shape_of(h).npar;
-  const size_t b_states = sizeof(double) * 2 * N * nB * (n_ticks + 1), b_goal = sizeof(double) * 3 * n_rows * nB, b_x = sizeof(double) * nx * nB,
-               b_tau = sizeof(double) * N * nB * n_ticks, b_f = sizeof(double) * nB * n_ticks, b_i = sizeof(int) * nB * n_ticks;
-  double *d_states, *d_goal, *d_p, *d_xa, *d_xb, *d_tau, *d_f;
-  int *d_it, *d_st;
-  int rc = stage_carve(h, [&](Carver c) {
-    d_states = c.take<double>(2 * N * nB * (n_ticks + 1));
-    d_goal = c.take<double>(3 * n_rows * nB);
-    d_p = c.take<double>(np_ * nB);
-    d_xa = c.take<double>(nx * nB);
-    d_xb = c.take<double>(nx * nB);
-    d_tau = c.take<double>(N * nB * n_ticks);
-    d_f = c.take<double>(nB * n_ticks);
-    d_it = c.take<int>(nB * n_ticks);
-    d_st = c.take<int>(nB * n_ticks);
-    return c.bytes();
-  });
-  if (rc) return rc;
-  hipStream_t s = h->stream;
-  HIPCHK(hipMemcpyAsync(d_states, state0, sizeof(double) * 2 * N * (size_t)B, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_goal, goal_table, b_goal, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(d_xa, 0, b_x, s));  // first tick: zero accelerations (the cold solve of oh_solve from a constant-configuration seed)
-  double ms_total = 0.0, launched = 0.0, work = 0.0;
-  for (int k = 0; k < n_ticks; ++k) {
-    double* st_k = d_states + 2 * (size_t)N * B * k;
-    oh_launch_tq_tick_params(s, B, T, N, k * advance, (int)n_rows, st_k, d_goal, d_p);
-    double* x_seed = d_xa;  // the seed of this tick; the solution lands in d_xb and is shifted back into d_xa for the next one
-    double* x_sol = d_xb;
-    rc = tq_solve_device(h, B, x_seed, d_p, x_sol, d_f + (size_t)B * k, nullptr, d_it + (size_t)B * k, d_st + (size_t)B * k, k > 0 ? mu_warm : 0.0);
-    if (rc) return rc;
-    ms_total += h->timing[4];
-    launched += h->timing[5];
-    work += h->timing[6];
-    oh_launch_tq_advance(s, B, T, N, advance, x_sol, st_k + 2 * (size_t)N * B, tau0 ? d_tau + (size_t)N * B * k : nullptr);
-    oh_launch_tq_shift_seed(s, B, T, N, advance, x_sol, x_seed);
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  reset_counters(h);
-  h->timing[4] = ms_total;  // device time of the solves (HIP events around each)
-  h->timing[5] = launched;
-  h->timing[6] = work;
-  if (states) HIPCHK(hipMemcpy(states, d_states, b_states, hipMemcpyDeviceToHost));
-  if (tau0) HIPCHK(hipMemcpy(tau0, d_tau, b_tau, hipMemcpyDeviceToHost));
-  if (f) HIPCHK(hipMemcpy(f, d_f, b_f, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, d_it, b_i, hipMemcpyDeviceToHost));
-  if (status) HIPCHK(hipMemcpy(status, d_st, b_i, hipMemcpyDeviceToHost));
-  h->last = LastSolve{B, {{h, B}}, false};
-  return OH_OK;
-}
-
 extern "C" int oh_get_multipliers(oh_handle* h, int B, double* lam_h) {
   if (!h || !lam_h) return fail(OH_ERR_INVALID, "oh_get_multipliers: null argument");
   const LastSolve& r = h->last;
-  if ((h->desc.kind != OH_PROBLEM_FIGURE_EIGHT && h->desc.kind != OH_PROBLEM_IK && h->desc.kind != OH_PROBLEM_QP && h->desc.kind != OH_PROBLEM_TAPE &&
-       h->desc.kind != OH_PROBLEM_TORQUE_MPC) ||
-      B != r.B || B < 1)
-    return fail(OH_ERR_STATE, "oh_get_multipliers: B does not match the last solve");
+  // (a handle without a problem never has a last solve; the point-mass family reports no multipliers)
+  if (h->desc.kind == OH_PROBLEM_POINT_MASS_MPC || B != r.B || B < 1) return fail(OH_ERR_STATE, "oh_get_multipliers: B does not match the last solve");
   HIPCHK(hipSetDevice(h->device));
   const size_t per = shape_of(h).mult;
   if (!per && h->desc.kind == OH_PROBLEM_FIGURE_EIGHT) return fail(OH_ERR_STATE, "oh_get_multipliers: this problem has no nonlinear equality rows");
@@ -2243,233 +1241,6 @@ extern "C" int oh_get_multipliers(oh_handle* h, int B, double* lam_h) {
     if (const int rc = copy_multipliers(part.q, part.n, lam_h + o * per)) return rc;
     o += (size_t)part.n;
   }
-  return OH_OK;
-}
-
-extern "C" int oh_set_dynamics(oh_handle* h, const oh_dynamics* dyn) {
-  if (!h || !dyn) return fail(OH_ERR_INVALID, "oh_set_dynamics: null argument");
-  if (dyn->n < 2 || dyn->n > OH_MAX_BODIES - 1 || dyn->ndof != dyn->n - 1)
-    return fail(OH_ERR_INVALID, "oh_set_dynamics: need 2 <= n <= 9 bodies and ndof == n - 1");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(h->d_dyn.reserve(1));
-  HIPCHK(hipMemcpy(h->d_dyn, dyn, sizeof(oh_dynamics), hipMemcpyHostToDevice));
-  h->dyn_host = *dyn;
-  h->have_dyn = true;
-  drop_peers(h);
-  return OH_OK;
-}
-// Launch, check the launch, wait: the one order of the dynamics entry points.  launch() returns false for an unsupported number of bodies.
-template <class Launch>
-static int run_dyn(oh_handle* h, const char* unsupported, Launch&& launch) {
-  if (!launch()) return fail(OH_ERR_INVALID, unsupported);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OH_OK;
-}
-// oh_rnea, oh_rnea_jac, oh_rnea_hess: the host inputs (n x ndof each) staged one behind the other in 256-byte aligned slots, the output of
-// out_per_sample doubles per sample behind them; launch(d_in, d_out) runs on the staged copies, then the output is copied back.
-template <size_t NIN, class Launch>
-static int run_dyn_staged(oh_handle* h, const int n, const std::array<const double*, NIN>& in, double* out, const size_t out_per_sample,
-                          const char* unsupported, Launch&& launch) {
-  HIPCHK(hipSetDevice(h->device));
-  const size_t n_in = h->dyn_host.ndof * (size_t)n, n_out = out_per_sample * (size_t)n;
-  std::array<const double*, NIN> d_in;
-  double* d_out;
-  const int src = stage_carve(h, [&](Carver c) {
-    for (size_t k = 0; k < NIN; ++k) d_in[k] = c.take<double>(n_in);
-    d_out = c.take<double>(n_out);
-    return c.bytes();
-  });
-  if (src) return src;
-  for (size_t k = 0; k < NIN; ++k) HIPCHK(hipMemcpy((void*)d_in[k], in[k], sizeof(double) * n_in, hipMemcpyHostToDevice));
-  if (const int rc = run_dyn(h, unsupported, [&] { return launch(d_in, d_out); })) return rc;
-  HIPCHK(hipMemcpy(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost));
-  return OH_OK;
-}
-
-extern "C" int oh_rnea_device(oh_handle* h, int n, const void* d_q, const void* d_qd, const void* d_qdd, void* d_tau) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_rnea: null handle");
-  if (n < 1 || !d_q || !d_qd || !d_qdd || !d_tau) return fail(OH_ERR_INVALID, "oh_rnea: bad arguments");
-  if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea: call oh_set_dynamics first");
-  HIPCHK(hipSetDevice(h->device));
-  return run_dyn(h, "oh_rnea: unsupported number of bodies", [&] {
-    return oh_launch_rnea(h->stream, h->d_dyn, h->dyn_host.n, n, (const double*)d_q, (const double*)d_qd, (const double*)d_qdd, (double*)d_tau);
-  });
-}
-extern "C" int oh_rnea(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, double* tau) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_rnea: null handle");
-  if (n < 1 || !q || !qd || !qdd || !tau) return fail(OH_ERR_INVALID, "oh_rnea: bad arguments");
-  if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea: call oh_set_dynamics first");
-  return run_dyn_staged<3>(h, n, {q, qd, qdd}, tau, h->dyn_host.ndof, "oh_rnea: unsupported number of bodies", [&](const auto& d, double* d_tau) {
-    return oh_launch_rnea(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d_tau);
-  });
-}
-
-extern "C" int oh_rnea_jac(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, double* J) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_rnea_jac: null handle");
-  if (n < 1 || !q || !qd || !qdd || !J) return fail(OH_ERR_INVALID, "oh_rnea_jac: bad arguments");
-  if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea_jac: call oh_set_dynamics first");
-  const size_t nd = h->dyn_host.ndof;
-  return run_dyn_staged<3>(h, n, {q, qd, qdd}, J, 3 * nd * nd, "oh_rnea_jac: unsupported number of bodies", [&](const auto& d, double* d_J) {
-    return oh_launch_rnea_jac(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d_J);
-  });
-}
-
-extern "C" int oh_rnea_hess(oh_handle* h, int n, const double* q, const double* qd, const double* qdd, const double* c, double* H) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_rnea_hess: null handle");
-  if (n < 1 || !q || !qd || !qdd || !c || !H) return fail(OH_ERR_INVALID, "oh_rnea_hess: bad arguments");
-  if (!h->have_dyn) return fail(OH_ERR_STATE, "oh_rnea_hess: call oh_set_dynamics first");
-  const size_t nd = h->dyn_host.ndof;
-  return run_dyn_staged<4>(h, n, {q, qd, qdd, c}, H, 9 * nd * nd, "oh_rnea_hess: unsupported number of bodies", [&](const auto& d, double* d_H) {
-    return oh_launch_rnea_hess(h->stream, h->d_dyn, h->dyn_host.n, n, d[0], d[1], d[2], d[3], d_H);
-  });
-}
-
-static int fk_common(oh_handle* h, int n, bool soa, const void* d_q, void* d_pose, void* d_J) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_fk_jac: null handle");
-  if (n < 1 || !d_q) return fail(OH_ERR_INVALID, "oh_fk_jac: bad arguments");
-  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_fk_jac: call oh_set_constants first");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->fk_spec && !h->fk_spec_failed && (h->sch.specialize == OH_SPECIALIZE_ALWAYS || (h->sch.specialize == OH_SPECIALIZE_AUTO && n >= h->specialize_min_units)))
-    specialize_fk(h);  // on failure the generic kernel runs; oh_last_error keeps the reason
-  if (h->fk_spec) HIPCHK(oh_spec_launch_fk(*h->fk_spec, h->stream, soa, n, (const double*)d_q, (double*)d_pose, (double*)d_J));
-  else oh_launch_fk_jac(h->stream, soa, h->d_chain, h->chain_host.n_chain, h->chain_host.ndof, n, (const double*)d_q, (double*)d_pose, (double*)d_J);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OH_OK;
-}
-extern "C" int oh_fk_jac_device(oh_handle* h, int n, const void* d_q, void* d_pose, void* d_J) {
-  return fk_common(h, n, false, d_q, d_pose, d_J);
-}
-extern "C" int oh_fk_jac_soa_device(oh_handle* h, int n, const void* d_q, void* d_pose, void* d_J) {
-  return fk_common(h, n, true, d_q, d_pose, d_J);
-}
-extern "C" int oh_fk_jac(oh_handle* h, int n, const double* q, double* pose, double* J) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_fk_jac: null handle");
-  if (n < 1 || !q) return fail(OH_ERR_INVALID, "oh_fk_jac: bad arguments");
-  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_fk_jac: call oh_set_constants first");
-  HIPCHK(hipSetDevice(h->device));
-  const int ndof = h->chain_host.ndof;
-  const size_t b_q = sizeof(double) * ndof * (size_t)n, b_p = sizeof(double) * 7 * (size_t)n,
-               b_J = sizeof(double) * 6 * ndof * (size_t)n;
-  double *d_q, *d_pose, *d_J;
-  int rc = stage_carve(h, [&](Carver c) {
-    d_q = c.take<double>(ndof * (size_t)n);
-    d_pose = c.take<double>(7 * (size_t)n);
-    d_J = c.take<double>(6 * ndof * (size_t)n);
-    return c.bytes();
-  });
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(d_q, q, b_q, hipMemcpyHostToDevice));
-  rc = fk_common(h, n, false, d_q, pose ? d_pose : nullptr, J ? d_J : nullptr);
-  if (rc) return rc;
-  if (pose) HIPCHK(hipMemcpy(pose, d_pose, b_p, hipMemcpyDeviceToHost));
-  if (J) HIPCHK(hipMemcpy(J, d_J, b_J, hipMemcpyDeviceToHost));
-  return OH_OK;
-}
-
-// ---- kinematics of a link in the frame of another link (k_link_kin, oh_linkkin.hip) ----------------------------------------------------------------
-static int validate_frame_chain(const oh_chain& c, const char* which) {
-  const std::string who = std::string("oh_set_link_frames: ") + which;
-  if (c.ndof < 1 || c.ndof > OH_MAX_CHAIN || c.n_chain < 0 || c.n_chain > OH_MAX_CHAIN || c.n_chain > c.ndof) return fail(OH_ERR_INVALID, who + " chain: bad n_chain/ndof");
-  for (int k = 0; k < c.n_chain; ++k) {
-    if (c.jtype[k] != 0 && c.jtype[k] != 1) return fail(OH_ERR_INVALID, who + " chain: joint type not supported");
-    if (c.qidx[k] < 0 || c.qidx[k] >= c.ndof) return fail(OH_ERR_INVALID, who + " chain: qidx out of range");
-  }
-  return OH_OK;
-}
-
-extern "C" int oh_set_link_frames(oh_handle* h, const oh_chain* link, const oh_chain* base) {
-  if (!h || !link) return fail(OH_ERR_INVALID, "oh_set_link_frames: null argument");
-  if (h->desc.kind != OH_PROBLEM_KINEMATICS) return fail(OH_ERR_INVALID, "oh_set_link_frames: the handle is not an OH_PROBLEM_KINEMATICS handle");
-  OhLinkFrames f{};
-  f.link = *link;
-  if (base) {
-    f.base = *base;
-  } else {  // the root frame: no joints, identity tool transform
-    f.base.ndof = link->ndof;
-    f.base.R_tool[0] = f.base.R_tool[4] = f.base.R_tool[8] = 1.0;
-    f.base.quat_tool[3] = 1.0;
-  }
-  int rc = validate_frame_chain(f.link, "link");
-  if (!rc) rc = validate_frame_chain(f.base, "base");
-  if (rc) return rc;
-  if (f.link.ndof != f.base.ndof) return fail(OH_ERR_INVALID, "oh_set_link_frames: link.ndof != base.ndof");
-  if (f.link.ndof != h->desc.ndof) return fail(OH_ERR_INVALID, "oh_set_link_frames: chain.ndof != desc.ndof");
-  // common prefix: the same joint with the same folded constants on both chains (the kernel gives such a joint an exactly zero d rpy / d q)
-  const oh_chain &a = f.link, &b = f.base;
-  int ns = 0;
-  while (ns < a.n_chain && ns < b.n_chain && a.qidx[ns] == b.qidx[ns] && a.jtype[ns] == b.jtype[ns] && !memcmp(a.R0[ns], b.R0[ns], sizeof a.R0[ns]) &&
-         !memcmp(a.p0[ns], b.p0[ns], sizeof a.p0[ns]) && !memcmp(a.axis[ns], b.axis[ns], sizeof a.axis[ns]))
-    ++ns;
-  for (int k = ns; k < a.n_chain; ++k)
-    for (int m = ns; m < b.n_chain; ++m)
-      if (a.qidx[k] == b.qidx[m]) return fail(OH_ERR_INVALID, "oh_set_link_frames: a joint past the chains' common prefix is on both chains");
-  f.n_shared = ns;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(h->d_frames.reserve(1));
-  HIPCHK(hipMemcpy(h->d_frames, &f, sizeof f, hipMemcpyHostToDevice));
-  h->frames_host = f;
-  h->have_frames = true;
-  return OH_OK;
-}
-
-// argument checks of both entry points (no device call before they pass); a3 <- axis3 / |axis3|
-static int link_kin_check(const char* who, oh_handle* h, int n, const void* q, const double* axis3, const oh_link_out* out, double (&a3)[3]) {
-  const std::string w(who);
-  if (!h) return fail(OH_ERR_INVALID, w + ": null handle");
-  if (!out) return fail(OH_ERR_INVALID, w + ": null out");
-  if (n < 1 || !q) return fail(OH_ERR_INVALID, w + ": bad arguments");
-  a3[0] = a3[1] = a3[2] = 0.0;
-  if (out->axis) {
-    if (!axis3) return fail(OH_ERR_INVALID, w + ": out->axis needs axis3");
-    const double nrm = std::sqrt(axis3[0] * axis3[0] + axis3[1] * axis3[1] + axis3[2] * axis3[2]);
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return fail(OH_ERR_INVALID, w + ": axis3 must be a nonzero finite vector");
-    for (int i = 0; i < 3; ++i) a3[i] = axis3[i] / nrm;
-  }
-  if (!h->have_frames) return fail(OH_ERR_STATE, w + ": call oh_set_link_frames first");
-  return OH_OK;
-}
-
-static int link_kin_launch(oh_handle* h, int n, bool soa, const double* d_q, const double (&a3)[3], const oh_link_out& d_out) {
-  oh_launch_link_kin(h->stream, soa, h->d_frames, h->frames_host.link.n_chain, n, d_q, a3, d_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OH_OK;
-}
-
-extern "C" int oh_link_kin_device(oh_handle* h, int n, const void* d_q, const double* axis3, const oh_link_out* d_out_soa) {
-  double a3[3];
-  int rc = link_kin_check("oh_link_kin_device", h, n, d_q, axis3, d_out_soa, a3);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  return link_kin_launch(h, n, true, (const double*)d_q, a3, *d_out_soa);
-}
-
-extern "C" int oh_link_kin(oh_handle* h, int n, const double* q, const double* axis3, const oh_link_out* out) {
-  double a3[3];
-  int rc = link_kin_check("oh_link_kin", h, n, q, axis3, out, a3);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  const int ndof = h->frames_host.link.ndof;
-  double* const host[7] = {out->pos, out->rot, out->quat, out->rpy, out->axis, out->Jg, out->Ja};
-  const size_t comps[7] = {3, 9, 4, 3, 3, 6 * (size_t)ndof, 6 * (size_t)ndof};
-  const size_t b_q = sizeof(double) * ndof * (size_t)n;
-  double* d_q;
-  double* dev[7] = {};
-  rc = stage_carve(h, [&](Carver c) {
-    d_q = c.take<double>(ndof * (size_t)n);
-    for (int i = 0; i < 7; ++i)
-      if (host[i]) dev[i] = c.take<double>(comps[i] * (size_t)n);
-    return c.bytes();
-  });
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(d_q, q, b_q, hipMemcpyHostToDevice));
-  const oh_link_out d_out{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
-  rc = link_kin_launch(h, n, false, d_q, a3, d_out);
-  if (rc) return rc;
-  for (int i = 0; i < 7; ++i)
-    if (host[i]) HIPCHK(hipMemcpy(host[i], dev[i], sizeof(double) * comps[i] * (size_t)n, hipMemcpyDeviceToHost));
   return OH_OK;
 }
 
@@ -2505,183 +1276,6 @@ extern "C" void oh_destroy(oh_handle* h) {
   if (h) delete h;  // ~oh_handle
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Multi-GPU: one process per GPU, instances sharded by the host, no data-path collective.  The single exchange of a job is the
-// broadcast of the URDF-derived constants from one rank; the library owns the RCCL communicator for it (and for the
-// barrier / MAX / SUM reductions a benchmark harness needs), so a ctypes host needs no other GPU runtime.  librccl is opened on first
-// use: single-GPU processes never load it.
-// ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct RcclApi {
-  void* lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*Broadcast)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;  // optional (oh_comm_allgather)
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;     // optional
-  ncclResult_t (*CommUserRank)(const ncclComm_t, int*) = nullptr;  // optional
-};
-RcclApi g_rccl;
-ncclComm_t g_comm = nullptr;
-int g_comm_rank = -1, g_comm_world = 0, g_comm_device = 0;
-hipStream_t g_comm_stream = nullptr;
-double* g_comm_scratch = nullptr;  // device, 2 doubles
-
-int rccl_load() {
-  if (g_rccl.lib) return OH_OK;
-  void* lib = nullptr;
-  for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-    lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-    if (lib) break;
-  }
-  if (!lib) return fail(OH_ERR_HIP, std::string("oh_comm: cannot open librccl: ") + dlerror());
-  RcclApi a;
-  a.lib = lib;
-  a.GetUniqueId = (decltype(a.GetUniqueId))dlsym(lib, "ncclGetUniqueId");
-  a.CommInitRank = (decltype(a.CommInitRank))dlsym(lib, "ncclCommInitRank");
-  a.CommDestroy = (decltype(a.CommDestroy))dlsym(lib, "ncclCommDestroy");
-  a.Broadcast = (decltype(a.Broadcast))dlsym(lib, "ncclBroadcast");
-  a.AllReduce = (decltype(a.AllReduce))dlsym(lib, "ncclAllReduce");
-  a.AllGather = (decltype(a.AllGather))dlsym(lib, "ncclAllGather");
-  a.GetErrorString = (decltype(a.GetErrorString))dlsym(lib, "ncclGetErrorString");
-  a.CommCount = (decltype(a.CommCount))dlsym(lib, "ncclCommCount");
-  a.CommUserRank = (decltype(a.CommUserRank))dlsym(lib, "ncclCommUserRank");
-  if (!a.GetUniqueId || !a.CommInitRank || !a.CommDestroy || !a.Broadcast || !a.AllReduce || !a.GetErrorString) {
-    dlclose(lib);
-    return fail(OH_ERR_HIP, "oh_comm: librccl lacks an expected symbol");
-  }
-  g_rccl = a;
-  return OH_OK;
-}
-int rccl_fail(const char* what, ncclResult_t r) { return fail(OH_ERR_HIP, std::string(what) + ": " + g_rccl.GetErrorString(r)); }
-#define RCCLCHK(expr)                                  \
-  do {                                                 \
-    ncclResult_t _r = (expr);                          \
-    if (_r != ncclSuccess) return rccl_fail(#expr, _r); \
-  } while (0)
-}  // namespace
-
-extern "C" int oh_comm_unique_id(char* id) {
-  if (!id) return fail(OH_ERR_INVALID, "oh_comm_unique_id: null");
-  static_assert(OH_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
-  if (const int rc = rccl_load()) return rc;
-  ncclUniqueId u;
-  RCCLCHK(g_rccl.GetUniqueId(&u));
-  memcpy(id, u.internal, OH_COMM_ID_BYTES);
-  return OH_OK;
-}
-
-extern "C" int oh_comm_init(int rank, int world, const char* id) {
-  if (!id || world < 1 || rank < 0 || rank >= world) return fail(OH_ERR_INVALID, "oh_comm_init: bad rank / world / id");
-  if (g_comm) return fail(OH_ERR_STATE, "oh_comm_init: this process already holds a communicator");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_comm_init: no HIP device available (this library has no CPU path)");
-  if (const int rc = rccl_load()) return rc;
-  HIPCHK(hipGetDevice(&g_comm_device));  // the device selected with oh_set_device
-  ncclUniqueId u;
-  memcpy(u.internal, id, OH_COMM_ID_BYTES);
-  HIPCHK(hipStreamCreate(&g_comm_stream));
-  // (oh_chain-sized: the broadcast of the constants lands here first and is validated before a handle adopts it)
-  if (hipMalloc((void**)&g_comm_scratch, 2 * sizeof(double) + sizeof(oh_chain)) != hipSuccess) {
-    hipStreamDestroy(g_comm_stream);
-    g_comm_stream = nullptr;
-    return fail(OH_ERR_HIP, "oh_comm_init: scratch allocation failed");
-  }
-  const ncclResult_t ir = g_rccl.CommInitRank(&g_comm, world, u, rank);
-  if (ir != ncclSuccess) {  // a retry must not leak the stream and the scratch
-    g_comm = nullptr;
-    hipFree(g_comm_scratch);
-    g_comm_scratch = nullptr;
-    hipStreamDestroy(g_comm_stream);
-    g_comm_stream = nullptr;
-    return rccl_fail("ncclCommInitRank", ir);
-  }
-  g_comm_rank = rank;
-  g_comm_world = world;
-  return OH_OK;
-}
-
-extern "C" int oh_comm_destroy(void) {
-  if (!g_comm) return OH_OK;
-  hipSetDevice(g_comm_device);
-  hipStreamSynchronize(g_comm_stream);
-  g_rccl.CommDestroy(g_comm);
-  g_comm = nullptr;
-  hipFree(g_comm_scratch);
-  g_comm_scratch = nullptr;
-  hipStreamDestroy(g_comm_stream);
-  g_comm_stream = nullptr;
-  g_comm_rank = -1;
-  g_comm_world = 0;
-  return OH_OK;
-}
-
-static int comm_allreduce(double* value, ncclRedOp_t op, const char* who) {
-  if (!value) return fail(OH_ERR_INVALID, std::string(who) + ": null");
-  if (!g_comm) return fail(OH_ERR_STATE, std::string(who) + ": call oh_comm_init first");
-  HIPCHK(hipSetDevice(g_comm_device));
-  HIPCHK(hipMemcpyAsync(g_comm_scratch, value, sizeof(double), hipMemcpyHostToDevice, g_comm_stream));
-  RCCLCHK(g_rccl.AllReduce(g_comm_scratch, g_comm_scratch + 1, 1, ncclFloat64, op, g_comm, g_comm_stream));
-  HIPCHK(hipMemcpyAsync(value, g_comm_scratch + 1, sizeof(double), hipMemcpyDeviceToHost, g_comm_stream));
-  HIPCHK(hipStreamSynchronize(g_comm_stream));
-  return OH_OK;
-}
-extern "C" int oh_comm_allreduce_max(double* value) { return comm_allreduce(value, ncclMax, "oh_comm_allreduce_max"); }
-extern "C" int oh_comm_allreduce_sum(double* value) { return comm_allreduce(value, ncclSum, "oh_comm_allreduce_sum"); }
-extern "C" int oh_comm_barrier(void) {
-  double one = 1.0;
-  return comm_allreduce(&one, ncclSum, "oh_comm_barrier");
-}
-
-extern "C" int oh_comm_broadcast_constants(oh_handle* h, int root) {
-  if (!h) return fail(OH_ERR_INVALID, "oh_comm_broadcast_constants: null handle");
-  if (!g_comm) return fail(OH_ERR_STATE, "oh_comm_broadcast_constants: call oh_comm_init first");
-  if (root < 0 || root >= g_comm_world) return fail(OH_ERR_INVALID, "oh_comm_broadcast_constants: bad root");
-  if (!h->d_chain) return fail(OH_ERR_STATE, "oh_comm_broadcast_constants: this handle takes no kinematic constants");
-  if (g_comm_rank == root && !h->have_chain) return fail(OH_ERR_STATE, "oh_comm_broadcast_constants: the root must call oh_set_constants first");
-  HIPCHK(hipSetDevice(h->device));
-  // one ncclBroadcast of the oh_chain block (2952 B) on the handle's stream: out of the root's constants buffer, into a scratch block on the
-  // other ranks -- a chain this handle rejects (wrong ndof, unsupported joint) must not have replaced its constants already
-  unsigned char* const land = (unsigned char*)(g_comm_scratch + 2);
-  RCCLCHK(g_rccl.Broadcast(h->d_chain, g_comm_rank == root ? (void*)h->d_chain : (void*)land, sizeof(oh_chain), ncclUint8, root, g_comm, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (g_comm_rank != root) {
-    oh_chain tmp;
-    HIPCHK(hipMemcpy(&tmp, land, sizeof(oh_chain), hipMemcpyDeviceToHost));
-    if (const int rc = validate_chain(h, tmp)) return rc;
-    HIPCHK(hipMemcpy(h->d_chain, land, sizeof(oh_chain), hipMemcpyDeviceToDevice));
-    adopt_chain(h, tmp);
-  }
-  return OH_OK;
-}
-
-// The optional gather of SURVEY 8(e): every rank contributes `bytes` bytes of a device buffer (objectives, statuses, or whole solutions of its shard) and
-// receives all ranks' blocks in rank order -- one ncclAllGather over xGMI on the communicator's stream, after the solves; never part of the data path.
-extern "C" int oh_comm_allgather(const void* d_send, void* d_recv, size_t bytes) {
-  if (!d_send || !d_recv || bytes == 0) return fail(OH_ERR_INVALID, "oh_comm_allgather: null buffer or zero size");
-  if (!g_comm) return fail(OH_ERR_STATE, "oh_comm_allgather: call oh_comm_init first");
-  if (!g_rccl.AllGather) return fail(OH_ERR_HIP, "oh_comm_allgather: librccl lacks ncclAllGather");
-  HIPCHK(hipSetDevice(g_comm_device));
-  RCCLCHK(g_rccl.AllGather(d_send, d_recv, bytes, ncclUint8, g_comm, g_comm_stream));
-  HIPCHK(hipStreamSynchronize(g_comm_stream));
-  return OH_OK;
-}
-
-// world size and rank as RCCL sees them (a harness prints them to prove the communicator spans the job)
-extern "C" int oh_comm_info(int* rank, int* world) {
-  if (!g_comm) return fail(OH_ERR_STATE, "oh_comm_info: call oh_comm_init first");
-  int r = -1, w = 0;
-  if (g_rccl.CommUserRank) RCCLCHK(g_rccl.CommUserRank(g_comm, &r)); else r = g_comm_rank;
-  if (g_rccl.CommCount) RCCLCHK(g_rccl.CommCount(g_comm, &w)); else w = g_comm_world;
-  if (rank) *rank = r;
-  if (world) *world = w;
-  return OH_OK;
-}
-
 extern "C" int oh_get_constants(oh_handle* h, oh_chain* out) {
   if (!h || !out) return fail(OH_ERR_INVALID, "oh_get_constants: null argument");
   if (!h->have_chain) return fail(OH_ERR_STATE, "oh_get_constants: no constants set");
@@ -2697,17 +1291,6 @@ static bool spec_applies(const oh_handle* h) {
 static bool spec_tail_vel_applies(const oh_handle* h) {
   return h->desc.kind == OH_PROBLEM_FIGURE_EIGHT && h->have_chain && h->desc.lock_orientation && h->have_guards && !h->chain_host.has_lead &&
          (h->guards.limits || h->guards.vel_limits) && h->guards.n_links == 0 && h->sch.tail_vel;
-}
-static int specialize_fk(oh_handle* h) {
-  if (h->fk_spec) return OH_OK;
-  std::string err;
-  const FkSpec* sp = nullptr;
-  if (oh_jit_fkjac(h->chain_host, &sp, &err)) {
-    h->fk_spec_failed = true;
-    return fail(OH_ERR_HIP, "oh_specialize: " + err);
-  }
-  h->fk_spec = sp;
-  return OH_OK;
 }
 extern "C" int oh_specialize(oh_handle* h) {
   if (!h) return fail(OH_ERR_INVALID, "oh_specialize: null handle");
@@ -2765,13 +1348,13 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
     *value = h->P.zc;
   } else if (n == "tail_threshold") *value = h->sch.tail_threshold;
   else if (n == "specialized") *value = h->spec ? 1 : 0;
-  else if (n == "tape_wave") *value = h->tape_wave.ready ? (h->tape_wave.hist_lds ? 2 : 1) : 0;
-  else if (n == "tape_regs_lds") *value = h->tape_wave.ready && h->tape_wave.reg_lds ? 1 : 0;
-  else if (n == "tape_jit_lds") *value = h->tape_phi_lds;
-  else if (n == "tape_metric") *value = (h->TP.h0 && h->TP.lbfgs > 0) ? 1 : 0;
-  else if (n == "tape_levels") *value = h->tape_wave.n_levels;
-  else if (n == "tape_passes") *value = h->tape_wave.n_fw_pass + h->tape_wave.n_rv_pass;
-  else if (n == "qp_block") *value = h->qp_last_block;
+  else if (n == "tape_wave") *value = h->tape.wave.ready ? (h->tape.wave.hist_lds ? 2 : 1) : 0;
+  else if (n == "tape_regs_lds") *value = h->tape.wave.ready && h->tape.wave.reg_lds ? 1 : 0;
+  else if (n == "tape_jit_lds") *value = h->tape.phi_lds;
+  else if (n == "tape_metric") *value = (h->tape.P.h0 && h->tape.P.lbfgs > 0) ? 1 : 0;
+  else if (n == "tape_levels") *value = h->tape.wave.n_levels;
+  else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;
+  else if (n == "qp_block") *value = h->qp.last_block;
   else if (n == "free_sweep") *value = h->free_sweep_last;
   else if (n == "free_sweeps_used") *value = h->free_sweeps_used;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);

@@ -1,0 +1,47 @@
+// Host side of the inverse-kinematics family (OH_PROBLEM_IK): creation and the solve.  State: oh_handle::ik.
+#include "oh_handle.h"
+
+extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
+  if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_ik: null argument");
+  *out = nullptr;
+  if (desc->ndof < 2 || desc->ndof > 8) return fail(OH_ERR_INVALID, "oh_create_ik: kernels are instantiated for 2 ... 8 actuated joints");
+  if (!(desc->w_nominal > 0.0)) return fail(OH_ERR_INVALID, "oh_create_ik: w_nominal must be positive");
+  for (int i = 0; i < desc->ndof; ++i)
+    if (!(desc->q_lo[i] <= desc->q_up[i])) return fail(OH_ERR_INVALID, "oh_create_ik: q_lo must not exceed q_up");
+  int rc = OH_OK;
+  oh_handle* h = open_handle("oh_create_ik", OH_PROBLEM_IK, 1, desc->ndof, OPEN_CHAIN, &rc);
+  if (!h) return rc;
+  oh_ik_desc& d = h->ik.desc;
+  d = *desc;
+  if (d.max_iter <= 0) d.max_iter = 200;
+  if (!(d.tol > 0.0)) d.tol = 1e-6;
+  if (!(d.tol_feas > 0.0)) d.tol_feas = 1e-9;
+  if (!(d.rho0 > 0.0)) d.rho0 = 100.0 * d.w_nominal;
+  *out = h;
+  return OH_OK;
+}
+
+int ik_solve_device(oh_handle* h, const Solve& a) {
+  if (!h->have_chain) return fail(OH_ERR_STATE, "oh_solve_device: call oh_set_constants first");
+  if (!solver_chain_ok(h->chain_host))
+    return fail(OH_ERR_INVALID, "oh_solve_device: the solver needs a chain that covers every model joint in order");
+  HIPCHK(hipSetDevice(h->device));
+  const oh_ik_desc& d = h->ik.desc;
+  const int N = d.ndof;
+  HIPCHK(h->ik.mult.reserve((3 + 2 * (size_t)N) * a.B));
+  IkParams P{};
+  P.ndof = N;
+  P.max_iter = d.max_iter;
+  P.w = d.w_nominal;
+  P.tol = d.tol;
+  P.tol_feas = d.tol_feas;
+  P.rho0 = d.rho0;
+  for (int i = 0; i < N; ++i) {
+    P.lo[i] = d.q_lo[i];
+    P.up[i] = d.q_up[i];
+  }
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  if (!oh_launch_ik_solve(h->stream, h->d_chain, P, a.B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, h->ik.mult))
+    return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
+  return finish_solve(h, 1);
+}

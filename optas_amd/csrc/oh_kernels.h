@@ -1,4 +1,4 @@
-// Shared host/device declarations between oh_kernels.hip (device code) and oh_api.hip (C ABI).
+// Shared host/device declarations between the kernel sources (device code) and the host sources of the C ABI (oh_api.hip, oh_api_<family>.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void k_carry_scatter(FigParams P, FigBuffers D
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers (called from oh_api.hip)
+// launchers (called from the trajectory solve of oh_api.hip)
 // ---------------------------------------------------------------------------------------------
 template <int N>
 static void launch_setup_t(hipStream_t s, const FigParams& P, const FigBuffers& D, const double* x0, const double* p) {

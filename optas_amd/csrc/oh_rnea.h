@@ -7,7 +7,7 @@
 
 #include "oh_device.h"
 
-// launchers of oh_rnea.hip (called from oh_api.hip); false: unsupported number of bodies
+// launchers of oh_rnea.hip (called from oh_api_kin.hip); false: unsupported number of bodies
 bool oh_launch_rnea(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, double* tau);
 bool oh_launch_rnea_jac(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, double* J);
 bool oh_launch_rnea_hess(hipStream_t s, const oh_dynamics* d_dyn, int nbodies, int n, const double* q, const double* qd, const double* qdd, const double* c, double* H);

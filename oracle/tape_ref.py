@@ -181,7 +181,7 @@ SCALE_FIRST = True  # dense form: the first pair scales the identity before upda
 def solve_tape_al(tape, x0, p, tol=1e-6, tol_feas=1e-9, max_iter=2000, rho0=10.0, lbfgs=None, trace=None, h0=None):
     """Generic NLP on a tape: min f s.t. rows[:n_ineq] >= 0, rows[n_ineq:] = 0.  Augmented Lagrangian (PHR for the inequality rows)
     minimised by BFGS with Armijo backtracking -- the dense inverse Hessian up to 48 variables, the limited-memory form with `lbfgs` = 12 pairs
-    beyond, as oh_api.hip:tape_params chooses; one forward + one reverse sweep per evaluation.  Port of k_tape_solve.  h0: the initial metric of the
+    beyond, as oh_api_tape.hip:tape_params chooses; one forward + one reverse sweep per evaluation.  Port of k_tape_solve.  h0: the initial metric of the
     limited-memory form (oh_tape_set_metric; the product passes tape.py:quadratic_cost_metric), ignored by the dense form."""
     n, ni, ne = tape.nx, tape.n_ineq, tape.n_eq
     lbfgs = (12 if n > 48 else 0) if lbfgs is None else lbfgs

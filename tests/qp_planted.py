@@ -213,7 +213,7 @@ def assert_certificate(cert, kkt=None):
         assert abs(float(kkt[0]) - cert["stat"]) <= cert["stat_bound"], (kkt, cert)
 
 
-# ---- which kernel a solve runs: restatement of oh_launch_qp_solve (oh_qp.hip) and of Q.np / Q.nwork (oh_api.hip) --------------------------
+# ---- which kernel a solve runs: restatement of oh_launch_qp_solve (oh_qp.hip) and of Q.np / Q.nwork (oh_api_qp.hip) -----------------------
 def qp_sizes(n, m, me):
     np_ = n * n + n + m * n + m + me * n + me
     nwork = n + 2 * m + me + n * n + 2 * n + 2 * m + me * n + me * me + me + n

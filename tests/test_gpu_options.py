@@ -268,3 +268,39 @@ def test_tolerance_option_of_an_existing_handle(hip_lib, monkeypatch):
     again = be.solve(x0, qc)
     assert np.array_equal(again.x, loose.x) and np.array_equal(again.iters, loose.iters)
     be.close()
+
+
+@pytest.mark.parametrize("path", ["split_device", "pipelined_host"])
+def test_split_and_pipelined_solves_with_null_optional_outputs_equal_the_full_call(hip_lib, monkeypatch, path):
+    """f, kkt and iters are optional outputs of oh_solve / oh_solve_device.  A solve in parts offsets every output pointer it was given (a null must stay
+    null: csrc/oh_handle.h:Solve::part), a pipelined one downloads only what was asked for: x, status and the multipliers of such a call are those of the
+    call with every output, bit for bit.  split_device: B = 8192 from device buffers with split_min = 8192 (two parts of 4096); pipelined_host: B = 2500
+    from host buffers with pipe_chunk = 1024 (chunks of 1024, 1024, 452 on lanes 0, 1, 0)."""
+    monkeypatch.delenv("OH_DEBUG_OPTIONS", raising=False)
+    lib = _lib.load()
+    B, opts = (8192, {"split_min": 8192, "streams": 2}) if path == "split_device" else (2500, {"pipe_chunk": 1024})
+    x0, qc = bench.make_inputs(B, 13)
+    be = _backend().set_options(opts)
+    be.specialize()  # (both calls with the kernels compiled for the chain: left to itself, lane 0 of a pipelined solve adopts a cached object during the first call and its peer only from the second call on)
+
+    def solve(full):
+        x, f, kkt = np.empty_like(x0), np.empty(B), np.empty((B, 3))
+        iters, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        if path == "pipelined_host":
+            opt = [_lib._ptr(a) if full else None for a in (f, kkt, iters)]
+            _lib.check(lib.oh_solve(be.handle, B, _lib._ptr(x0), _lib._ptr(qc), _lib._ptr(x), opt[0], opt[1], opt[2], _lib._ptr(status)), "oh_solve")
+        else:
+            d_x0, d_p = _lib.DeviceBuffer(x0.nbytes).upload(x0), _lib.DeviceBuffer(qc.nbytes).upload(qc)
+            d_x, d_st = _lib.DeviceBuffer(x0.nbytes), _lib.DeviceBuffer(B * 4)
+            d_f, d_k, d_it = (_lib.DeviceBuffer(B * 8), _lib.DeviceBuffer(B * 24), _lib.DeviceBuffer(B * 4)) if full else (None, None, None)
+            be.solve_device(B, d_x0, d_p, d_x, d_f, d_k, d_it, d_st)
+            x, status = d_x.download(np.float64, x0.shape), d_st.download(np.int32, (B,))
+            if full:
+                f, kkt, iters = d_f.download(np.float64, (B,)), d_k.download(np.float64, (B, 3)), d_it.download(np.int32, (B,))
+        return x, f, kkt, iters, status, be.multipliers(B)
+
+    x, f, kkt, iters, status, lam = solve(True)
+    assert (status == 0).all() and np.isfinite(f).all() and (kkt[:, 0] <= 1e-6).all() and (iters > 0).all()
+    x_n, _, _, _, status_n, lam_n = solve(False)
+    assert np.array_equal(x_n, x) and np.array_equal(status_n, status) and np.array_equal(lam_n, lam)
+    be.close()
