@@ -441,8 +441,8 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *                         (0: never; invariant_move_slim / invariant_move_live (1): arrays no kernel carries across launches, and the slot of the
  *                         judged trial, stay behind), and a large batch is still solved in parts on two streams (invariant_split, 1).
  *                         Costs 1.3 x device time at 262 144 instances (3.0 x without the moving compaction).
- *   tail_threshold (16384), tail_vel (1), tail_vel_threshold, compaction (1), compact_frac (0.97), compact_sort (1), compact_carry (1), compact_fused (1),
- *   sparse_check_below (2048), check_every (1), fuse_couple (1), lg_split (1), row_pad (13)            -- figure-eight family scheduling
+ *   tail_threshold (16384), tail_vel (1), tail_vel_threshold, compaction (1), compact_frac (0.97), compact_sort (1), compact_carry (1), compact_fused (2: see out[11..13] of oh_get_timing; 1: round-7 sequence; 0: gather),
+ *   lean_count (0; 1: the lean compactions count the survivors whose gradient moved, out[12]), sparse_check_below (2048), check_every (1), fuse_couple (1), lg_split (1), row_pad (13)            -- figure-eight family scheduling
  *   streams (2), split_min (65536): a batch of the plain orientation-locked family of at least split_min instances is solved in `streams` contiguous parts,
  *       each on a HIP stream and a host thread of its own (results at every index = the part solved as a batch of its own); 1: one stream
  *       (the torque-MPC family likewise from tq_split_min (1024) instances on: its answers do not depend on the batch, so the split is invisible)
@@ -557,9 +557,11 @@ int oh_link_kin_device(oh_handle* h, int N, const void* d_q, const double* axis3
    of instances still running (a launch touches only those: work actually done), out[7]=batch compactions,
    out[8]=couple kernel total ms, out[9]=rejected steps (summed over instances), out[10]=iterations run
    inside the persistent tail kernel (summed over instances).
+   Lean carried compactions (compact_fused = 2): out[11]=instances whose rejected trial sent them through the rescue list,
+   out[12]=survivors whose Lagrangian gradient moved, out[13]=survivors moved.  out must hold 14 doubles.
    out[0..3] need oh_set_profiling(h,1) (one hipEventRecord after every kernel). */
 int oh_set_profiling(oh_handle* h, int enable);
-int oh_get_timing(oh_handle* h, double* out11);
+int oh_get_timing(oh_handle* h, double* out14);
 
 /* Run-time specialisation.  The reference's own speed comes from code generated for one problem: CasADi turns the robot model into a
    straight-line SX program with the URDF constants folded in (models.py:826-868 builds the chain walk symbolically, solver.py:333-398

@@ -77,7 +77,7 @@ class _SolveMixin(_OptionsMixin):
         )
 
     def solve_ms(self) -> float:
-        out = (C.c_double * 11)()
+        out = (C.c_double * 14)()
         _lib.check(_lib.load().oh_get_timing(self._h, out), "oh_get_timing")
         return out[4]
 
@@ -516,7 +516,7 @@ class TorqueBackend(_SolveMixin):
         return states, tau0, f, iters, status
 
     def timing(self) -> dict:
-        out = (C.c_double * 11)()
+        out = (C.c_double * 14)()
         _lib.check(_lib.load().oh_get_timing(self._h, out), "oh_get_timing")
         return {"solve_ms": out[4], "iterations_launched": int(out[5]), "work_instances": out[6], "eval_ms": out[0], "step_ms": out[2]}  # (eval / step: profiled solves only)
 
@@ -689,7 +689,7 @@ class FigureEightBackend(_OptionsMixin):
         ch = getattr(self, "_chunked", None)
         if ch is not None:
             return dict(ch["timing"])
-        out = (C.c_double * 11)()
+        out = (C.c_double * 14)()
         _lib.check(_lib.load().oh_get_timing(self._h, out), "oh_get_timing")
         return {
             "eval_ms": out[0],
@@ -703,6 +703,9 @@ class FigureEightBackend(_OptionsMixin):
             "couple_ms": out[8],
             "rejected_steps": int(out[9]),
             "tail_iterations": int(out[10]),
+            "rescued_instances": int(out[11]),
+            "gradient_lanes_moved": int(out[12]),
+            "lanes_moved": int(out[13]),
         }
 
     def fk_jac_soa_device(self, n: int, d_q, d_pose, d_J) -> None:

@@ -43,7 +43,7 @@ struct FieldOpt {
 static const FieldOpt FIELD_OPTS[] = {
     {"tail_threshold", &Sched::tail_threshold}, {"free_pcr_max", &Sched::free_pcr_max}, {"compaction", &Sched::compaction, nullptr, true},
     {"compact_frac", nullptr, &Sched::compact_frac}, {"compact_sort", &Sched::compact_sort}, {"compact_carry", &Sched::compact_carry},
-    {"compact_fused", &Sched::compact_fused, nullptr, true},
+    {"compact_fused", &Sched::compact_fused},
     {"tail_vel", &Sched::tail_vel}, {"lg_split", &Sched::lg_split}, {"tail_vel_threshold", &Sched::tail_vel_threshold},
     {"fuse_couple", &Sched::fuse_couple, nullptr, true}, {"sparse_check_below", &Sched::sparse_check_below}, {"specialize", &Sched::specialize},
     {"tq_check", &Sched::tq_check},
@@ -153,7 +153,7 @@ oh_handle* open_handle(const std::string& who, const int kind, const int T, cons
   bool ok = hipStreamCreate(&h->stream) == hipSuccess;
   for (hipEvent_t* e : {&h->ev0, &h->ev1, &h->evt0, &h->evt1}) ok = ok && hipEventCreate(e) == hipSuccess;
   if ((want & OPEN_CHAIN) && ok) ok = h->d_chain.reserve(1) == hipSuccess;
-  if ((want & OPEN_FLAG) && ok) ok = h->h_flag.reserve(1) == hipSuccess;
+  if ((want & OPEN_FLAG) && ok) ok = h->h_flag.reserve(16) == hipSuccess;  // (the look of the lean sequence brings the list counters along)
   if (!ok) {
     delete h;
     *rc = fail(OH_ERR_HIP, who + (want ? ": stream/event/allocation failed" : ": stream/event creation failed"));
@@ -165,7 +165,7 @@ oh_handle* open_handle(const std::string& who, const int kind, const int T, cons
 // every solve reports counters of its own only (oh_get_timing)
 void reset_counters(oh_handle* h) {
   for (double& t : h->timing) t = 0.0;
-  h->timing_couple = h->rejects = h->tail_iters = 0.0;
+  h->timing_couple = h->rejects = h->tail_iters = h->rescued = h->grad_moved = h->lanes_moved = 0.0;
 }
 // the tail every solve shares: wait for the launches since ev0, report a launch error, time the solve ([4]) and count its launches ([5])
 int finish_solve(oh_handle* h, const double launched) {
@@ -621,7 +621,7 @@ static int ensure_peers(oh_handle* h, const int n) {
 static int solve_device(oh_handle* h, const Solve& a, bool may_fan_out, LastSolve* rec);
 // counters of the solves one lane ran, merged into the handle's timing by fan_out
 struct Tally {
-  double launched = 0, work = 0, compactions = 0, rejects = 0, tails = 0;
+  double launched = 0, work = 0, compactions = 0, rejects = 0, tails = 0, rescued = 0, grad_moved = 0, lanes_moved = 0;
 };
 // one solve of a lane: never fans out again (the lanes ARE the streams)
 static int lane_solve(oh_handle* q, Tally& t, const Solve& a) {
@@ -631,6 +631,7 @@ static int lane_solve(oh_handle* q, Tally& t, const Solve& a) {
   t.compactions += q->timing[7];
   t.rejects += q->rejects;
   t.tails += q->tail_iters;
+  t.rescued += q->rescued; t.grad_moved += q->grad_moved; t.lanes_moved += q->lanes_moved;
   return OH_OK;
 }
 // Runs work(lane, handle, tally) on n lanes: lane 0 is the handle itself on the calling thread, lanes 1 .. n-1 its peers, each on a host thread bound
@@ -672,6 +673,7 @@ static int fan_out(oh_handle* h, const int n, Work&& work) {
     h->timing[7] += t.compactions;
     h->rejects += t.rejects;
     h->tail_iters += t.tails;
+    h->rescued += t.rescued; h->grad_moved += t.grad_moved; h->lanes_moved += t.lanes_moved;
   }
   return OH_OK;
 }
@@ -703,6 +705,7 @@ struct Traj {
   double *x, *f, *kkt;
   int *iters, *status;
   int launched, compactions;
+  double lanes_moved;  // survivors of the lean carried compactions
   size_t ne;  // profiling events recorded
 };
 // The one place that chooses the sweep of a position-tracking launch of nb instances (the launchers in oh_free.hip take the choice).  start: nb is
@@ -744,14 +747,24 @@ static int mark(oh_handle* h, Traj& r, const int tag, const size_t room = 2) {
 static bool check_after(const oh_handle* h, const Traj& r, const int it, const bool tail_ok) {
   return (it + 1) % ((!tail_ok && r.check_every == 1 && h->D.B <= h->sch.sparse_check_below) ? 8 : r.check_every) == 0;
 }
-// the running count the last sweep left, when the host looks (check); -1 otherwise
-static int look(oh_handle* h, const bool check, int* nrun) {
+// the running count the last sweep left, when the host looks (check); -1 otherwise.  lists (may be null): the same transfer also brings the lengths of
+// the two deferral lists and of the rescue list -- n_running, n_new and the counter block follow each other in the pool (layout_fig)
+struct ListCounts { int defer[2], rescue; };
+static int look(oh_handle* h, const bool check, int* nrun, ListCounts* lists = nullptr) {
   *nrun = -1;
   if (!check) return OH_OK;
   hipStream_t s = h->stream;
-  HIPCHK(hipMemcpyAsync(h->h_flag, h->D.n_running, sizeof(int), hipMemcpyDeviceToHost, s));
+  const FigBuffers& D = h->D;
+  const size_t span = (size_t)((const char*)(D.n_rescue + 1) - (const char*)D.n_running);
+  const bool wide = lists && (const char*)D.n_defer > (const char*)D.n_running && span <= 16 * sizeof(int);
+  HIPCHK(hipMemcpyAsync(h->h_flag, D.n_running, wide ? span : sizeof(int), hipMemcpyDeviceToHost, s));
+  if (lists && !wide) HIPCHK(hipMemcpyAsync(h->h_flag.p + 1, D.n_defer, 3 * sizeof(int), hipMemcpyDeviceToHost, s));  // (n_defer[2] and n_rescue are adjacent)
   HIPCHK(hipStreamSynchronize(s));
   *nrun = *h->h_flag;
+  if (lists) {
+    const int* c = wide ? h->h_flag.p + (D.n_defer - D.n_running) : h->h_flag.p + 1;
+    *lists = ListCounts{{c[0], c[1]}, c[2]};
+  }
   return OH_OK;
 }
 // results of finished instances (only_done) or of all: x through the library's LDS transpose, scalars and multipliers through the kernel compiled
@@ -821,7 +834,7 @@ static int traj_prologue(oh_handle* h, Traj& r, const double* x0) {
     }
   }
   HIPCHK(hipEventRecord(h->ev0, s));
-  HIPCHK(hipMemsetAsync(h->D.work, 0, 4 * sizeof(unsigned long long), s));  // (work[0..2] and the two deferral counters)
+  HIPCHK(hipMemsetAsync(h->D.work, 0, 7 * sizeof(unsigned long long), s));  // (work[0..2], the two deferral counters, the rescue list's and its two sums)
   if (!oh_launch_setup(s, r.N, h->P, h->D, x0, r.p)) return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
   if (r.guarded) oh_launch_setup_guards(s, r.N, h->P, h->D, h->GP, h->GB, r.p);
   h->prof_tags.clear();
@@ -866,6 +879,13 @@ static int locked_loop(oh_handle* h, Traj& r) {
   const bool carry = h->sch.compaction && h->sch.compact_carry && (size_t)h->desc.T * ((N - 3) * (N - 2) / 2) >= 22 && !r.guarded && !r.lead;
   const double inv_frac = optv(h, "invariant_compact_frac");
   const bool inv_move = r.invariant && !r.lead && inv_frac > 0.0, restart = h->sch.compaction && !r.lead, restart_moves = r.guarded && optv(h, "compact_move_all") != 0.0;
+  // lean (compact_fused = 2; plain handles on the kernels compiled for the chain, hybrid or exact curvature): the moving retraction leaves the accepted
+  // knot behind and moves the gradient where it will be read (eval_unit<.., MOVE>), k_sweep_lists fetches the knots of the few instances that fall back to
+  // them, and the list-driven copies behind a sweep are launched after the look, only when their list is not empty
+  const bool lean = carry && r.spec && r.spec->retract_move && h->sch.compact_fused >= 2 && P.zc && P.hessian != OH_HESSIAN_GAUSS_NEWTON && !r.invariant;
+  D.lean = 0;
+  if (lean) HIPCHK(h->h_flag.reserve(16));  // (room for the wide look)
+  int rescue_slot = -1;  // >= 0: the slot of a lean compaction whose q[1 - slot] / q_spare[1] swap waits for the sweep (and the rescue) of its iteration
   int nrun = -1, carry_pending = 0;  // the running count at the last look (-1: none after the last iteration); > 0: a carried compaction to this many
   for (int it = 0; it < r.hard_cap; ++it) {
     if (nrun >= 0)  // host synced: do not bill the idle gap to the eval kernel
@@ -883,6 +903,7 @@ static int locked_loop(oh_handle* h, Traj& r) {
         // the new indices first (the scan reads status and stat, final since the last sweep; the retraction writes neither): the retraction compiled
         // for the chain then lays the free knots down where they go, and what is left to gather are the pinned knots and the scalars
         finalize(h, r, 1);
+        D.lean = lean ? (optv(h, "lean_count") != 0.0 ? 3 : 1) : 0;  // (from here on: the scan writes the inverse map, the sweep's head fills the rescue list)
         oh_launch_scan_running(s, D, h->sch.compact_sort);
         scanned = true;
         if (const int rc = mark(h, r, 0)) return rc;
@@ -890,9 +911,14 @@ static int locked_loop(oh_handle* h, Traj& r) {
         if (moved) {
           if (const int rc = mark(h, r, 4)) return rc;
           oh_launch_carry(s, N, P, D, 2, 0, slot);
+          if (lean) {
+            rescue_slot = slot;
+            r.lanes_moved += carry_pending;
+          }
         } else {
           (void)hipGetLastError();
           h->spec_move_failed = true;
+          D.lean = 0;
         }
       }
       if (!moved) {
@@ -907,7 +933,7 @@ static int locked_loop(oh_handle* h, Traj& r) {
       oh_launch_carry(s, N, P, D, 1, carry_pending, slot);
       // the knots were laid down densely in the spare arrays: they become q[] / Gfull[] for the launches that follow (no copy back)
       std::swap(D.q[slot], D.q_spare[0]);
-      std::swap(D.q[1 - slot], D.q_spare[1]);
+      if (rescue_slot < 0) std::swap(D.q[1 - slot], D.q_spare[1]);  // (lean: after the sweep -- the accepted knots are still in the old layout)
       if (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc) std::swap(D.Gfull[1 - slot], D.G_spare);
       D.B = carry_pending;
       carry_pending = 0;
@@ -921,10 +947,22 @@ static int locked_loop(oh_handle* h, Traj& r) {
     const bool check = check_after(h, r, it, tail_ok);  // (k_couple resets the running count)
     if (const int rc = mark(h, r, 3)) return rc;
     if (r.guarded) oh_launch_step_locked_guarded(s, N, P, D, GP, GB, slot);
-    else oh_launch_step(s, N, P, D, slot);
+    else oh_launch_step(s, N, P, D, slot, !lean);
     if (const int rc = mark(h, r, 2)) return rc;
     ++r.launched;
-    if (const int rc = look(h, check, &nrun)) return rc;
+    ListCounts lists{{0, 0}, 0};
+    if (const int rc = look(h, check, &nrun, lean ? &lists : nullptr)) return rc;
+    if (lean) {
+      // without a look: unconditionally, as the sweep's launcher does.  The consumer of one deferral list zeroes the other's counter: skipped only when both
+      // are zero (and the rescue list is empty: the next scan zeroes that counter)
+      const bool rescue = rescue_slot >= 0;
+      if (!check || lists.defer[0] || lists.defer[1] || (rescue && lists.rescue))
+        oh_launch_sweep_lists(s, N, P, D, slot, rescue, check ? std::max(lists.defer[slot], rescue ? lists.rescue : 0) : -1);
+      if (rescue) {
+        std::swap(D.q[1 - rescue_slot], D.q_spare[1]);  // free knots: the rescued instances'; pinned knots: k_carry_gather<REST>'s
+        rescue_slot = -1;
+      }
+    }
     if (nrun == 0) break;
     if (tail_ok && nrun > 0 && nrun <= tail_threshold) {
       // drain: compact the survivors and let one wavefront per instance finish them without further launches
@@ -995,7 +1033,7 @@ static int traj_epilogue(oh_handle* h, Traj& r) {
   h->D.B = r.B;
   if (r.guarded) oh_launch_guard_infeasible(s, r.N, h->P, h->D, h->GP, r.p, r.B, r.kkt, r.status);  // constant rows of the pinned knots
   if (const int frc = finish_solve(h, r.launched)) return frc;
-  unsigned long long work[3] = {0, 0, 0};
+  unsigned long long work[7] = {0, 0, 0, 0, 0, 0, 0};
   // (on the handle's own stream: a hipMemcpy is an operation of the legacy null stream and waits for the kernels of every other handle's stream -- the other
   //  part of a split solve, the other lane of a pipelined one)
   HIPCHK(hipMemcpyAsync(work, h->D.work, sizeof(work), hipMemcpyDeviceToHost, s));
@@ -1003,6 +1041,7 @@ static int traj_epilogue(oh_handle* h, Traj& r) {
   h->timing[6] = (double)work[0];
   h->rejects = (double)work[1];
   h->tail_iters = (double)work[2];
+  h->rescued = (double)work[5]; h->grad_moved = (double)work[6]; h->lanes_moved = r.lanes_moved;
   if (r.prof) {  // device time by tag (mark): evaluation (1 and 4), sweep, coupling; launches: evaluations (1), sweeps
     double ms[4] = {0, 0, 0, 0};
     int n[5] = {0, 0, 0, 0, 0};
@@ -1249,12 +1288,15 @@ extern "C" int oh_set_profiling(oh_handle* h, int enable) {
   h->profiling = enable != 0;
   return OH_OK;
 }
-extern "C" int oh_get_timing(oh_handle* h, double* out8) {
+extern "C" int oh_get_timing(oh_handle* h, double* out8) {  // (14 entries, see optas_hip.h)
   if (!h || !out8) return fail(OH_ERR_INVALID, "oh_get_timing: null argument");
   for (int i = 0; i < 8; ++i) out8[i] = h->timing[i];
   out8[8] = h->timing_couple;
   out8[9] = h->rejects;
   out8[10] = h->tail_iters;
+  out8[11] = h->rescued;
+  out8[12] = h->grad_moved;
+  out8[13] = h->lanes_moved;
   return OH_OK;
 }
 extern "C" int oh_event_timer_start(oh_handle* h) {

@@ -73,6 +73,10 @@ inline void layout_fig(Carver& c, FigBuffers& D, const int N, const int lock, co
   D.feas = c.take<double>(Bp);
   D.lam_h = c.take<double>((size_t)4 * T * Bp);
   D.lead = c.take<double>(per_t);  // lead-joint angles
+  // (the two index arrays of the lean carried compaction live in the room of lead[]: that sequence runs on chains without a lead joint only, whose
+  //  kernels never touch lead[], and T doubles per instance hold two ints for every T >= 1 -- no array is added, every recorded offset stays)
+  D.oldidx = D.lead ? (int*)D.lead : nullptr;
+  D.rescue_list = D.lead ? (int*)D.lead + Bp : nullptr;
   if (!lock) D.lam_h = nullptr;    // no quaternion rows, no multipliers to report (the room stays)
   D.cur = c.take<int>(Bp);
   D.first = c.take<int>(Bp);
@@ -87,6 +91,8 @@ inline void layout_fig(Carver& c, FigBuffers& D, const int N, const int lock, co
   D.n_new = c.take<int>(1);
   D.work = c.take<unsigned long long>(14);  // the counter block (8-byte aligned: 9 Bp + 2 ints lie before it, Bp a multiple of 64)
   D.n_defer = D.work ? (int*)(D.work + 3) : nullptr;  // (two ints inside the spare part of the counter block: zeroed with it at the start of a solve)
+  // (work[4]: the length of the rescue list; work[5], work[6]: instances rescued / instances whose gradient moved, summed over a solve)
+  D.n_rescue = D.work ? (int*)(D.work + 4) : nullptr;
   D.scan_blk = c.take<int>(8 * 1024);
   D.defer_list = c.take<int>(2 * (size_t)Bp);  // [2][Bp]
   c.take<int>(2);  // slack the pool has always had behind its last array

@@ -124,6 +124,27 @@ OH_DEV void load_householder(const double* __restrict__ Vs, const int Bp, const 
 // carried compaction.  D.newidx is final (the scan reads status and stat, which the previous sweep left), and the lane lays its knot down where
 // k_carry_gather would have moved it: the trial at newidx in q_spare[0], the accepted knot in q_spare[1], the Lagrangian gradient of the accepted
 // point in G_spare.  Nothing goes to q[slot]; the arithmetic is that of the plain retraction, so the values are k_carry_gather's bit for bit.
+// D.lean (compact_fused = 2, hybrid and exact curvature): only what a later launch reads at the new index moves.
+//  * The accepted knot stays behind (no store to q_spare[1]).  At the new index it is read only by an instance whose trial this iteration's sweep
+//    rejects (step_head: stale, restart from q[1 - slot]); such an instance enters D.rescue_list and k_sweep_lists fetches its knots from the old
+//    layout after the sweep, before the host swaps q[1 - slot] with q_spare[1].  Every other survivor, a restart lane (skip, first: accepted
+//    unconditionally, cur = slot) included, overwrites the entry with its next trial; an instance that finishes has accepted (cur = slot).
+//  * The gradient of the accepted point moves only on the lanes for which this iteration's evaluation computes `exact` with `have_G`: hybrid
+//    curvature, not a restart lane (k_carry_scatter gives those first = 1: fresh, have_G false), stat <= hyb_switch -- stat and first are what
+//    k_carry_scatter lays down at the new index.  Handles with hessian = exact move it on every lane as before.  The readers of Gfull[1 - slot]
+//    at the new index, and why none of them sees an entry that did not move:
+//      eval_unit<EVAL_ONLY> (Gpre)  loads it on every lane, uses it only inside `exact && have_G` (eval_knot): the moved lanes.
+//      couple_unit                  writes Gfull[slot] only; not part of the folded-coupling sequence anyway.
+//      step_instance_zc             sweeps on `cur`, which after the sweep's head is `slot` for every compacted instance (accepted, first or polish);
+//                                   a rejected one is stale and restarts without a sweep.
+//      k_defer_copy                 copies Gfull[1 - slot] of lanes that defer in this sweep; only exact curvature fails to factorise: moved lanes.
+//      knot_multipliers, tail_block, k_compact_gather / k_compact_scatter
+//                                   read Gfull[D.cur[b]].  An instance that ends in this sweep (converged, NUMERICAL, MAX_ITER: all after the head
+//                                   accepted, or a non-finite first evaluation) has cur = slot.  A running instance has cur = 1 - slot only after a
+//                                   stale rejection; the hand-over restarts it with first = 2 and it reads that gradient if stat <= hyb_switch,
+//                                   the very condition under which it moved (a rejection changes neither stat nor the gradient).
+//      the next moving retraction   reads Gfull[cur'] = Gfull[slot] (this evaluation's) of running lanes; of a lane that restarts after a stale
+//                                   rejection it would copy Gfull[1 - slot], which lean restart lanes do not move.
 template <int N, bool GUARD = false, bool LEAD = false, int MODE = EVAL_FUSED, bool ZC = false, bool SPH = true, bool MOVE = false>
 OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, const int b, const int t, const GuardParams* GPp = nullptr,
                       const GuardBuffers* GBp = nullptr) {
@@ -150,7 +171,9 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
   // MOVE: the knot's place in the dense batch (-1: finished), and whether the Lagrangian gradient travels (k_carry_gather's condition)
   int nb = 0;
   if constexpr (MOVE) nb = D.newidx[b];
-  const bool move_G = MOVE && (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc);
+  const bool lean = MOVE && D.lean != 0;
+  bool move_G = MOVE && (P.hessian != OH_HESSIAN_GAUSS_NEWTON || P.zc);
+  if (lean && P.hessian == OH_HESSIAN_HYBRID) move_G = !skip_b && first_b == 0 && stat_b <= P.hyb_switch;  // `exact && have_G` of the evaluation that follows
   double Gmv[N];  // MOVE: Gfull[cur] of the knot, requested with the other inputs and stored before the arithmetic starts
   constexpr bool EARLY = MODE == EVAL_ONLY || OH_RETRACT_PREFETCH;  // the generic retraction kernel sits at the register limit: it fetches
                                                                     // its knot data after the branch, as before
@@ -223,7 +246,7 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
       for (int j = 0; j < N; ++j) {
         const double v = D.q[slot][IDX(t, N, j)];
         D.q_spare[0][SPARE(j)] = v;
-        D.q_spare[1][SPARE(j)] = v;
+        if (!lean) D.q_spare[1][SPARE(j)] = v;
       }
       if (move_G) {
 #pragma unroll
@@ -263,8 +286,10 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
         }
       }
       if constexpr (MOVE) {  // the accepted knot before the step is added to it, and its gradient: out of the registers before the arithmetic starts
+        if (!lean) {
 #pragma unroll
-        for (int j = 0; j < N; ++j) D.q_spare[1][SPARE(j)] = q[j];
+          for (int j = 0; j < N; ++j) D.q_spare[1][SPARE(j)] = q[j];
+        }
         if (move_G) {
 #pragma unroll
           for (int k = 0; k < N; ++k) D.G_spare[SPARE(k)] = Gmv[k];
@@ -374,7 +399,7 @@ OH_DEV void eval_unit(const FigParams& P, const FigBuffers& D, const int slot, c
     int nb;
   };
   const Hooks hooks{MOVE ? D.q_spare[0] : D.q[slot], D.g[slot], D.Z[slot], D.Gfull[cur], Bp, b, t, Gpre, D.q[slot], q, D.Gfull[slot], &sm_zc, 2.0 * P.kappa, t == P.T - 1, cpl_zc,
-                    (MOVE && first) ? D.q_spare[1] : nullptr, nb};
+                    (MOVE && first && !lean) ? D.q_spare[1] : nullptr, nb};
   double e_new[3], JZ_new[3][NZ];
   // A restart after a compaction (first_b == 2) evaluates the accepted point AS IT IS: its knots are the retracted
   // knots the instance accepted, and retracting them again (to the floor tolerance, as a seed would be) moved them by ~1e-10 -- enough to send an
@@ -702,6 +727,10 @@ OH_DEV StepHead step_head(const FigParams& P, const FigBuffers& D, const int b, 
       D.nun[b] = lm.nun;
       D.cur[b] = cur;
       oh_count(D.work + 1);
+      if (D.lean) {  // those knots stayed behind in the old layout (eval_unit<.., MOVE>): k_sweep_lists fetches them after this sweep
+        D.rescue_list[oh_take_ticket(D.n_rescue)] = b;
+        oh_count(D.work + 5);
+      }
       return StepHead{1, cur, lm};
     }
     if (accept) {

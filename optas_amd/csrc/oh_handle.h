@@ -74,8 +74,10 @@ struct Solve {
 struct Sched {
   int compaction = 1;
   int compact_carry = 1;     // compaction carries the pending trial along instead of restarting the survivors (k_carry_*)
-  int compact_fused = 1;     // ... and the retraction compiled for the chain lays the knots down at their new index itself (oh_spec_retract_move;
-                             // 0: k_retract, then k_carry_gather moves them)
+  int compact_fused = 2;     // ... and the retraction compiled for the chain lays the knots down at their new index itself (oh_spec_retract_move;
+                             // 0: k_retract, then k_carry_gather moves them); 2: lean -- hybrid / exact curvature: the accepted knot stays behind
+                             // and the gradient moves only where the evaluation reads it (eval_unit<.., MOVE>), and the list-driven copies behind
+                             // a sweep are launched only when their list is not empty
   int tail_vel_threshold = 1 << 30;  // ... from this many instances down: always (see locked_loop)
   int lg_split = 1;          // orientation-locked handles with limit rows and no sphere rows: k_retract + k_evalb_lg instead of the fused k_eval_lg (OH_LG_SPLIT=0)
   int tail_vel = 1;          // velocity-limited handles drain in the persistent kernel too (k_tail_vel; OH_TAIL_VEL=0: batched launches to the end)
@@ -185,6 +187,7 @@ struct oh_handle {
   double timing_couple = 0;
   double rejects = 0;
   double tail_iters = 0;
+  double rescued = 0, grad_moved = 0, lanes_moved = 0;  // lean carried compactions: instances through the rescue list; instances whose gradient moved, of these moved
   DevBuf<int, true> h_flag;  // pinned
   // ---- constants: the chain (every kind that takes one), the two chains of oh_link_kin*, the inverse-dynamics tables ----
   bool have_chain = false;
@@ -254,7 +257,7 @@ struct oh_handle {
 struct OptDoc { const char* name; double dflt; };
 // map-backed options and their defaults, the one place a default is written (field-backed ones: FIELD_OPTS; batch_invariant: set_option_impl)
 static constexpr OptDoc OPT_TABLE[] = {
-    {"check_every", 1},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
+    {"check_every", 1},        {"lean_count", 0},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
     {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30},
     {"tape_wave", 1},          {"tape_lbfgs", -1},       {"tape_wave_nt", 256},  {"tape_wave_regs", -1}, {"tape_wave_hist", -1},  {"tq_stall", 25},
     {"tq_curv_after", 3},      {"tq_ftb", 0.995},        {"tq_theta_mu", 1.35},  {"tq_kappa_mu", 0.4},   {"tq_curv_from", 0.1},   {"tq_jac_dual", 0},

@@ -33,7 +33,11 @@ bool oh_launch_carry(hipStream_t s, int n, const FigParams& P, const FigBuffers&
 bool oh_launch_eval_lead(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple_vel(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot);
-bool oh_launch_step(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
+// with_copy: k_defer_copy right behind the sweep of the folded-coupling family (false: the host launches oh_launch_sweep_lists itself)
+bool oh_launch_step(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool with_copy = true);
+// k_defer_copy's work and, behind the sweep of a lean carried compaction (rescue), the accepted knots of the instances in D.rescue_list from the old
+// layout to q_spare[1], in one launch; count: entries of the longer list, -1 unknown
+bool oh_launch_sweep_lists(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool rescue, int count);
 bool oh_launch_eval_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple_free(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot);
 bool oh_launch_couple_free_vel(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot);

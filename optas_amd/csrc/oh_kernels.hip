@@ -201,6 +201,43 @@ __global__ __launch_bounds__(256) void k_defer_copy(FigParams P, FigBuffers D, c
   }
 }
 
+// Lean carried compaction (eval_unit<.., MOVE>, D.lean): the instances whose trial the sweep after the compaction rejected (D.rescue_list, new indices)
+// fall back to their accepted knots, which the moving retraction left in the old layout.  A thread per (instance, free knot) of the list copies them from
+// q[1 - slot] at the old index (D.oldidx) to q_spare[1] at the new one; the host swaps the two arrays afterwards.  Two arrays: nothing is overwritten in place.
+// One launch with k_defer_copy's work (both lists are filled by the same sweep and are independent of each other): the lean sequence's launch behind a sweep,
+// which its host skips when it has seen that both lists are empty.  rescue: the sweep followed a lean compaction.  The next scan zeroes the list's counter.
+template <int N>
+__global__ __launch_bounds__(256) void k_sweep_lists(FigParams P, FigBuffers D, const int slot, const int rescue) {
+  const int Bp = D.Bp, nk = P.T - P.t0;
+  {  // k_defer_copy
+    const int n = min(D.n_defer[slot], D.B);
+    if (blockIdx.x == 0 && threadIdx.x == 0) D.n_defer[1 - slot] = 0;
+    const long long total = (long long)n * nk;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+      const int e = (int)(i / nk), t = P.t0 + (int)(i % nk);
+      const int b = D.defer_list[(size_t)slot * Bp + e];
+      const int cur = D.cur[b];
+      const double* __restrict__ Gold = D.Gfull[1 - cur];
+      double* __restrict__ Gnew = D.Gfull[cur];
+#pragma unroll
+      for (int k = 0; k < N; ++k) Gnew[IDX(t, N, k)] = Gold[IDX(t, N, k)];
+    }
+  }
+  if (rescue) {
+    const int n = min(*D.n_rescue, D.B);
+    const long long total = (long long)n * nk;
+    const double* __restrict__ src = D.q[1 - slot];
+    double* __restrict__ dst = D.q_spare[1];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+      const int e = (int)(i / nk), t = P.t0 + (int)(i % nk);
+      const int b = D.rescue_list[e];
+      const int ob = D.oldidx[b];
+#pragma unroll
+      for (int k = 0; k < N; ++k) dst[IDX(t, N, k)] = src[((size_t)t * N + k) * Bp + ob];
+    }
+  }
+}
+
 template <int N>
 __global__ __launch_bounds__(64) void k_tail(FigParams P, FigBuffers D, const int slot) { tail_block<N>(P, D, slot); }
 // ... for handles whose inequality rows are joint-velocity limits only (tail_block<N, true>)
@@ -289,6 +326,7 @@ __global__ __launch_bounds__(SCAN_MAXBLK) void k_scan_offsets(FigBuffers D, cons
     __syncthreads();
   }
   if (tid == 0) *D.n_new = carry;
+  if (tid == 0 && D.lean) *D.n_rescue = 0;  // (the list of the previous lean compaction was consumed behind its sweep)
 }
 __global__ __launch_bounds__(SCAN_TPB) void k_scan_assign(FigBuffers D, const int sort, const int chunk, const int* __restrict__ blk) {
   __shared__ int cnt[SCAN_NB][SCAN_TPB];
@@ -305,6 +343,7 @@ __global__ __launch_bounds__(SCAN_TPB) void k_scan_assign(FigBuffers D, const in
       for (int k = 0; k < SCAN_NB; ++k)
         if (k == kb) p = pos[k]++;
       D.newidx[b] = p;
+      if (D.lean) D.oldidx[p] = b;  // the inverse map: where k_sweep_lists finds what the moving retraction left behind
     } else {
       D.newidx[b] = -1;
     }
@@ -426,6 +465,11 @@ __global__ __launch_bounds__(256) void k_carry_gather(FigParams P, FigBuffers D,
     ts[(size_t)19 * Bp + nb] = D.stat[b];
     ts[(size_t)20 * Bp + nb] = D.feas[b];
     ts[(size_t)21 * Bp + nb] = (double)((restart ? 1 : 0) + 2 * (D.polish[b] != 0 ? 1 : 0) + 4 * (D.polish[b] == 2 ? 1 : 0));
+    if (REST && (D.lean & 2)) {  // option lean_count, for the profile: the instances whose gradient the lean retraction moved (its own condition), one atomic per wavefront
+      const bool mg = P.hessian != OH_HESSIAN_HYBRID || (!restart && D.stat[b] <= P.hyb_switch);
+      const unsigned long long m = __ballot(mg);
+      if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(D.work + 6, (unsigned long long)__popcll(m));
+    }
   }
 }
 template <int N>
@@ -489,10 +533,10 @@ static void launch_couple_t(hipStream_t s, const FigParams& P, const FigBuffers&
   hipLaunchKernelGGL(k_couple<N>, dim3(nbx8 * (P.T - P.t0)), dim3(256), 0, s, P, D, slot);
 }
 template <int N>
-static void launch_step_t(hipStream_t s, const FigParams& P, const FigBuffers& D, int slot) {
+static void launch_step_t(hipStream_t s, const FigParams& P, const FigBuffers& D, int slot, bool with_copy) {
   if (P.zc) {
     hipLaunchKernelGGL(k_step_zc<N>, dim3((D.B + 63) / 64), dim3(64), 0, s, P, D, slot);
-    if (P.hessian != OH_HESSIAN_GAUSS_NEWTON) hipLaunchKernelGGL(k_defer_copy<N>, dim3(512), dim3(256), 0, s, P, D, slot);
+    if (P.hessian != OH_HESSIAN_GAUSS_NEWTON && with_copy) hipLaunchKernelGGL(k_defer_copy<N>, dim3(512), dim3(256), 0, s, P, D, slot);
   } else hipLaunchKernelGGL(k_step<N>, dim3((D.B + 63) / 64), dim3(64), 0, s, P, D, slot);
 }
 template <int N>
@@ -578,8 +622,21 @@ bool oh_launch_couple_vel(hipStream_t s, int n, const FigParams& P, const FigBuf
 #undef C
   return true;
 }
-bool oh_launch_step(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot) {
-#define C(NN) launch_step_t<NN>(s, P, D, slot)
+bool oh_launch_step(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool with_copy) {
+#define C(NN) launch_step_t<NN>(s, P, D, slot, with_copy)
+  OH_DISPATCH_N(n, C)
+#undef C
+  return true;
+}
+// the list-driven copies behind a sweep of the lean sequence in one launch (k_sweep_lists), for a host that skips it when both lists are empty
+bool oh_launch_sweep_lists(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, int slot, bool rescue, int count) {
+  // count: entries of the longer list where the host knows it (-1: the fixed grid strides over whatever the counters say)
+  const int nk = P.T - P.t0;
+  const long long thr = count < 0 ? 512LL * 256 : (long long)count * nk;
+  const long long nb = (thr + 255) / 256;
+  const int blocks = nb > 512 ? 512 : (nb < 1 ? 1 : (int)nb);
+  const int resc = rescue ? 1 : 0;
+#define C(NN) hipLaunchKernelGGL(k_sweep_lists<NN>, dim3(blocks), dim3(256), 0, s, P, D, slot, resc)
   OH_DISPATCH_N(n, C)
 #undef C
   return true;

@@ -122,5 +122,11 @@ struct FigBuffers {
   // deferred refactorisation (k_step_zc, round 6): instances whose older Lagrangian gradient k_defer_copy puts back after the sweep, by launch parity
   int* n_defer;           // [2]
   int* defer_list;        // [2][Bp]
+  // lean carried compaction (compact_fused = 2, plain handles on the kernels compiled for the chain): the moving retraction leaves the accepted knot
+  // behind and moves the Lagrangian gradient only on the lanes whose evaluation will read it (eval_unit<.., MOVE>)
+  int lean;               // 1 while a solve runs that sequence
+  int* oldidx;            // [Bp] inverse of newidx: the index an instance had before the last compaction (k_scan_assign)
+  int* rescue_list;       // [Bp] instances whose trial was rejected in the sweep after a compaction: k_sweep_lists fetches their accepted knots
+  int* n_rescue;          // [1] length of that list
 };
 

@@ -19,7 +19,7 @@ import sqlite3
 import subprocess
 import sys
 
-NAMES = ("k_tail", "k_tq_eval3", "k_tq_eval", "k_tq_step", "k_step_zc", "k_evalb_zc", "k_tq_setup", "k_tq_finalize", "k_tq_list", "k_retract_move", "k_retract", "k_evalb", "k_eval", "k_couple", "k_step", "k_fk_jac", "k_setup", "k_finalize", "k_compact_gather", "k_compact_scatter", "k_carry_gather", "k_carry_scatter", "k_scan_count", "k_scan_offsets", "k_scan_assign")
+NAMES = ("k_defer_copy", "k_sweep_lists", "k_tail", "k_tq_eval3", "k_tq_eval", "k_tq_step", "k_step_zc", "k_evalb_zc", "k_tq_setup", "k_tq_finalize", "k_tq_list", "k_retract_move", "k_retract", "k_evalb", "k_eval", "k_couple", "k_step", "k_fk_jac", "k_setup", "k_finalize", "k_compact_gather", "k_compact_scatter", "k_carry_gather", "k_carry_scatter", "k_scan_count", "k_scan_offsets", "k_scan_assign")
 
 
 # the run-time specialised kernels (optas_amd/csrc/oh_jit.hip) appear under their own names; they are the same kernels compiled for one chain
