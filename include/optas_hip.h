@@ -352,6 +352,21 @@ int oh_tape_probe(oh_handle* h, int B, const double* x, const double* p, int n_r
 int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, double* merit, double* f, double* rows,
                 double* grad, double* cmax, double* meas);
 
+/* Exact second-order information of an OH_PROBLEM_TAPE handle's tape, on the device: Hessian-vector products of the seeded combination
+     L(x) = seeds[0] f(x, p) + sum_i seeds[1 + i] row_i(x, p)        (oh_tape_probe's convention; the Lagrangian f - lam^T g - mu^T c is (1, -lam, -mu))
+   by one forward-over-reverse pass of the interpreter per (instance, direction), a GPU lane each (csrc/oh_tape.hip:k_tape_hvp).
+   x [B][nx], p [B][np], seeds [B][1 + n_ineq + n_eq] (required); V [B][nv][nx] the directions; HV [B][nv][nx] receives (d2 L / dx2) V[b][d];
+   grad [B][nx] (optional) the gradient of L, bit for bit oh_tape_probe's.  V == NULL requires nv == nx and means the identity: the kernel forms the
+   unit vectors itself and HV is the dense Hessian [B][nx][nx].  Host buffers.  Works on every OH_PROBLEM_TAPE handle whatever evaluator its solves use,
+   on the tape the handle holds -- a handle on the wavefront path holds the tape with its sums re-associated.
+   Conventions: the first-order ones of oh_tape_phi (every adjoint and tangent is multiplied through, also one that is exactly 0; instructions neither the
+   cost nor a row depends on take no part), and a kink holds the selection of the base point: FMIN / FMAX pass value, tangent and adjoint of the chosen
+   operand (a tie goes to a), FABS has slope +-1 or 0 and no curvature, IFZ passes b where a != 0 and nothing to the condition, comparisons and logic have
+   zero tangent.  The result of an (instance, direction) does not depend on B, nv or the other directions.  The work area, 4 len + 3 nx doubles per
+   (instance, direction), is kept under option tape_hvp_work_mb (256) by launching whole 64-lane blocks in chunks; oh_get_flag "tape_hvp_launches".
+   oh_get_timing out[4] is then the device time of these launches (the copies in and out are outside it), out[5] their number. */
+int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p, const double* seeds, int nv, const double* V, double* HV, double* grad);
+
 /* Initial metric of an OH_PROBLEM_TAPE handle's limited-memory quasi-Newton iteration: H0 [nx][nx], symmetric positive definite, host memory (copied);
    NULL takes it away again.  The two-loop recursion then starts from r = H0 q instead of the identity scaled by the newest pair.  The reference hands
    IPOPT the exact Hessian of the Lagrangian (optimization.py:8-24, solver.py:355-384); this is the part of it that is known before the first solve:
@@ -420,7 +435,7 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    k_retract + k_evalb_zc + k_step_zc, the neighbour coupling folded in; 0: k_couple runs as a launch of its own), "tail_threshold",
    "specialized"; OH_PROBLEM_TAPE handles: "tape_wave" (0: one thread per instance; 1 / 2: one block of wavefronts per instance, the quasi-Newton
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
-   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_jit_lds" (1: the last oh_tape_phi ran
+   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_hvp_launches" (kernel launches of the last oh_tape_hvp), "tape_jit_lds" (1: the last oh_tape_phi ran
    the generated code's entry with its work set in LDS); OH_PROBLEM_QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance
    kernel k_qp_solve_block); position-tracking handles (lock_orientation = 0): "free_sweep", the kernel that solved the block-tridiagonal system
    of the last oh_solve / oh_solve_device call's first launch -- 0 k_step_free (one lane per instance), 1 k_step_free_pcr, 2 k_step_free_cp,
@@ -452,6 +467,7 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *   hyb_switch (1e-5, x w_path), relax (1.5), relax_from (4), retract_min (1e-13), settle_k (1)          -- algorithm constants (change the iterates)
  *   tol (0 = the descriptor's): stopping tolerance on the reduced gradient of a trajectory handle, changeable between solves
  *   pm_wave_max (20480), qp_mode (-1), tape_lds_max                                                     -- point-mass / QP / tape launch shapes
+ *   tape_hvp_work_mb (256)                                                                              -- oh_tape_hvp: budget of its work area, MB
  *       (qp_mode: -1 automatic; 0 / 1 / 2 force where the thread-per-instance kernel keeps its work set, falling back when it does not fit;
  *        3 forces the workgroup-per-instance kernel on any handle; large handles take that kernel under every value)
  *   tape_wave (1), tape_lbfgs (-1 = by size), tape_wave_nt (256), tape_wave_regs (-1), tape_wave_hist (-1) -- tape evaluator (rebuilt when set)

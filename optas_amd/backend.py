@@ -254,8 +254,30 @@ class TapeBackend(_SolveMixin):
                                            ptr(out["rows"]), _lib._ptr(out["grad"]), _lib._ptr(out["cmax"]), _lib._ptr(out["meas"])), "oh_tape_phi")
         return out
 
+    def hvp(self, x, p, seeds, V):
+        """oh_tape_hvp: exact Hessian-vector products of the combination of (cost, rows) weighted by seeds (B, 1 + n_ineq + n_eq) -- the Lagrangian is
+        (1, -lam, -mu) -- at x (B, nx), p (B, np) along the directions V (B, nv, nx).  Returns (HV (B, nv, nx), grad (B, nx))."""
+        x = _lib.as_f64(x).reshape(-1, self.nx)
+        B = x.shape[0]
+        V = _lib.as_f64(V).reshape(B, -1, self.nx)
+        return self._hvp(x, p, seeds, V.shape[1], V)
+
+    def hessian(self, x, p, seeds):
+        """The dense Hessian (B, nx, nx) of the same combination: oh_tape_hvp with V = NULL (the device forms the unit vectors)."""
+        x = _lib.as_f64(x).reshape(-1, self.nx)
+        return self._hvp(x, p, seeds, self.nx, None)[0]
+
+    def _hvp(self, x, p, seeds, nv, V):
+        B = x.shape[0]
+        p = _lib.as_f64(p).reshape(B, -1) if self._np_real else np.zeros((B, 1))
+        seeds = _lib.as_f64(seeds).reshape(B, 1 + int(self.tape.n_ineq) + int(self.tape.n_eq))
+        HV, grad = np.empty((B, nv, self.nx)), np.empty((B, self.nx))
+        _lib.check(_lib.load().oh_tape_hvp(self._h, B, _lib._ptr(x), _lib._ptr(p), _lib._ptr(seeds), int(nv), None if V is None else _lib._ptr(V), _lib._ptr(HV),
+                                           _lib._ptr(grad)), "oh_tape_hvp")
+        return HV, grad
+
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric'."""
+        """oh_get_flag: 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian())."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)
@@ -314,14 +336,24 @@ class EliminatedTapeBackend:
         seeds[:, 0] = 1.0
         seeds[:, 1 : 1 + lam.shape[1]] = -lam
         seeds[:, 1 + lam.shape[1] + el.rows_kept] = -mu
-        if self._orig is None:
-            self._orig = TapeBackend(self.full, jit=False, wave=False, metric=False)
-        _, _, grad = self._orig.probe(x, p, None, seeds)
+        _, _, grad = self._as_written().probe(x, p, None, seeds)
         nu = np.linalg.solve(el.A_pivot.T, grad[:, el.pivot].T).T
         mu_full = np.zeros((B, n_eq))
         mu_full[:, el.rows_kept] = mu
         mu_full[:, el.rows_out] = nu
         return lam, mu_full
+
+    def _as_written(self):
+        if self._orig is None:
+            self._orig = TapeBackend(self.full, jit=False, wave=False, metric=False)
+        return self._orig
+
+    def hvp(self, x, p, seeds, V):
+        """TapeBackend.hvp of the problem AS WRITTEN: x (B, nx) holds every variable, seeds weigh (cost, rows) in the original order."""
+        return self._as_written().hvp(x, p, seeds, V)
+
+    def hessian(self, x, p, seeds):
+        return self._as_written().hessian(x, p, seeds)
 
     def flag(self, name: str) -> int:
         return self.inner.flag(name)

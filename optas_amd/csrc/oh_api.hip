@@ -79,7 +79,7 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     for (const OptDoc& d : OPT_TABLE) known = known || name == d.name;
     if (!known) return fail(OH_ERR_INVALID, "oh_set_option: unknown option '" + name + "'");
     h->opt[name] = v;
-    if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max") return tape_configure(h);
+    if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max" && name != "tape_hvp_work_mb") return tape_configure(h);
   }
   return OH_OK;
 }
@@ -1380,7 +1380,7 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 // How the handle's last solve was (or its next one will be) scheduled, by name: "fuse_couple" (1: coupling folded into evaluation and sweep, no
 // k_couple launch), "tail_threshold", "specialized"; tape handles: "tape_wave" (0: thread per instance, 1 / 2: wavefront per instance with the (s, y)
 // pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
-// oh_tape_phi ran the generated code's entry with the work set in LDS); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
+// oh_tape_phi ran the generated code's entry with the work set in LDS), "tape_hvp_launches" (launches of the last oh_tape_hvp); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
 // position-tracking handles: "free_sweep" (the FreeSweep the last solve started with, -1 before the first), "free_sweeps_used" (bit mask over its launches).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
@@ -1393,6 +1393,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_wave") *value = h->tape.wave.ready ? (h->tape.wave.hist_lds ? 2 : 1) : 0;
   else if (n == "tape_regs_lds") *value = h->tape.wave.ready && h->tape.wave.reg_lds ? 1 : 0;
   else if (n == "tape_jit_lds") *value = h->tape.phi_lds;
+  else if (n == "tape_hvp_launches") *value = h->tape.hvp_launches;
   else if (n == "tape_metric") *value = (h->tape.P.h0 && h->tape.P.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape.wave.n_levels;
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;

@@ -188,6 +188,55 @@ extern "C" int oh_tape_probe(oh_handle* h, int B, const double* x, const double*
   return OH_OK;
 }
 
+extern "C" int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p, const double* seeds, int nv, const double* V, double* HV, double* grad) {
+  if (!h || !x || !seeds || !HV) return fail(OH_ERR_INVALID, "oh_tape_hvp: null argument");
+  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_hvp: handle is not an OH_PROBLEM_TAPE problem");
+  TapeState& tp = h->tape;
+  const TapeParams& T = tp.P;
+  if (B < 1 || nv < 1 || (T.np > 0 && !p)) return fail(OH_ERR_INVALID, "oh_tape_hvp: bad sizes");
+  if (!V && nv != T.nx) return fail(OH_ERR_INVALID, "oh_tape_hvp: V == NULL means the identity and needs nv == nx");
+  const size_t nB = (size_t)B, U = nB * (size_t)nv;  // units: (instance, direction)
+  if (U > (size_t)0x7fffffc0) return fail(OH_ERR_INVALID, "oh_tape_hvp: B * nv does not fit an int");
+  HIPCHK(hipSetDevice(h->device));
+  // whole 64-lane blocks per launch, as many as keep the work area under the budget (at least one)
+  const size_t per_unit = sizeof(double) * oh_tape_hvp_work_rows(T);
+  const double budget = optv(h, "tape_hvp_work_mb") * 1048576.0;
+  size_t chunk = budget > 0.0 ? (size_t)(budget / (double)per_unit) / 64 * 64 : 0;
+  if (chunk < 64) chunk = 64;
+  const size_t Up = (U + 63) / 64 * 64;
+  if (chunk > Up) chunk = Up;
+  const int nrow = T.n_ineq + T.n_eq;
+  const size_t b_x = sizeof(double) * (size_t)T.nx * nB, b_u = sizeof(double) * (size_t)T.nx * U;
+  double *d_x, *d_g, *d_p, *d_s, *d_v, *d_hv, *d_w;
+  auto layout = [&](Carver c) {
+    d_x = c.take<double>((size_t)T.nx * nB);
+    d_g = c.take<double>((size_t)T.nx * nB);
+    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
+    d_s = c.take<double>((size_t)(1 + nrow) * nB);
+    d_v = c.take<double>(V ? (size_t)T.nx * U : 1);
+    d_hv = c.take<double>((size_t)T.nx * U);
+    d_w = c.take<double>(oh_tape_hvp_work_rows(T) * chunk);
+    return c.bytes();
+  };
+  if (const int rc = stage_carve(h, layout)) return rc;
+  hipStream_t s = h->stream;
+  HIPCHK(hipMemcpyAsync(d_x, x, b_x, hipMemcpyHostToDevice, s));
+  if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * nB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_s, seeds, sizeof(double) * (size_t)(1 + nrow) * nB, hipMemcpyHostToDevice, s));
+  if (V) HIPCHK(hipMemcpyAsync(d_v, V, b_u, hipMemcpyHostToDevice, s));
+  tp.hvp_launches = 0;
+  HIPCHK(hipEventRecord(h->ev0, s));  // oh_get_timing out[4]: device time of the launches, the copies outside
+  for (size_t u0 = 0; u0 < U; u0 += chunk) {  // (one stream: a launch has the work area to itself)
+    const size_t n = U - u0 < chunk ? U - u0 : chunk;
+    oh_launch_tape_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, (int)u0, (int)n, (int)chunk, nv, d_x, d_p, d_s, V ? d_v : nullptr, d_w, d_hv, grad ? d_g : nullptr);
+    ++tp.hvp_launches;
+  }
+  if (const int rc = finish_solve(h, tp.hvp_launches)) return rc;
+  HIPCHK(hipMemcpy(HV, d_hv, b_u, hipMemcpyDeviceToHost));
+  if (grad) HIPCHK(hipMemcpy(grad, d_g, b_x, hipMemcpyDeviceToHost));
+  return OH_OK;
+}
+
 extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
   if (!h) return fail(OH_ERR_INVALID, "oh_tape_set_metric: null argument");
   if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_INVALID, "oh_tape_set_metric: not an OH_PROBLEM_TAPE handle");

@@ -219,6 +219,11 @@ void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const
                         double* grad, double* cmax, double* meas);
 void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
                           const double* x, const double* p, double* work, int n_regs, const int* regs, double* val, const double* seeds, double* adj, double* grad);
+// forward-over-reverse on the interpreter (oh_tape_hvp): the units [u0, u0 + n) of u = instance * nv + direction, one lane each; work is
+// [oh_tape_hvp_work_rows][Bp] with Bp >= n; x, p, seeds, V (null: the unit vectors), HV and grad are the whole batch's arrays
+size_t oh_tape_hvp_work_rows(const TapeParams& T);  // 4 len + 3 nx
+void oh_launch_tape_hvp(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int u0, int n, int Bp,
+                        int nv, const double* x, const double* p, const double* seeds, const double* V, double* work, double* HV, double* grad);
 void oh_launch_tape_solve(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
                           const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status, double* mult);
 // solve = false: the program of the single-evaluation kernels (k_tape_jit_phi, k_tape_jit_phi_lds) around the same evaluator text

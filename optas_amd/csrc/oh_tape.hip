@@ -191,6 +191,175 @@ __global__ __launch_bounds__(64) void k_tape_probe(TapeParams T, TapeView tv, in
     for (int k = 0; k < T.nx; ++k) grad_out[(size_t)b * T.nx + k] = gr[TIDX(k)];
 }
 
+// Exact Hessian-vector products of the seeded combination of (cost, rows) by forward-over-reverse on the interpreter (oh_tape_hvp).  One lane per unit
+// u = b nv + d (instance b, direction d, the direction fastest); the launch covers the units [u0, u0 + n) and lane l = u - u0 owns column l of the work
+// area [4 len + 3 nx][Bp]: registers, tangents, adjoints, the adjoints' directional derivatives, then the point, the gradient and H v.  The forward sweep is
+// InterpEval::forward with the tangent dval = (d val / d x) v beside every value, the reverse sweep InterpEval::reverse with dadj = (d adj / d x) v
+// beside every adjoint: the primal operations are those sweeps' operations in their order, so the gradient has oh_tape_probe's bits, and a unit
+// reads nothing of another unit, so its result does not depend on B, nv or the launch it falls into.  A kink holds the selection of the base point
+// (FMIN / FMAX: value, tangent and adjoint of the chosen operand, a tie to a; FABS: slope +-1 or 0, no curvature; IFZ: b where a != 0, nothing to the
+// condition; 17 .. 23: zero tangent, no adjoint).  Zero adjoints and tangents are multiplied through like every other.
+// V null: direction d is e_d (nv == nx), formed here.  The tape is the one the handle holds: on a wave handle the re-associated one.
+__global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int u0, int n, int Bp, int nv, const double* __restrict__ x,
+                                                 const double* __restrict__ par, const double* __restrict__ seeds, const double* __restrict__ V,
+                                                 double* __restrict__ work, double* __restrict__ HV, double* __restrict__ grad_out) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;  // the unit's column of the work area (TIDX)
+  if (b >= n) return;
+  const size_t u = (size_t)u0 + b;
+  const size_t inst = u / (size_t)nv;
+  const int dir = (int)(u % (size_t)nv);
+  const size_t L = (size_t)T.len * Bp;
+  double* __restrict__ val = work;
+  double* __restrict__ dval = work + L;
+  double* __restrict__ adj = work + 2 * L;
+  double* __restrict__ dadj = work + 3 * L;
+  double* __restrict__ xs = work + 4 * L;
+  double* __restrict__ gr = xs + (size_t)T.nx * Bp;
+  double* __restrict__ hv = gr + (size_t)T.nx * Bp;
+  const double* __restrict__ pb = par + inst * T.np;
+  const double* __restrict__ vd = V ? V + u * T.nx : nullptr;
+  for (int k = 0; k < T.nx; ++k) xs[TIDX(k)] = x[inst * T.nx + k];
+  // ---- forward: InterpEval::forward, and the tangent of every register
+  for (int i = 0; i < T.len; ++i) {
+    const int o = tv.op[i] & 31, ia = tv.a[i], ib = tv.bb[i];
+    double v, t;
+    switch (o) {
+      case 0: v = tv.c[i]; t = 0.0; break;
+      case 1: v = xs[TIDX(ia)]; t = vd ? vd[ia] : (ia == dir ? 1.0 : 0.0); break;
+      case 2: v = pb[ia]; t = 0.0; break;
+      case 3: v = val[TIDX(ia)] + val[TIDX(ib)]; t = dval[TIDX(ia)] + dval[TIDX(ib)]; break;
+      case 4: v = val[TIDX(ia)] - val[TIDX(ib)]; t = dval[TIDX(ia)] - dval[TIDX(ib)]; break;
+      case 5: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va * vb; t = dval[TIDX(ia)] * vb + va * dval[TIDX(ib)]; } break;
+      case 6: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va / vb; t = (dval[TIDX(ia)] - v * dval[TIDX(ib)]) / vb; } break;
+      case 7: v = -val[TIDX(ia)]; t = -dval[TIDX(ia)]; break;
+      case 8: { const double va = val[TIDX(ia)]; v = sin(va); t = cos(va) * dval[TIDX(ia)]; } break;
+      case 9: { const double va = val[TIDX(ia)]; v = cos(va); t = -(sin(va) * dval[TIDX(ia)]); } break;
+      case 10: {
+        const double va = val[TIDX(ia)], vb = val[TIDX(ib)];
+        v = atan2(va, vb);
+        t = (vb * dval[TIDX(ia)] - va * dval[TIDX(ib)]) / (va * va + vb * vb);
+      } break;
+      case 11: v = sqrt(val[TIDX(ia)]); t = 0.5 / v * dval[TIDX(ia)]; break;
+      case 12: { const double va = val[TIDX(ia)]; v = va * va; t = 2.0 * va * dval[TIDX(ia)]; } break;
+      case 13: { const double va = val[TIDX(ia)]; v = asin(va); t = dval[TIDX(ia)] / sqrt((1.0 - va) * (1.0 + va)); } break;
+      case 14: { const double va = val[TIDX(ia)]; v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * dval[TIDX(ia)]; } break;
+      case 15: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmin(va, vb); t = va <= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
+      case 16: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmax(va, vb); t = va >= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
+      case 17: v = val[TIDX(ia)] < val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case 18: v = val[TIDX(ia)] <= val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case 19: v = val[TIDX(ia)] == val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case 20: v = val[TIDX(ia)] != val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case 21: v = val[TIDX(ia)] == 0.0 ? 1.0 : 0.0; t = 0.0; break;
+      case 22: v = (val[TIDX(ia)] != 0.0 && val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+      case 23: v = (val[TIDX(ia)] != 0.0 || val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+      case 24: { const bool on = val[TIDX(ia)] != 0.0; v = on ? val[TIDX(ib)] : 0.0; t = on ? dval[TIDX(ib)] : 0.0; } break;
+      case 25: v = exp(val[TIDX(ia)]); t = v * dval[TIDX(ia)]; break;
+      default: { const double va = val[TIDX(ia)]; v = log(va); t = dval[TIDX(ia)] / va; } break;  // 26
+    }
+    val[TIDX(i)] = v;
+    dval[TIDX(i)] = t;
+  }
+  // ---- seeds: oh_tape_probe's (the weights do not depend on x: their tangent is zero)
+  for (int i = 0; i < T.len; ++i) { adj[TIDX(i)] = 0.0; dadj[TIDX(i)] = 0.0; }
+  const int nrow = T.n_ineq + T.n_eq;
+  const double* sd = seeds + inst * (1 + nrow);
+  adj[TIDX(T.out_cost)] += sd[0];
+  for (int i = 0; i < nrow; ++i) adj[TIDX(tv.rows[i])] += sd[1 + i];
+  // ---- reverse: InterpEval::reverse, and beside every  adj[r] += w q  its derivative along v,  dadj[r] += dw q + w dq
+  // (the operands' values and tangents are read before anything is accumulated, and the two accumulations of a binary instruction are separate
+  //  read-modify-writes: MUL a a adds both contributions to the one register)
+  for (int k = 0; k < T.nx; ++k) { gr[TIDX(k)] = 0.0; hv[TIDX(k)] = 0.0; }
+  for (int i = T.len - 1; i >= 0; --i) {
+    const double w = adj[TIDX(i)], dw = dadj[TIDX(i)];
+    const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
+    if (o & 32) continue;  // dead: no part in the gradient, none in H v
+    switch (o) {
+      case 0: case 2: break;
+      case 1: gr[TIDX(ia)] += w; hv[TIDX(ia)] += dw; break;
+      case 3: adj[TIDX(ia)] += w; adj[TIDX(ib)] += w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] += dw; break;
+      case 4: adj[TIDX(ia)] += w; adj[TIDX(ib)] -= w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] -= dw; break;
+      case 5: {
+        const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
+        adj[TIDX(ia)] += w * vb;
+        adj[TIDX(ib)] += w * va;
+        dadj[TIDX(ia)] += dw * vb + w * tb;
+        dadj[TIDX(ib)] += dw * va + w * ta;
+      } break;
+      case 6: {
+        const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
+        adj[TIDX(ia)] += w / vb;
+        adj[TIDX(ib)] -= w * va / (vb * vb);
+        // d (1 / b) = -tb / b^2;   d (a / b^2) = ta / b^2 - 2 a tb / b^3
+        dadj[TIDX(ia)] += (dw - w * tb / vb) / vb;
+        dadj[TIDX(ib)] -= (dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb);
+      } break;
+      case 7: adj[TIDX(ia)] -= w; dadj[TIDX(ia)] -= dw; break;
+      case 8: {
+        const double va = val[TIDX(ia)], ta = dval[TIDX(ia)], c = cos(va);
+        adj[TIDX(ia)] += w * c;
+        dadj[TIDX(ia)] += dw * c - w * sin(va) * ta;
+      } break;
+      case 9: {
+        const double va = val[TIDX(ia)], ta = dval[TIDX(ia)], s = sin(va);
+        adj[TIDX(ia)] -= w * s;
+        dadj[TIDX(ia)] -= dw * s + w * cos(va) * ta;
+      } break;
+      case 10: {
+        const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)], d = va * va + vb * vb;
+        adj[TIDX(ia)] += w * vb / d;
+        adj[TIDX(ib)] -= w * va / d;
+        // d (b / d) = (tb - b dd / d) / d,  d (a / d) = (ta - a dd / d) / d  with  dd = 2 (a ta + b tb)
+        const double dd = 2.0 * (va * ta + vb * tb);
+        dadj[TIDX(ia)] += (dw * vb + w * (tb - vb * dd / d)) / d;
+        dadj[TIDX(ib)] -= (dw * va + w * (ta - va * dd / d)) / d;
+      } break;
+      case 11: {  // q = 0.5 / sqrt(a);  dq = -q (q ta) / sqrt(a)
+        const double r = val[TIDX(i)], q = 0.5 / r;
+        adj[TIDX(ia)] += w * 0.5 / r;
+        dadj[TIDX(ia)] += dw * q - w * (q * dval[TIDX(i)] / r);
+      } break;
+      case 12: {
+        const double va = val[TIDX(ia)];
+        adj[TIDX(ia)] += w * 2.0 * va;
+        dadj[TIDX(ia)] += dw * 2.0 * va + w * 2.0 * dval[TIDX(ia)];
+      } break;
+      case 13: {  // q = 1 / sqrt((1 - a)(1 + a));  dq = a ta q / ((1 - a)(1 + a))
+        const double va = val[TIDX(ia)], s = (1.0 - va) * (1.0 + va), r = sqrt(s);
+        adj[TIDX(ia)] += w / r;
+        dadj[TIDX(ia)] += dw / r + w * (va * dval[TIDX(ia)] / (s * r));
+      } break;
+      case 14: {
+        const double va = val[TIDX(ia)], sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0);
+        adj[TIDX(ia)] += w * sg;
+        dadj[TIDX(ia)] += dw * sg;
+      } break;
+      case 15:
+        if (val[TIDX(ia)] <= val[TIDX(ib)]) { adj[TIDX(ia)] += w; dadj[TIDX(ia)] += dw; } else { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
+        break;
+      case 16:
+        if (val[TIDX(ia)] >= val[TIDX(ib)]) { adj[TIDX(ia)] += w; dadj[TIDX(ia)] += dw; } else { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
+        break;
+      case 24:
+        if (val[TIDX(ia)] != 0.0) { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
+        break;
+      case 25: {  // q = exp(a) = val[i], dq = dval[i]
+        adj[TIDX(ia)] += w * val[TIDX(i)];
+        dadj[TIDX(ia)] += dw * val[TIDX(i)] + w * dval[TIDX(i)];
+      } break;
+      case 26: {
+        const double va = val[TIDX(ia)];
+        adj[TIDX(ia)] += w / va;
+        dadj[TIDX(ia)] += (dw - w * dval[TIDX(ia)] / va) / va;
+      } break;
+      default: break;  // 17..23
+    }
+  }
+  for (int k = 0; k < T.nx; ++k) HV[u * T.nx + k] = hv[TIDX(k)];
+  if (grad_out && dir == 0)
+    for (int k = 0; k < T.nx; ++k) grad_out[inst * T.nx + k] = gr[TIDX(k)];
+}
+
 // One InterpEval::phi per instance at given points, multipliers and penalty (oh_tape_phi).  work: the solve kernel's layout.
 __global__ __launch_bounds__(64) void k_tape_phi(TapeParams T, TapeView tv, int B, int Bp, const double* __restrict__ x, const double* __restrict__ par,
                                                  const double* __restrict__ lam, const double* __restrict__ mu, double rho, double* __restrict__ work,
@@ -420,6 +589,14 @@ void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, con
                           const double* x, const double* p, double* work, int n_regs, const int* regs, double* val, const double* seeds, double* adj, double* grad) {
   TapeView tv{op, a, b, c, rows};
   hipLaunchKernelGGL(k_tape_probe, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, x, p, work, n_regs, regs, val, seeds, adj, grad);
+}
+
+size_t oh_tape_hvp_work_rows(const TapeParams& T) { return 4 * (size_t)T.len + 3 * (size_t)T.nx; }
+
+void oh_launch_tape_hvp(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int u0, int n, int Bp,
+                        int nv, const double* x, const double* p, const double* seeds, const double* V, double* work, double* HV, double* grad) {
+  TapeView tv{op, a, b, c, rows};
+  hipLaunchKernelGGL(k_tape_hvp, dim3((n + 63) / 64), dim3(64), 0, s, T, tv, u0, n, Bp, nv, x, p, seeds, V, work, HV, grad);
 }
 
 void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,

@@ -355,6 +355,7 @@ class HIPSolver(Solver):
                 target = target.be
             target.set_options(handle_options)
         self._stats: Optional[dict] = None
+        self._p_solved = None
         self._x0_batch: Optional[np.ndarray] = None
         self._p_batch: Optional[np.ndarray] = None
         return self
@@ -362,11 +363,12 @@ class HIPSolver(Solver):
     # ---- scalar interface (one instance), solver.py:103-157 ---------------------------------------------
     def _solve(self) -> np.ndarray:
         res = self._backend.solve(self.x0.reshape(1, -1), self.p.reshape(1, -1))
-        self._record(res)
+        self._record(res, self.p.reshape(1, -1))
         return res.x[0]
 
-    def _record(self, res: BatchResult) -> None:
+    def _record(self, res: BatchResult, p=None) -> None:
         self._solution = res
+        self._p_solved = None if p is None else np.array(p, dtype=np.float64).reshape(len(res.x), -1)  # the parameters of this solve (lagrangian_hessian)
         self._stats = {
             "success": bool(np.all(_lib.status_ok(res.status))),
             "iter_count": int(res.iters.max()),
@@ -405,7 +407,7 @@ class HIPSolver(Solver):
         x0 = self._x0_batch if self._x0_batch is not None else np.zeros((B, self.opt.nx))
         assert x0.shape[0] == B, "seed and parameter batches differ in size"
         res = self._backend.solve(x0, self._p_batch)
-        self._record(res)
+        self._record(res, self._p_batch)
         if self._error_on_fail and (not self.did_solve()):
             raise RuntimeError("Solver failed!")
         sol = self.opt.decision_variables.vec2dict_batch(res.x)
@@ -429,8 +431,38 @@ class HIPSolver(Solver):
     def solve_batch_arrays(self, x0: np.ndarray, p: np.ndarray) -> BatchResult:
         """Array-in/array-out fast path (no dict shuffling): x0 (B, nx), p (B, np) in vec() order."""
         res = self._backend.solve(x0, p)
-        self._record(res)
+        self._record(res, p)
         return res
+
+    def lagrangian_hessian(self, x=None, lam=None, mu=None) -> np.ndarray:
+        """The exact Hessian in x of the Lagrangian f - lam^T g - mu^T c of a problem on the tape path (what the reference hands IPOPT,
+        optimization.py:8-24), for every instance of the last solve: (B, nx, nx) in vec() order, computed on the device (oh_tape_hvp) on the problem as
+        written.  x (B, nx), lam (B, n_ineq), mu (B, n_eq) default to the last solution and the multipliers the backend returns for it; before a solve
+        all three must be given (the parameters are then the ones set with reset_parameters / reset_parameters_batch)."""
+        if not isinstance(self._spec, TapeSpec):
+            family = {FigureEightSpec: "figure-eight", TorqueSpec: "torque-MPC", PointMassSpec: "point-mass", MultiArmSpec: "multi-arm", IkSpec: "inverse-kinematics",
+                      QpSpec: "dense QP"}.get(type(self._spec), type(self._spec).__name__)
+            raise NotImplementedError(f"lagrangian_hessian: the {family} family has no exact Hessian entry; only problems on the tape path do")
+        be, tp = self._backend, self._spec.tape
+        ni, ne = int(tp.n_ineq), int(tp.n_eq)
+        if self._solution is None or self._p_solved is None:
+            if x is None or lam is None or mu is None:
+                raise ValueError("lagrangian_hessian: before a solve x, lam and mu must all be given")
+            x = np.asarray(x, dtype=np.float64).reshape(-1, self.opt.nx)
+            p = self._p_batch if self._p_batch is not None else np.tile(self.p.reshape(1, -1), (len(x), 1))
+        else:
+            p = self._p_solved
+            if lam is None or mu is None:
+                lam_s, mu_s = be.multipliers(len(self._solution.x))
+                lam, mu = (lam_s if lam is None else lam), (mu_s if mu is None else mu)
+            x = np.asarray(self._solution.x if x is None else x, dtype=np.float64).reshape(-1, self.opt.nx)
+        B = len(x)
+        p = np.asarray(p, dtype=np.float64).reshape(B, -1)
+        seeds = np.empty((B, 1 + ni + ne))
+        seeds[:, 0] = 1.0
+        seeds[:, 1 : 1 + ni] = -np.asarray(lam, dtype=np.float64).reshape(B, ni)
+        seeds[:, 1 + ni :] = -np.asarray(mu, dtype=np.float64).reshape(B, ne)
+        return be.hessian(x, p, seeds)
 
     @property
     def backend(self):
