@@ -659,6 +659,124 @@ OH_DEV int free_decide(const FigParams& P, const FigBuffers& D, const GuardBuffe
   }
   return -1;
 }
+// the predicted reduction of the step just solved for (gd = g . z, z2 = |z|^2 over all knots), the line search's two numbers and the damping; the
+// caller counts the step in D.iters
+template <bool GUARD>
+OH_DEV void free_finish(const FigBuffers& D, const GuardBuffers& GB, const int b, const double gd, const double z2, const double mu) {
+  D.pred[b] = -0.5 * gd + 0.5 * mu * z2;
+  if constexpr (GUARD) {
+    GB.ls_gd[b] = gd;
+    GB.ls_q[b] = gd + mu * z2;
+  }
+  D.mu[b] = mu;
+}
+
+// ---- scaffolding of the block-per-instance sweeps (k_step_free_pcr, k_step_free_cp, step_free_bb_block): everything around the linear solve.  The
+// ratio test and the outer-loop decisions are the serial kernel's (free_accept / free_decide) on thread 0, published to the block through the
+// kernel's own LDS words ctl[2] / ctld; each kernel keeps its LDS arrays and passes pointers. ----
+// The instance of a block: blocks are dealt round-robin to the 8 XCDs, XCD x takes the instances [x per, (x + 1) per) -- the stage arrays are read
+// knot-major (a lane's doubles lie a row apart), and instances that share a line go to the same XCD.  May be >= D.B (the grid is rounded up): the
+// block leaves.  free_block_grid is the grid that goes with it.
+OH_DEV int free_block_instance(const FigBuffers& D) {
+  const int per = (D.B + 7) / 8;
+  return (blockIdx.x % 8) * per + blockIdx.x / 8;
+}
+static dim3 free_block_grid(const FigBuffers& D) { return dim3(8 * ((D.B + 7) / 8)); }
+// knots per wavefront of the twisted factorisation (step_free_bb_block) and its dynamic LDS: [2][KH][64] X | w, then [2][KH][8] right-hand sides
+static int free_bb_half(const FigParams& P) { return (P.T - P.t0) - (P.T - P.t0) / 2; }
+static size_t free_bb_lds(const int KH) { return sizeof(double) * 2 * (size_t)KH * 72; }
+
+// Whether the block goes on: not when its instance has finished, nor when it sits this launch out (then it is counted as running, as k_step_free's
+// wrapper does by ballot).
+OH_DEV bool free_block_gate(const FigBuffers& D, const int b, const int tid, int* ctl) {
+  if (tid == 0) ctl[0] = D.status[b] >= 0 ? 0 : (D.skip[b] ? 1 : 2);
+  __syncthreads();
+  const int st = ctl[0];
+  if (st == 0) return false;
+  if (st == 1) {
+    if (tid == 0) {
+      D.skip[b] = 0;
+      atomicAdd(D.n_running, 1);
+    }
+    return false;
+  }
+  return true;
+}
+// The ratio test of a block: the threads with `stage` set put merit / penalty / violation of knot kn of the trial slot into the rows s0 / s1 / s2
+// (kn >= nK: zeros), thread 0 sums them and calls free_accept.  Returns free_accept's verdict to every thread, (cur, mu) in ctl[1] / *ctld.  On 2 the
+// caller scales its part of D.zstep by OH_LS_SHRINK (the layouts differ), then thread 0 does free_line_search's bookkeeping and counts the instance.
+template <int N, bool GUARD>
+OH_DEV int free_block_accept(const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, const int b, const int slot, const int tid, const bool stage,
+                             const int kn, double* s0, double* s1, double* s2, int* ctl, double* ctld) {
+  const int Bp = D.Bp;
+  const int nK = P.T - P.t0;
+  if (stage) {
+    const bool active = kn < nK;
+    const int tl = active ? P.t0 + kn : P.T - 1;
+    s0[kn] = active ? SEL(D.merit, slot)[(size_t)tl * Bp + b] : 0.0;
+    if constexpr (GUARD) {
+      s1[kn] = active ? SEL(GB.psi, slot)[(size_t)tl * Bp + b] : 0.0;
+      s2[kn] = active ? SEL(D.cv, slot)[(size_t)tl * Bp + b] : 0.0;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    atomicAdd(D.work, 1ULL);
+    double f = D.fconst[b], fpsi = 0.0, meas = 0.0;
+    for (int l = 0; l < nK; ++l) {  // in knot order, like the serial sweep
+      f += s0[l];
+      if constexpr (GUARD) {
+        fpsi += s1[l];
+        meas = fmax(meas, s2[l]);
+      }
+    }
+    LMState lm{D.mu[b], D.nun[b]};
+    int cur = 1 - slot;
+    const int act = free_accept<N, GUARD>(P, D, GB, b, slot, f, fpsi, meas, cur, lm);
+    ctl[0] = act;
+    ctl[1] = cur;
+    *ctld = lm.mu;
+  }
+  __syncthreads();
+  return ctl[0];
+}
+// Sum or maximum over the block, every thread gets the result: butterfly in the wavefront, one LDS word per wavefront, combined in wavefront order.
+// SYNC_FIRST: a barrier before the store, for a kernel whose previous reduction into the same row may still have readers.
+template <int NW, bool SYNC_FIRST = false>
+OH_DEV double block_reduce(double v, double* red_row, const int tid, const bool is_max) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const double o = __shfl_xor(v, m);
+    v = is_max ? fmax(v, o) : v + o;
+  }
+  if constexpr (SYNC_FIRST) __syncthreads();
+  if ((tid & 63) == 0) red_row[tid >> 6] = v;
+  __syncthreads();
+  double out = red_row[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) out = is_max ? fmax(out, red_row[w]) : out + red_row[w];
+  return out;
+}
+// free_decide on thread 0, its verdict to every thread: 0 the block returns; 1 a multiplier update -- with al_fuse = 0 without a step (see
+// step_instance_free): the caller zeroes its part of D.zstep, counts the instance and returns; otherwise, and on -1, the step is taken.
+template <int N, bool GUARD>
+OH_DEV int free_block_decide(const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, const int b, const int tid, const double stat, const double mu,
+                             int* ctl) {
+  if (tid == 0) ctl[0] = free_decide<N, GUARD>(P, D, GB, b, stat, mu, D.iters[b]);
+  __syncthreads();
+  return ctl[0];
+}
+// the end of a block's launch: thread 0 books the step (gd, z2: block sums) and counts it (unless free_decide has: a multiplier update with its step
+// taken along, al_fuse) and the instance
+template <bool GUARD>
+OH_DEV void free_block_finish(const FigBuffers& D, const GuardBuffers& GB, const int b, const int tid, const double gd, const double z2, const double mu,
+                              const bool counted) {
+  if (tid == 0) {
+    free_finish<GUARD>(D, GB, b, gd, z2, mu);
+    if (!counted) D.iters[b] += 1;
+    atomicAdd(D.n_running, 1);
+  }
+}
 
 template <int N, bool GUARD, bool VEL = false>
 OH_DEV bool step_instance_free(const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, const int b, const int ts) {
@@ -774,8 +892,8 @@ OH_DEV bool step_instance_free(const FigParams& P, const FigBuffers& D, const Gu
     mu = fmax(4.0 * mu, 1e-2);
   }
   if (!factored) stat = __builtin_nan("");  // no damping (up to 4^40) made the matrix factorisable: free_decide reports NUMERICAL
+  const int r = free_decide<N, GUARD>(P, D, GB, b, stat, mu, iters);
   {
-    const int r = free_decide<N, GUARD>(P, D, GB, b, stat, mu, iters);
     // multiplier update (r == 1).  Until round 5 the instance stayed put for that launch (zero step); now it also takes the step the sweep has just
     // solved for -- small, the inner iteration has converged to omega -- and the evaluation that refreshes the multipliers looks at that point and
     // accepts it as it is (free_accept): 7 of an arm's ~27 launches were updates without a step (port, 64 arms: 26.6 -> 24.8 steps, slowest 48 -> 44)
@@ -835,13 +953,8 @@ OH_DEV bool step_instance_free(const FigParams& P, const FigBuffers& D, const Gu
         z2 += zz[a] * zz[a];
       }
     }
-    D.pred[b] = -0.5 * gd + 0.5 * mu * z2;
-    if constexpr (GUARD) {
-      GB.ls_gd[b] = gd;
-      GB.ls_q[b] = gd + mu * z2;
-    }
+    free_finish<GUARD>(D, GB, b, gd, z2, mu);
   }
-  D.mu[b] = mu;
   D.iters[b] = iters + 1;
   return true;
 }
@@ -872,7 +985,6 @@ __global__ __launch_bounds__(64) void k_step_free(FigParams P, FigBuffers D, Gua
 // goes through LDS in two passes (A^{-1} L and A^{-1} r, then A^{-1} U: 56 rows x NT lanes = 57 KB at NT = 128).  All pivots are positive
 // definite iff the matrix is (Haynsworth: each level is a Schur complement onto the lanes of one parity class), so the damping loop raises mu
 // exactly when the serial sweep would.  The ratio test and the outer-loop decisions are the serial kernel's (free_accept / free_decide, lane 0).
-// The stage arrays are read knot-major (a lane's doubles lie a row apart): instances that share a line are dealt to the same XCD.
 template <int N, bool GUARD, int NT, bool VEL = false>
 __global__ __launch_bounds__(NT) void k_step_free_pcr(FigParams P, FigBuffers D, GuardBuffers GB, const int slot_batch) {
   constexpr int NP = N * (N + 1) / 2;
@@ -881,8 +993,7 @@ __global__ __launch_bounds__(NT) void k_step_free_pcr(FigParams P, FigBuffers D,
   __shared__ double red[3][2];
   __shared__ int ctl[2];
   __shared__ double ctld;
-  const int per = (D.B + 7) / 8;  // blocks are dealt round-robin to the 8 XCDs: XCD x takes the instances [x per, (x + 1) per)
-  const int b = (blockIdx.x % 8) * per + blockIdx.x / 8;
+  const int b = free_block_instance(D);
   if (b >= D.B) return;
   const int slot = OH_FREE_SLOT(D, b);  // (uniform over the block: one instance)
   const int lane = threadIdx.x;
@@ -894,19 +1005,9 @@ __global__ __launch_bounds__(NT) void k_step_free_pcr(FigParams P, FigBuffers D,
   const int tl = active ? t : T - 1;
   const bool last = (t == T - 1);
   const double kap2 = 2.0 * P.kappa;
-  if (lane == 0) ctl[0] = D.status[b] >= 0 ? 0 : (D.skip[b] ? 1 : 2);
-  __syncthreads();
-  {
-    const int st = ctl[0];
-    if (st == 0) return;
-    if (st == 1) {  // sits this launch out (k_step_free's wrapper)
-      if (lane == 0) {
-        D.skip[b] = 0;
-        atomicAdd(D.n_running, 1);
-      }
-      return;
-    }
-  }
+  if (!free_block_gate(D, b, lane, ctl)) return;
+  // (the ratio test and the reduction are spelt out in this kernel, not taken from free_block_accept / block_reduce: with either of them
+  // <6, true, 128> takes 1.6 % longer per launch, profiles/free_sweeps_scaffold_ab.json)
   sm[0][lane] = active ? SEL(D.merit, slot)[(size_t)tl * Bp + b] : 0.0;
   if constexpr (GUARD) {
     sm[1][lane] = active ? SEL(GB.psi, slot)[(size_t)tl * Bp + b] : 0.0;
@@ -1080,9 +1181,7 @@ __global__ __launch_bounds__(NT) void k_step_free_pcr(FigParams P, FigBuffers D,
     mu = fmax(4.0 * mu, 1e-2);
   }
   if (!factored) stat = __builtin_nan("");  // (see step_instance_free)
-  if (lane == 0) ctl[0] = free_decide<N, GUARD>(P, D, GB, b, stat, mu, D.iters[b]);
-  __syncthreads();
-  const int dec = ctl[0];
+  const int dec = free_block_decide<N, GUARD>(P, D, GB, b, lane, stat, mu, ctl);
   if (dec == 0) return;
   if (dec == 1 && !P.al_fuse) {  // outer iteration without a step (al_fuse = 0; see step_instance_free)
     if (active) {
@@ -1103,18 +1202,16 @@ __global__ __launch_bounds__(NT) void k_step_free_pcr(FigParams P, FigBuffers D,
   }
   gd = block_sum(gd, 1, false);
   z2 = block_sum(z2, 2, false);
-  if (lane == 0) {
-    D.pred[b] = -0.5 * gd + 0.5 * mu * z2;
-    if constexpr (GUARD) {
-      GB.ls_gd[b] = gd;
-      GB.ls_q[b] = gd + mu * z2;
-    }
-    D.mu[b] = mu;
-    if (dec != 1) D.iters[b] += 1;  // (a multiplier update was counted by free_decide)
-    atomicAdd(D.n_running, 1);
-  }
+  free_block_finish<GUARD>(D, GB, b, lane, gd, z2, mu, dec == 1);
 }
 
+// hardware reciprocal, two Newton steps: to the last bit or two (an IEEE division is 30 instructions on the critical path of every pivot)
+OH_DEV double rcp_newton2(const double x) {
+  double d = __builtin_amdgcn_rcp(x);
+  d = d * fma(-x, d, 2.0);
+  d = d * fma(-x, d, 2.0);
+  return d;
+}
 // K3 of a latency-bound launch, round 4: one block of two wavefronts per instance, the block-tridiagonal system solved by a twisted factorisation
 // ("burn at both ends").  Wavefront 0 eliminates the knots 0, 1, .. m-1 downwards, wavefront 1 the knots nK-1, .. m+1 upwards at the same time;
 // knot m then sees both neighbours eliminated, its solve gives z_m, and the two halves substitute back outwards in parallel: T / 2 dependent knots each
@@ -1137,8 +1234,7 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
   __shared__ int ctl[2];
   __shared__ double ctld;
   __shared__ double zmid[8];
-  const int per = (D.B + 7) / 8;  // blocks are dealt round-robin to the 8 XCDs: XCD x takes the instances [x per, (x + 1) per)
-  const int b = (blockIdx.x % 8) * per + blockIdx.x / 8;
+  const int b = free_block_instance(D);
   if (b >= D.B) return;
   const int slot = OH_FREE_SLOT(D, b);
   const int lane = threadIdx.x;
@@ -1163,48 +1259,10 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
       if (w == 12 + k) wi = __builtin_nontemporal_load(iptr[k] + b);
     if (wd == -1.2345e300 || wi == -2047483647) sm[2][lane] = 1.0;  // (keeps the loads; never true)
   }
-  if (lane == 0) ctl[0] = D.status[b] >= 0 ? 0 : (D.skip[b] ? 1 : 2);
-  __syncthreads();
-  {
-    const int st = ctl[0];
-    if (st == 0) return;
-    if (st == 1) {
-      if (lane == 0) {
-        D.skip[b] = 0;
-        atomicAdd(D.n_running, 1);
-      }
-      return;
-    }
-  }
-  {
-    const bool act = lane < nK;
-    const int tl = act ? P.t0 + lane : T - 1;
-    sm[0][lane] = act ? SEL(D.merit, slot)[(size_t)tl * Bp + b] : 0.0;
-    if constexpr (GUARD) {
-      sm[1][lane] = act ? SEL(GB.psi, slot)[(size_t)tl * Bp + b] : 0.0;
-      sm[2][lane] = act ? SEL(D.cv, slot)[(size_t)tl * Bp + b] : 0.0;
-    }
-  }
-  __syncthreads();
-  if (lane == 0) {
-    atomicAdd(D.work, 1ULL);
-    double f = D.fconst[b], fpsi = 0.0, meas = 0.0;
-    for (int l = 0; l < nK; ++l) {  // in knot order, like the serial sweep
-      f += sm[0][l];
-      if constexpr (GUARD) {
-        fpsi += sm[1][l];
-        meas = fmax(meas, sm[2][l]);
-      }
-    }
-    LMState lm{D.mu[b], D.nun[b]};
-    int cur = 1 - slot;
-    ctl[0] = free_accept<N, GUARD>(P, D, GB, b, slot, f, fpsi, meas, cur, lm);
-    ctl[1] = cur;
-    ctld = lm.mu;
-  }
-  __syncthreads();
-  if (ctl[0] == 0) return;
-  if (ctl[0] == 2) {  // line search: the rejected step again, shorter
+  if (!free_block_gate(D, b, lane, ctl)) return;
+  const int act = free_block_accept<N, GUARD>(P, D, GB, b, slot, lane, true, lane, sm[0], sm[1], sm[2], ctl, &ctld);
+  if (act == 0) return;
+  if (act == 2) {  // line search: the rejected step again, shorter
     if (lane < nK) {
       const int t = P.t0 + lane;
 #pragma unroll
@@ -1215,6 +1273,7 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
   }
   const int cur = ctl[1];
   double mu = ctld;
+  // (not block_reduce: with it a launch with velocity rows at T = 100 takes 0.4 % longer, profiles/free_sweeps_scaffold_ab.json)
   auto block_sum = [&](double v, const int slot_r, const bool is_max) {  // all lanes get the result
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -1235,10 +1294,8 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
     for (int a = 0; a < N; ++a) stat = fmax(stat, fabs(gtc[GTX(t, a)]));
   }
   stat = block_sum(stat, 0, true);
-  if (lane == 0) ctl[0] = free_decide<N, GUARD>(P, D, GB, b, stat, mu, D.iters[b]);
-  __syncthreads();
   {
-    const int dec = ctl[0];
+    const int dec = free_block_decide<N, GUARD>(P, D, GB, b, lane, stat, mu, ctl);
     if (dec == 0) return;
     if (dec == 1 && !P.al_fuse) {  // outer iteration without a step (al_fuse = 0; see step_instance_free)
       if (lane < nK) {
@@ -1324,9 +1381,7 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
         const double v0 = __shfl(a, 8 * j + c), v1 = __shfl(a, 8 * j + 8 + c);
         const double det = fma(p00, p11, -(p01 * p01));
         if (!(p00 > 1e-12) || !(det > 1e-14 * p00 * p11) || !(det < 1e300)) ok = false;
-        double d = __builtin_amdgcn_rcp(det);
-        d = d * fma(-det, d, 2.0);
-        d = d * fma(-det, d, 2.0);
+        const double d = rcp_newton2(det);
         const double q00 = p11 * d, q01 = -(p01 * d), q11 = p00 * d;
         const double w0 = fma(q00, v0, q01 * v1), w1 = fma(q01, v0, q11 * v1);  // rows of Q a[J][c]
         const double gen = a - fma(u0, w0, u1 * w1);
@@ -1341,9 +1396,7 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
         const double piv = readlane_f64(a, 9 * j);
         const double cj = __shfl(a, 8 * r + j), rj = __shfl(a, 8 * j + c);
         if (!(piv > 1e-12) || !(piv < 1e300)) ok = false;
-        double d = __builtin_amdgcn_rcp(piv);
-        d = d * fma(-piv, d, 2.0);
-        d = d * fma(-piv, d, 2.0);
+        const double d = rcp_newton2(piv);
         const double gen = fma(-(cj * rj), d, a), sc = a * d;
         a = (r == j) ? ((c == j) ? d : sc) : ((c == j) ? -sc : gen);
       }
@@ -1400,16 +1453,7 @@ OH_DEV void step_free_bb_block(const FigParams& P, const FigBuffers& D, const Gu
   }
   gd = block_sum(gd, 1, false);
   z2 = block_sum(z2, 2, false);
-  if (lane == 0) {
-    D.pred[b] = -0.5 * gd + 0.5 * mu * z2;
-    if constexpr (GUARD) {
-      GB.ls_gd[b] = gd;
-      GB.ls_q[b] = gd + mu * z2;
-    }
-    D.mu[b] = mu;
-    if (!upd) D.iters[b] += 1;  // (a multiplier update was counted by free_decide)
-    atomicAdd(D.n_running, 1);
-  }
+  free_block_finish<GUARD>(D, GB, b, lane, gd, z2, mu, upd);
 }
 
 template <int N, bool GUARD, bool VEL = false>
@@ -1424,8 +1468,7 @@ __global__ __launch_bounds__(128) void k_step_free_bb(FigParams P, FigBuffers D,
 template <int N>
 __global__ __launch_bounds__(128) void k_free_persist(FigParams P, FigBuffers D, GuardParams GP, GuardBuffers GB, const int KH, const int max_rounds) {
   __shared__ int go;
-  const int per = (D.B + 7) / 8;
-  const int b = (blockIdx.x % 8) * per + blockIdx.x / 8;  // (as step_free_bb_block deals the instances)
+  const int b = free_block_instance(D);
   if (b >= D.B) return;
   const int lane = threadIdx.x;
   const int nK = P.T - P.t0;
@@ -1462,8 +1505,7 @@ __global__ __launch_bounds__(8 * KN) void k_step_free_cp(FigParams P, FigBuffers
   __shared__ double red[3][NW];
   __shared__ int ctl[2];
   __shared__ double ctld;
-  const int per = (D.B + 7) / 8;  // blocks are dealt round-robin to the 8 XCDs (see k_step_free_pcr)
-  const int b = (blockIdx.x % 8) * per + blockIdx.x / 8;
+  const int b = free_block_instance(D);
   if (b >= D.B) return;
   const int slot = OH_FREE_SLOT(D, b);  // (uniform over the block: one instance)
   const int tid = threadIdx.x;
@@ -1478,71 +1520,21 @@ __global__ __launch_bounds__(8 * KN) void k_step_free_cp(FigParams P, FigBuffers
   const int cr = row ? c : 0;
   const bool last = (t == T - 1);
   const double kap2 = 2.0 * P.kappa;
-  if (tid == 0) ctl[0] = D.status[b] >= 0 ? 0 : (D.skip[b] ? 1 : 2);
-  __syncthreads();
-  {
-    const int st = ctl[0];
-    if (st == 0) return;
-    if (st == 1) {
-      if (tid == 0) {
-        D.skip[b] = 0;
-        atomicAdd(D.n_running, 1);
-      }
-      return;
-    }
-  }
-  if (c == 0) {
-    TY[0][kn] = active ? SEL(D.merit, slot)[(size_t)tl * Bp + b] : 0.0;
-    if constexpr (GUARD) {
-      TY[1][kn] = active ? SEL(GB.psi, slot)[(size_t)tl * Bp + b] : 0.0;
-      TY[2][kn] = active ? SEL(D.cv, slot)[(size_t)tl * Bp + b] : 0.0;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    atomicAdd(D.work, 1ULL);
-    double f = D.fconst[b], fpsi = 0.0, meas = 0.0;
-    for (int l = 0; l < nK; ++l) {  // in knot order, like the serial sweep
-      f += TY[0][l];
-      if constexpr (GUARD) {
-        fpsi += TY[1][l];
-        meas = fmax(meas, TY[2][l]);
-      }
-    }
-    LMState lm{D.mu[b], D.nun[b]};
-    int cur = 1 - slot;
-    ctl[0] = free_accept<N, GUARD>(P, D, GB, b, slot, f, fpsi, meas, cur, lm);
-    ctl[1] = cur;
-    ctld = lm.mu;
-  }
-  __syncthreads();
-  if (ctl[0] == 0) return;
-  if (ctl[0] == 2) {  // line search: the rejected step again, shorter
+  if (!free_block_gate(D, b, tid, ctl)) return;
+  const int act = free_block_accept<N, GUARD>(P, D, GB, b, slot, tid, c == 0, kn, TY[0], TY[1], TY[2], ctl, &ctld);
+  if (act == 0) return;
+  if (act == 2) {  // line search: the rejected step again, shorter
     if (active && row) D.zstep[IDX(t, N, c)] *= OH_LS_SHRINK;
     if (tid == 0 && free_line_search<GUARD>(P, D, GB, b)) atomicAdd(D.n_running, 1);
     return;
   }
   const int cur = ctl[1];
   double mu = ctld;
-  auto block_sum = [&](double v, const int slot_r, const bool is_max) {  // all lanes get the result
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const double o = __shfl_xor(v, m);
-      v = is_max ? fmax(v, o) : v + o;
-    }
-    __syncthreads();  // (the previous reduction's readers are through)
-    if ((tid & 63) == 0) red[slot_r][tid >> 6] = v;
-    __syncthreads();
-    double out = red[slot_r][0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) out = is_max ? fmax(out, red[slot_r][w]) : out + red[slot_r][w];
-    return out;
-  };
   const double* __restrict__ Drc = cur ? D.Dr[1] : D.Dr[0];
   const double* __restrict__ gtc = cur ? D.gt[1] : D.gt[0];
   const double* __restrict__ Ec = cur ? D.E[1] : D.E[0];
   const double gmine = (active && row) ? gtc[GTX(tl, cr)] : 0.0;
-  const double stat = block_sum(fabs(gmine), 0, true);
+  double stat = block_reduce<NW, true>(fabs(gmine), red[0], tid, true);  // (barrier first: the previous reduction's readers are through)
   double z = 0.0;  // the step component (t, c) at the end
   bool factored = false;
   for (int attempt = 0; attempt < 40; ++attempt) {
@@ -1665,11 +1657,8 @@ __global__ __launch_bounds__(8 * KN) void k_step_free_cp(FigParams P, FigBuffers
     }
     mu = fmax(4.0 * mu, 1e-2);
   }
-  double stat_out = stat;
-  if (!factored) stat_out = __builtin_nan("");  // (see step_instance_free)
-  if (tid == 0) ctl[0] = free_decide<N, GUARD>(P, D, GB, b, stat_out, mu, D.iters[b]);
-  __syncthreads();
-  const int dec = ctl[0];
+  if (!factored) stat = __builtin_nan("");  // (see step_instance_free)
+  const int dec = free_block_decide<N, GUARD>(P, D, GB, b, tid, stat, mu, ctl);
   if (dec == 0) return;
   if (dec == 1 && !P.al_fuse) {  // outer iteration without a step (al_fuse = 0; see step_instance_free)
     if (active && row) D.zstep[IDX(t, N, c)] = 0.0;
@@ -1682,18 +1671,9 @@ __global__ __launch_bounds__(8 * KN) void k_step_free_cp(FigParams P, FigBuffers
     gd = gmine * z;
     z2 = z * z;
   }
-  gd = block_sum(gd, 1, false);
-  z2 = block_sum(z2, 2, false);
-  if (tid == 0) {
-    D.pred[b] = -0.5 * gd + 0.5 * mu * z2;
-    if constexpr (GUARD) {
-      GB.ls_gd[b] = gd;
-      GB.ls_q[b] = gd + mu * z2;
-    }
-    D.mu[b] = mu;
-    if (dec != 1) D.iters[b] += 1;  // (a multiplier update was counted by free_decide)
-    atomicAdd(D.n_running, 1);
-  }
+  gd = block_reduce<NW, true>(gd, red[1], tid, false);
+  z2 = block_reduce<NW, true>(z2, red[2], tid, false);
+  free_block_finish<GUARD>(D, GB, b, tid, gd, z2, mu, dec == 1);
 }
 
 // Chain lengths (round 5): the one-thread-per-unit kernels of this family are instantiated for 2 ... 8 actuated joints (planar_3dof, the tester
@@ -1727,11 +1707,11 @@ bool oh_launch_couple_free(hipStream_t s, int n, const FigParams& P, const FigBu
 // the block-per-instance sweeps (FREE_PCR, FREE_CP, FREE_BB; the knots fit 128 lanes, 64 for FREE_CP: the host's choice)
 template <int N, bool GUARD, bool VEL = false>
 static void launch_step_free_block(hipStream_t s, const FigParams& P, const FigBuffers& D, const GuardBuffers& GB, int slot, FreeSweep sweep) {
-  const dim3 g(8 * ((D.B + 7) / 8));
+  const dim3 g = free_block_grid(D);
   if constexpr (N == 7) {
     if (sweep == FREE_BB) {
-      const int nK = P.T - P.t0, KH = nK - nK / 2;
-      hipLaunchKernelGGL((k_step_free_bb<N, GUARD, VEL>), g, dim3(128), sizeof(double) * 2 * (size_t)KH * 72, s, P, D, GB, slot, KH);
+      const int KH = free_bb_half(P);
+      hipLaunchKernelGGL((k_step_free_bb<N, GUARD, VEL>), g, dim3(128), free_bb_lds(KH), s, P, D, GB, slot, KH);
       return;
     }
   }
@@ -1761,9 +1741,9 @@ bool oh_launch_setup_guards(hipStream_t s, int n, const FigParams& P, const FigB
   return true;
 }
 bool oh_launch_free_persist(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB) {
-  const int nK = P.T - P.t0, KH = nK - nK / 2;
+  const int nK = P.T - P.t0, KH = free_bb_half(P);
   if (n != 7 || nK > 128) return false;  // (instantiated for 7 joints; the LDS holds up to 128 knots)
-  hipLaunchKernelGGL(k_free_persist<7>, dim3(8 * ((D.B + 7) / 8)), dim3(128), sizeof(double) * 2 * (size_t)KH * 72, s, P, D, GP, GB, KH, 2 * P.max_iter + 8);
+  hipLaunchKernelGGL(k_free_persist<7>, free_block_grid(D), dim3(128), free_bb_lds(KH), s, P, D, GP, GB, KH, 2 * P.max_iter + 8);
   return true;
 }
 bool oh_launch_eval_guarded(hipStream_t s, int n, const FigParams& P, const FigBuffers& D, const GuardParams& GP, const GuardBuffers& GB, int slot) {
