@@ -36,9 +36,8 @@ extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
     std::vector<char> dep((size_t)d->len, 0);
     std::vector<int> list;
     for (int i = 0; i < d->len; ++i) {
-      const int o = d->op[i];
-      const bool two = tape_op_arity(o) == 2, one = tape_op_arity(o) == 1;
-      dep[i] = o == 1 || ((one || two) && dep[d->a[i]]) || (two && dep[d->b[i]]);
+      const int o = d->op[i], n = tape_op_arity(o);
+      dep[i] = o == OP_X || (n >= 1 && dep[d->a[i]]) || (n == 2 && dep[d->b[i]]);
       if (dep[i]) list.push_back(i);
     }
     qp.xdep.release();

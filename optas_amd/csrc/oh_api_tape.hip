@@ -11,11 +11,9 @@ int tape_validate(const oh_tape_desc* d, const char* who) {
       !d->b || !d->c || (d->n_ineq + d->n_eq > 0 && !d->rows) || d->out_cost < 0 || d->out_cost >= d->len)
     return fail(OH_ERR_INVALID, (w + ": bad sizes or null arrays").c_str());
   for (int i = 0; i < d->len; ++i) {
-    const int o = d->op[i];
-    const bool two = (o >= 3 && o <= 6) || o == 10 || (o >= 15 && o <= 20) || (o >= 22 && o <= 24);
-    const bool one = o == 7 || o == 8 || o == 9 || o == 11 || o == 12 || o == 13 || o == 14 || o == 21 || o == 25 || o == 26;
-    if (o < 0 || o > 26 || (o == 1 && (d->a[i] < 0 || d->a[i] >= d->nx)) || (o == 2 && (d->a[i] < 0 || d->a[i] >= d->np)) ||
-        ((one || two) && (d->a[i] < 0 || d->a[i] >= i)) || (two && (d->b[i] < 0 || d->b[i] >= i)))
+    const int o = d->op[i], n = tape_op_arity(o);  // (b of a unary instruction is not looked at, here or by any evaluator)
+    if (o < 0 || o >= OP_COUNT || (o == OP_X && (d->a[i] < 0 || d->a[i] >= d->nx)) || (o == OP_P && (d->a[i] < 0 || d->a[i] >= d->np)) ||
+        (n >= 1 && (d->a[i] < 0 || d->a[i] >= i)) || (n == 2 && (d->b[i] < 0 || d->b[i] >= i)))
       return fail(OH_ERR_INVALID, (w + ": malformed instruction (operands must be earlier registers / valid indices)").c_str());
   }
   for (int i = 0; i < d->n_ineq + d->n_eq; ++i)
@@ -123,21 +121,11 @@ extern "C" int oh_create_tape(const oh_tape_desc* d, oh_handle** out) {
     delete h;  // (releases the wavefront schedule / the generated module as well)
     return rc;
   }
-  // the interpreter's copy of the opcodes carries bit 5 on every instruction that neither the cost nor a row depends on: its reverse sweep passes them by
-  // (oh_tape.hip:InterpEval::reverse), as the generated code and the wavefront schedule do
+  // the interpreter's copy of the opcodes carries OP_DEAD on every instruction that neither the cost nor a row depends on (oh_tape_ops.h)
   std::vector<int> op_dev(d->op, d->op + d->len);
-  {
-    std::vector<char> live(d->len, 0);
-    live[d->out_cost] = 1;
-    for (int i = 0; i < d->n_ineq + d->n_eq; ++i) live[d->rows[i]] = 1;
-    for (int i = d->len - 1; i >= 0; --i) {
-      if (!live[i]) { op_dev[i] |= 32; continue; }
-      if (d->op[i] >= 3) {
-        live[d->a[i]] = 1;
-        if (tape_op_arity(d->op[i]) == 2) live[d->b[i]] = 1;
-      }
-    }
-  }
+  const std::vector<char> live = tape_live(d->len, d->op, d->a, d->b, d->rows, d->n_ineq + d->n_eq, d->out_cost);
+  for (int i = 0; i < d->len; ++i)
+    if (!live[i]) op_dev[i] |= OP_DEAD;
   if ((rc = upload_tape(h, d, op_dev.data()))) {
     delete h;
     return rc;

@@ -175,6 +175,7 @@ int oh_launch_qp_solve_block(hipStream_t s, const QpParams& Q, int B, const doub
 #define OH_TAPE_ST_MAX_ITER OH_STATUS_MAX_ITER
 #define OH_TAPE_ST_NUMERICAL OH_STATUS_NUMERICAL
 #include "oh_tape_solver.h"  // TapeParams, TapeWork and the solver shared by the interpreter and the generated code
+#include "oh_tape_ops.h"     // the tape vocabulary: named opcodes, arity, value and adjoint rule of each, liveness
 // QP data read off a tape on the device (oh_qp_set_tape): val = [T.len][Bp] work, rows_out = [B][Q.np], f0 = [B]
 void oh_launch_qp_assemble(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
                            const int* xdep, int n_xdep, int B, int Bp, const double* p_raw, double* val, double* rows_out, double* f0);  // xdep: x-dependent instructions

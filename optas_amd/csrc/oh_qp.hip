@@ -480,6 +480,16 @@ struct QpTape {
 };
 constexpr int QP_SMALL_N = 32;  // n of the handles these two kernels serve (their per-lane and static LDS arrays); larger ones: k_qp_assemble_block
 #define QIDX(i) ((size_t)(i) * Bp + b)
+// What tape_value (oh_tape_ops.h) sees of an instruction here: operand values the caller has loaded (b only where the opcode has one).  CONST, X and P
+// never arrive (what X loads is what the two assemblies differ in), nor do ADD, SUB and MUL, which the callers keep as cases of their own.
+struct QpRegs {
+  const double va, vb;
+  __device__ double cst() const { return 0.0; }
+  __device__ double x() const { return 0.0; }
+  __device__ double p() const { return 0.0; }
+  __device__ double a() const { return va; }
+  __device__ double b() const { return vb; }
+};
 // FULL: every instruction; else only the x-dependent ones (the others keep the values of an earlier full sweep at the same p)
 template <bool FULL>
 __device__ double qp_tape_forward(const QpTape& tp, const double* xs, const double* __restrict__ pb, double* __restrict__ val, const int Bp, const int b) {
@@ -490,13 +500,13 @@ __device__ double qp_tape_forward(const QpTape& tp, const double* xs, const doub
     const int o = tp.op[i], ia = tp.a[i], ib = tp.bb[i];
     double v;
     switch (o) {
-      case 0: v = tp.c[i]; break;
-      case 1: v = xs[ia]; break;
-      case 2: v = pb[ia]; break;
-      case 3: v = val[QIDX(ia)] + val[QIDX(ib)]; break;
-      case 4: v = val[QIDX(ia)] - val[QIDX(ib)]; break;
-      case 5: v = val[QIDX(ia)] * val[QIDX(ib)]; break;
-      default: v = tape_op_value(o, val[QIDX(ia)], tape_op_arity(o) == 2 ? val[QIDX(ib)] : 0.0); break;  // 6 .. 26 (coefficients may be any function of p)
+      case OP_CONST: v = tp.c[i]; break;
+      case OP_X: v = xs[ia]; break;
+      case OP_P: v = pb[ia]; break;
+      case OP_ADD: v = val[QIDX(ia)] + val[QIDX(ib)]; break;  // (these three make up a QP's tape: as cases of their own 0.5 - 2 % faster, 72-variable MPC at B = 256)
+      case OP_SUB: v = val[QIDX(ia)] - val[QIDX(ib)]; break;
+      case OP_MUL: v = val[QIDX(ia)] * val[QIDX(ib)]; break;
+      default: v = tape_value(o, QpRegs{val[QIDX(ia)], tape_op_arity(o) == 2 ? val[QIDX(ib)] : 0.0}); break;  // (coefficients may be any function of p)
     }
     val[QIDX(i)] = v;
   }
@@ -648,13 +658,13 @@ __global__ __launch_bounds__(64) void k_qp_assemble_block(QpParams Q, QpTape tp,
       const int o = tp.op[k], ia = tp.a[k], ib = tp.bb[k];
       double v;
       switch (o) {
-        case 0: v = tp.c[k]; break;
-        case 1: v = (ia == pi || ia == pj) ? sign : 0.0; break;
-        case 2: v = pb[ia]; break;
-        case 3: v = val[QIDX(ia)] + val[QIDX(ib)]; break;
-        case 4: v = val[QIDX(ia)] - val[QIDX(ib)]; break;
-        case 5: v = val[QIDX(ia)] * val[QIDX(ib)]; break;
-        default: v = tape_op_value(o, val[QIDX(ia)], tape_op_arity(o) == 2 ? val[QIDX(ib)] : 0.0); break;
+        case OP_CONST: v = tp.c[k]; break;
+        case OP_X: v = (ia == pi || ia == pj) ? sign : 0.0; break;
+        case OP_P: v = pb[ia]; break;
+        case OP_ADD: v = val[QIDX(ia)] + val[QIDX(ib)]; break;  // (as in qp_tape_forward)
+        case OP_SUB: v = val[QIDX(ia)] - val[QIDX(ib)]; break;
+        case OP_MUL: v = val[QIDX(ia)] * val[QIDX(ib)]; break;
+        default: v = tape_value(o, QpRegs{val[QIDX(ia)], tape_op_arity(o) == 2 ? val[QIDX(ib)] : 0.0}); break;
       }
       val[QIDX(k)] = v;
     }

@@ -5,10 +5,12 @@
 //
 // One thread owns one instance.  An evaluation is one forward sweep and ONE reverse sweep seeded with the augmented-Lagrangian weights of
 // all rows at once (cost 1, equality rows -mu + rho c, active inequality rows -(lam - rho g)), so the gradient of the merit costs two
-// passes over the tape whatever the number of rows.  Two evaluators share the solver of oh_tape_solver.h:
-//   * the interpreter below: all lanes of a wavefront execute the same tape instruction on registers that live in HBM/L2 as val[i][b]
-//     (every access one coalesced line).  No set-up cost, but each instruction is a dependent memory round trip: latency bound;
-//   * straight-line HIP code generated from the tape and compiled with hiprtc for gfx950 when the handle is created (desc.jit): SSA values
+// passes over the tape whatever the number of rows.  What an opcode computes and how its adjoint propagates is stated in oh_tape_ops.h; this file holds
+// the two thread-per-instance evaluators behind the solver of oh_tape_solver.h (the third, one wavefront per instance, is oh_tape_wave.hip):
+//   * the interpreter (InterpEval; k_tape_solve, k_tape_phi, k_tape_probe, and with tangents beside it k_tape_hvp): all lanes of a wavefront execute
+//     the same tape instruction on registers that live in HBM/L2 as val[i][b] (every access one coalesced line).  No set-up cost, but each
+//     instruction is a dependent memory round trip: latency bound;
+//   * straight-line HIP code written by generate() below and compiled with hiprtc for gfx950 when the handle is created (desc.jit): SSA values
 //     become VGPRs, the device compiler schedules, folds and shares the transcendentals.  Both compute the same IEEE operations in the
 //     same order (contraction is switched off inside the generated evaluator), so they agree bit for bit.
 // numpy restatement of evaluator and solver: oracle/tape_ref.py.
@@ -38,6 +40,30 @@ struct TapeView {
   const int* __restrict__ rows;
 };
 
+// What the rules of oh_tape_ops.h see of instruction i of an interpreter: a register read is a load from val[register][lane], a contribution a
+// read-modify-write of adj[register][lane] (TIDX), each a dependent round trip -- a rule that does not name an operand does not load it.
+struct InterpRegs {
+  const TapeView& tv;
+  const double* __restrict__ val;
+  double* __restrict__ adj;
+  const double* __restrict__ xs;   // the point, [variable][lane]
+  const double* __restrict__ pb;   // the instance's parameters
+  double* __restrict__ grad;       // [variable][lane]
+  const int i, ia, ib, Bp, lane;
+  __device__ size_t at(const int r) const { return (size_t)r * Bp + lane; }
+  __device__ double cst() const { return tv.c[i]; }
+  __device__ double x() const { return xs[at(ia)]; }
+  __device__ double p() const { return pb[ia]; }
+  __device__ double a() const { return val[at(ia)]; }
+  __device__ double b() const { return val[at(ib)]; }
+  __device__ double self() const { return val[at(i)]; }
+  __device__ void add_a(const double v) { adj[at(ia)] += v; }
+  __device__ void add_b(const double v) { adj[at(ib)] += v; }
+  __device__ void sub_a(const double v) { adj[at(ia)] -= v; }
+  __device__ void sub_b(const double v) { adj[at(ib)] -= v; }
+  __device__ void add_x(const double v) { grad[at(ia)] += v; }
+};
+
 struct InterpEval {
   const TapeParams& T;
   const TapeView& tv;
@@ -51,40 +77,8 @@ struct InterpEval {
   __device__ void forward(const double* __restrict__ xs) {
 #pragma clang fp contract(off)
     for (int i = 0; i < T.len; ++i) {
-      const int o = tv.op[i] & 31, ia = tv.a[i], ib = tv.bb[i];  // (bit 5: dead, see reverse)
-      double v;
-      switch (o) {
-        case 0: v = tv.c[i]; break;
-        case 1: v = xs[TIDX(ia)]; break;
-        case 2: v = pb[ia]; break;
-        case 3: v = val[TIDX(ia)] + val[TIDX(ib)]; break;
-        case 4: v = val[TIDX(ia)] - val[TIDX(ib)]; break;
-        case 5: v = val[TIDX(ia)] * val[TIDX(ib)]; break;
-        case 6: v = val[TIDX(ia)] / val[TIDX(ib)]; break;
-        case 7: v = -val[TIDX(ia)]; break;
-        case 8: v = sin(val[TIDX(ia)]); break;
-        case 9: v = cos(val[TIDX(ia)]); break;
-        case 10: v = atan2(val[TIDX(ia)], val[TIDX(ib)]); break;
-        case 11: v = sqrt(val[TIDX(ia)]); break;
-        case 12: { const double t = val[TIDX(ia)]; v = t * t; } break;
-        // round 4: the rest of what the reference's graphs emit (Quaternion.getrpy, optas.clip): values as casadi's SX machine computes them
-        case 13: v = asin(val[TIDX(ia)]); break;
-        case 14: v = fabs(val[TIDX(ia)]); break;
-        case 15: v = fmin(val[TIDX(ia)], val[TIDX(ib)]); break;
-        case 16: v = fmax(val[TIDX(ia)], val[TIDX(ib)]); break;
-        case 17: v = val[TIDX(ia)] < val[TIDX(ib)] ? 1.0 : 0.0; break;
-        case 18: v = val[TIDX(ia)] <= val[TIDX(ib)] ? 1.0 : 0.0; break;
-        case 19: v = val[TIDX(ia)] == val[TIDX(ib)] ? 1.0 : 0.0; break;
-        case 20: v = val[TIDX(ia)] != val[TIDX(ib)] ? 1.0 : 0.0; break;
-        case 21: v = val[TIDX(ia)] == 0.0 ? 1.0 : 0.0; break;
-        case 22: v = (val[TIDX(ia)] != 0.0 && val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; break;
-        case 23: v = (val[TIDX(ia)] != 0.0 || val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; break;
-        case 24: v = val[TIDX(ia)] != 0.0 ? val[TIDX(ib)] : 0.0; break;  // if_else_zero
-        // round 5: exp and log -- with them the walker expresses pow, tanh, sinh, cosh, acos, atan, the inverse hyperbolics (casadi_tape.py)
-        case 25: v = exp(val[TIDX(ia)]); break;
-        default: v = log(val[TIDX(ia)]); break;  // 26
-      }
-      val[TIDX(i)] = v;
+      const int o = tv.op[i] & OP_MASK;
+      val[TIDX(i)] = tape_value(o, InterpRegs{tv, val, adj, xs, pb, nullptr, i, tv.a[i], tv.bb[i], Bp, b});
     }
   }
 
@@ -94,33 +88,10 @@ struct InterpEval {
     for (int k = 0; k < T.nx; ++k) grad[TIDX(k)] = 0.0;
     for (int i = T.len - 1; i >= 0; --i) {
       const double w = adj[TIDX(i)];
-      const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
-      // An instruction neither the cost nor a row depends on (marked by the host, oh_create_tape) has no part in the gradient: the generated code and the
-      // wavefront schedule leave it out, and so does this sweep -- its adjoint is 0, but 0 times a non-finite partial derivative (a dead x / 0) is not.
-      if (o & 32) continue;
-      switch (o) {
-        case 0: case 2: break;
-        case 1: grad[TIDX(ia)] += w; break;
-        case 3: adj[TIDX(ia)] += w; adj[TIDX(ib)] += w; break;
-        case 4: adj[TIDX(ia)] += w; adj[TIDX(ib)] -= w; break;
-        case 5: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; adj[TIDX(ia)] += w * vb; adj[TIDX(ib)] += w * va; } break;
-        case 6: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; adj[TIDX(ia)] += w / vb; adj[TIDX(ib)] -= w * va / (vb * vb); } break;
-        case 7: adj[TIDX(ia)] -= w; break;
-        case 8: adj[TIDX(ia)] += w * cos(val[TIDX(ia)]); break;
-        case 9: adj[TIDX(ia)] -= w * sin(val[TIDX(ia)]); break;
-        case 10: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)], d = va * va + vb * vb; adj[TIDX(ia)] += w * vb / d; adj[TIDX(ib)] -= w * va / d; } break;
-        case 11: adj[TIDX(ia)] += w * 0.5 / val[TIDX(i)]; break;
-        case 12: adj[TIDX(ia)] += w * 2.0 * val[TIDX(ia)]; break;
-        // (1 - a)(1 + a), not 1 - a a: both factors are exact near |a| = 1, where a a rounds by as much as is left of 1 - a a (half the digits of the slope at 1 - 1e-8, all of them at 1 - 1e-16)
-        case 13: { const double va = val[TIDX(ia)]; adj[TIDX(ia)] += w / sqrt((1.0 - va) * (1.0 + va)); } break;
-        case 14: { const double va = val[TIDX(ia)]; adj[TIDX(ia)] += w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); } break;
-        case 15: if (val[TIDX(ia)] <= val[TIDX(ib)]) adj[TIDX(ia)] += w; else adj[TIDX(ib)] += w; break;  // casadi: d fmin = (x <= y, !(x <= y))
-        case 16: if (val[TIDX(ia)] >= val[TIDX(ib)]) adj[TIDX(ia)] += w; else adj[TIDX(ib)] += w; break;
-        case 24: if (val[TIDX(ia)] != 0.0) adj[TIDX(ib)] += w; break;
-        case 25: adj[TIDX(ia)] += w * val[TIDX(i)]; break;
-        case 26: adj[TIDX(ia)] += w / val[TIDX(ia)]; break;
-        default: break;  // 17..23: comparisons and logic are piecewise constant
-      }
+      const int o = tv.op[i];
+      if (o & OP_DEAD) continue;  // no part in the gradient (oh_tape_ops.h)
+      InterpRegs r{tv, val, adj, nullptr, pb, grad, i, tv.a[i], tv.bb[i], Bp, b};
+      tape_adjoint(o, w, r);
     }
   }
 
@@ -198,8 +169,11 @@ __global__ __launch_bounds__(64) void k_tape_probe(TapeParams T, TapeView tv, in
 // beside every adjoint: the primal operations are those sweeps' operations in their order, so the gradient has oh_tape_probe's bits, and a unit
 // reads nothing of another unit, so its result does not depend on B, nv or the launch it falls into.  A kink holds the selection of the base point
 // (FMIN / FMAX: value, tangent and adjoint of the chosen operand, a tie to a; FABS: slope +-1 or 0, no curvature; IFZ: b where a != 0, nothing to the
-// condition; 17 .. 23: zero tangent, no adjoint).  Zero adjoints and tangents are multiplied through like every other.
+// condition; LT .. OR: zero tangent, no adjoint).  Zero adjoints and tangents are multiplied through like every other.
 // V null: direction d is e_d (nv == nx), formed here.  The tape is the one the handle holds: on a wave handle the re-associated one.
+// The primal lines are written out beside their second-order lines, with oh_tape_ops.h's names -- a third statement of the rules, to be changed
+// with them: taken from tape_value / tape_adjoint (one call per case, the tangent and dadj lines kept here) every bit was the same and the dense
+// Hessian of the 280-variable planner at B = 256 took 351.5 ms against 349.5 ms (six runs each, no overlap).
 __global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int u0, int n, int Bp, int nv, const double* __restrict__ x,
                                                  const double* __restrict__ par, const double* __restrict__ seeds, const double* __restrict__ V,
                                                  double* __restrict__ work, double* __restrict__ HV, double* __restrict__ grad_out) {
@@ -220,42 +194,42 @@ __global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int 
   const double* __restrict__ pb = par + inst * T.np;
   const double* __restrict__ vd = V ? V + u * T.nx : nullptr;
   for (int k = 0; k < T.nx; ++k) xs[TIDX(k)] = x[inst * T.nx + k];
-  // ---- forward: InterpEval::forward, and the tangent of every register
+  // ---- forward: tape_value's rules (InterpEval::forward), and the tangent of every register
   for (int i = 0; i < T.len; ++i) {
-    const int o = tv.op[i] & 31, ia = tv.a[i], ib = tv.bb[i];
+    const int o = tv.op[i] & OP_MASK, ia = tv.a[i], ib = tv.bb[i];
     double v, t;
     switch (o) {
-      case 0: v = tv.c[i]; t = 0.0; break;
-      case 1: v = xs[TIDX(ia)]; t = vd ? vd[ia] : (ia == dir ? 1.0 : 0.0); break;
-      case 2: v = pb[ia]; t = 0.0; break;
-      case 3: v = val[TIDX(ia)] + val[TIDX(ib)]; t = dval[TIDX(ia)] + dval[TIDX(ib)]; break;
-      case 4: v = val[TIDX(ia)] - val[TIDX(ib)]; t = dval[TIDX(ia)] - dval[TIDX(ib)]; break;
-      case 5: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va * vb; t = dval[TIDX(ia)] * vb + va * dval[TIDX(ib)]; } break;
-      case 6: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va / vb; t = (dval[TIDX(ia)] - v * dval[TIDX(ib)]) / vb; } break;
-      case 7: v = -val[TIDX(ia)]; t = -dval[TIDX(ia)]; break;
-      case 8: { const double va = val[TIDX(ia)]; v = sin(va); t = cos(va) * dval[TIDX(ia)]; } break;
-      case 9: { const double va = val[TIDX(ia)]; v = cos(va); t = -(sin(va) * dval[TIDX(ia)]); } break;
-      case 10: {
+      case OP_CONST: v = tv.c[i]; t = 0.0; break;
+      case OP_X: v = xs[TIDX(ia)]; t = vd ? vd[ia] : (ia == dir ? 1.0 : 0.0); break;
+      case OP_P: v = pb[ia]; t = 0.0; break;
+      case OP_ADD: v = val[TIDX(ia)] + val[TIDX(ib)]; t = dval[TIDX(ia)] + dval[TIDX(ib)]; break;
+      case OP_SUB: v = val[TIDX(ia)] - val[TIDX(ib)]; t = dval[TIDX(ia)] - dval[TIDX(ib)]; break;
+      case OP_MUL: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va * vb; t = dval[TIDX(ia)] * vb + va * dval[TIDX(ib)]; } break;
+      case OP_DIV: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = va / vb; t = (dval[TIDX(ia)] - v * dval[TIDX(ib)]) / vb; } break;
+      case OP_NEG: v = -val[TIDX(ia)]; t = -dval[TIDX(ia)]; break;
+      case OP_SIN: { const double va = val[TIDX(ia)]; v = sin(va); t = cos(va) * dval[TIDX(ia)]; } break;
+      case OP_COS: { const double va = val[TIDX(ia)]; v = cos(va); t = -(sin(va) * dval[TIDX(ia)]); } break;
+      case OP_ATAN2: {
         const double va = val[TIDX(ia)], vb = val[TIDX(ib)];
         v = atan2(va, vb);
         t = (vb * dval[TIDX(ia)] - va * dval[TIDX(ib)]) / (va * va + vb * vb);
       } break;
-      case 11: v = sqrt(val[TIDX(ia)]); t = 0.5 / v * dval[TIDX(ia)]; break;
-      case 12: { const double va = val[TIDX(ia)]; v = va * va; t = 2.0 * va * dval[TIDX(ia)]; } break;
-      case 13: { const double va = val[TIDX(ia)]; v = asin(va); t = dval[TIDX(ia)] / sqrt((1.0 - va) * (1.0 + va)); } break;
-      case 14: { const double va = val[TIDX(ia)]; v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * dval[TIDX(ia)]; } break;
-      case 15: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmin(va, vb); t = va <= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
-      case 16: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmax(va, vb); t = va >= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
-      case 17: v = val[TIDX(ia)] < val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
-      case 18: v = val[TIDX(ia)] <= val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
-      case 19: v = val[TIDX(ia)] == val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
-      case 20: v = val[TIDX(ia)] != val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
-      case 21: v = val[TIDX(ia)] == 0.0 ? 1.0 : 0.0; t = 0.0; break;
-      case 22: v = (val[TIDX(ia)] != 0.0 && val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-      case 23: v = (val[TIDX(ia)] != 0.0 || val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-      case 24: { const bool on = val[TIDX(ia)] != 0.0; v = on ? val[TIDX(ib)] : 0.0; t = on ? dval[TIDX(ib)] : 0.0; } break;
-      case 25: v = exp(val[TIDX(ia)]); t = v * dval[TIDX(ia)]; break;
-      default: { const double va = val[TIDX(ia)]; v = log(va); t = dval[TIDX(ia)] / va; } break;  // 26
+      case OP_SQRT: v = sqrt(val[TIDX(ia)]); t = 0.5 / v * dval[TIDX(ia)]; break;
+      case OP_SQR: { const double va = val[TIDX(ia)]; v = va * va; t = 2.0 * va * dval[TIDX(ia)]; } break;
+      case OP_ASIN: { const double va = val[TIDX(ia)]; v = asin(va); t = dval[TIDX(ia)] / sqrt((1.0 - va) * (1.0 + va)); } break;
+      case OP_FABS: { const double va = val[TIDX(ia)]; v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * dval[TIDX(ia)]; } break;
+      case OP_FMIN: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmin(va, vb); t = va <= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
+      case OP_FMAX: { const double va = val[TIDX(ia)], vb = val[TIDX(ib)]; v = fmax(va, vb); t = va >= vb ? dval[TIDX(ia)] : dval[TIDX(ib)]; } break;
+      case OP_LT: v = val[TIDX(ia)] < val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case OP_LE: v = val[TIDX(ia)] <= val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case OP_EQ: v = val[TIDX(ia)] == val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case OP_NE: v = val[TIDX(ia)] != val[TIDX(ib)] ? 1.0 : 0.0; t = 0.0; break;
+      case OP_NOT: v = val[TIDX(ia)] == 0.0 ? 1.0 : 0.0; t = 0.0; break;
+      case OP_AND: v = (val[TIDX(ia)] != 0.0 && val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+      case OP_OR: v = (val[TIDX(ia)] != 0.0 || val[TIDX(ib)] != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+      case OP_IFZ: { const bool on = val[TIDX(ia)] != 0.0; v = on ? val[TIDX(ib)] : 0.0; t = on ? dval[TIDX(ib)] : 0.0; } break;
+      case OP_EXP: v = exp(val[TIDX(ia)]); t = v * dval[TIDX(ia)]; break;
+      default: { const double va = val[TIDX(ia)]; v = log(va); t = dval[TIDX(ia)] / va; } break;  // OP_LOG
     }
     val[TIDX(i)] = v;
     dval[TIDX(i)] = t;
@@ -266,27 +240,27 @@ __global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int 
   const double* sd = seeds + inst * (1 + nrow);
   adj[TIDX(T.out_cost)] += sd[0];
   for (int i = 0; i < nrow; ++i) adj[TIDX(tv.rows[i])] += sd[1 + i];
-  // ---- reverse: InterpEval::reverse, and beside every  adj[r] += w q  its derivative along v,  dadj[r] += dw q + w dq
+  // ---- reverse: tape_adjoint's rules (InterpEval::reverse), and beside every  adj[r] += w q  its derivative along v,  dadj[r] += dw q + w dq
   // (the operands' values and tangents are read before anything is accumulated, and the two accumulations of a binary instruction are separate
   //  read-modify-writes: MUL a a adds both contributions to the one register)
   for (int k = 0; k < T.nx; ++k) { gr[TIDX(k)] = 0.0; hv[TIDX(k)] = 0.0; }
   for (int i = T.len - 1; i >= 0; --i) {
     const double w = adj[TIDX(i)], dw = dadj[TIDX(i)];
     const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
-    if (o & 32) continue;  // dead: no part in the gradient, none in H v
+    if (o & OP_DEAD) continue;  // dead: no part in the gradient, none in H v
     switch (o) {
-      case 0: case 2: break;
-      case 1: gr[TIDX(ia)] += w; hv[TIDX(ia)] += dw; break;
-      case 3: adj[TIDX(ia)] += w; adj[TIDX(ib)] += w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] += dw; break;
-      case 4: adj[TIDX(ia)] += w; adj[TIDX(ib)] -= w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] -= dw; break;
-      case 5: {
+      case OP_CONST: case OP_P: break;
+      case OP_X: gr[TIDX(ia)] += w; hv[TIDX(ia)] += dw; break;
+      case OP_ADD: adj[TIDX(ia)] += w; adj[TIDX(ib)] += w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] += dw; break;
+      case OP_SUB: adj[TIDX(ia)] += w; adj[TIDX(ib)] -= w; dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] -= dw; break;
+      case OP_MUL: {
         const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
         adj[TIDX(ia)] += w * vb;
         adj[TIDX(ib)] += w * va;
         dadj[TIDX(ia)] += dw * vb + w * tb;
         dadj[TIDX(ib)] += dw * va + w * ta;
       } break;
-      case 6: {
+      case OP_DIV: {
         const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
         adj[TIDX(ia)] += w / vb;
         adj[TIDX(ib)] -= w * va / (vb * vb);
@@ -294,18 +268,18 @@ __global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int 
         dadj[TIDX(ia)] += (dw - w * tb / vb) / vb;
         dadj[TIDX(ib)] -= (dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb);
       } break;
-      case 7: adj[TIDX(ia)] -= w; dadj[TIDX(ia)] -= dw; break;
-      case 8: {
+      case OP_NEG: adj[TIDX(ia)] -= w; dadj[TIDX(ia)] -= dw; break;
+      case OP_SIN: {
         const double va = val[TIDX(ia)], ta = dval[TIDX(ia)], c = cos(va);
         adj[TIDX(ia)] += w * c;
         dadj[TIDX(ia)] += dw * c - w * sin(va) * ta;
       } break;
-      case 9: {
+      case OP_COS: {
         const double va = val[TIDX(ia)], ta = dval[TIDX(ia)], s = sin(va);
         adj[TIDX(ia)] -= w * s;
         dadj[TIDX(ia)] -= dw * s + w * cos(va) * ta;
       } break;
-      case 10: {
+      case OP_ATAN2: {
         const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)], d = va * va + vb * vb;
         adj[TIDX(ia)] += w * vb / d;
         adj[TIDX(ib)] -= w * va / d;
@@ -314,45 +288,45 @@ __global__ __launch_bounds__(64) void k_tape_hvp(TapeParams T, TapeView tv, int 
         dadj[TIDX(ia)] += (dw * vb + w * (tb - vb * dd / d)) / d;
         dadj[TIDX(ib)] -= (dw * va + w * (ta - va * dd / d)) / d;
       } break;
-      case 11: {  // q = 0.5 / sqrt(a);  dq = -q (q ta) / sqrt(a)
+      case OP_SQRT: {  // q = 0.5 / sqrt(a);  dq = -q (q ta) / sqrt(a)
         const double r = val[TIDX(i)], q = 0.5 / r;
         adj[TIDX(ia)] += w * 0.5 / r;
         dadj[TIDX(ia)] += dw * q - w * (q * dval[TIDX(i)] / r);
       } break;
-      case 12: {
+      case OP_SQR: {
         const double va = val[TIDX(ia)];
         adj[TIDX(ia)] += w * 2.0 * va;
         dadj[TIDX(ia)] += dw * 2.0 * va + w * 2.0 * dval[TIDX(ia)];
       } break;
-      case 13: {  // q = 1 / sqrt((1 - a)(1 + a));  dq = a ta q / ((1 - a)(1 + a))
+      case OP_ASIN: {  // q = 1 / sqrt((1 - a)(1 + a));  dq = a ta q / ((1 - a)(1 + a))
         const double va = val[TIDX(ia)], s = (1.0 - va) * (1.0 + va), r = sqrt(s);
         adj[TIDX(ia)] += w / r;
         dadj[TIDX(ia)] += dw / r + w * (va * dval[TIDX(ia)] / (s * r));
       } break;
-      case 14: {
+      case OP_FABS: {
         const double va = val[TIDX(ia)], sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0);
         adj[TIDX(ia)] += w * sg;
         dadj[TIDX(ia)] += dw * sg;
       } break;
-      case 15:
+      case OP_FMIN:
         if (val[TIDX(ia)] <= val[TIDX(ib)]) { adj[TIDX(ia)] += w; dadj[TIDX(ia)] += dw; } else { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
         break;
-      case 16:
+      case OP_FMAX:
         if (val[TIDX(ia)] >= val[TIDX(ib)]) { adj[TIDX(ia)] += w; dadj[TIDX(ia)] += dw; } else { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
         break;
-      case 24:
+      case OP_IFZ:
         if (val[TIDX(ia)] != 0.0) { adj[TIDX(ib)] += w; dadj[TIDX(ib)] += dw; }
         break;
-      case 25: {  // q = exp(a) = val[i], dq = dval[i]
+      case OP_EXP: {  // q = exp(a) = val[i], dq = dval[i]
         adj[TIDX(ia)] += w * val[TIDX(i)];
         dadj[TIDX(ia)] += dw * val[TIDX(i)] + w * dval[TIDX(i)];
       } break;
-      case 26: {
+      case OP_LOG: {
         const double va = val[TIDX(ia)];
         adj[TIDX(ia)] += w / va;
         dadj[TIDX(ia)] += (dw - w * dval[TIDX(ia)] / va) / va;
       } break;
-      default: break;  // 17..23
+      default: break;  // LT .. OR
     }
   }
   for (int k = 0; k < T.nx; ++k) HV[u * T.nx + k] = hv[TIDX(k)];
@@ -405,52 +379,45 @@ std::string generate(const TapeParams& T, const int* op, const int* a, const int
        "  __device__ double phi(const double* __restrict__ xs, double* __restrict__ gout, const double rho, double* fout, double* cmax, double* meas) {\n"
        "#pragma clang fp contract(off)\n";
   // which registers the reverse sweep reaches: everything the cost and the rows depend on
-  std::vector<char> live(T.len, 0);
-  live[T.out_cost] = 1;
-  for (int i = 0; i < T.n_ineq + T.n_eq; ++i) live[rows[i]] = 1;
-  auto is_binary = [](int o) { return (o >= 3 && o <= 6) || o == 10 || (o >= 15 && o <= 20) || (o >= 22 && o <= 24); };
-  for (int i = T.len - 1; i >= 0; --i)
-    if (live[i] && op[i] >= 3) {
-      live[a[i]] = 1;
-      if (is_binary(op[i])) live[bb[i]] = 1;
-    }
+  const std::vector<char> live = tape_live(T.len, op, a, bb, rows, T.n_ineq + T.n_eq, T.out_cost);
+  // value table: the text of tape_value's rules (oh_tape_ops.h) -- keep the two in step
   for (int i = 0; i < T.len; ++i) {
     if (!live[i]) continue;
     switch (op[i]) {
-      case 0: emit(s, "    const double v%d = %s;\n", i, literal(c[i]).c_str()); break;
-      case 1: emit(s, "    const double v%d = xs[TIDX(%d)];\n", i, a[i]); break;
-      case 2: emit(s, "    const double v%d = pb[%d];\n", i, a[i]); break;
-      case 3: emit(s, "    const double v%d = v%d + v%d;\n", i, a[i], bb[i]); break;
-      case 4: emit(s, "    const double v%d = v%d - v%d;\n", i, a[i], bb[i]); break;
-      case 5: emit(s, "    const double v%d = v%d * v%d;\n", i, a[i], bb[i]); break;
-      case 6: emit(s, "    const double v%d = v%d / v%d;\n", i, a[i], bb[i]); break;
-      case 7: emit(s, "    const double v%d = -v%d;\n", i, a[i]); break;
-      case 8: emit(s, "    const double v%d = sin(v%d);\n", i, a[i]); break;
-      case 9: emit(s, "    const double v%d = cos(v%d);\n", i, a[i]); break;
-      case 10: emit(s, "    const double v%d = atan2(v%d, v%d);\n", i, a[i], bb[i]); break;
-      case 11: emit(s, "    const double v%d = sqrt(v%d);\n", i, a[i]); break;
-      case 13: emit(s, "    const double v%d = asin(v%d);\n", i, a[i]); break;
-      case 14: emit(s, "    const double v%d = fabs(v%d);\n", i, a[i]); break;
-      case 15: emit(s, "    const double v%d = fmin(v%d, v%d);\n", i, a[i], bb[i]); break;
-      case 16: emit(s, "    const double v%d = fmax(v%d, v%d);\n", i, a[i], bb[i]); break;
-      case 17: emit(s, "    const double v%d = v%d < v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 18: emit(s, "    const double v%d = v%d <= v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 19: emit(s, "    const double v%d = v%d == v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 20: emit(s, "    const double v%d = v%d != v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 21: emit(s, "    const double v%d = v%d == 0.0 ? 1.0 : 0.0;\n", i, a[i]); break;
-      case 22: emit(s, "    const double v%d = (v%d != 0.0 && v%d != 0.0) ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 23: emit(s, "    const double v%d = (v%d != 0.0 || v%d != 0.0) ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
-      case 24: emit(s, "    const double v%d = v%d != 0.0 ? v%d : 0.0;\n", i, a[i], bb[i]); break;
-      case 25: emit(s, "    const double v%d = exp(v%d);\n", i, a[i]); break;
-      case 26: emit(s, "    const double v%d = log(v%d);\n", i, a[i]); break;
-      default: emit(s, "    const double v%d = v%d * v%d;\n", i, a[i], a[i]); break;
+      case OP_CONST: emit(s, "    const double v%d = %s;\n", i, literal(c[i]).c_str()); break;
+      case OP_X: emit(s, "    const double v%d = xs[TIDX(%d)];\n", i, a[i]); break;
+      case OP_P: emit(s, "    const double v%d = pb[%d];\n", i, a[i]); break;
+      case OP_ADD: emit(s, "    const double v%d = v%d + v%d;\n", i, a[i], bb[i]); break;
+      case OP_SUB: emit(s, "    const double v%d = v%d - v%d;\n", i, a[i], bb[i]); break;
+      case OP_MUL: emit(s, "    const double v%d = v%d * v%d;\n", i, a[i], bb[i]); break;
+      case OP_DIV: emit(s, "    const double v%d = v%d / v%d;\n", i, a[i], bb[i]); break;
+      case OP_NEG: emit(s, "    const double v%d = -v%d;\n", i, a[i]); break;
+      case OP_SIN: emit(s, "    const double v%d = sin(v%d);\n", i, a[i]); break;
+      case OP_COS: emit(s, "    const double v%d = cos(v%d);\n", i, a[i]); break;
+      case OP_ATAN2: emit(s, "    const double v%d = atan2(v%d, v%d);\n", i, a[i], bb[i]); break;
+      case OP_SQRT: emit(s, "    const double v%d = sqrt(v%d);\n", i, a[i]); break;
+      case OP_SQR: emit(s, "    const double v%d = v%d * v%d;\n", i, a[i], a[i]); break;
+      case OP_ASIN: emit(s, "    const double v%d = asin(v%d);\n", i, a[i]); break;
+      case OP_FABS: emit(s, "    const double v%d = fabs(v%d);\n", i, a[i]); break;
+      case OP_FMIN: emit(s, "    const double v%d = fmin(v%d, v%d);\n", i, a[i], bb[i]); break;
+      case OP_FMAX: emit(s, "    const double v%d = fmax(v%d, v%d);\n", i, a[i], bb[i]); break;
+      case OP_LT: emit(s, "    const double v%d = v%d < v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_LE: emit(s, "    const double v%d = v%d <= v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_EQ: emit(s, "    const double v%d = v%d == v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_NE: emit(s, "    const double v%d = v%d != v%d ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_NOT: emit(s, "    const double v%d = v%d == 0.0 ? 1.0 : 0.0;\n", i, a[i]); break;
+      case OP_AND: emit(s, "    const double v%d = (v%d != 0.0 && v%d != 0.0) ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_OR: emit(s, "    const double v%d = (v%d != 0.0 || v%d != 0.0) ? 1.0 : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_IFZ: emit(s, "    const double v%d = v%d != 0.0 ? v%d : 0.0;\n", i, a[i], bb[i]); break;
+      case OP_EXP: emit(s, "    const double v%d = exp(v%d);\n", i, a[i]); break;
+      case OP_LOG: emit(s, "    const double v%d = log(v%d);\n", i, a[i]); break;
     }
   }
   for (int i = 0; i < T.len; ++i)
-    if (live[i] && op[i] != 0 && op[i] != 2) emit(s, "    double a%d = 0.0;\n", i);
+    if (live[i] && tape_op_has_adjoint(op[i])) emit(s, "    double a%d = 0.0;\n", i);
   for (int k = 0; k < T.nx; ++k) emit(s, "    double g%d = 0.0;\n", k);
   emit(s, "    double val = v%d, cm = 0.0, ms = 0.0;\n", T.out_cost);
-  auto has_adj = [&](int i) { return op[i] != 0 && op[i] != 2; };
+  auto has_adj = [&](int i) { return tape_op_has_adjoint(op[i]); };
   if (has_adj(T.out_cost)) emit(s, "    a%d = 1.0;\n", T.out_cost);
   for (int i = 0; i < T.n_ineq; ++i) {
     const int r = rows[i];
@@ -464,73 +431,74 @@ std::string generate(const TapeParams& T, const int* op, const int* a, const int
     if (has_adj(r)) emit(s, " a%d += w;", r);
     s += " }\n";
   }
+  // adjoint table: the text of tape_adjoint's rules
   for (int i = T.len - 1; i >= 0; --i) {
     if (!live[i]) continue;
     const int ia = a[i], ib = bb[i];
-    const bool da = op[i] >= 3 && has_adj(ia), db = is_binary(op[i]) && has_adj(ib);
+    const bool da = tape_op_arity(op[i]) >= 1 && has_adj(ia), db = tape_op_arity(op[i]) == 2 && has_adj(ib);
     switch (op[i]) {
-      case 0: case 2: break;
-      case 1: emit(s, "    g%d += a%d;\n", ia, i); break;
-      case 3:
+      case OP_CONST: case OP_P: break;
+      case OP_X: emit(s, "    g%d += a%d;\n", ia, i); break;
+      case OP_ADD:
         if (da) emit(s, "    a%d += a%d;\n", ia, i);
         if (db) emit(s, "    a%d += a%d;\n", ib, i);
         break;
-      case 4:
+      case OP_SUB:
         if (da) emit(s, "    a%d += a%d;\n", ia, i);
         if (db) emit(s, "    a%d -= a%d;\n", ib, i);
         break;
-      case 5:
+      case OP_MUL:
         if (da) emit(s, "    a%d += a%d * v%d;\n", ia, i, ib);
         if (db) emit(s, "    a%d += a%d * v%d;\n", ib, i, ia);
         break;
-      case 6:
+      case OP_DIV:
         if (da) emit(s, "    a%d += a%d / v%d;\n", ia, i, ib);
         if (db) emit(s, "    a%d -= a%d * v%d / (v%d * v%d);\n", ib, i, ia, ib, ib);
         break;
-      case 7:
+      case OP_NEG:
         if (da) emit(s, "    a%d -= a%d;\n", ia, i);
         break;
-      case 8:
+      case OP_SIN:
         if (da) emit(s, "    a%d += a%d * cos(v%d);\n", ia, i, ia);
         break;
-      case 9:
+      case OP_COS:
         if (da) emit(s, "    a%d -= a%d * sin(v%d);\n", ia, i, ia);
         break;
-      case 10:
+      case OP_ATAN2:
         emit(s, "    { const double d = v%d * v%d + v%d * v%d;", ia, ia, ib, ib);
         if (da) emit(s, " a%d += a%d * v%d / d;", ia, i, ib);
         if (db) emit(s, " a%d -= a%d * v%d / d;", ib, i, ia);
         s += " }\n";
         break;
-      case 11:
+      case OP_SQRT:
         if (da) emit(s, "    a%d += a%d * 0.5 / v%d;\n", ia, i, i);
         break;
-      case 12:
+      case OP_SQR:
         if (da) emit(s, "    a%d += a%d * 2.0 * v%d;\n", ia, i, ia);
         break;
-      case 13:
+      case OP_ASIN:
         if (da) emit(s, "    a%d += a%d / sqrt((1.0 - v%d) * (1.0 + v%d));\n", ia, i, ia, ia);
         break;
-      case 14:
+      case OP_FABS:
         if (da) emit(s, "    a%d += a%d * (v%d > 0.0 ? 1.0 : (v%d < 0.0 ? -1.0 : 0.0));\n", ia, i, ia, ia);
         break;
-      case 15:
-      case 16: {
-        const char* cmp = op[i] == 15 ? "<=" : ">=";
+      case OP_FMIN:
+      case OP_FMAX: {
+        const char* cmp = op[i] == OP_FMIN ? "<=" : ">=";
         if (da && db) emit(s, "    if (v%d %s v%d) a%d += a%d; else a%d += a%d;\n", ia, cmp, ib, ia, i, ib, i);
         else if (da) emit(s, "    if (v%d %s v%d) a%d += a%d;\n", ia, cmp, ib, ia, i);
         else if (db) emit(s, "    if (!(v%d %s v%d)) a%d += a%d;\n", ia, cmp, ib, ib, i);
       } break;
-      case 24:
+      case OP_IFZ:
         if (db) emit(s, "    if (v%d != 0.0) a%d += a%d;\n", ia, ib, i);
         break;
-      case 25:
+      case OP_EXP:
         if (da) emit(s, "    a%d += a%d * v%d;\n", ia, i, i);
         break;
-      case 26:
+      case OP_LOG:
         if (da) emit(s, "    a%d += a%d / v%d;\n", ia, i, ia);
         break;
-      default:  // 17..23: comparisons and logic are piecewise constant
+      default:  // LT .. OR: comparisons and logic are piecewise constant
         break;
     }
   }

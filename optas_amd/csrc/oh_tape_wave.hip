@@ -142,26 +142,28 @@ struct WaveEval {
         const double b2 = bsel(fmask(fl, F_SQR), va, vb);
         double v = bsel(mM, va * b2, bflip(va, fmask(fl, F_NEGA)) + bkeep(bflip(b2, fmask(fl, F_NEGB)), ~fmask(fl, F_ZB)));
         if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
+          // tape_value's rules (oh_tape_ops.h) for the opcodes the straight-line path does not cover, on the operands loaded above: through tape_value
+          // itself the planner's solves took 3 % longer (B = 1024: 15.4 against 14.9 ms)
           switch (o) {
-            case 6: v = va / vb; break;
-            case 8: v = sin(va); break;
-            case 9: v = cos(va); break;
-            case 10: v = atan2(va, vb); break;
-            case 11: v = sqrt(va); break;
-            case 13: v = asin(va); break;
-            case 14: v = fabs(va); break;
-            case 15: v = fmin(va, vb); break;
-            case 16: v = fmax(va, vb); break;
-            case 17: v = va < vb ? 1.0 : 0.0; break;
-            case 18: v = va <= vb ? 1.0 : 0.0; break;
-            case 19: v = va == vb ? 1.0 : 0.0; break;
-            case 20: v = va != vb ? 1.0 : 0.0; break;
-            case 21: v = va == 0.0 ? 1.0 : 0.0; break;
-            case 22: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; break;
-            case 23: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; break;
-            case 24: v = va != 0.0 ? vb : 0.0; break;  // if_else_zero
-            case 25: v = exp(va); break;
-            case 26: v = log(va); break;
+            case OP_DIV: v = va / vb; break;
+            case OP_SIN: v = sin(va); break;
+            case OP_COS: v = cos(va); break;
+            case OP_ATAN2: v = atan2(va, vb); break;
+            case OP_SQRT: v = sqrt(va); break;
+            case OP_ASIN: v = asin(va); break;
+            case OP_FABS: v = fabs(va); break;
+            case OP_FMIN: v = fmin(va, vb); break;
+            case OP_FMAX: v = fmax(va, vb); break;
+            case OP_LT: v = va < vb ? 1.0 : 0.0; break;
+            case OP_LE: v = va <= vb ? 1.0 : 0.0; break;
+            case OP_EQ: v = va == vb ? 1.0 : 0.0; break;
+            case OP_NE: v = va != vb ? 1.0 : 0.0; break;
+            case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; break;
+            case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; break;
+            case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; break;
+            case OP_IFZ: v = va != 0.0 ? vb : 0.0; break;
+            case OP_EXP: v = exp(va); break;
+            case OP_LOG: v = log(va); break;
             default: break;
           }
         }
@@ -221,20 +223,22 @@ struct WaveEval {
           const bool rare = (fl & F_RARE) != 0;
           if (__builtin_amdgcn_ballot_w64(rare) != 0) {
             if (rare) { ca = 0.0; cb = 0.0; }
+            // tape_adjoint's rules (oh_tape_ops.h), each contribution a value, not an accumulation: behind an accessor that stores into ca / cb the
+            // compiler merges the cases' stores into one store through a pointer and both variables end up in scratch memory (24 bytes a lane)
             switch (o) {
-              case 6: ca = w / vb; cb = -(w * va / (vb * vb)); break;
-              case 8: ca = w * cos(va); break;
-              case 9: ca = -(w * sin(va)); break;
-              case 10: { const double d = va * va + vb * vb; ca = w * vb / d; cb = -(w * va / d); } break;
-              case 11: ca = w * 0.5 / val[i]; break;
-              case 13: ca = w / sqrt((1.0 - va) * (1.0 + va)); break;  // (as InterpEval::reverse writes it)
-              case 14: ca = w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); break;
-              case 15: if (va <= vb) ca = w; else cb = w; break;
-              case 16: if (va >= vb) ca = w; else cb = w; break;
-              case 24: if (va != 0.0) cb = w; break;
-              case 25: ca = w * val[i]; break;
-              case 26: ca = w / va; break;
-              default: break;  // 17..23: piecewise constant
+              case OP_DIV: ca = w / vb; cb = -(w * va / (vb * vb)); break;
+              case OP_SIN: ca = w * cos(va); break;
+              case OP_COS: ca = -(w * sin(va)); break;
+              case OP_ATAN2: { const double d = va * va + vb * vb; ca = w * vb / d; cb = -(w * va / d); } break;
+              case OP_SQRT: ca = w * 0.5 / val[i]; break;
+              case OP_ASIN: ca = w / sqrt((1.0 - va) * (1.0 + va)); break;
+              case OP_FABS: ca = w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); break;
+              case OP_FMIN: if (va <= vb) ca = w; else cb = w; break;
+              case OP_FMAX: if (va >= vb) ca = w; else cb = w; break;
+              case OP_IFZ: if (va != 0.0) cb = w; break;
+              case OP_EXP: ca = w * val[i]; break;
+              case OP_LOG: ca = w / va; break;
+              default: break;  // LT .. OR: piecewise constant
             }
           }
           val[i] = ca;
@@ -596,34 +600,27 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   const int NT = nt == 64 ? 64 : 256;  // option "tape_wave_nt"
   out->nt = NT;
   const int L = T.len, nrows = T.n_ineq + T.n_eq;
-  auto is_binary = [](int o) { return (o >= 3 && o <= 6) || o == 10 || (o >= 15 && o <= 20) || (o >= 22 && o <= 24); };
-  auto has_adj = [&](int i) { return op[i] != 0 && op[i] != 2; };
-  std::vector<char> live(L, 0);
-  live[T.out_cost] = 1;
-  for (int i = 0; i < nrows; ++i) live[rows[i]] = 1;
-  for (int i = L - 1; i >= 0; --i)
-    if (live[i] && op[i] >= 3) {
-      live[a[i]] = 1;
-      if (is_binary(op[i])) live[b[i]] = 1;
-    }
+  auto is_binary = [](int o) { return tape_op_arity(o) == 2; };
+  auto has_adj = [&](int i) { return tape_op_has_adjoint(op[i]); };
+  const std::vector<char> live = tape_live(L, op, a, b, rows, nrows, T.out_cost);
   // compact registers; every load of the same variable is one register
   std::vector<int> reg(L, -1), xreg(T.nx, -1), level(L, 0);
   int n_reg = XREG0 + T.nx;  // 0: the zero register, 1: trash, then one register per variable (every load of a variable is that register)
   for (int k = 0; k < T.nx; ++k) xreg[k] = XREG0 + k;
   for (int i = 0; i < L; ++i) {
     if (!live[i]) continue;
-    if (op[i] == 1) {
+    if (op[i] == OP_X) {
       reg[i] = xreg[a[i]];
     } else {
       reg[i] = n_reg++;
     }
-    if (op[i] >= 3) level[i] = 1 + std::max(level[a[i]], is_binary(op[i]) ? level[b[i]] : 0);
+    if (op[i] >= OP_ADD) level[i] = 1 + std::max(level[a[i]], is_binary(op[i]) ? level[b[i]] : 0);
   }
   // NEG runs as a product with a register that holds -1 (exact, and -1 * +0 = -0 as IEEE negation gives it); the selector form (-a) + (+0) of the
   // entry turned -(+0) into +0, which atan2(-x, c < 0) and 1 / (-x) then showed as 2 pi and as the other infinity at x = 0
   int neg_one = -1;
   for (int i = 0; i < L && neg_one < 0; ++i)
-    if (live[i] && op[i] == 7) neg_one = n_reg++;
+    if (live[i] && op[i] == OP_NEG) neg_one = n_reg++;
   if (n_reg >= (1 << 18)) return 0;
   out->n_reg = n_reg;
   int n_lvl = 0;
@@ -631,16 +628,16 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
     if (live[i]) n_lvl = std::max(n_lvl, level[i]);
   // ---- forward schedule
   std::vector<int4> fw;
-  const int4 idle_entry{TRASH | (3 << OPSH), ZREG, ZREG, 0};  // trash = zero + zero
-  auto flags_of = [](int o) { return o == 3 ? 0 : o == 4 ? F_NEGB : o == 5 ? F_MUL : o == 12 ? (F_MUL | F_SQR) : o == 7 ? (F_NEGA | F_ZB) : F_RARE; };
+  const int4 idle_entry{TRASH | (OP_ADD << OPSH), ZREG, ZREG, 0};  // trash = zero + zero
+  auto flags_of = [](int o) { return o == OP_ADD ? 0 : o == OP_SUB ? F_NEGB : o == OP_MUL ? F_MUL : o == OP_SQR ? (F_MUL | F_SQR) : o == OP_NEG ? (F_NEGA | F_ZB) : F_RARE; };
   std::vector<std::vector<int>> by_level(n_lvl + 1);
   for (int i = 0; i < L; ++i)
-    if (live[i] && op[i] >= 3) by_level[level[i]].push_back(i);
+    if (live[i] && op[i] >= OP_ADD) by_level[level[i]].push_back(i);
   // A wavefront executes the bodies of all the operations its 64 lanes hold one after the other: what a pass costs is the most expensive set of
   // distinct operations any of its wavefronts holds.  Within a level (sorted by operation, NT instructions per pass) the groups of equal
   // operation are dealt to the block's wavefronts, dearest first, each to the wavefront with the cheapest set so far: a narrow level runs its
   // sines, cosines, divisions and products side by side on four SIMDs instead of in a row on one.  Slots: instruction index, -1 idle.
-  auto body_cost = [](int o) { return (o == 8 || o == 9) ? 40 : (o == 10 || o == 13) ? 60 : o == 6 ? 12 : o == 11 ? 10 : 1; };
+  auto body_cost = [](int o) { return (o == OP_SIN || o == OP_COS) ? 40 : (o == OP_ATAN2 || o == OP_ASIN) ? 60 : o == OP_DIV ? 12 : o == OP_SQRT ? 10 : 1; };
   auto arrange = [&](std::vector<int> ids) {
     std::stable_sort(ids.begin(), ids.end(), [&](int p, int q) { return op[p] < op[q]; });
     std::vector<int> slots;
@@ -681,14 +678,14 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
     slots_of[l] = arrange(by_level[l]);
     for (int i : slots_of[l])
       fw.push_back(i < 0          ? idle_entry
-                   : op[i] == 7 ? int4{reg[i] | (5 << OPSH), reg[a[i]], neg_one, F_MUL}
+                   : op[i] == OP_NEG ? int4{reg[i] | (OP_MUL << OPSH), reg[a[i]], neg_one, F_MUL}
                                 : int4{reg[i] | (op[i] << OPSH), reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0, flags_of(op[i])});
   }
   // ---- consumers of every register that carries an adjoint, in the order the serial reverse sweep adds them (descending instruction index)
   std::vector<std::vector<int>> cons(n_reg);
   for (int i = L - 1; i >= 0; --i) {
-    if (!live[i] || op[i] < 3 || (op[i] >= 17 && op[i] <= 23)) continue;
-    if (op[i] != 24 && has_adj(a[i])) cons[reg[a[i]]].push_back(reg[i] << 1);
+    if (!live[i] || op[i] < OP_ADD || (op[i] >= OP_LT && op[i] <= OP_OR)) continue;  // (LT .. OR: piecewise constant, they contribute nothing)
+    if (op[i] != OP_IFZ && has_adj(a[i])) cons[reg[a[i]]].push_back(reg[i] << 1);
     if (is_binary(op[i]) && has_adj(b[i])) cons[reg[b[i]]].push_back((reg[i] << 1) | 1);
   }
   // ---- seeds
@@ -721,14 +718,14 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   for (int l = n_lvl; l >= 1; --l)
     for (int i : slots_of[l]) {
       if (i >= 0) {
-        if (op[i] == 7) rv_entry(reg[i], 5, reg[a[i]], neg_one);  // (its share for the -1 register lands in a slot nobody gathers)
+        if (op[i] == OP_NEG) rv_entry(reg[i], OP_MUL, reg[a[i]], neg_one);  // (its share for the -1 register lands in a slot nobody gathers)
         else rv_entry(reg[i], op[i], reg[a[i]], is_binary(op[i]) ? reg[b[i]] : 0);
       } else {
         rv.push_back(idle_entry);
         rv.push_back(int4{0, 0, 0, 0});
       }
     }
-  for (int k = 0; k < T.nx; ++k) rv_entry(xreg[k], 3, ZREG, ZREG);  // every variable, read or not: "+ zero" leaves the gathered adjoint in its slots
+  for (int k = 0; k < T.nx; ++k) rv_entry(xreg[k], OP_ADD, ZREG, ZREG);  // every variable, read or not: "+ zero" leaves the gathered adjoint in its slots
   while (rv.size() % (2 * (size_t)NT)) {
     rv.push_back(idle_entry);
     rv.push_back(int4{0, 0, 0, 0});
@@ -740,8 +737,8 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   std::vector<double> cst_val;
   for (int i = 0; i < L; ++i) {
     if (!live[i]) continue;
-    if (op[i] == 0) { cst_reg.push_back(reg[i]); cst_val.push_back(c[i]); }
-    if (op[i] == 2) { par_reg.push_back(reg[i]); par_k.push_back(a[i]); }
+    if (op[i] == OP_CONST) { cst_reg.push_back(reg[i]); cst_val.push_back(c[i]); }
+    if (op[i] == OP_P) { par_reg.push_back(reg[i]); par_k.push_back(a[i]); }
   }
   if (neg_one >= 0) { cst_reg.push_back(neg_one); cst_val.push_back(-1.0); }
   for (int r = 0; r < nrows; ++r) small.push_back(reg[rows[r]]);
