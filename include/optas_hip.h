@@ -368,6 +368,26 @@ int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const dou
    oh_get_timing out[4] is then the device time of these launches (the copies in and out are outside it), out[5] their number. */
 int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p, const double* seeds, int nv, const double* V, double* HV, double* grad);
 
+/* Truncated Newton-CG inner solver of an OH_PROBLEM_TAPE handle (option tape_newton != 0, off by default; csrc/oh_tape_newton.h): the outer
+   augmented-Lagrangian loop is unchanged, the merit is minimised by line-search Newton-CG whose every CG iteration is one exact product of the merit's
+   generalised Hessian with a vector, computed on the device (csrc/oh_tape.hip: InterpEval::hess_vec, forward-over-reverse with seed tangents on the
+   registers the last evaluation left).  Such a handle builds neither the wavefront schedule nor generated code; oh_solve / oh_solve_device launch
+   k_tape_solve_newton (oh_get_flag "tape_newton": 1 after such a solve).  A metric of the handle (oh_tape_set_metric) is the preconditioner of CG.
+   max_iter caps evaluations plus products and iters [B] reports that sum; x, f, kkt, status and the multipliers keep their meaning and layout.
+   oh_tape_newton_stats: steps [B] accepted line-search steps, hvps [B] products of every instance of the last solve, which must have been a Newton-CG
+   solve of B instances (OH_ERR_STATE otherwise).  Host buffers. */
+int oh_tape_newton_stats(oh_handle* h, int B, int* steps, int* hvps);
+
+/* The counterpart of oh_tape_phi for that solver's product: per instance ONE evaluation of the merit at x [B][nx], p [B][np] with multipliers
+   lam [B][n_ineq], mu [B][n_eq] and penalty rho > 0 by the interpreter, then nv calls of the very hess_vec the solver calls:
+   HV [B][nv][nx] = (generalised Hessian of the merit) V [B][nv][nx].  An inequality row with lam - rho g > 0 (a tie is inactive) contributes its
+   curvature weighted by -(lam - rho g) and rho grad g grad g^T, an inactive one nothing, an equality row (-mu + rho c) and rho grad c grad c^T; kinks hold
+   the selection of the base point (oh_tape_hvp's conventions).  grad [B][nx] (optional, may be NULL): the gradient that evaluation returned, bit for bit
+   oh_tape_phi's on an interpreter handle.  Works on every OH_PROBLEM_TAPE handle, on the tape the handle holds; arguments are checked before any device
+   call.  Host buffers. */
+int oh_tape_phi_hvp(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, int nv, const double* V, double* HV,
+                    double* grad);
+
 /* Initial metric of an OH_PROBLEM_TAPE handle's limited-memory quasi-Newton iteration: H0 [nx][nx], symmetric positive definite, host memory (copied);
    NULL takes it away again.  The two-loop recursion then starts from r = H0 q instead of the identity scaled by the newest pair.  The reference hands
    IPOPT the exact Hessian of the Lagrangian (optimization.py:8-24, solver.py:355-384); this is the part of it that is known before the first solve:
@@ -436,7 +456,7 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    k_retract + k_evalb_zc + k_step_zc, the neighbour coupling folded in; 0: k_couple runs as a launch of its own), "tail_threshold",
    "specialized"; OH_PROBLEM_TAPE handles: "tape_wave" (0: one thread per instance; 1 / 2: one block of wavefronts per instance, the quasi-Newton
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
-   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_hvp_launches" (kernel launches of the last oh_tape_hvp), "tape_jit_lds" (1: the last oh_tape_phi ran
+   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_hvp_launches" (kernel launches of the last oh_tape_hvp), "tape_newton" (1: the last solve ran k_tape_solve_newton), "tape_jit_lds" (1: the last oh_tape_phi ran
    the generated code's entry with its work set in LDS); OH_PROBLEM_QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance
    kernel k_qp_solve_block); position-tracking handles (lock_orientation = 0): "free_sweep", the kernel that solved the block-tridiagonal system
    of the last oh_solve / oh_solve_device call's first launch -- 0 k_step_free (one lane per instance), 1 k_step_free_pcr, 2 k_step_free_cp,
@@ -472,6 +492,8 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *       (qp_mode: -1 automatic; 0 / 1 / 2 force where the thread-per-instance kernel keeps its work set, falling back when it does not fit;
  *        3 forces the workgroup-per-instance kernel on any handle; large handles take that kernel under every value)
  *   tape_wave (1), tape_lbfgs (-1 = by size), tape_wave_nt (256), tape_wave_regs (-1), tape_wave_hist (-1) -- tape evaluator (rebuilt when set)
+ *   tape_newton (0; != 0: the inner solver is truncated Newton-CG on exact merit curvature, oh_tape_newton_stats -- changes the iterates; OH_PROBLEM_TAPE
+ *       handles only, OH_ERR_INVALID on others), tape_newton_cg (-1 = by size: min(nx, 50); CG iterations per Newton step, negative values are refused)
  *   tq_check (4), tq_rebuild (0.9), tq_stall (25), tq_curv_after (3), tq_curv_from (0.1), tq_ftb (0.995), tq_theta_mu (1.35), tq_kappa_mu (0.4),
  *   tq_kappa_eps (10), tq_curv_late (1), tq_max_back (3), tq_mu_dec (1/3; warm ticks of oh_tq_rollout: tq_mu_dec_warm, 0.1), tq_ls_curv (1), tq_curv_lag (3: the exact-curvature term is computed at every 4th evaluation of an instance and reused in between; 0: always),
  *   tq_jac_dual (0)                                                                                     -- torque-MPC family

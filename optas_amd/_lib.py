@@ -224,6 +224,8 @@ SYMBOLS = [
     "oh_tape_probe",
     "oh_tape_phi",
     "oh_tape_hvp",
+    "oh_tape_phi_hvp",
+    "oh_tape_newton_stats",
     "oh_tape_set_metric",
     "oh_set_constants",
     "oh_set_constants_device",
@@ -318,6 +320,8 @@ def load() -> C.CDLL:
     lib.oh_tape_probe.argtypes = [vp, i, vp, vp, i, vp, vp, vp, vp, vp]
     lib.oh_tape_phi.argtypes = [vp, i, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.oh_tape_hvp.argtypes = [vp, i, vp, vp, vp, i, vp, vp, vp]
+    lib.oh_tape_phi_hvp.argtypes = [vp, i, vp, vp, vp, vp, C.c_double, i, vp, vp, vp]
+    lib.oh_tape_newton_stats.argtypes = [vp, i, vp, vp]
     lib.oh_tape_set_metric.argtypes = [vp, vp]
     lib.oh_set_constants.argtypes = [vp, C.POINTER(oh_chain)]
     lib.oh_set_constants_device.argtypes = [vp, vp, C.c_size_t]

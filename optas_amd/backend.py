@@ -152,7 +152,11 @@ class TapeBackend(_SolveMixin):
             from .tape import quadratic_cost_metric
 
             self._h0 = quadratic_cost_metric(tape)
-        want_wave = bool(wave) and int(tape.nx) > 48 and float((options or {}).get("tape_wave", 1)) != 0.0
+        # Newton-CG (option tape_newton) runs on the interpreter: no re-association for the wavefront evaluator and no generated code, neither would run
+        self.newton = float((options or {}).get("tape_newton", 0)) != 0.0
+        if self.newton:
+            jit = False
+        want_wave = bool(wave) and not self.newton and int(tape.nx) > 48 and float((options or {}).get("tape_wave", 1)) != 0.0
         if want_wave:
             # chains of additions are dependency levels for that evaluator, so sums go in as balanced trees (same values to the rounding of the
             # summation order).  Whether the path is taken is the library's decision (limited-memory regime, LDS fit): the handle is asked, and a
@@ -176,7 +180,7 @@ class TapeBackend(_SolveMixin):
         if not want_wave:
             opts = dict(options or {})
             if int(tape.nx) > 48:
-                opts["tape_wave"] = 0
+                opts["tape_wave"] = 0  # (travels in the descriptor: the schedule is not built at creation either)
             self._create(tape, max_iter, tol, tol_feas, rho0, jit, opts)
         self.wave = self.flag("tape_wave") != 0
         self.jit = bool(jit) and not self.wave  # what actually runs: generated code only where the wavefront evaluator does not
@@ -276,8 +280,30 @@ class TapeBackend(_SolveMixin):
                                            _lib._ptr(grad)), "oh_tape_hvp")
         return HV, grad
 
+    def phi_hvp(self, x, p, lam, mu, rho, V):
+        """oh_tape_phi_hvp: per instance one evaluation of the merit at x (B, nx), p (B, np), lam (B, n_ineq), mu (B, n_eq), penalty rho, then the products of the
+        merit's generalised Hessian with the directions V (B, nv, nx) by the hess_vec the Newton-CG solver calls.  Returns (HV (B, nv, nx), grad (B, nx))."""
+        x = _lib.as_f64(x).reshape(-1, self.nx)
+        B = x.shape[0]
+        ni, ne = int(self.tape.n_ineq), int(self.tape.n_eq)
+        p = _lib.as_f64(p).reshape(B, -1) if self._np_real else np.zeros((B, 1))
+        lam = _lib.as_f64(np.zeros((B, 0)) if lam is None else lam).reshape(B, ni)
+        mu = _lib.as_f64(np.zeros((B, 0)) if mu is None else mu).reshape(B, ne)
+        V = _lib.as_f64(V).reshape(B, -1, self.nx)
+        HV, grad = np.empty_like(V), np.empty((B, self.nx))
+        ptr = lambda a: _lib._ptr(a) if a.size else None
+        _lib.check(_lib.load().oh_tape_phi_hvp(self._h, B, _lib._ptr(x), _lib._ptr(p), ptr(lam), ptr(mu), float(rho), int(V.shape[1]), _lib._ptr(V), _lib._ptr(HV),
+                                               _lib._ptr(grad)), "oh_tape_phi_hvp")
+        return HV, grad
+
+    def newton_stats(self, B: int):
+        """oh_tape_newton_stats: (steps (B,), products (B,)) of the last solve, which ran the Newton-CG solver (option tape_newton) on B instances."""
+        steps, hvps = np.empty(int(B), dtype=np.int32), np.empty(int(B), dtype=np.int32)
+        _lib.check(_lib.load().oh_tape_newton_stats(self._h, int(B), _lib._ptr(steps), _lib._ptr(hvps)), "oh_tape_newton_stats")
+        return steps, hvps
+
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian())."""
+        """oh_get_flag: 'tape_newton' (1: the last solve ran the Newton-CG kernel), 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian())."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)
@@ -357,6 +383,9 @@ class EliminatedTapeBackend:
 
     def flag(self, name: str) -> int:
         return self.inner.flag(name)
+
+    def newton_stats(self, B: int):
+        return self.inner.newton_stats(B)
 
     def timing(self) -> dict:
         return self.inner.timing()

@@ -78,6 +78,7 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     bool known = false;
     for (const OptDoc& d : OPT_TABLE) known = known || name == d.name;
     if (!known) return fail(OH_ERR_INVALID, "oh_set_option: unknown option '" + name + "'");
+    if (name == "tape_newton_cg" && !(v >= 0.0)) return fail(OH_ERR_INVALID, "oh_set_option: tape_newton_cg must be a count of CG iterations (0: by size)");
     h->opt[name] = v;
     if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max" && name != "tape_hvp_work_mb") return tape_configure(h);
   }
@@ -85,6 +86,9 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
 }
 extern "C" int oh_set_option(oh_handle* h, const char* name, double value) {
   if (!h || !name) return fail(OH_ERR_INVALID, "oh_set_option: null argument");
+  // (here, not in set_option_impl: OH_DEBUG_OPTIONS is applied to a handle before its kind is known, and to handles of every kind)
+  if (std::string(name) == "tape_newton" && value != 0.0 && h->desc.kind != OH_PROBLEM_TAPE)
+    return fail(OH_ERR_INVALID, "oh_set_option: tape_newton is an option of OH_PROBLEM_TAPE handles");
   return set_option_impl(h, name, value);
 }
 extern "C" int oh_get_option(oh_handle* h, const char* name, double* value) {
@@ -1394,6 +1398,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_regs_lds") *value = h->tape.wave.ready && h->tape.wave.reg_lds ? 1 : 0;
   else if (n == "tape_jit_lds") *value = h->tape.phi_lds;
   else if (n == "tape_hvp_launches") *value = h->tape.hvp_launches;
+  else if (n == "tape_newton") *value = h->tape.last_newton;
   else if (n == "tape_metric") *value = (h->tape.P.h0 && h->tape.P.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape.wave.n_levels;
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;

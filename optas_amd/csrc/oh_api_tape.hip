@@ -1,5 +1,6 @@
 // Host side of the tape family (OH_PROBLEM_TAPE; the tape of a QP handle): validation, evaluator choice, the tape's device arrays,
 // probes and the solve.  State: oh_handle::tape.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -48,7 +49,8 @@ extern "C" int oh_tape_compile(const oh_tape_desc* d, size_t* code_bytes, char* 
 }
 
 // (Re)build the evaluator of an OH_PROBLEM_TAPE handle from its host copy of the tape and its options: the wavefront-per-instance schedule where it
-// applies (tape_wave != 0, limited-memory regime, LDS fit), otherwise generated code (desc.jit) or the interpreter.
+// applies (tape_wave != 0, limited-memory regime, LDS fit), otherwise generated code (desc.jit) or the interpreter.  With tape_newton != 0 the solves run
+// k_tape_solve_newton on the interpreter: neither the schedule nor generated code is built for an evaluator that will not run.
 int tape_configure(oh_handle* h) {
   TapeState& tp = h->tape;
   oh_tape_desc d = tp.desc;
@@ -59,6 +61,7 @@ int tape_configure(oh_handle* h) {
   tp.wave = TapeWave{};
   tp.work.release();  // the work arrays were sized for the other evaluator
   tp.mult.release();
+  if (optv(h, "tape_newton") != 0.0) return OH_OK;
   int lds_limit = 0;
   if (optv(h, "tape_wave") != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
     std::string err;
@@ -225,6 +228,56 @@ extern "C" int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p
   return OH_OK;
 }
 
+extern "C" int oh_tape_phi_hvp(oh_handle* h, int B, const double* x, const double* p, const double* lam, const double* mu, double rho, int nv, const double* V,
+                               double* HV, double* grad) {
+  if (!h || !x || !V || !HV) return fail(OH_ERR_INVALID, "oh_tape_phi_hvp: null argument");
+  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_phi_hvp: handle is not an OH_PROBLEM_TAPE problem");
+  TapeState& tp = h->tape;
+  const TapeParams& T = tp.P;
+  if (B < 1 || nv < 1 || (T.np > 0 && !p) || (T.n_ineq > 0 && !lam) || (T.n_eq > 0 && !mu)) return fail(OH_ERR_INVALID, "oh_tape_phi_hvp: bad sizes");
+  if (!(rho > 0.0)) return fail(OH_ERR_INVALID, "oh_tape_phi_hvp: the penalty must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  const int Bp = (B + 63) / 64 * 64;
+  const size_t nB = (size_t)B, b_u = sizeof(double) * (size_t)T.nx * nB * (size_t)nv;
+  double *d_x, *d_g, *d_p, *d_l, *d_m, *d_v, *d_hv, *d_w;
+  auto layout = [&](Carver c) {
+    d_x = c.take<double>((size_t)T.nx * nB);
+    d_g = c.take<double>((size_t)T.nx * nB);
+    d_p = c.take<double>((size_t)(T.np > 0 ? T.np : 1) * nB);
+    d_l = c.take<double>((size_t)(T.n_ineq > 0 ? T.n_ineq : 1) * nB);
+    d_m = c.take<double>((size_t)(T.n_eq > 0 ? T.n_eq : 1) * nB);
+    d_v = c.take<double>((size_t)T.nx * nB * nv);
+    d_hv = c.take<double>((size_t)T.nx * nB * nv);
+    d_w = c.take<double>(oh_tape_newton_work_rows(T) * Bp);
+    return c.bytes();
+  };
+  if (const int rc = stage_carve(h, layout)) return rc;
+  hipStream_t s = h->stream;
+  HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T.nx * nB, hipMemcpyHostToDevice, s));
+  if (T.np > 0) HIPCHK(hipMemcpyAsync(d_p, p, sizeof(double) * (size_t)T.np * nB, hipMemcpyHostToDevice, s));
+  if (T.n_ineq > 0) HIPCHK(hipMemcpyAsync(d_l, lam, sizeof(double) * (size_t)T.n_ineq * nB, hipMemcpyHostToDevice, s));
+  if (T.n_eq > 0) HIPCHK(hipMemcpyAsync(d_m, mu, sizeof(double) * (size_t)T.n_eq * nB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_v, V, b_u, hipMemcpyHostToDevice, s));
+  oh_launch_tape_phi_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, B, Bp, d_x, d_p, d_l, d_m, rho, nv, d_v, d_w, d_hv, grad ? d_g : nullptr);
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(HV, d_hv, b_u, hipMemcpyDeviceToHost));
+  if (grad) HIPCHK(hipMemcpy(grad, d_g, sizeof(double) * (size_t)T.nx * nB, hipMemcpyDeviceToHost));
+  return OH_OK;
+}
+
+extern "C" int oh_tape_newton_stats(oh_handle* h, int B, int* steps, int* hvps) {
+  if (!h || !steps || !hvps) return fail(OH_ERR_INVALID, "oh_tape_newton_stats: null argument");
+  if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_STATE, "oh_tape_newton_stats: handle is not an OH_PROBLEM_TAPE problem");
+  TapeState& tp = h->tape;
+  if (!tp.last_newton || B < 1 || B != tp.nstat_B) return fail(OH_ERR_STATE, "oh_tape_newton_stats: the last solve of this handle was not a Newton-CG solve of B instances");
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<int> both(2 * (size_t)B);
+  HIPCHK(hipMemcpy(both.data(), tp.nstat, sizeof(int) * both.size(), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) { steps[b] = both[2 * (size_t)b]; hvps[b] = both[2 * (size_t)b + 1]; }
+  return OH_OK;
+}
+
 extern "C" int oh_tape_set_metric(oh_handle* h, const double* H0) {
   if (!h) return fail(OH_ERR_INVALID, "oh_tape_set_metric: null argument");
   if (h->desc.kind != OH_PROBLEM_TAPE) return fail(OH_ERR_INVALID, "oh_tape_set_metric: not an OH_PROBLEM_TAPE handle");
@@ -257,7 +310,10 @@ static int tape_ensure_work(oh_handle* h, const int Bp) {
   if (Bp > tp.cap()) {  // both at the new stride, or (an allocation failed) cap() == 0
     tp.work.release();
     tp.mult.release();
-    if (!tp.wave.ready) HIPCHK(tp.work.reserve((size_t)oh_tape_work_rows(tp.P, tp.jit.fn != nullptr) * Bp));
+    size_t rows = oh_tape_work_rows(tp.P, tp.jit.fn != nullptr);
+    // (a Newton-CG handle: its own work set, and room for the interpreter's layout, which oh_tape_phi launches on such a handle)
+    if (optv(h, "tape_newton") != 0.0) rows = std::max(oh_tape_newton_work_rows(tp.P), oh_tape_work_rows(tp.P, false));
+    if (!tp.wave.ready) HIPCHK(tp.work.reserve(rows * Bp));
     HIPCHK(tp.mult.reserve((size_t)(tp.P.n_ineq + tp.P.n_eq + 1) * Bp));
   }
   return OH_OK;
@@ -325,6 +381,16 @@ int tape_solve_device(oh_handle* h, const Solve& a) {
   TapeState& tp = h->tape;
   const int B = a.B, Bp = (B + 63) / 64 * 64;
   if (const int rc = tape_ensure_work(h, Bp)) return rc;
+  tp.last_newton = optv(h, "tape_newton") != 0.0 ? 1 : 0;
+  if (tp.last_newton) {
+    const int cg = (int)optv(h, "tape_newton_cg");
+    HIPCHK(tp.nstat.reserve(2 * (size_t)B));
+    tp.nstat_B = B;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    oh_launch_tape_solve_newton(h->stream, tp.P, tp.op, tp.a, tp.b, tp.c, tp.rows, B, tp.cap(), cg > 0 ? cg : std::min(tp.P.nx, 50), a.x0, a.p, tp.work, a.x, a.f,
+                                a.kkt, a.iters, a.status, tp.mult, tp.nstat);
+    return finish_solve(h, 1);
+  }
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   if (tp.wave.ready)
     HIPCHK(oh_launch_tape_wave(h->stream, tp.wave, tp.P, B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, tp.mult));

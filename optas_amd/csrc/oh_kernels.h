@@ -225,6 +225,15 @@ void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, con
 size_t oh_tape_hvp_work_rows(const TapeParams& T);  // 4 len + 3 nx
 void oh_launch_tape_hvp(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int u0, int n, int Bp,
                         int nv, const double* x, const double* p, const double* seeds, const double* V, double* work, double* HV, double* grad);
+// truncated Newton-CG on the interpreter (option tape_newton; oh_tape_newton.h): work is [oh_tape_newton_work_rows][Bp], stats [B][2] (Newton steps, products)
+size_t oh_tape_newton_work_rows(const TapeParams& T);  // 4 len + tape_newton_rows
+void oh_launch_tape_solve_newton(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                                 int cg_cap, const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status,
+                                 double* mult, int* stats);
+// one InterpEval::phi, then nv InterpEval::hess_vec per instance (oh_tape_phi_hvp); work as for oh_launch_tape_solve_newton; grad may be null
+void oh_launch_tape_phi_hvp(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                            const double* x, const double* p, const double* lam, const double* mu, double rho, int nv, const double* V, double* work,
+                            double* HV, double* grad);
 void oh_launch_tape_solve(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
                           const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status, double* mult);
 // solve = false: the program of the single-evaluation kernels (k_tape_jit_phi, k_tape_jit_phi_lds) around the same evaluator text

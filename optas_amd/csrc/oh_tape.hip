@@ -7,7 +7,8 @@
 // all rows at once (cost 1, equality rows -mu + rho c, active inequality rows -(lam - rho g)), so the gradient of the merit costs two
 // passes over the tape whatever the number of rows.  What an opcode computes and how its adjoint propagates is stated in oh_tape_ops.h; this file holds
 // the two thread-per-instance evaluators behind the solver of oh_tape_solver.h (the third, one wavefront per instance, is oh_tape_wave.hip):
-//   * the interpreter (InterpEval; k_tape_solve, k_tape_phi, k_tape_probe, and with tangents beside it k_tape_hvp): all lanes of a wavefront execute
+//   * the interpreter (InterpEval; k_tape_solve, k_tape_phi, k_tape_probe, with tangents beside it k_tape_hvp, and behind the Newton-CG solver of
+//     oh_tape_newton.h k_tape_solve_newton and k_tape_phi_hvp, which call InterpEval::hess_vec): all lanes of a wavefront execute
 //     the same tape instruction on registers that live in HBM/L2 as val[i][b] (every access one coalesced line).  No set-up cost, but each
 //     instruction is a dependent memory round trip: latency bound;
 //   * straight-line HIP code written by generate() below and compiled with hiprtc for gfx950 when the handle is created (desc.jit): SSA values
@@ -29,6 +30,7 @@
 #include "oh_jit.h"  // the disk cache of run-time compiled code objects
 #include "oh_kernels.h"
 #include "oh_tape_solver_src.h"  // OH_TAPE_SOLVER_SRC: the text of oh_tape_solver.h, written by optas_amd/build.py
+#include "oh_tape_newton.h"      // the truncated Newton-CG state machine behind InterpEval::hess_vec (option tape_newton); never part of a generated program
 
 namespace {
 
@@ -72,6 +74,8 @@ struct InterpEval {
   double* __restrict__ adj;
   const double* __restrict__ pb;
   const int Bp, b;
+  double* __restrict__ dval = nullptr;  // tangents and the adjoints' directional derivatives, [len][Bp] each: set only where hess_vec is called
+  double* __restrict__ dadj = nullptr;
 
   // contraction off: one IEEE operation per tape operation, like the generated code and the numpy restatement
   __device__ void forward(const double* __restrict__ xs) {
@@ -119,6 +123,101 @@ struct InterpEval {
     *meas = ms;
     return v;
   }
+
+  // out = (generalised Hessian of the merit at x) v, forward-over-reverse with SEED TANGENTS (v, out: SoA [variable][lane]).
+  // INVARIANT: the call follows a phi at the same x with the same multipliers (W.lam, W.mu) and the same rho, and nothing has written val, adj or W.rowv
+  // since.  Then val[] holds the values and adj[] every register's FINAL adjoint -- the w of the second-order reverse rules -- so a product is one tangent
+  // sweep and one dadj sweep and repeats no primal work.  An inequality row with lam - rho g > 0 (tape_al_ineq's own expression: a tie is inactive) has the
+  // seed -(lam - rho g), whose tangent is rho dval[row]; an inactive one seed and tangent 0; an equality row -mu + rho c and rho dval[row].  Kinks hold the
+  // selection of the base point, as k_tape_hvp documents.  Dead instructions take no part in either sweep (no live one reads them).
+  // The second-order lines are written out here a second time beside k_tape_hvp's: there each stands next to the primal accumulation adj += ... it
+  // differentiates, which this method must NOT repeat (adj is final), and that kernel's text is kept as measured (see its comment).  Names: oh_tape_ops.h.
+  __device__ void hess_vec(const double* __restrict__ v, const double rho, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < T.len; ++i) {
+      const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
+      if (o & OP_DEAD) continue;
+      double t;
+      switch (o) {
+        case OP_X: t = v[TIDX(ia)]; break;
+        case OP_ADD: t = dval[TIDX(ia)] + dval[TIDX(ib)]; break;
+        case OP_SUB: t = dval[TIDX(ia)] - dval[TIDX(ib)]; break;
+        case OP_MUL: t = dval[TIDX(ia)] * val[TIDX(ib)] + val[TIDX(ia)] * dval[TIDX(ib)]; break;
+        case OP_DIV: t = (dval[TIDX(ia)] - val[TIDX(i)] * dval[TIDX(ib)]) / val[TIDX(ib)]; break;
+        case OP_NEG: t = -dval[TIDX(ia)]; break;
+        case OP_SIN: t = cos(val[TIDX(ia)]) * dval[TIDX(ia)]; break;
+        case OP_COS: t = -(sin(val[TIDX(ia)]) * dval[TIDX(ia)]); break;
+        case OP_ATAN2: {
+          const double va = val[TIDX(ia)], vb = val[TIDX(ib)];
+          t = (vb * dval[TIDX(ia)] - va * dval[TIDX(ib)]) / (va * va + vb * vb);
+        } break;
+        case OP_SQRT: t = 0.5 / val[TIDX(i)] * dval[TIDX(ia)]; break;
+        case OP_SQR: t = 2.0 * val[TIDX(ia)] * dval[TIDX(ia)]; break;
+        case OP_ASIN: { const double va = val[TIDX(ia)]; t = dval[TIDX(ia)] / sqrt((1.0 - va) * (1.0 + va)); } break;
+        case OP_FABS: { const double va = val[TIDX(ia)]; t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * dval[TIDX(ia)]; } break;
+        case OP_FMIN: t = val[TIDX(ia)] <= val[TIDX(ib)] ? dval[TIDX(ia)] : dval[TIDX(ib)]; break;
+        case OP_FMAX: t = val[TIDX(ia)] >= val[TIDX(ib)] ? dval[TIDX(ia)] : dval[TIDX(ib)]; break;
+        case OP_IFZ: t = val[TIDX(ia)] != 0.0 ? dval[TIDX(ib)] : 0.0; break;
+        case OP_EXP: t = val[TIDX(i)] * dval[TIDX(ia)]; break;
+        case OP_LOG: t = dval[TIDX(ia)] / val[TIDX(ia)]; break;
+        default: t = 0.0; break;  // CONST, P, LT .. OR
+      }
+      dval[TIDX(i)] = t;
+    }
+    for (int i = 0; i < T.len; ++i) dadj[TIDX(i)] = 0.0;
+    for (int i = 0; i < T.n_ineq; ++i) {
+      const int r = tv.rows[i];
+      double v0 = 0.0, c0 = 0.0, m0 = 0.0;
+      if (tape_al_ineq(W.rowv[TIDX(i)], W.lam[TIDX(i)], rho, v0, c0, m0) < 0.0) dadj[TIDX(r)] += rho * dval[TIDX(r)];  // the seed phi planted is not zero: active
+    }
+    for (int i = 0; i < T.n_eq; ++i) {
+      const int r = tv.rows[T.n_ineq + i];
+      dadj[TIDX(r)] += rho * dval[TIDX(r)];
+    }
+    for (int k = 0; k < T.nx; ++k) out[TIDX(k)] = 0.0;
+    for (int i = T.len - 1; i >= 0; --i) {
+      const int o = tv.op[i], ia = tv.a[i], ib = tv.bb[i];
+      if (o & OP_DEAD) continue;
+      const double w = adj[TIDX(i)], dw = dadj[TIDX(i)];
+      switch (o) {
+        case OP_X: out[TIDX(ia)] += dw; break;
+        case OP_ADD: dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] += dw; break;
+        case OP_SUB: dadj[TIDX(ia)] += dw; dadj[TIDX(ib)] -= dw; break;
+        case OP_MUL: {
+          const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
+          dadj[TIDX(ia)] += dw * vb + w * tb;
+          dadj[TIDX(ib)] += dw * va + w * ta;
+        } break;
+        case OP_DIV: {
+          const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)];
+          dadj[TIDX(ia)] += (dw - w * tb / vb) / vb;
+          dadj[TIDX(ib)] -= (dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb);
+        } break;
+        case OP_NEG: dadj[TIDX(ia)] -= dw; break;
+        case OP_SIN: { const double va = val[TIDX(ia)]; dadj[TIDX(ia)] += dw * cos(va) - w * sin(va) * dval[TIDX(ia)]; } break;
+        case OP_COS: { const double va = val[TIDX(ia)]; dadj[TIDX(ia)] -= dw * sin(va) + w * cos(va) * dval[TIDX(ia)]; } break;
+        case OP_ATAN2: {
+          const double va = val[TIDX(ia)], vb = val[TIDX(ib)], ta = dval[TIDX(ia)], tb = dval[TIDX(ib)], d = va * va + vb * vb;
+          const double dd = 2.0 * (va * ta + vb * tb);
+          dadj[TIDX(ia)] += (dw * vb + w * (tb - vb * dd / d)) / d;
+          dadj[TIDX(ib)] -= (dw * va + w * (ta - va * dd / d)) / d;
+        } break;
+        case OP_SQRT: { const double r = val[TIDX(i)], q = 0.5 / r; dadj[TIDX(ia)] += dw * q - w * (q * dval[TIDX(i)] / r); } break;
+        case OP_SQR: dadj[TIDX(ia)] += dw * 2.0 * val[TIDX(ia)] + w * 2.0 * dval[TIDX(ia)]; break;
+        case OP_ASIN: {
+          const double va = val[TIDX(ia)], s = (1.0 - va) * (1.0 + va), r = sqrt(s);
+          dadj[TIDX(ia)] += dw / r + w * (va * dval[TIDX(ia)] / (s * r));
+        } break;
+        case OP_FABS: { const double va = val[TIDX(ia)]; dadj[TIDX(ia)] += dw * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); } break;
+        case OP_FMIN: if (val[TIDX(ia)] <= val[TIDX(ib)]) dadj[TIDX(ia)] += dw; else dadj[TIDX(ib)] += dw; break;
+        case OP_FMAX: if (val[TIDX(ia)] >= val[TIDX(ib)]) dadj[TIDX(ia)] += dw; else dadj[TIDX(ib)] += dw; break;
+        case OP_IFZ: if (val[TIDX(ia)] != 0.0) dadj[TIDX(ib)] += dw; break;
+        case OP_EXP: dadj[TIDX(ia)] += dw * val[TIDX(i)] + w * dval[TIDX(i)]; break;
+        case OP_LOG: { const double va = val[TIDX(ia)]; dadj[TIDX(ia)] += (dw - w * dval[TIDX(ia)] / va) / va; } break;
+        default: break;  // CONST, P, LT .. OR
+      }
+    }
+  }
 };
 
 __global__ __launch_bounds__(64) void k_tape_solve(TapeParams T, TapeView tv, int B, int Bp, const double* __restrict__ x0, const double* __restrict__ par,
@@ -129,6 +228,48 @@ __global__ __launch_bounds__(64) void k_tape_solve(TapeParams T, TapeView tv, in
   const TapeWork W = tape_carve(T, work + 2 * (size_t)T.len * Bp, Bp);
   InterpEval ev{T, tv, W, work, work + (size_t)T.len * Bp, par + (size_t)b * T.np, Bp, b};
   tape_solve_instance(T, ev, W, Bp, b, b, x0, xo, fo, kkt, iters, status, mult);
+}
+
+// The Newton-CG solve (option tape_newton): one thread per instance.  work: [4 len + tape_newton_rows][Bp] -- registers, adjoints, tangents, the adjoints'
+// directional derivatives, then the solver's vectors (tape_newton_carve).
+__global__ __launch_bounds__(64) void k_tape_solve_newton(TapeParams T, TapeView tv, int B, int Bp, int cg_cap, const double* __restrict__ x0,
+                                                          const double* __restrict__ par, double* __restrict__ work, double* __restrict__ xo,
+                                                          double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters, int* __restrict__ status,
+                                                          double* __restrict__ mult, int* __restrict__ stats) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const size_t L = (size_t)T.len * Bp;
+  const TapeNewtonWork N = tape_newton_carve(T, work + 4 * L, Bp);
+  InterpEval ev{T, tv, N.W, work, work + L, par + (size_t)b * T.np, Bp, b, work + 2 * L, work + 3 * L};
+  tape_newton_instance(T, ev, N, cg_cap, Bp, b, b, x0, xo, fo, kkt, iters, status, mult, stats);
+}
+
+// One InterpEval::phi per instance at given points, multipliers and penalty, then nv calls of the hess_vec the solver calls (oh_tape_phi_hvp).
+// V, HV: [B][nv][nx]; grad (may be null): the gradient that phi returned.  work: the Newton solve kernel's layout.
+__global__ __launch_bounds__(64) void k_tape_phi_hvp(TapeParams T, TapeView tv, int B, int Bp, const double* __restrict__ x, const double* __restrict__ par,
+                                                     const double* __restrict__ lam, const double* __restrict__ mu, double rho, int nv,
+                                                     const double* __restrict__ V, double* __restrict__ work, double* __restrict__ HV,
+                                                     double* __restrict__ grad) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const size_t L = (size_t)T.len * Bp;
+  const TapeNewtonWork N = tape_newton_carve(T, work + 4 * L, Bp);
+  const TapeWork& W = N.W;
+  InterpEval ev{T, tv, W, work, work + L, par + (size_t)b * T.np, Bp, b, work + 2 * L, work + 3 * L};
+  const int n = T.nx;
+  for (int k = 0; k < n; ++k) W.x[TIDX(k)] = x[(size_t)b * n + k];
+  for (int i = 0; i < T.n_ineq; ++i) W.lam[TIDX(i)] = lam[(size_t)b * T.n_ineq + i];
+  for (int i = 0; i < T.n_eq; ++i) W.mu[TIDX(i)] = mu[(size_t)b * T.n_eq + i];
+  double fv, cm, ms;
+  ev.phi(W.x, W.g, rho, &fv, &cm, &ms);
+  if (grad)
+    for (int k = 0; k < n; ++k) grad[(size_t)b * n + k] = W.g[TIDX(k)];
+  for (int d = 0; d < nv; ++d) {
+    const size_t at = ((size_t)b * nv + d) * n;
+    for (int k = 0; k < n; ++k) N.p[TIDX(k)] = V[at + k];
+    ev.hess_vec(N.p, rho, N.hp);
+    for (int k = 0; k < n; ++k) HV[at + k] = N.hp[TIDX(k)];
+  }
 }
 
 // One forward sweep (and, seeded, one reverse sweep) at given points: values / adjoints of chosen registers and the gradient wrt x (oh_tape_probe).
@@ -551,6 +692,22 @@ void oh_launch_tape_solve(hipStream_t s, const TapeParams& T, const int* op, con
                           const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status, double* mult) {
   TapeView tv{op, a, b, c, rows};
   hipLaunchKernelGGL(k_tape_solve, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
+}
+
+size_t oh_tape_newton_work_rows(const TapeParams& T) { return 4 * (size_t)T.len + tape_newton_rows(T); }
+
+void oh_launch_tape_solve_newton(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                                 int cg_cap, const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters, int* status,
+                                 double* mult, int* stats) {
+  TapeView tv{op, a, b, c, rows};
+  hipLaunchKernelGGL(k_tape_solve_newton, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, cg_cap, x0, p, work, x, f, kkt, iters, status, mult, stats);
+}
+
+void oh_launch_tape_phi_hvp(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,
+                            const double* x, const double* p, const double* lam, const double* mu, double rho, int nv, const double* V, double* work,
+                            double* HV, double* grad) {
+  TapeView tv{op, a, b, c, rows};
+  hipLaunchKernelGGL(k_tape_phi_hvp, dim3((B + 63) / 64), dim3(64), 0, s, T, tv, B, Bp, x, p, lam, mu, rho, nv, V, work, HV, grad);
 }
 
 void oh_launch_tape_probe(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,

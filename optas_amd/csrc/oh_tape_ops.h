@@ -7,12 +7,14 @@
 //     keys the disk cache and what sets the compile time;
 //   * k_tape_hvp (oh_tape.hip), which has every primal line beside its second-order lines: through this header its bits were the same and the
 //     planner's dense Hessian 0.5 % slower;
+//   * InterpEval::hess_vec (oh_tape.hip), the tangent and second-order lines of k_tape_hvp once more without the primal accumulations beside them:
+//     it runs on the adjoints a finished reverse sweep left and must not repeat them;
 //   * the two rare-path switches of WaveEval::phi (oh_tape_wave.hip), values and adjoint rules of the opcodes its straight-line path does not
 //     cover, on operands it has loaded already: through this header the forward one was 3 % slower on the planner and the reverse one kept its
 //     two contributions in scratch memory;
 //   * ADD, SUB and MUL in the two sweeps of the QP assembly (oh_qp.hip), 0.5 - 2 % faster as cases of their own.
 // The measured reasons are written at each.  All of them use the names below.
-// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
+// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit, tests/test_gpu_tape_newton.py hess_vec to the 60-digit reference.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
 //
 // A rule takes its operands through a small accessor R of the caller -- values: cst(), x(), p() (what CONST, X and P load, from wherever the caller
 // keeps constants, the point and the parameters), a(), b(), self() (the instruction's own value); contributions: add_a(v), add_b(v), sub_a(v),
