@@ -365,7 +365,15 @@ int oh_tape_phi(oh_handle* h, int B, const double* x, const double* p, const dou
    operand (a tie goes to a), FABS has slope +-1 or 0 and no curvature, IFZ passes b where a != 0 and nothing to the condition, comparisons and logic have
    zero tangent.  The result of an (instance, direction) does not depend on B, nv or the other directions.  The work area, 4 len + 3 nx doubles per
    (instance, direction), is kept under option tape_hvp_work_mb (256) by launching whole 64-lane blocks in chunks; oh_get_flag "tape_hvp_launches".
-   oh_get_timing out[4] is then the device time of these launches (the copies in and out are outside it), out[5] their number. */
+   oh_get_timing out[4] is then the device time of these launches (the copies in and out are outside it), out[5] their number.
+   Option tape_hvp_wave (0): != 0 on a handle whose wavefront schedule is ready (oh_get_flag "tape_wave" >= 1) runs the same products on that schedule,
+   one block of the handle's width per (instance, direction) (csrc/oh_tape_wave.hip:k_tape_wave_hvp): the forward passes with a tangent beside every value, the
+   reverse passes with four register columns [val | adj | tan | dadj], every sum the schedule's fixed-order gather -- same conventions, same independence of
+   B, nv, the other directions, the chunking, the register placement and the block width; not the interpreter's bits (another summation order).  The columns
+   live in LDS (one launch) when 4 n_reg doubles fit, otherwise (256-thread handles only) in a work area of 4 n_reg doubles per unit in flight, kept under
+   tape_hvp_work_mb by chunking the grid, at least one unit a launch; tape_wave_regs (0 / 1) forces a placement where both are possible.  Any other handle,
+   and a 64-thread handle whose four columns do not fit, silently stays on the interpreter.  oh_get_flag "tape_hvp_path" says what the last call ran:
+   0 interpreter lanes, 1 / 2 the wavefront kernel with its registers in LDS / in global memory. */
 int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p, const double* seeds, int nv, const double* V, double* HV, double* grad);
 
 /* Truncated Newton-CG inner solver of an OH_PROBLEM_TAPE handle (option tape_newton != 0, off by default; csrc/oh_tape_newton.h): the outer
@@ -489,6 +497,7 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *   tol (0 = the descriptor's): stopping tolerance on the reduced gradient of a trajectory handle, changeable between solves
  *   pm_wave_max (20480), qp_mode (-1), tape_lds_max                                                     -- point-mass / QP / tape launch shapes
  *   tape_hvp_work_mb (256)                                                                              -- oh_tape_hvp: budget of its work area, MB
+ *   tape_hvp_wave (0; != 0: oh_tape_hvp runs on the wavefront schedule where the handle has one, see oh_tape_hvp; read per call, nothing is rebuilt)
  *       (qp_mode: -1 automatic; 0 / 1 / 2 force where the thread-per-instance kernel keeps its work set, falling back when it does not fit;
  *        3 forces the workgroup-per-instance kernel on any handle; large handles take that kernel under every value)
  *   tape_wave (1), tape_lbfgs (-1 = by size), tape_wave_nt (256), tape_wave_regs (-1), tape_wave_hist (-1) -- tape evaluator (rebuilt when set)

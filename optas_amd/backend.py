@@ -303,7 +303,7 @@ class TapeBackend(_SolveMixin):
         return steps, hvps
 
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'tape_newton' (1: the last solve ran the Newton-CG kernel), 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian())."""
+        """oh_get_flag: 'tape_newton' (1: the last solve ran the Newton-CG kernel), 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian()), 'tape_hvp_path' (what they ran: 0 the interpreter, one lane per (instance, direction); with option tape_hvp_wave on a wavefront handle 1 / 2: a block per (instance, direction) on the level schedule, registers in LDS / in global memory)."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)
@@ -334,7 +334,9 @@ class EliminatedTapeBackend:
         self.inner = TapeBackend(elim.tape, keep_regs=elim.def_regs, **kw)
         self.tape = tape
         self.jit, self.wave = self.inner.jit, self.inner.wave
-        self._orig = None  # the problem as written, interpreter only: created when multipliers are asked for
+        self._orig = None  # the problem as written: created when multipliers or second derivatives are asked for
+        # option tape_hvp_wave: the handle of the problem as written gets the wavefront schedule, and hvp() / hessian() run on it (k_tape_wave_hvp)
+        self._hvp_wave = float((kw.get("options") or {}).get("tape_hvp_wave", 0)) != 0.0
         self._last = None
 
     def solve(self, x0, p):
@@ -371,7 +373,10 @@ class EliminatedTapeBackend:
 
     def _as_written(self):
         if self._orig is None:
-            self._orig = TapeBackend(self.full, jit=False, wave=False, metric=False)
+            if self._hvp_wave:  # (re-association keeps the row order: probe() and multipliers() read the same rows)
+                self._orig = TapeBackend(self.full, jit=False, wave=True, metric=False, options={"tape_hvp_wave": 1})
+            else:
+                self._orig = TapeBackend(self.full, jit=False, wave=False, metric=False)
         return self._orig
 
     def hvp(self, x, p, seeds, V):
@@ -382,6 +387,8 @@ class EliminatedTapeBackend:
         return self._as_written().hessian(x, p, seeds)
 
     def flag(self, name: str) -> int:
+        if name == "tape_hvp_path":  # (products run on the handle of the problem as written)
+            return self._as_written().flag(name)
         return self.inner.flag(name)
 
     def newton_stats(self, B: int):

@@ -80,7 +80,7 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
     if (!known) return fail(OH_ERR_INVALID, "oh_set_option: unknown option '" + name + "'");
     if (name == "tape_newton_cg" && !(v >= 0.0)) return fail(OH_ERR_INVALID, "oh_set_option: tape_newton_cg must be a count of CG iterations (0: by size)");
     h->opt[name] = v;
-    if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max" && name != "tape_hvp_work_mb") return tape_configure(h);
+    if (h->desc.kind == OH_PROBLEM_TAPE && !h->tape.h_op.empty() && name.rfind("tape_", 0) == 0 && name != "tape_lds_max" && name != "tape_hvp_work_mb" && name != "tape_hvp_wave") return tape_configure(h);
   }
   return OH_OK;
 }
@@ -1384,7 +1384,8 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 // How the handle's last solve was (or its next one will be) scheduled, by name: "fuse_couple" (1: coupling folded into evaluation and sweep, no
 // k_couple launch), "tail_threshold", "specialized"; tape handles: "tape_wave" (0: thread per instance, 1 / 2: wavefront per instance with the (s, y)
 // pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
-// oh_tape_phi ran the generated code's entry with the work set in LDS), "tape_hvp_launches" (launches of the last oh_tape_hvp); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
+// oh_tape_phi ran the generated code's entry with the work set in LDS), "tape_hvp_launches" (launches of the last oh_tape_hvp),
+// "tape_hvp_path" (what the last oh_tape_hvp ran: 0 interpreter lanes, 1 / 2 k_tape_wave_hvp with its registers in LDS / in global memory); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
 // position-tracking handles: "free_sweep" (the FreeSweep the last solve started with, -1 before the first), "free_sweeps_used" (bit mask over its launches).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
@@ -1398,6 +1399,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_regs_lds") *value = h->tape.wave.ready && h->tape.wave.reg_lds ? 1 : 0;
   else if (n == "tape_jit_lds") *value = h->tape.phi_lds;
   else if (n == "tape_hvp_launches") *value = h->tape.hvp_launches;
+  else if (n == "tape_hvp_path") *value = h->tape.hvp_path;
   else if (n == "tape_newton") *value = h->tape.last_newton;
   else if (n == "tape_metric") *value = (h->tape.P.h0 && h->tape.P.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape.wave.n_levels;
@@ -1426,7 +1428,7 @@ extern "C" int oh_kernel_info(const char* kernel, int* out5) {
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_kernel_info: no HIP device available (this library has no CPU path)");
   OhKernelInfo k{};
   if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_linkkin(kernel, &k) && !oh_kernel_info_torque(kernel, &k) &&
-      !oh_kernel_info_qp_block(kernel, &k))
+      !oh_kernel_info_qp_block(kernel, &k) && !oh_kernel_info_tape_wave(kernel, &k))
     return fail(OH_ERR_INVALID, std::string("oh_kernel_info: unknown kernel or attribute query failed: ") + kernel);
   out5[0] = k.vgprs; out5[1] = k.scratch_bytes; out5[2] = k.lds_bytes; out5[3] = k.block; out5[4] = k.blocks_per_cu;
   return OH_OK;

@@ -189,13 +189,17 @@ extern "C" int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p
   const size_t nB = (size_t)B, U = nB * (size_t)nv;  // units: (instance, direction)
   if (U > (size_t)0x7fffffc0) return fail(OH_ERR_INVALID, "oh_tape_hvp: B * nv does not fit an int");
   HIPCHK(hipSetDevice(h->device));
-  // whole 64-lane blocks per launch, as many as keep the work area under the budget (at least one)
-  const size_t per_unit = sizeof(double) * oh_tape_hvp_work_rows(T);
+  // option tape_hvp_wave on a handle whose wavefront schedule is ready: one block per unit on that schedule (k_tape_wave_hvp), the four register columns in
+  // LDS (one launch) or in a work area of 4 n_reg doubles per unit in flight; every other handle, and a schedule whose columns fit nowhere: the interpreter
+  const int path = optv(h, "tape_hvp_wave") != 0.0 ? oh_tape_wave_hvp_place(tp.wave) : 0;
+  // the work area stays under the budget: whole 64-lane blocks of the interpreter per launch, units of the wavefront kernel (at least one block either way)
+  const size_t per_unit = sizeof(double) * (path ? 4 * (size_t)tp.wave.n_reg : oh_tape_hvp_work_rows(T));
+  const size_t grain = path ? 1 : 64;
   const double budget = optv(h, "tape_hvp_work_mb") * 1048576.0;
-  size_t chunk = budget > 0.0 ? (size_t)(budget / (double)per_unit) / 64 * 64 : 0;
-  if (chunk < 64) chunk = 64;
-  const size_t Up = (U + 63) / 64 * 64;
-  if (chunk > Up) chunk = Up;
+  size_t chunk = budget > 0.0 ? (size_t)(budget / (double)per_unit) / grain * grain : 0;
+  if (chunk < grain) chunk = grain;
+  const size_t Up = (U + grain - 1) / grain * grain;
+  if (chunk > Up || path == 1) chunk = Up;  // (registers in LDS: no work area, one launch)
   const int nrow = T.n_ineq + T.n_eq;
   const size_t b_x = sizeof(double) * (size_t)T.nx * nB, b_u = sizeof(double) * (size_t)T.nx * U;
   double *d_x, *d_g, *d_p, *d_s, *d_v, *d_hv, *d_w;
@@ -206,7 +210,7 @@ extern "C" int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p
     d_s = c.take<double>((size_t)(1 + nrow) * nB);
     d_v = c.take<double>(V ? (size_t)T.nx * U : 1);
     d_hv = c.take<double>((size_t)T.nx * U);
-    d_w = c.take<double>(oh_tape_hvp_work_rows(T) * chunk);
+    d_w = c.take<double>(path == 1 ? 1 : per_unit / sizeof(double) * chunk);
     return c.bytes();
   };
   if (const int rc = stage_carve(h, layout)) return rc;
@@ -216,10 +220,14 @@ extern "C" int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p
   HIPCHK(hipMemcpyAsync(d_s, seeds, sizeof(double) * (size_t)(1 + nrow) * nB, hipMemcpyHostToDevice, s));
   if (V) HIPCHK(hipMemcpyAsync(d_v, V, b_u, hipMemcpyHostToDevice, s));
   tp.hvp_launches = 0;
+  tp.hvp_path = path;
   HIPCHK(hipEventRecord(h->ev0, s));  // oh_get_timing out[4]: device time of the launches, the copies outside
   for (size_t u0 = 0; u0 < U; u0 += chunk) {  // (one stream: a launch has the work area to itself)
     const size_t n = U - u0 < chunk ? U - u0 : chunk;
-    oh_launch_tape_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, (int)u0, (int)n, (int)chunk, nv, d_x, d_p, d_s, V ? d_v : nullptr, d_w, d_hv, grad ? d_g : nullptr);
+    if (path)
+      HIPCHK(oh_launch_tape_wave_hvp(s, tp.wave, T, path == 1, (int)u0, (int)n, nv, d_x, d_p, d_s, V ? d_v : nullptr, d_w, d_hv, grad ? d_g : nullptr));
+    else
+      oh_launch_tape_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, (int)u0, (int)n, (int)chunk, nv, d_x, d_p, d_s, V ? d_v : nullptr, d_w, d_hv, grad ? d_g : nullptr);
     ++tp.hvp_launches;
   }
   if (const int rc = finish_solve(h, tp.hvp_launches)) return rc;

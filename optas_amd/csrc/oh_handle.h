@@ -120,7 +120,8 @@ struct TapeState {
   TapeJit jit;
   TapeJit jit_phi;   // the single-evaluation kernels of the same generated evaluator: compiled by the first oh_tape_phi, not with the handle
   int phi_lds = 0;   // whether the last oh_tape_phi ran the generated code's entry with the work set in LDS
-  int hvp_launches = 0;  // launches of k_tape_hvp the last oh_tape_hvp took (oh_get_flag "tape_hvp_launches")
+  int hvp_launches = 0;  // launches the last oh_tape_hvp took (oh_get_flag "tape_hvp_launches")
+  int hvp_path = 0;      // what they ran: 0 k_tape_hvp, 1 / 2 k_tape_wave_hvp with its registers in LDS / in global memory ("tape_hvp_path")
   DevBuf<int> nstat;     // [nstat_B][2]: Newton steps and Hessian-vector products of every instance of the last Newton-CG solve (oh_tape_newton_stats)
   int nstat_B = 0;
   int last_newton = 0;   // the last solve ran k_tape_solve_newton (oh_get_flag "tape_newton")
@@ -262,7 +263,7 @@ struct OptDoc { const char* name; double dflt; };
 // map-backed options and their defaults, the one place a default is written (field-backed ones: FIELD_OPTS; batch_invariant: set_option_impl)
 static constexpr OptDoc OPT_TABLE[] = {
     {"check_every", 1},        {"lean_count", 0},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
-    {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30}, {"tape_hvp_work_mb", 256},
+    {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30}, {"tape_hvp_work_mb", 256}, {"tape_hvp_wave", 0},
     {"tape_newton", 0},        {"tape_newton_cg", -1},
     {"tape_wave", 1},          {"tape_lbfgs", -1},       {"tape_wave_nt", 256},  {"tape_wave_regs", -1}, {"tape_wave_hist", -1},  {"tq_stall", 25},
     {"tq_curv_after", 3},      {"tq_ftb", 0.995},        {"tq_theta_mu", 1.35},  {"tq_kappa_mu", 0.4},   {"tq_curv_from", 0.1},   {"tq_jac_dual", 0},

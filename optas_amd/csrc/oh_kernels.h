@@ -17,6 +17,7 @@ bool oh_kernel_info_fkjac(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_torque(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_linkkin(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_qp_block(const char* name, OhKernelInfo* out);
+bool oh_kernel_info_tape_wave(const char* name, OhKernelInfo* out);
 
 void oh_launch_fk_jac(hipStream_t s, bool soa, const oh_chain* d_chain, int n_chain, int ndof, int n, const double* q, double* pose, double* J);
 // What oh_set_link_frames keeps on the device for k_link_kin (oh_linkkin.hip): the chains root->link and root->base, and the number of leading
@@ -202,6 +203,7 @@ struct TapeWave {
   int *d_cons = nullptr, *d_cst_reg = nullptr, *d_par_reg = nullptr, *d_par_k = nullptr, *d_small = nullptr;
   double *d_cst_val = nullptr, *d_hist = nullptr, *d_regs = nullptr;
   int hist_cap = 0, regs_cap = 0;
+  size_t lds_limit = 0;  // what oh_tape_wave_build was given: the product kernel's placement is decided against it per call
 };
 // nt: threads per instance (256 or 64; option tape_wave_nt), regs: register file -1 chosen per launch, 0 global memory, 1 LDS (tape_wave_regs),
 // hist: quasi-Newton pairs -1 in LDS when they fit, 0 global memory (tape_wave_hist)
@@ -213,6 +215,13 @@ hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, 
 // one WaveEval::phi per instance (oh_tape_phi): the register placement oh_launch_tape_wave would choose for this B
 hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x, const double* p, const double* lam, const double* mu,
                                    double rho, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas);
+// forward-over-reverse on the level schedule, one block per unit (oh_tape_hvp with option tape_hvp_wave; k_tape_wave_hvp): oh_tape_wave_hvp_place says where
+// the four register columns go (0: the interpreter stays, 1: LDS, 2: global memory); a launch covers the units [u0, u0 + n),
+// regs (global placement only) is [n][4 n_reg]; x, p, seeds, V (null: the unit vectors), HV and grad (may be null) are the whole batch's arrays
+int oh_tape_wave_hvp_place(const TapeWave& W);
+size_t oh_tape_wave_hvp_lds_bytes(const TapeWave& W, bool reg_lds);
+hipError_t oh_launch_tape_wave_hvp(hipStream_t s, const TapeWave& W, const TapeParams& T, bool reg_lds, int u0, int n, int nv, const double* x, const double* p,
+                                   const double* seeds, const double* V, double* regs, double* HV, double* grad);
 size_t oh_tape_work_rows(const TapeParams& T, bool jit);
 // one InterpEval::phi per instance (oh_tape_phi); work as for oh_launch_tape_solve
 void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,

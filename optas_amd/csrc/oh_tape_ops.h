@@ -12,9 +12,13 @@
 //   * the two rare-path switches of WaveEval::phi (oh_tape_wave.hip), values and adjoint rules of the opcodes its straight-line path does not
 //     cover, on operands it has loaded already: through this header the forward one was 3 % slower on the planner and the reverse one kept its
 //     two contributions in scratch memory;
+//   * k_tape_wave_hvp (oh_tape_wave.hip), the tangent and second-order lines a third time, beside WaveEval::phi's two switches: the wavefront's reverse sweep has no
+//     accumulation to differentiate -- an instruction leaves its contribution to each operand as a VALUE in its own slots (ca, cb) and the consumers'
+//     slots are gathered later -- so each rule is the pair (contribution, its directional derivative) of one operand, on operands and tangents the pass has
+//     loaded already, and an accessor that stored them through a pointer put them in scratch memory as it did for phi;
 //   * ADD, SUB and MUL in the two sweeps of the QP assembly (oh_qp.hip), 0.5 - 2 % faster as cases of their own.
 // The measured reasons are written at each.  All of them use the names below.
-// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit, tests/test_gpu_tape_newton.py hess_vec to the 60-digit reference.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
+// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit, tests/test_gpu_tape_hvp_wave.py k_tape_wave_hvp to the 60-digit reference, tests/test_gpu_tape_newton.py hess_vec to the 60-digit reference.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
 //
 // A rule takes its operands through a small accessor R of the caller -- values: cst(), x(), p() (what CONST, X and P load, from wherever the caller
 // keeps constants, the point and the parameters), a(), b(), self() (the instruction's own value); contributions: add_a(v), add_b(v), sub_a(v),

@@ -571,6 +571,201 @@ __global__ __launch_bounds__(NT) void k_tape_wave_phi(TapeParams T, WaveSchedDev
   for (int k = lane; k < n; k += NT) grad[(size_t)gb * n + k] = G[k];
 }
 
+// Exact Hessian-vector products by forward-over-reverse on the level schedule (oh_tape_hvp with option tape_hvp_wave): ONE BLOCK PER UNIT
+// u = b nv + d (instance b, direction d, the direction fastest), the launch covers the units [u0, u0 + gridDim.x).  The schedule is the one
+// WaveEval::phi runs, untouched; the register file has four columns [val | adj | tan | dadj] of n_reg doubles each, tan = (d val / d x) v,
+// dadj = (d adj / d x) v.  Forward: phi's passes with the tangent beside every value.  Reverse: phi's slot trick twice over -- when instruction
+// c is reached all its consumers are done, so c leaves its contributions (ca, cb) to its operands in val[c], adj[c] and their directional
+// derivatives (dca, dcb) in tan[c], dadj[c]; w gathers seed + slots as phi does, dw gathers the same slot indices displaced by 2 n_reg (the
+// weights are constants: no seed).  The gather order is the schedule's, every sum of a unit is that gather: a unit's bits do not depend on B, nv,
+// the other units, the launch it falls into, the register placement or the block width.  The variables' "+ zero" entries leave the gradient
+// in val[XREG0 + k] and H v in tan[XREG0 + k].  Conventions at kinks: k_tape_hvp's (oh_tape.hip).  A third statement of the second-order
+// rules (oh_tape_ops.h says why): here each is a pair of values per operand, not an accumulation.
+template <int NT, bool REG_LDS>
+__global__ __launch_bounds__(NT) void k_tape_wave_hvp(TapeParams T, WaveSchedDev S, int u0, int nv, const double* __restrict__ x, const double* __restrict__ par,
+                                                      const double* __restrict__ seeds, const double* __restrict__ V, double* regs_g, double* __restrict__ HV,
+                                                      double* __restrict__ grad) {
+#pragma clang fp contract(off)
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const size_t u = (size_t)u0 + blockIdx.x;
+  const size_t inst = u / (size_t)nv;
+  const int dir = (int)(u % (size_t)nv);
+  const int n = T.nx, nr = S.n_reg, D2 = 2 * S.n_reg;  // D2: from a slot of [val | adj] to the same slot of [tan | dadj]
+  double* val;
+  int* small;
+  if constexpr (REG_LDS) {
+    val = lds;
+    small = reinterpret_cast<int*>(lds + 4 * (size_t)nr);
+  } else {  // [val | adj | tan | dadj] of this block in the launch's work area
+    val = regs_g + (size_t)blockIdx.x * 4 * nr;
+    small = reinterpret_cast<int*>(lds);
+  }
+  double* adj = val + nr;
+  double* tan = val + D2;
+  double* dadj = tan + nr;
+  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
+  const int* seed_reg = small + S.nrows;
+  const int* seed_off = seed_reg + S.n_seed;
+  const int* seed_rows = seed_off + S.n_seed + 1;
+  const double* pb = par + inst * T.np;
+  const double* xb = x + inst * n;
+  const double* vd = V ? V + u * n : nullptr;
+  if (lane == 0) {
+    val[ZREG] = 0.0; adj[ZREG] = 0.0; tan[ZREG] = 0.0; dadj[ZREG] = 0.0;
+    val[TRASH] = 0.0; adj[TRASH] = 0.0; tan[TRASH] = 0.0; dadj[TRASH] = 0.0;
+  }
+  for (int k = lane; k < S.n_cst; k += NT) { val[S.cst_reg[k]] = S.cst_val[k]; tan[S.cst_reg[k]] = 0.0; }  // (the -1 register is among them)
+  for (int k = lane; k < S.n_par; k += NT) { val[S.par_reg[k]] = pb[S.par_k[k]]; tan[S.par_reg[k]] = 0.0; }
+  for (int k = lane; k < n; k += NT) { val[XREG0 + k] = xb[k]; tan[XREG0 + k] = vd ? vd[k] : (k == dir ? 1.0 : 0.0); }
+  auto pass_barrier = [] { WaveEval<NT, REG_LDS>::pass_barrier(); };
+  // ---- forward: four entries in flight, as in phi
+  const int last = S.n_fw_pass - 1;
+  auto fwi = [&](int p) { return S.fw[(size_t)(p < last ? p : last) * NT + lane]; };
+  int4 q0 = fwi(0), q1 = fwi(1), q2 = fwi(2), q3 = fwi(3);
+  __syncthreads();
+  auto fw_pass = [&](const int4 ins) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+    const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
+    const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
+    const int fl = ins.w;
+    const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+    const double b2 = bsel(mS, va, vb), tb2 = bsel(mS, ta, tb);
+    double v = bsel(mM, va * b2, bflip(va, mA) + bkeep(bflip(b2, mB), mZ));
+    // product rule; a square is ta va + va ta = 2 va ta to the bit
+    double t = bsel(mM, ta * b2 + va * tb2, bflip(ta, mA) + bkeep(bflip(tb2, mB), mZ));
+    if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
+      switch (o) {
+        case OP_DIV: v = va / vb; t = (ta - v * tb) / vb; break;
+        case OP_SIN: v = sin(va); t = cos(va) * ta; break;
+        case OP_COS: v = cos(va); t = -(sin(va) * ta); break;
+        case OP_ATAN2: v = atan2(va, vb); t = (vb * ta - va * tb) / (va * va + vb * vb); break;
+        case OP_SQRT: v = sqrt(va); t = 0.5 / v * ta; break;
+        case OP_ASIN: v = asin(va); t = ta / sqrt((1.0 - va) * (1.0 + va)); break;
+        case OP_FABS: v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * ta; break;
+        case OP_FMIN: v = fmin(va, vb); t = va <= vb ? ta : tb; break;
+        case OP_FMAX: v = fmax(va, vb); t = va >= vb ? ta : tb; break;
+        case OP_LT: v = va < vb ? 1.0 : 0.0; t = 0.0; break;
+        case OP_LE: v = va <= vb ? 1.0 : 0.0; t = 0.0; break;
+        case OP_EQ: v = va == vb ? 1.0 : 0.0; t = 0.0; break;
+        case OP_NE: v = va != vb ? 1.0 : 0.0; t = 0.0; break;
+        case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; t = 0.0; break;
+        case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+        case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+        case OP_IFZ: v = va != 0.0 ? vb : 0.0; t = va != 0.0 ? tb : 0.0; break;
+        case OP_EXP: v = exp(va); t = v * ta; break;
+        case OP_LOG: v = log(va); t = ta / va; break;
+        default: break;
+      }
+    }
+    val[i] = v;
+    tan[i] = t;
+    pass_barrier();
+  };
+  for (int p = 0; p < S.n_fw_pass; p += 4) {
+    const int4 i0 = q0;
+    q0 = fwi(p + 4);
+    fw_pass(i0);
+    const int4 i1 = q1;
+    q1 = fwi(p + 5);
+    fw_pass(i1);
+    const int4 i2 = q2;
+    q2 = fwi(p + 6);
+    fw_pass(i2);
+    const int4 i3 = q3;
+    q3 = fwi(p + 7);
+    fw_pass(i3);
+  }
+  // ---- seeds: oh_tape_probe's weights in the order it adds them; their tangent is zero, so dadj has no seed at all
+  const double* sd = seeds + inst * (size_t)(1 + S.nrows);
+  for (int s = lane; s < S.n_seed; s += NT) {
+    double acc = s == S.seed_cost ? sd[0] : 0.0;
+    for (int e = seed_off[s]; e < seed_off[s + 1]; ++e) acc += sd[1 + seed_rows[e]];
+    adj[seed_reg[s]] = acc;
+  }
+  __syncthreads();
+  // ---- reverse
+  const int rlast = S.n_rv_pass - 1;
+  auto rvi = [&](int p, int h) { return S.rv[((size_t)(p < rlast ? p : rlast) * NT + lane) * 2 + h]; };
+  int4 a0 = rvi(0, 0), b0 = rvi(0, 1), a1 = rvi(1, 0), b1 = rvi(1, 1), a2 = rvi(2, 0), b2 = rvi(2, 1), a3 = rvi(3, 0), b3 = rvi(3, 1);
+  auto rv_pass = [&](const int4 ins, const int4 meta) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+    const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
+    const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
+    const double sd_ = adj[i], s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
+    const double e0 = val[meta.y + D2], e1 = val[meta.z + D2], e2 = val[meta.w + D2];
+    double w = bkeep(sd_, fmask(meta.x >> 16, 1));
+    w += s0;
+    w += s1;
+    w += s2;
+    double dw = e0;
+    dw += e1;
+    dw += e2;
+    if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
+      for (int e = 3; e < nc; ++e) {
+        const int sl = S.cons[ins.w + e - 3];
+        w += val[sl];
+        dw += val[sl + D2];
+      }
+    const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
+    const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+    const double qa = bsel(mS, va + va, vb), dqa = bsel(mS, ta + ta, tb);  // d (a b) / d a = b, d (a a) / d a = 2 a, and their tangents
+    double ca = bsel(mM, w * qa, bflip(w, mA));
+    double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, mB), mZ));
+    double dca = bsel(mM, dw * qa + w * dqa, bflip(dw, mA));
+    double dcb = bsel(mM, bkeep(dw * va + w * ta, ~mS), bkeep(bflip(dw, mB), mZ));
+    const bool rare = (fl & F_RARE) != 0;
+    if (__builtin_amdgcn_ballot_w64(rare) != 0) {
+      if (rare) { ca = 0.0; cb = 0.0; dca = 0.0; dcb = 0.0; }
+      // each contribution a value, assigned in its case (an accessor that stores through a pointer puts the four in scratch memory, as in phi)
+      switch (o) {
+        case OP_DIV:
+          ca = w / vb; cb = -(w * va / (vb * vb));
+          dca = (dw - w * tb / vb) / vb; dcb = -((dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb));
+          break;
+        case OP_SIN: { const double c = cos(va); ca = w * c; dca = dw * c - w * sin(va) * ta; } break;
+        case OP_COS: { const double s = sin(va); ca = -(w * s); dca = -(dw * s + w * cos(va) * ta); } break;
+        case OP_ATAN2: {
+          const double d = va * va + vb * vb, dd = 2.0 * (va * ta + vb * tb);
+          ca = w * vb / d; cb = -(w * va / d);
+          dca = (dw * vb + w * (tb - vb * dd / d)) / d; dcb = -((dw * va + w * (ta - va * dd / d)) / d);
+        } break;
+        case OP_SQRT: { const double r = val[i], q = 0.5 / r; ca = w * 0.5 / r; dca = dw * q - w * (q * tan[i] / r); } break;  // own value and tangent, read before the stores below
+        case OP_ASIN: { const double s = (1.0 - va) * (1.0 + va), r = sqrt(s); ca = w / r; dca = dw / r + w * (va * ta / (s * r)); } break;
+        case OP_FABS: { const double sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0); ca = w * sg; dca = dw * sg; } break;
+        case OP_FMIN: if (va <= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+        case OP_FMAX: if (va >= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+        case OP_IFZ: if (va != 0.0) { cb = w; dcb = dw; } break;
+        case OP_EXP: { const double q = val[i]; ca = w * q; dca = dw * q + w * tan[i]; } break;
+        case OP_LOG: ca = w / va; dca = (dw - w * ta / va) / va; break;
+        default: break;  // LT .. OR: piecewise constant
+      }
+    }
+    val[i] = ca;
+    adj[i] = cb;
+    tan[i] = dca;
+    dadj[i] = dcb;
+    pass_barrier();
+  };
+  for (int p = 0; p < S.n_rv_pass; p += 4) {
+    const int4 x0 = a0, y0 = b0;
+    a0 = rvi(p + 4, 0); b0 = rvi(p + 4, 1);
+    rv_pass(x0, y0);
+    const int4 x1 = a1, y1 = b1;
+    a1 = rvi(p + 5, 0); b1 = rvi(p + 5, 1);
+    rv_pass(x1, y1);
+    const int4 x2 = a2, y2 = b2;
+    a2 = rvi(p + 6, 0); b2 = rvi(p + 6, 1);
+    rv_pass(x2, y2);
+    const int4 x3 = a3, y3 = b3;
+    a3 = rvi(p + 7, 0); b3 = rvi(p + 7, 1);
+    rv_pass(x3, y3);
+  }
+  for (int k = lane; k < n; k += NT) HV[u * n + k] = tan[XREG0 + k];
+  if (grad && dir == 0)
+    for (int k = lane; k < n; k += NT) grad[inst * n + k] = val[XREG0 + k];
+}
+
 template <class V>
 int upload(V** dst, const std::vector<V>& src) {
   *dst = nullptr;
@@ -767,6 +962,7 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   // (the block's own lines; the LDS then holds the vectors and the pairs only: two or more blocks per CU) for large ones and for tapes whose
   // registers do not fit -- the planner: 4 instances 96 / 125 ms, 4096 instances 1.99 / 1.60 s.  Same arithmetic, same bits either way.
   out->reg_choice = regs;  // option "tape_wave_regs": 0 global / 1 LDS forces one placement
+  out->lds_limit = lds_limit;
   out->reg_lds_fits = oh_tape_wave_lds_bytes(T, *out, false, true) <= lds_limit;
   const bool global_ok = NT == 256 && oh_tape_wave_lds_bytes(T, *out, false, false) <= lds_limit;  // (the global-memory placement is built for four wavefronts)
   if (!out->reg_lds_fits && !global_ok) return 0;  // not even the vectors fit: the thread-per-instance path stays
@@ -867,4 +1063,57 @@ hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams&
   else OH_TW_PHI(256, true);
 #undef OH_TW_PHI
   return hipGetLastError();
+}
+
+// ---- k_tape_wave_hvp: [val | adj | tan | dadj] and the small index arrays; in the global placement the LDS holds the index arrays only
+size_t oh_tape_wave_hvp_lds_bytes(const TapeWave& W, bool reg_lds) {
+  return (reg_lds ? 4 * (size_t)W.n_reg * sizeof(double) : 0) + sizeof(int) * (((size_t)W.n_small + 1) & ~(size_t)1);
+}
+
+// Placement of the four columns of k_tape_wave_hvp: 0 the schedule cannot run the product (not ready; NT = 64 and the columns do not fit), 1 LDS,
+// 2 global memory.  Option tape_wave_regs forces one where both are possible.  The rule without it: LDS whenever the columns fit, at every unit
+// count -- unlike the solver (wave_place_registers: global memory from 512 instances on), whose blocks live for thousands of evaluations; a unit
+// is two sweeps, and what global memory buys in resident blocks per CU it pays in every pass (dense Hessians, device time, LDS / global:
+// the planner as written, 71 680 units, 7.15 / 14.8 ms; the 65-variable shape tape, 266 240 units, 6.04 / 9.86 ms; profiles/tape_hvp_wave_rates.json).
+int oh_tape_wave_hvp_place(const TapeWave& W) {
+  if (!W.ready) return 0;
+  const bool lds_ok = oh_tape_wave_hvp_lds_bytes(W, true) <= W.lds_limit;
+  const bool global_ok = W.nt == 256 && oh_tape_wave_hvp_lds_bytes(W, false) <= W.lds_limit;  // (the global placement is built for four wavefronts, as the solver's)
+  if (!lds_ok && !global_ok) return 0;
+  if (!global_ok) return 1;
+  if (!lds_ok) return 2;
+  return W.reg_choice == 0 ? 2 : 1;
+}
+
+hipError_t oh_launch_tape_wave_hvp(hipStream_t s, const TapeWave& W, const TapeParams& T, bool reg_lds, int u0, int n, int nv, const double* x, const double* p,
+                                   const double* seeds, const double* V, double* regs, double* HV, double* grad) {
+  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  const size_t bytes = oh_tape_wave_hvp_lds_bytes(W, reg_lds);
+#define OH_TW_HVP(NTv, Rv)                                                                                                                        \
+  do {                                                                                                                                            \
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_hvp<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
+    if (e != hipSuccess) return e;                                                                                                                \
+    hipLaunchKernelGGL((k_tape_wave_hvp<NTv, Rv>), dim3(n), dim3(NTv), bytes, s, T, S, u0, nv, x, p, seeds, V, regs, HV, grad);                         \
+  } while (0)
+  if (!reg_lds) OH_TW_HVP(256, false);
+  else if (W.nt == 64) OH_TW_HVP(64, true);
+  else OH_TW_HVP(256, true);
+#undef OH_TW_HVP
+  return hipGetLastError();
+}
+
+// code-object facts of the product kernel: four wavefronts, the columns in LDS at the largest register file the device's LDS takes
+bool oh_kernel_info_tape_wave(const char* name, OhKernelInfo* out) {
+  if (std::string(name) != "k_tape_wave_hvp") return false;
+  int dev = 0, lds_limit = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
+  const void* fn = reinterpret_cast<const void*>(k_tape_wave_hvp<256, true>);
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess) { (void)hipGetLastError(); return false; }
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, fn) != hipSuccess) return false;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tape_wave_hvp<256, true>, 256, (size_t)lds_limit) != hipSuccess) nb = 0;
+  *out = OhKernelInfo{a.numRegs, (int)a.localSizeBytes, (int)(a.sharedSizeBytes + lds_limit), 256, nb};
+  return true;
 }
