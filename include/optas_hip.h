@@ -383,7 +383,12 @@ int oh_tape_hvp(oh_handle* h, int B, const double* x, const double* p, const dou
    k_tape_solve_newton (oh_get_flag "tape_newton": 1 after such a solve).  A metric of the handle (oh_tape_set_metric) is the preconditioner of CG.
    max_iter caps evaluations plus products and iters [B] reports that sum; x, f, kkt, status and the multipliers keep their meaning and layout.
    oh_tape_newton_stats: steps [B] accepted line-search steps, hvps [B] products of every instance of the last solve, which must have been a Newton-CG
-   solve of B instances (OH_ERR_STATE otherwise).  Host buffers. */
+   solve of B instances (OH_ERR_STATE otherwise).  Host buffers.
+   With option tape_newton_wave != 0 as well the handle builds the wavefront schedule (tape_wave's rules) and the solve runs k_tape_wave_newton, one block
+   per instance, every CG iteration one self-contained forward-over-reverse sweep of the merit on the level schedule; oh_tape_phi_hvp then runs that
+   sweep, one block per (instance, direction).  oh_get_flag "tape_newton_path": what the last Newton-CG solve or oh_tape_phi_hvp ran -- 0 the
+   interpreter (also where the handle has no schedule: nx <= 48 without tape_lbfgs, or a 64-thread handle whose columns do not fit), 1 / 2 the schedule
+   with its four register columns in LDS / in global memory. */
 int oh_tape_newton_stats(oh_handle* h, int B, int* steps, int* hvps);
 
 /* The counterpart of oh_tape_phi for that solver's product: per instance ONE evaluation of the merit at x [B][nx], p [B][np] with multipliers
@@ -464,7 +469,7 @@ int oh_solve(oh_handle* h, int B, const double* x0, const double* p, double* x, 
    k_retract + k_evalb_zc + k_step_zc, the neighbour coupling folded in; 0: k_couple runs as a launch of its own), "tail_threshold",
    "specialized"; OH_PROBLEM_TAPE handles: "tape_wave" (0: one thread per instance; 1 / 2: one block of wavefronts per instance, the quasi-Newton
    pairs in global memory / in LDS), "tape_regs_lds" (1: the tape's registers of the last launch in LDS, 0: in global memory -- batches beyond 512 instances and tapes that do
-   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_hvp_launches" (kernel launches of the last oh_tape_hvp), "tape_newton" (1: the last solve ran k_tape_solve_newton), "tape_jit_lds" (1: the last oh_tape_phi ran
+   not fit), "tape_levels" and "tape_passes" (dependency levels of the tape; instruction passes of one evaluation), "tape_hvp_launches" (kernel launches of the last oh_tape_hvp), "tape_newton" (1: the last solve ran a Newton-CG kernel), "tape_newton_path" (0 / 1 / 2: see oh_tape_newton_stats), "tape_jit_lds" (1: the last oh_tape_phi ran
    the generated code's entry with its work set in LDS); OH_PROBLEM_QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance
    kernel k_qp_solve_block); position-tracking handles (lock_orientation = 0): "free_sweep", the kernel that solved the block-tridiagonal system
    of the last oh_solve / oh_solve_device call's first launch -- 0 k_step_free (one lane per instance), 1 k_step_free_pcr, 2 k_step_free_cp,
@@ -503,6 +508,9 @@ int oh_get_flag(oh_handle* h, const char* name, int* value);
  *   tape_wave (1), tape_lbfgs (-1 = by size), tape_wave_nt (256), tape_wave_regs (-1), tape_wave_hist (-1) -- tape evaluator (rebuilt when set)
  *   tape_newton (0; != 0: the inner solver is truncated Newton-CG on exact merit curvature, oh_tape_newton_stats -- changes the iterates; OH_PROBLEM_TAPE
  *       handles only, OH_ERR_INVALID on others), tape_newton_cg (-1 = by size: min(nx, 50); CG iterations per Newton step, negative values are refused)
+ *   tape_newton_wave (0; != 0 with tape_newton: the wavefront schedule is built under tape_wave's rules and Newton-CG runs on it, one block per instance
+ *       (k_tape_wave_newton; oh_get_flag "tape_newton_path"); silently the interpreter where there is no schedule or no placement; without tape_newton: nothing;
+ *       OH_PROBLEM_TAPE handles only; rebuilt when set)
  *   tq_check (4), tq_rebuild (0.9), tq_stall (25), tq_curv_after (3), tq_curv_from (0.1), tq_ftb (0.995), tq_theta_mu (1.35), tq_kappa_mu (0.4),
  *   tq_kappa_eps (10), tq_curv_late (1), tq_max_back (3), tq_mu_dec (1/3; warm ticks of oh_tq_rollout: tq_mu_dec_warm, 0.1), tq_ls_curv (1), tq_curv_lag (3: the exact-curvature term is computed at every 4th evaluation of an instance and reused in between; 0: always),
  *   tq_jac_dual (0)                                                                                     -- torque-MPC family

@@ -152,11 +152,13 @@ class TapeBackend(_SolveMixin):
             from .tape import quadratic_cost_metric
 
             self._h0 = quadratic_cost_metric(tape)
-        # Newton-CG (option tape_newton) runs on the interpreter: no re-association for the wavefront evaluator and no generated code, neither would run
+        # Newton-CG (option tape_newton) runs on the interpreter: no re-association for the wavefront evaluator and no generated code, neither would run --
+        # unless tape_newton_wave asks for the level schedule too (k_tape_wave_newton): then the tape is re-associated as for the quasi-Newton solver
         self.newton = float((options or {}).get("tape_newton", 0)) != 0.0
+        newton_wave = self.newton and float((options or {}).get("tape_newton_wave", 0)) != 0.0
         if self.newton:
             jit = False
-        want_wave = bool(wave) and not self.newton and int(tape.nx) > 48 and float((options or {}).get("tape_wave", 1)) != 0.0
+        want_wave = bool(wave) and (not self.newton or newton_wave) and int(tape.nx) > 48 and float((options or {}).get("tape_wave", 1)) != 0.0
         if want_wave:
             # chains of additions are dependency levels for that evaluator, so sums go in as balanced trees (same values to the rounding of the
             # summation order).  Whether the path is taken is the library's decision (limited-memory regime, LDS fit): the handle is asked, and a
@@ -303,7 +305,7 @@ class TapeBackend(_SolveMixin):
         return steps, hvps
 
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'tape_newton' (1: the last solve ran the Newton-CG kernel), 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian()), 'tape_hvp_path' (what they ran: 0 the interpreter, one lane per (instance, direction); with option tape_hvp_wave on a wavefront handle 1 / 2: a block per (instance, direction) on the level schedule, registers in LDS / in global memory)."""
+        """oh_get_flag: 'tape_newton' (1: the last solve ran a Newton-CG kernel), 'tape_newton_path' (what the last Newton-CG solve or phi_hvp() ran: 0 the interpreter, 1 / 2 the level schedule with options tape_newton + tape_newton_wave, registers in LDS / in global memory), 'tape_jit_lds' (the last phi() ran the generated code's entry with its work set in LDS), 'tape_wave' (0 thread per instance, 1 / 2 wavefront per instance), 'tape_regs_lds', 'tape_levels', 'tape_passes', 'tape_metric', 'tape_hvp_launches' (kernel launches of the last hvp() / hessian()), 'tape_hvp_path' (what they ran: 0 the interpreter, one lane per (instance, direction); with option tape_hvp_wave on a wavefront handle 1 / 2: a block per (instance, direction) on the level schedule, registers in LDS / in global memory)."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)

@@ -87,8 +87,8 @@ static int set_option_impl(oh_handle* h, const std::string& name, double v) {
 extern "C" int oh_set_option(oh_handle* h, const char* name, double value) {
   if (!h || !name) return fail(OH_ERR_INVALID, "oh_set_option: null argument");
   // (here, not in set_option_impl: OH_DEBUG_OPTIONS is applied to a handle before its kind is known, and to handles of every kind)
-  if (std::string(name) == "tape_newton" && value != 0.0 && h->desc.kind != OH_PROBLEM_TAPE)
-    return fail(OH_ERR_INVALID, "oh_set_option: tape_newton is an option of OH_PROBLEM_TAPE handles");
+  if ((std::string(name) == "tape_newton" || std::string(name) == "tape_newton_wave") && value != 0.0 && h->desc.kind != OH_PROBLEM_TAPE)
+    return fail(OH_ERR_INVALID, std::string("oh_set_option: ") + name + " is an option of OH_PROBLEM_TAPE handles");
   return set_option_impl(h, name, value);
 }
 extern "C" int oh_get_option(oh_handle* h, const char* name, double* value) {
@@ -1401,6 +1401,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_hvp_launches") *value = h->tape.hvp_launches;
   else if (n == "tape_hvp_path") *value = h->tape.hvp_path;
   else if (n == "tape_newton") *value = h->tape.last_newton;
+  else if (n == "tape_newton_path") *value = h->tape.newton_path;
   else if (n == "tape_metric") *value = (h->tape.P.h0 && h->tape.P.lbfgs > 0) ? 1 : 0;
   else if (n == "tape_levels") *value = h->tape.wave.n_levels;
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;

@@ -50,7 +50,8 @@ extern "C" int oh_tape_compile(const oh_tape_desc* d, size_t* code_bytes, char* 
 
 // (Re)build the evaluator of an OH_PROBLEM_TAPE handle from its host copy of the tape and its options: the wavefront-per-instance schedule where it
 // applies (tape_wave != 0, limited-memory regime, LDS fit), otherwise generated code (desc.jit) or the interpreter.  With tape_newton != 0 the solves run
-// k_tape_solve_newton on the interpreter: neither the schedule nor generated code is built for an evaluator that will not run.
+// k_tape_solve_newton on the interpreter: neither the schedule nor generated code is built for an evaluator that will not run -- unless tape_newton_wave != 0
+// asks for the schedule too, under the same rules, for k_tape_wave_newton (generated code is never built for a Newton-CG handle).
 int tape_configure(oh_handle* h) {
   TapeState& tp = h->tape;
   oh_tape_desc d = tp.desc;
@@ -61,7 +62,8 @@ int tape_configure(oh_handle* h) {
   tp.wave = TapeWave{};
   tp.work.release();  // the work arrays were sized for the other evaluator
   tp.mult.release();
-  if (optv(h, "tape_newton") != 0.0) return OH_OK;
+  const bool newton = optv(h, "tape_newton") != 0.0;
+  if (newton && optv(h, "tape_newton_wave") == 0.0) return OH_OK;
   int lds_limit = 0;
   if (optv(h, "tape_wave") != 0.0 && hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess) {
     std::string err;
@@ -69,7 +71,7 @@ int tape_configure(oh_handle* h) {
                            (int)optv(h, "tape_wave_hist"), &tp.wave, &err))
       return fail(OH_ERR_HIP, ("oh_create_tape: " + err).c_str());
   }
-  if (d.jit && !tp.wave.ready && !tp.jit.fn) {
+  if (d.jit && !newton && !tp.wave.ready && !tp.jit.fn) {
     std::vector<char> code;
     std::string err;
     const std::string src = oh_tape_jit_source(tp.P, d.op, d.a, d.b, d.c, d.rows);
@@ -247,6 +249,11 @@ extern "C" int oh_tape_phi_hvp(oh_handle* h, int B, const double* x, const doubl
   HIPCHK(hipSetDevice(h->device));
   const int Bp = (B + 63) / 64 * 64;
   const size_t nB = (size_t)B, b_u = sizeof(double) * (size_t)T.nx * nB * (size_t)nv;
+  // options tape_newton + tape_newton_wave on a handle whose schedule is ready: the sweep k_tape_wave_newton runs, one block per (instance, direction); every
+  // other handle, and a schedule whose work set fits nowhere: the interpreter's hess_vec
+  if (nB * (size_t)nv > (size_t)0x3fffffff) return fail(OH_ERR_INVALID, "oh_tape_phi_hvp: B * nv does not fit an int");
+  const int path = (optv(h, "tape_newton") != 0.0 && optv(h, "tape_newton_wave") != 0.0) ? oh_tape_wave_newton_place(tp.wave, T) : 0;
+  const int nrow1 = T.n_ineq + T.n_eq > 0 ? T.n_ineq + T.n_eq : 1;
   double *d_x, *d_g, *d_p, *d_l, *d_m, *d_v, *d_hv, *d_w;
   auto layout = [&](Carver c) {
     d_x = c.take<double>((size_t)T.nx * nB);
@@ -256,7 +263,7 @@ extern "C" int oh_tape_phi_hvp(oh_handle* h, int B, const double* x, const doubl
     d_m = c.take<double>((size_t)(T.n_eq > 0 ? T.n_eq : 1) * nB);
     d_v = c.take<double>((size_t)T.nx * nB * nv);
     d_hv = c.take<double>((size_t)T.nx * nB * nv);
-    d_w = c.take<double>(oh_tape_newton_work_rows(T) * Bp);
+    d_w = c.take<double>(path ? (4 + (size_t)nrow1) * nB : oh_tape_newton_work_rows(T) * Bp);
     return c.bytes();
   };
   if (const int rc = stage_carve(h, layout)) return rc;
@@ -266,7 +273,11 @@ extern "C" int oh_tape_phi_hvp(oh_handle* h, int B, const double* x, const doubl
   if (T.n_ineq > 0) HIPCHK(hipMemcpyAsync(d_l, lam, sizeof(double) * (size_t)T.n_ineq * nB, hipMemcpyHostToDevice, s));
   if (T.n_eq > 0) HIPCHK(hipMemcpyAsync(d_m, mu, sizeof(double) * (size_t)T.n_eq * nB, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(d_v, V, b_u, hipMemcpyHostToDevice, s));
-  oh_launch_tape_phi_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, B, Bp, d_x, d_p, d_l, d_m, rho, nv, d_v, d_w, d_hv, grad ? d_g : nullptr);
+  tp.newton_path = path;
+  if (path)
+    HIPCHK(oh_launch_tape_wave_phi_hvp(s, tp.wave, T, path, B, nv, d_x, d_p, d_l, d_m, rho, d_v, d_hv, d_g, d_w));
+  else
+    oh_launch_tape_phi_hvp(s, T, tp.op, tp.a, tp.b, tp.c, tp.rows, B, Bp, d_x, d_p, d_l, d_m, rho, nv, d_v, d_w, d_hv, grad ? d_g : nullptr);
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(HV, d_hv, b_u, hipMemcpyDeviceToHost));
@@ -321,7 +332,8 @@ static int tape_ensure_work(oh_handle* h, const int Bp) {
     size_t rows = oh_tape_work_rows(tp.P, tp.jit.fn != nullptr);
     // (a Newton-CG handle: its own work set, and room for the interpreter's layout, which oh_tape_phi launches on such a handle)
     if (optv(h, "tape_newton") != 0.0) rows = std::max(oh_tape_newton_work_rows(tp.P), oh_tape_work_rows(tp.P, false));
-    if (!tp.wave.ready) HIPCHK(tp.work.reserve(rows * Bp));
+    // (a Newton-CG handle with a schedule keeps the interpreter's arrays too: k_tape_solve_newton is where it falls back to when the work set fits nowhere)
+    if (!tp.wave.ready || (optv(h, "tape_newton") != 0.0 && oh_tape_wave_newton_place(tp.wave, tp.P) == 0)) HIPCHK(tp.work.reserve(rows * Bp));
     HIPCHK(tp.mult.reserve((size_t)(tp.P.n_ineq + tp.P.n_eq + 1) * Bp));
   }
   return OH_OK;
@@ -394,7 +406,14 @@ int tape_solve_device(oh_handle* h, const Solve& a) {
     const int cg = (int)optv(h, "tape_newton_cg");
     HIPCHK(tp.nstat.reserve(2 * (size_t)B));
     tp.nstat_B = B;
+    // option tape_newton_wave on a handle whose schedule is ready and whose work set has a placement: one block per instance on the level schedule
+    tp.newton_path = optv(h, "tape_newton_wave") != 0.0 ? oh_tape_wave_newton_place(tp.wave, tp.P) : 0;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (tp.newton_path) {
+      HIPCHK(oh_launch_tape_wave_newton(h->stream, tp.wave, tp.P, tp.newton_path, B, cg > 0 ? cg : std::min(tp.P.nx, 50), a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status,
+                                        tp.mult, tp.nstat));
+      return finish_solve(h, 1);
+    }
     oh_launch_tape_solve_newton(h->stream, tp.P, tp.op, tp.a, tp.b, tp.c, tp.rows, B, tp.cap(), cg > 0 ? cg : std::min(tp.P.nx, 50), a.x0, a.p, tp.work, a.x, a.f,
                                 a.kkt, a.iters, a.status, tp.mult, tp.nstat);
     return finish_solve(h, 1);

@@ -124,7 +124,9 @@ struct TapeState {
   int hvp_path = 0;      // what they ran: 0 k_tape_hvp, 1 / 2 k_tape_wave_hvp with its registers in LDS / in global memory ("tape_hvp_path")
   DevBuf<int> nstat;     // [nstat_B][2]: Newton steps and Hessian-vector products of every instance of the last Newton-CG solve (oh_tape_newton_stats)
   int nstat_B = 0;
-  int last_newton = 0;   // the last solve ran k_tape_solve_newton (oh_get_flag "tape_newton")
+  int last_newton = 0;   // the last solve ran a Newton-CG kernel (oh_get_flag "tape_newton")
+  int newton_path = 0;   // what the last Newton-CG solve or oh_tape_phi_hvp ran: 0 the interpreter (k_tape_solve_newton, k_tape_phi_hvp), 1 / 2 the level
+                         // schedule (k_tape_wave_newton, k_tape_wave_merit_hvp) with its registers in LDS / in global memory ("tape_newton_path")
   TapeWave wave;     // trajectory-sized tapes: one wavefront per instance (oh_tape_wave.hip)
   // host copy of the tape of an OH_PROBLEM_TAPE handle: the evaluator is rebuilt when an option that shapes it changes (tape_wave, tape_lbfgs, ...)
   std::vector<int> h_op, h_a, h_b, h_rows;
@@ -264,7 +266,7 @@ struct OptDoc { const char* name; double dflt; };
 static constexpr OptDoc OPT_TABLE[] = {
     {"check_every", 1},        {"lean_count", 0},        {"row_pad", 13},          {"retract_min", 1e-13}, {"hyb_switch", 1e-5},   {"relax", 1.5},          {"relax_from", 4},         {"settle_k", 1.0},   {"al_fuse", 1},   {"streams", 2},         {"split_min", 65536},  {"tq_split_min", 1024}, {"free_split_min", 256},
     {"free_bb", 1},            {"free_persist", -1},     {"free_cp_max", 512},   {"pm_wave_max", 20480}, {"qp_mode", -1},         {"tape_lds_max", 1 << 30}, {"tape_hvp_work_mb", 256}, {"tape_hvp_wave", 0},
-    {"tape_newton", 0},        {"tape_newton_cg", -1},
+    {"tape_newton", 0},        {"tape_newton_cg", -1},   {"tape_newton_wave", 0},
     {"tape_wave", 1},          {"tape_lbfgs", -1},       {"tape_wave_nt", 256},  {"tape_wave_regs", -1}, {"tape_wave_hist", -1},  {"tq_stall", 25},
     {"tq_curv_after", 3},      {"tq_ftb", 0.995},        {"tq_theta_mu", 1.35},  {"tq_kappa_mu", 0.4},   {"tq_curv_from", 0.1},   {"tq_jac_dual", 0},
     {"tq_rebuild", 0.9},         {"compact_move_all", 1},  {"tq_curv_late", 1.0},  {"tq_kappa_eps", 10.0}, {"tq_max_back", 3},     {"tq_mu_dec", 1.0 / 3.0},     {"tq_ls_curv", 1},   {"tq_mu_dec_warm", 0.1}, {"tq_curv_lag", 3},

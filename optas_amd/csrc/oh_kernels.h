@@ -222,6 +222,16 @@ int oh_tape_wave_hvp_place(const TapeWave& W);
 size_t oh_tape_wave_hvp_lds_bytes(const TapeWave& W, bool reg_lds);
 hipError_t oh_launch_tape_wave_hvp(hipStream_t s, const TapeWave& W, const TapeParams& T, bool reg_lds, int u0, int n, int nv, const double* x, const double* p,
                                    const double* seeds, const double* V, double* regs, double* HV, double* grad);
+// truncated Newton-CG on the level schedule, one block per instance (options tape_newton + tape_newton_wave; k_tape_wave_newton): oh_tape_wave_newton_place
+// says where the four register columns go (0: the interpreter's kernel stays, 1: LDS, 2: the global register buffer)
+int oh_tape_wave_newton_place(const TapeWave& W, const TapeParams& T);
+size_t oh_tape_wave_newton_lds_bytes(const TapeParams& T, const TapeWave& W, bool reg_lds);
+hipError_t oh_launch_tape_wave_newton(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int cg_cap, const double* x0, const double* p, double* x,
+                                      double* f, double* kkt, int* iters, int* status, double* mult, int* stats);
+// oh_tape_phi_hvp on such a handle: one k_tape_wave_phi per instance (grad; scratch: [(4 + max(nrows, 1)) B] doubles), then the merit's product by the
+// solver's sweep, one block per (instance, direction) (k_tape_wave_merit_hvp)
+hipError_t oh_launch_tape_wave_phi_hvp(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int nv, const double* x, const double* p, const double* lam,
+                                       const double* mu, double rho, const double* V, double* HV, double* grad, double* scratch);
 size_t oh_tape_work_rows(const TapeParams& T, bool jit);
 // one InterpEval::phi per instance (oh_tape_phi); work as for oh_launch_tape_solve
 void oh_launch_tape_phi(hipStream_t s, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows, int B, int Bp,

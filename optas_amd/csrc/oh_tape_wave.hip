@@ -766,6 +766,517 @@ __global__ __launch_bounds__(NT) void k_tape_wave_hvp(TapeParams T, WaveSchedDev
     for (int k = lane; k < n; k += NT) grad[inst * n + k] = val[XREG0 + k];
 }
 
+// The product of the merit's generalised Hessian with a vector on the level schedule (options tape_newton + tape_newton_wave): k_tape_wave_hvp's
+// four-column sweep over [val | adj | tan | dadj] with SEED TANGENTS.  WaveEval::phi destroys val[] in its reverse sweep, so nothing of an evaluation
+// survives for a product to reuse (the interpreter's hess_vec reuses all of it): the sweep is self-contained, from (xs, vs, lam, mu, rho) alone.
+//   forward  phi's passes with the tangent beside every value (k_tape_wave_hvp's, to the letter);
+//   rows     the seed of row r is tape_al_ineq / tape_al_eq as in phi; its tangent is rho tan[row_reg[r]] for an equality row and for an inequality row
+//            whose seed is not zero (lam - rho g > 0 by tape_al_ineq's own expression: a tie is inactive, as InterpEval::hess_vec has it), else 0 (rowt);
+//   seeds    adj[seed_reg[s]] as phi fills it, dadj[seed_reg[s]] the same sum over rowt -- started from -0, the one value that leaves every addend's bits
+//            alone: a seed register without rows then gathers exactly what k_tape_wave_hvp, which has no dadj seed, gathers;
+//   reverse  k_tape_wave_hvp's passes, dw starting from that seed where the entry has one.  Kinks hold the base point's selection.
+// The variables' entries leave the merit's gradient in val[XREG0 + k] (phi's bits: the two left columns see phi's arithmetic in phi's order) and
+// H v in tan[XREG0 + k].  Contraction off, the gather order the schedule's: a product's bits depend on the instance and the direction alone.
+// A FOURTH statement of the second-order rare-opcode rules (oh_tape_ops.h): k_tape_wave_hvp's text, its 169 VGPRs without scratch and the bits of
+// profiles/tape_hvp_wave_ab.json are pinned, and a device function both would call has to take the four columns and the entry through pointers or
+// references -- the form that put phi's contributions into scratch memory (see the comment in phi's reverse pass).  Change one, change all four.
+template <int NT, bool REG_LDS>
+struct WaveSweep {
+  const TapeParams& T;
+  const WaveSchedDev& S;
+  double *val, *lam, *mu, *roww, *rowt;  // val: the four columns, n_reg doubles each
+  const int *row_reg, *seed_reg, *seed_off, *seed_rows;
+  const int lane;
+
+  // xs, vs: the point and the direction (element k anywhere); gout (may be null): the merit's gradient; hout: H v.  EVAL: also what phi returns -- the
+  // rows into rowv, the merit's value (uniform) -- so that the sweep can stand in for phi (the one-site variant of k_tape_wave_newton).
+  template <bool EVAL = false>
+  __device__ __attribute__((always_inline)) double hvp(const double* xs, const double* vs, double* gout, double* hout, const double rho, double* rowv = nullptr,
+                                                       Red<NT>* red = nullptr, double* fout = nullptr, double* cmax = nullptr, double* meas = nullptr) {
+#pragma clang fp contract(off)
+    const int n = T.nx, nr = S.n_reg, D2 = 2 * S.n_reg;
+    double* adj = val + nr;
+    double* tan = val + D2;
+    double* dadj = tan + nr;
+    auto pass_barrier = [] { WaveEval<NT, REG_LDS>::pass_barrier(); };
+    __syncthreads();  // xs and vs were written element-wise by their owners
+    const int last = S.n_fw_pass - 1;
+    auto fwi = [&](int p) { return S.fw[(size_t)(p < last ? p : last) * NT + lane]; };
+    int4 q0 = fwi(0), q1 = fwi(1), q2 = fwi(2), q3 = fwi(3);
+    for (int k = lane; k < n; k += NT) { val[XREG0 + k] = xs[k]; tan[XREG0 + k] = vs[k]; }
+    pass_barrier();
+    auto fw_pass = [&](const int4 ins) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
+      const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
+      const int fl = ins.w;
+      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+      const double b2 = bsel(mS, va, vb), tb2 = bsel(mS, ta, tb);
+      double v = bsel(mM, va * b2, bflip(va, mA) + bkeep(bflip(b2, mB), mZ));
+      double t = bsel(mM, ta * b2 + va * tb2, bflip(ta, mA) + bkeep(bflip(tb2, mB), mZ));
+      if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
+        switch (o) {
+          case OP_DIV: v = va / vb; t = (ta - v * tb) / vb; break;
+          case OP_SIN: v = sin(va); t = cos(va) * ta; break;
+          case OP_COS: v = cos(va); t = -(sin(va) * ta); break;
+          case OP_ATAN2: v = atan2(va, vb); t = (vb * ta - va * tb) / (va * va + vb * vb); break;
+          case OP_SQRT: v = sqrt(va); t = 0.5 / v * ta; break;
+          case OP_ASIN: v = asin(va); t = ta / sqrt((1.0 - va) * (1.0 + va)); break;
+          case OP_FABS: v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * ta; break;
+          case OP_FMIN: v = fmin(va, vb); t = va <= vb ? ta : tb; break;
+          case OP_FMAX: v = fmax(va, vb); t = va >= vb ? ta : tb; break;
+          case OP_LT: v = va < vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_LE: v = va <= vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_EQ: v = va == vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_NE: v = va != vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; t = 0.0; break;
+          case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+          case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+          case OP_IFZ: v = va != 0.0 ? vb : 0.0; t = va != 0.0 ? tb : 0.0; break;
+          case OP_EXP: v = exp(va); t = v * ta; break;
+          case OP_LOG: v = log(va); t = ta / va; break;
+          default: break;
+        }
+      }
+      val[i] = v;
+      tan[i] = t;
+      pass_barrier();
+    };
+    for (int p = 0; p < S.n_fw_pass; p += 4) {
+      const int4 i0 = q0;
+      q0 = fwi(p + 4);
+      fw_pass(i0);
+      const int4 i1 = q1;
+      q1 = fwi(p + 5);
+      fw_pass(i1);
+      const int4 i2 = q2;
+      q2 = fwi(p + 6);
+      fw_pass(i2);
+      const int4 i3 = q3;
+      q3 = fwi(p + 7);
+      fw_pass(i3);
+    }
+    // ---- rows: phi's seeds and their tangents
+    const double f = EVAL ? val[S.seed_cost >= 0 ? seed_reg[S.seed_cost] : 0] : 0.0;
+    double v0 = 0.0, c0 = 0.0, m0 = 0.0;
+    for (int r = lane; r < S.nrows; r += NT) {
+      const double g = val[row_reg[r]], tg = tan[row_reg[r]];
+      if constexpr (EVAL) rowv[r] = g;
+      if (r < T.n_ineq) {
+        const double sd = tape_al_ineq(g, lam[r], rho, v0, c0, m0);
+        roww[r] = sd;
+        rowt[r] = sd < 0.0 ? rho * tg : 0.0;  // the seed phi plants is not zero: active
+      } else {
+        roww[r] = tape_al_eq(g, mu[r - T.n_ineq], rho, v0, c0, m0);
+        rowt[r] = rho * tg;
+      }
+    }
+    __syncthreads();
+    for (int s = lane; s < S.n_seed; s += NT) {
+      double acc = s == S.seed_cost ? 1.0 : 0.0, dacc = -0.0;
+      for (int e = seed_off[s]; e < seed_off[s + 1]; ++e) { acc += roww[seed_rows[e]]; dacc += rowt[seed_rows[e]]; }
+      adj[seed_reg[s]] = acc;
+      dadj[seed_reg[s]] = dacc;
+    }
+    __syncthreads();
+    // ---- reverse
+    const int rlast = S.n_rv_pass - 1;
+    auto rvi = [&](int p, int h) { return S.rv[((size_t)(p < rlast ? p : rlast) * NT + lane) * 2 + h]; };
+    int4 a0 = rvi(0, 0), b0 = rvi(0, 1), a1 = rvi(1, 0), b1 = rvi(1, 1), a2 = rvi(2, 0), b2 = rvi(2, 1), a3 = rvi(3, 0), b3 = rvi(3, 1);
+    auto rv_pass = [&](const int4 ins, const int4 meta) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
+      const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
+      const long long mSeed = fmask(meta.x >> 16, 1);
+      const double sd_ = adj[i], dsd_ = dadj[i], s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
+      const double e0 = val[meta.y + D2], e1 = val[meta.z + D2], e2 = val[meta.w + D2];
+      double w = bkeep(sd_, mSeed);
+      w += s0;
+      w += s1;
+      w += s2;
+      double dw = bsel(mSeed, dsd_, -0.0);  // (-0 + e0 is e0 to the bit)
+      dw += e0;
+      dw += e1;
+      dw += e2;
+      if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
+        for (int e = 3; e < nc; ++e) {
+          const int sl = S.cons[ins.w + e - 3];
+          w += val[sl];
+          dw += val[sl + D2];
+        }
+      const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
+      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+      const double qa = bsel(mS, va + va, vb), dqa = bsel(mS, ta + ta, tb);
+      double ca = bsel(mM, w * qa, bflip(w, mA));
+      double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, mB), mZ));
+      double dca = bsel(mM, dw * qa + w * dqa, bflip(dw, mA));
+      double dcb = bsel(mM, bkeep(dw * va + w * ta, ~mS), bkeep(bflip(dw, mB), mZ));
+      const bool rare = (fl & F_RARE) != 0;
+      if (__builtin_amdgcn_ballot_w64(rare) != 0) {
+        if (rare) { ca = 0.0; cb = 0.0; dca = 0.0; dcb = 0.0; }
+        switch (o) {
+          case OP_DIV:
+            ca = w / vb; cb = -(w * va / (vb * vb));
+            dca = (dw - w * tb / vb) / vb; dcb = -((dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb));
+            break;
+          case OP_SIN: { const double c = cos(va); ca = w * c; dca = dw * c - w * sin(va) * ta; } break;
+          case OP_COS: { const double s = sin(va); ca = -(w * s); dca = -(dw * s + w * cos(va) * ta); } break;
+          case OP_ATAN2: {
+            const double d = va * va + vb * vb, dd = 2.0 * (va * ta + vb * tb);
+            ca = w * vb / d; cb = -(w * va / d);
+            dca = (dw * vb + w * (tb - vb * dd / d)) / d; dcb = -((dw * va + w * (ta - va * dd / d)) / d);
+          } break;
+          case OP_SQRT: { const double r = val[i], q = 0.5 / r; ca = w * 0.5 / r; dca = dw * q - w * (q * tan[i] / r); } break;
+          case OP_ASIN: { const double s = (1.0 - va) * (1.0 + va), r = sqrt(s); ca = w / r; dca = dw / r + w * (va * ta / (s * r)); } break;
+          case OP_FABS: { const double sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0); ca = w * sg; dca = dw * sg; } break;
+          case OP_FMIN: if (va <= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+          case OP_FMAX: if (va >= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+          case OP_IFZ: if (va != 0.0) { cb = w; dcb = dw; } break;
+          case OP_EXP: { const double q = val[i]; ca = w * q; dca = dw * q + w * tan[i]; } break;
+          case OP_LOG: ca = w / va; dca = (dw - w * ta / va) / va; break;
+          default: break;  // LT .. OR: piecewise constant
+        }
+      }
+      val[i] = ca;
+      adj[i] = cb;
+      tan[i] = dca;
+      dadj[i] = dcb;
+      pass_barrier();
+    };
+    for (int p = 0; p < S.n_rv_pass; p += 4) {
+      const int4 x0 = a0, y0 = b0;
+      a0 = rvi(p + 4, 0); b0 = rvi(p + 4, 1);
+      rv_pass(x0, y0);
+      const int4 x1 = a1, y1 = b1;
+      a1 = rvi(p + 5, 0); b1 = rvi(p + 5, 1);
+      rv_pass(x1, y1);
+      const int4 x2 = a2, y2 = b2;
+      a2 = rvi(p + 6, 0); b2 = rvi(p + 6, 1);
+      rv_pass(x2, y2);
+      const int4 x3 = a3, y3 = b3;
+      a3 = rvi(p + 7, 0); b3 = rvi(p + 7, 1);
+      rv_pass(x3, y3);
+    }
+    if (gout)
+      for (int k = lane; k < n; k += NT) gout[k] = val[XREG0 + k];
+    for (int k = lane; k < n; k += NT) hout[k] = tan[XREG0 + k];
+    __syncthreads();
+    if constexpr (EVAL) {
+      v0 = f + red->sum(v0);
+      *fout = f;
+      *cmax = red->max(c0);
+      *meas = red->max(m0);
+    }
+    return v0;
+  }
+};
+
+// LDS layout of the two Newton kernels: [the four columns, when in LDS] x xt g gt d r y p hp | lam | mu | rowv | roww | rowt | reduction buffer | index arrays
+struct NewtonLds {
+  double *val, *X, *XT, *G, *GT, *D, *R, *Y, *PV, *HP, *lam, *mu, *rowv, *roww, *rowt, *redbuf;
+  int* small;
+};
+template <bool REG_LDS>
+__device__ inline NewtonLds newton_carve(const TapeParams& T, const WaveSchedDev& S, double* lds, double* regs_slice) {
+  const size_t n = T.nx, ni = T.n_ineq > 0 ? T.n_ineq : 1, ne = T.n_eq > 0 ? T.n_eq : 1, nr = S.nrows > 0 ? S.nrows : 1;
+  NewtonLds L;
+  double* w = lds;
+  if constexpr (REG_LDS) { L.val = w; w += 4 * (size_t)S.n_reg; } else { L.val = regs_slice; }
+  auto take = [&](size_t k) { double* o = w; w += k; return o; };
+  L.X = take(n); L.XT = take(n); L.G = take(n); L.GT = take(n); L.D = take(n); L.R = take(n); L.Y = take(n); L.PV = take(n); L.HP = take(n);
+  L.lam = take(ni); L.mu = take(ne); L.rowv = take(nr); L.roww = take(nr); L.rowt = take(nr);
+  L.redbuf = take(8);
+  L.small = reinterpret_cast<int*>(w);
+  return L;
+}
+// the registers nobody writes after the set-up: zero and trash in all four columns, constants and parameters with a zero tangent
+template <int NT>
+__device__ inline void newton_setup_registers(const WaveSchedDev& S, double* val, const double* pb, const int lane) {
+  const int nr = S.n_reg;
+  if (lane == 0)
+    for (int c = 0; c < 4; ++c) { val[c * (size_t)nr + ZREG] = 0.0; val[c * (size_t)nr + TRASH] = 0.0; }
+  for (int k = lane; k < S.n_cst; k += NT) { val[S.cst_reg[k]] = S.cst_val[k]; val[2 * (size_t)nr + S.cst_reg[k]] = 0.0; }
+  for (int k = lane; k < S.n_par; k += NT) { val[S.par_reg[k]] = pb[S.par_k[k]]; val[2 * (size_t)nr + S.par_reg[k]] = 0.0; }
+}
+
+// Truncated Newton-CG on the level schedule (options tape_newton + tape_newton_wave): ONE BLOCK PER INSTANCE, the state machine of
+// oh_tape_newton.h:tape_newton_instance -- COPIED, as that one is copied from oh_tape_solver.h: a change to either must be made here too -- with every
+// vector spread over the threads (element k on thread k mod NT) and every dot product a Red.  Two sweep sites in one loop, each inlined once (against the
+// sweep as the only site, an evaluation being a product with a zero tangent -- 85 KB of code instead of 122 KB -- the planner is 4 - 5 % faster this way, 7.64 against 7.97 ms at B = 256): WaveEval::phi
+// for evaluations (why = EV_START .. EV_AGAIN) and WaveSweep::hvp for the CG's products (EV_HVP); what follows a site runs until the next sweep is
+// needed, sets `why` and goes round.  Every decision that leaves the loop or chooses the site is taken from a Red result or a kernel argument:
+// block-uniform, no thread skips a barrier.  max_iter caps evaluations plus products, iters is their sum, stats [B][2] = (steps, products).
+template <int NT, bool REG_LDS>
+__global__ __launch_bounds__(NT) void k_tape_wave_newton(TapeParams T, WaveSchedDev S, int B, int cg_cap, const double* __restrict__ x0, const double* __restrict__ par,
+                                                         double* regs_g, double* __restrict__ xo, double* __restrict__ fo, double* __restrict__ kkt,
+                                                         int* __restrict__ iters, int* __restrict__ status, double* __restrict__ mult, int* __restrict__ stats) {
+  extern __shared__ double lds[];
+  const int gb = blockIdx.x, lane = threadIdx.x;
+  if (gb >= B) return;
+  const int n = T.nx, ni = T.n_ineq, ne = T.n_eq;
+  const NewtonLds L = newton_carve<REG_LDS>(T, S, lds, REG_LDS ? nullptr : regs_g + (size_t)gb * 4 * S.n_reg);
+  double *val = L.val, *X = L.X, *XT = L.XT, *G = L.G, *GT = L.GT, *D = L.D, *R = L.R, *Y = L.Y, *PV = L.PV, *HP = L.HP, *lam = L.lam, *mu = L.mu, *rowv = L.rowv;
+  int* small = L.small;
+  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
+  const int* row_reg = small;
+  const int* seed_reg = row_reg + S.nrows;
+  const int* seed_off = seed_reg + S.n_seed;
+  const int* seed_rows = seed_off + S.n_seed + 1;
+  newton_setup_registers<NT>(S, val, par + (size_t)gb * T.np, lane);
+  for (int k = lane; k < n; k += NT) X[k] = x0[(size_t)gb * n + k];
+  for (int i = lane; i < ni; i += NT) lam[i] = 0.0;
+  for (int i = lane; i < ne; i += NT) mu[i] = 0.0;
+  __syncthreads();
+  Red<NT> red{L.redbuf};
+  WaveEval<NT, REG_LDS> ev{T, S, val, val + S.n_reg, lam, mu, rowv, L.roww, row_reg, seed_reg, seed_off, seed_rows, lane, red};
+  WaveSweep<NT, REG_LDS> sw{T, S, val, lam, mu, L.roww, L.rowt, row_reg, seed_reg, seed_off, seed_rows, lane};
+
+  // y = M r: the handle's metric (k_tape_wave's four-chain column loop for r = H0 q), else the identity.  r is spread over the threads: complete before
+  // anyone reads all of it; y[k] is written by its owner.
+  auto precond = [&](const double* r, double* y) __attribute__((always_inline)) {
+    if (T.h0 == nullptr) {
+      for (int k = lane; k < n; k += NT) y[k] = r[k];
+      return;
+    }
+    __syncthreads();
+    for (int k = lane; k < n; k += NT) {
+      const double* __restrict__ col = T.h0 + k;
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      int j = 0;
+      for (; j + 3 < n; j += 4) {
+        a0 = fma(col[(size_t)j * n], r[j], a0);
+        a1 = fma(col[(size_t)(j + 1) * n], r[j + 1], a1);
+        a2 = fma(col[(size_t)(j + 2) * n], r[j + 2], a2);
+        a3 = fma(col[(size_t)(j + 3) * n], r[j + 3], a3);
+      }
+      for (; j < n; ++j) a0 = fma(col[(size_t)j * n], r[j], a0);
+      y[k] = (a0 + a1) + (a2 + a3);
+    }
+  };
+
+  const bool metric = T.h0 != nullptr;
+  double rho = T.rho0, omega = fmax(T.tol, 1e-2), meas_prev = 1e300, msum = 0.0;
+  double fval = 0.0, cmax = 0.0, meas = 0.0, val_m = 0.0, stat = 0.0;
+  int evals = 0, hvps = 0, steps = 0, st = OH_TAPE_ST_MAX_ITER;
+  bool force_sd = false, newton = false, unit = false;
+  enum { EV_START, EV_OUTER, EV_TRIAL, EV_AGAIN, EV_HVP };
+  int why = EV_START, ls = 0, cgj = 0;
+  const double* xs = X;
+  double* gout = G;
+  double slope = 0.0, alpha = 1.0, slack = 0.0, gg = 0.0, ry = 0.0, gnorm = 0.0, eta = 0.0;
+  for (;;) {
+    const bool prod = why == EV_HVP;
+    double v_ = 0.0, f_ = 0.0, c_ = 0.0, m_ = 0.0;
+#ifdef OH_TAPE_NEWTON_WAVE_ONE_SITE
+    // variant (b) of DESIGN 2.6, kept buildable for the measurement: the four-column sweep is the ONLY site, an evaluation is a product with a zero tangent
+    if (!prod)
+      for (int k = lane; k < n; k += NT) PV[k] = 0.0;  // (free between two CG runs, as HP is)
+    v_ = sw.template hvp<true>(prod ? X : xs, PV, prod ? nullptr : gout, HP, rho, rowv, &red, &f_, &c_, &m_);
+    (void)ev;
+#else
+    if (prod) sw.hvp(X, PV, nullptr, HP, rho);
+    else v_ = ev.phi(xs, gout, rho, &f_, &c_, &m_);
+#endif
+    if (prod) {
+      ++hvps;
+      double pk_ = 0.0, pp_ = 0.0;
+      for (int k = lane; k < n; k += NT) { const double pk = PV[k]; pk_ += pk * HP[k]; pp_ += pk * pk; }
+      const double kappa = red.sum(pk_), pp = red.sum(pp_);
+      bool more = false;
+      if (!(kappa > 1e-12 * pp)) {  // negative or vanishing curvature, or NaN
+        if (cgj == 0) {
+          for (int k = lane; k < n; k += NT) D[k] = -Y[k];
+          unit = true;
+          newton = metric;  // without a metric this IS steepest descent: a failed search from it ends the instance
+        }
+      } else {
+        const double a = ry / kappa;
+        double rr_ = 0.0;
+        for (int k = lane; k < n; k += NT) {
+          D[k] += a * PV[k];
+          const double rk = R[k] + a * HP[k];
+          R[k] = rk;
+          rr_ += rk * rk;
+        }
+        const double rr = red.sum(rr_);
+        if (!(sqrt(rr) <= eta * gnorm) && !(cgj + 1 == cg_cap || evals + hvps + 1 >= T.max_iter)) {  // (the cap; or what is left of the budget is the line search's first trial)
+          precond(R, Y);
+          double ryn_ = 0.0;
+          for (int k = lane; k < n; k += NT) ryn_ += R[k] * Y[k];
+          const double ryn = red.sum(ryn_), beta = ryn / ry;
+          for (int k = lane; k < n; k += NT) PV[k] = -Y[k] + beta * PV[k];
+          ry = ryn;
+          ++cgj;
+          more = true;
+        }
+      }
+      if (more) continue;  // the next product
+    } else {
+      ++evals;
+      if (why == EV_TRIAL) {
+        bool ok = false;  // tape_newton_armijo
+        const double need = -1e-4 * alpha * slope;
+        if (need > slack) {
+          ok = (v_ == v_) && v_ <= val_m - need + slack;
+        } else if ((v_ == v_) && v_ <= val_m - slack) {
+          ok = true;
+        } else if ((v_ == v_) && v_ <= val_m + slack) {
+          double gq = 0.0;
+          for (int k = lane; k < n; k += NT) gq += GT[k] * GT[k];
+          const double ggt = red.sum(gq);
+          ok = ggt <= (1.0 - 1e-4 * alpha) * gg && ggt < gg;
+        }
+        if (!ok) {
+          alpha *= 0.5;
+          ++ls;
+          if (evals + hvps >= T.max_iter || ls >= 40) {  // rowv belongs to the rejected trial: re-evaluate at x before anything reads the rows again
+            why = EV_AGAIN;
+            xs = X;
+            gout = G;
+          } else {
+            for (int k = lane; k < n; k += NT) XT[k] = X[k] + alpha * D[k];
+          }
+          continue;
+        }
+        force_sd = false;
+        ++steps;
+        for (int k = lane; k < n; k += NT) { X[k] = XT[k]; G[k] = GT[k]; }
+      } else if (why == EV_AGAIN) {
+        if (!newton || evals + hvps >= T.max_iter) {  // steepest descent cannot improve: rounding floor
+          val_m = v_; fval = f_; cmax = c_; meas = m_;
+          break;
+        }
+        force_sd = true;
+      }
+      val_m = v_; fval = f_; cmax = c_; meas = m_;
+      // ---- top of the iteration
+      double sm = 0.0, bad = 0.0;
+      for (int k = lane; k < n; k += NT) {
+        const double g = G[k];
+        sm = fmax(sm, fabs(g));
+        if (!(g == g)) bad = 1.0;
+      }
+      stat = red.max(sm);
+      const bool finite = (val_m == val_m) && (fabs(val_m) < 1e300) && red.max(bad) == 0.0;
+      if (!finite) { st = OH_TAPE_ST_NUMERICAL; break; }
+      if (stat <= omega) {
+        if (stat <= T.tol && meas <= T.tol_feas) { st = OH_TAPE_ST_CONVERGED; break; }
+        if (evals + hvps >= T.max_iter) break;
+        double ms_ = 0.0;
+        for (int i = lane; i < ne; i += NT) {
+          const double v = mu[i] - rho * rowv[ni + i];
+          mu[i] = v;
+          ms_ += fabs(v);
+        }
+        for (int i = lane; i < ni; i += NT) {
+          const double v = fmax(0.0, lam[i] - rho * rowv[i]);
+          lam[i] = v;
+          ms_ += v;
+        }
+        msum = red.sum(ms_);
+        if (meas > 0.25 * meas_prev) rho = fmin(rho * 10.0, 1e8);
+        meas_prev = meas;
+        omega = fmax(T.tol, fmin(omega, 0.1 * meas));
+        why = EV_OUTER;
+        xs = X;
+        gout = G;
+        continue;
+      }
+      if (evals + hvps >= T.max_iter) break;
+      newton = !force_sd;  // a failed search from this direction may retry with steepest descent
+      unit = false;        // the direction carries no Newton scale: first trial within unit length
+      if (newton) {
+        // truncated CG on H d = -g: z (in D) = 0, r = g, y = M r, p = -y
+        precond(G, Y);
+        double ry_ = 0.0, gn_ = 0.0;
+        for (int k = lane; k < n; k += NT) {
+          const double gk = G[k], yk = Y[k];
+          D[k] = 0.0;
+          R[k] = gk;
+          PV[k] = -yk;
+          ry_ += gk * yk;
+          gn_ += gk * gk;
+        }
+        ry = red.sum(ry_);
+        gnorm = sqrt(red.sum(gn_));
+        eta = fmin(0.5, sqrt(gnorm));
+        cgj = 0;
+        why = EV_HVP;
+        continue;
+      }
+      for (int k = lane; k < n; k += NT) D[k] = -G[k];
+      unit = true;
+    }
+    // ---- the direction is in D: slope, first trial
+    double sp = 0.0;
+    for (int k = lane; k < n; k += NT) sp += G[k] * D[k];
+    slope = red.sum(sp);
+    if (!(slope < 0.0)) {
+      sp = 0.0;
+      for (int k = lane; k < n; k += NT) { D[k] = -G[k]; sp -= G[k] * G[k]; }
+      slope = red.sum(sp);
+      unit = true;
+      newton = false;
+    }
+    alpha = 1.0;
+    if (unit) {  // the cap tape_solve_instance applies to a fresh metric
+      double dm = 0.0;
+      for (int k = lane; k < n; k += NT) dm = fmax(dm, fabs(D[k]));
+      alpha = fmin(1.0, 1.0 / red.max(dm));
+    }
+    slack = 4e-16 * (fmax(1.0, fabs(val_m)) + msum);
+    double gp = 0.0;
+    for (int k = lane; k < n; k += NT) gp += G[k] * G[k];
+    gg = red.sum(gp);
+    ls = 0;
+    for (int k = lane; k < n; k += NT) XT[k] = X[k] + alpha * D[k];
+    why = EV_TRIAL;
+    xs = XT;
+    gout = GT;
+  }
+  for (int k = lane; k < n; k += NT)
+    if (xo) xo[(size_t)gb * n + k] = X[k];
+  if (lane == 0) {
+    if (fo) fo[gb] = fval;
+    if (kkt) { kkt[3 * (size_t)gb] = stat; kkt[3 * (size_t)gb + 1] = cmax; kkt[3 * (size_t)gb + 2] = meas; }
+    if (iters) iters[gb] = evals + hvps;
+    if (status) status[gb] = st;
+    if (stats) { stats[2 * (size_t)gb] = steps; stats[2 * (size_t)gb + 1] = hvps; }
+  }
+  if (mult) {
+    for (int i = lane; i < ni; i += NT) mult[(size_t)gb * (ni + ne) + i] = lam[i];
+    for (int i = lane; i < ne; i += NT) mult[(size_t)gb * (ni + ne) + ni + i] = mu[i];
+  }
+}
+
+// The products oh_tape_phi_hvp grades (options tape_newton + tape_newton_wave): ONE BLOCK PER UNIT u = b nv + d, the work set of k_tape_wave_newton, one
+// WaveSweep::hvp at (x_b, V_u) under the given multipliers and penalty.  The sweep's gradient is left where oh_tape_phi_hvp's evaluation (k_tape_wave_phi,
+// launched before this kernel) has already written the same bits.
+template <int NT, bool REG_LDS>
+__global__ __launch_bounds__(NT) void k_tape_wave_merit_hvp(TapeParams T, WaveSchedDev S, int nv, const double* __restrict__ x, const double* __restrict__ par,
+                                                            const double* __restrict__ lam_in, const double* __restrict__ mu_in, double rho, const double* __restrict__ V,
+                                                            double* regs_g, double* __restrict__ HV) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const size_t u = blockIdx.x, inst = u / (size_t)nv;
+  const int n = T.nx, ni = T.n_ineq, ne = T.n_eq;
+  const NewtonLds L = newton_carve<REG_LDS>(T, S, lds, REG_LDS ? nullptr : regs_g + u * 4 * S.n_reg);
+  int* small = L.small;
+  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
+  const int* row_reg = small;
+  const int* seed_reg = row_reg + S.nrows;
+  const int* seed_off = seed_reg + S.n_seed;
+  const int* seed_rows = seed_off + S.n_seed + 1;
+  newton_setup_registers<NT>(S, L.val, par + inst * T.np, lane);
+  for (int k = lane; k < n; k += NT) { L.X[k] = x[inst * n + k]; L.PV[k] = V[u * n + k]; }
+  for (int i = lane; i < ni; i += NT) L.lam[i] = lam_in[inst * ni + i];
+  for (int i = lane; i < ne; i += NT) L.mu[i] = mu_in[inst * ne + i];
+  __syncthreads();
+  WaveSweep<NT, REG_LDS> sw{T, S, L.val, L.lam, L.mu, L.roww, L.rowt, row_reg, seed_reg, seed_off, seed_rows, lane};
+  sw.hvp(L.X, L.PV, nullptr, L.HP, rho);
+  for (int k = lane; k < n; k += NT) HV[u * n + k] = L.HP[k];
+}
+
 template <class V>
 int upload(V** dst, const std::vector<V>& src) {
   *dst = nullptr;
@@ -1103,8 +1614,106 @@ hipError_t oh_launch_tape_wave_hvp(hipStream_t s, const TapeWave& W, const TapeP
   return hipGetLastError();
 }
 
-// code-object facts of the product kernel: four wavefronts, the columns in LDS at the largest register file the device's LDS takes
+// ---- k_tape_wave_newton, k_tape_wave_merit_hvp: the layout of newton_carve
+size_t oh_tape_wave_newton_lds_bytes(const TapeParams& T, const TapeWave& W, bool reg_lds) {
+  const size_t nrows = T.n_ineq + T.n_eq;
+  const size_t d = (reg_lds ? 4 * (size_t)W.n_reg : 0) + 9 * (size_t)T.nx + (T.n_ineq > 0 ? T.n_ineq : 1) + (T.n_eq > 0 ? T.n_eq : 1) + 3 * (nrows > 0 ? nrows : 1) + 8;
+  return d * sizeof(double) + sizeof(int) * (((size_t)W.n_small + 1) & ~(size_t)1);
+}
+
+// Placement of the four columns of the Newton kernels: 0 the schedule cannot run them (not ready; NT = 64 and the work
+// set does not fit), 1 LDS, 2 a slice per block of the global register buffer.  Option tape_wave_regs forces one where both are possible.  Without it:
+// LDS whenever the work set fits, at every batch size -- NOT the quasi-Newton solver's rule (wave_place_registers: global memory beyond 512 instances).
+// That rule buys resident blocks per CU with the LDS it frees; k_tape_wave_newton holds 256 VGPRs and 44 AGPRs, one wavefront per SIMD, so a CU
+// runs one block of four wavefronts wherever the registers are, and global memory only costs in every pass.  Eliminated planner, device ms,
+// LDS / global: B = 256 7.62 / 10.69, B = 4096 105.2 / 149.5 (profiles/tape_newton_wave_rates.json).
+int oh_tape_wave_newton_place(const TapeWave& W, const TapeParams& T) {
+  if (!W.ready) return 0;
+  const bool lds_ok = oh_tape_wave_newton_lds_bytes(T, W, true) <= W.lds_limit;
+  const bool global_ok = W.nt == 256 && oh_tape_wave_newton_lds_bytes(T, W, false) <= W.lds_limit;
+  if (!lds_ok && !global_ok) return 0;
+  if (!global_ok) return 1;
+  if (!lds_ok) return 2;
+  return W.reg_choice == 0 ? 2 : 1;
+}
+
+// the global register buffer, counted in slices of 2 n_reg doubles (what wave_place_registers allocates per instance): a block of the Newton kernels takes two
+static hipError_t wave_grow_registers(TapeWave& W, const size_t slices) {
+  if (slices <= (size_t)W.regs_cap) return hipSuccess;
+  if (slices > (size_t)0x7fffffff) return hipErrorOutOfMemory;
+  if (W.d_regs) hipFree(W.d_regs);
+  W.d_regs = nullptr;
+  W.regs_cap = 0;
+  const hipError_t e = hipMalloc((void**)&W.d_regs, sizeof(double) * 2 * (size_t)W.n_reg * slices);
+  if (e != hipSuccess) return e;
+  W.regs_cap = (int)slices;
+  return hipSuccess;
+}
+
+hipError_t oh_launch_tape_wave_newton(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int cg_cap, const double* x0, const double* p, double* x,
+                                      double* f, double* kkt, int* iters, int* status, double* mult, int* stats) {
+  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  const bool reg_lds = place == 1;
+  if (!reg_lds)
+    if (const hipError_t e = wave_grow_registers(W, 2 * (size_t)B)) return e;
+  const size_t bytes = oh_tape_wave_newton_lds_bytes(T, W, reg_lds);
+  double* rg = reg_lds ? nullptr : W.d_regs;
+#define OH_TW_NEWTON(NTv, Rv)                                                                                                                       \
+  do {                                                                                                                                              \
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_newton<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
+    if (e != hipSuccess) return e;                                                                                                                  \
+    hipLaunchKernelGGL((k_tape_wave_newton<NTv, Rv>), dim3(B), dim3(NTv), bytes, s, T, S, B, cg_cap, x0, p, rg, x, f, kkt, iters, status, mult, stats);         \
+  } while (0)
+  if (!reg_lds) OH_TW_NEWTON(256, false);
+  else if (W.nt == 64) OH_TW_NEWTON(64, true);
+  else OH_TW_NEWTON(256, true);
+#undef OH_TW_NEWTON
+  return hipGetLastError();
+}
+
+// one k_tape_wave_phi over the B instances (grad: the evaluation's gradient; the other outputs go to scratch [4 B + max(nrows, 1) B]), then one block per
+// (instance, direction) of k_tape_wave_merit_hvp
+hipError_t oh_launch_tape_wave_phi_hvp(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int nv, const double* x, const double* p, const double* lam,
+                                       const double* mu, double rho, const double* V, double* HV, double* grad, double* scratch) {
+  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  const bool reg_lds = place == 1;
+  const size_t U = (size_t)B * nv;
+  // (before the evaluation is launched: its own placement may read the same buffer, which must not be reallocated under it)
+  if (!reg_lds)
+    if (const hipError_t e = wave_grow_registers(W, 2 * U)) return e;
+  double* sc = scratch;
+  if (const hipError_t e = oh_launch_tape_wave_phi(s, W, T, B, x, p, lam, mu, rho, sc, sc + B, sc + 4 * (size_t)B, grad, sc + 2 * (size_t)B, sc + 3 * (size_t)B)) return e;
+  const size_t bytes = oh_tape_wave_newton_lds_bytes(T, W, reg_lds);
+  double* rg = reg_lds ? nullptr : W.d_regs;
+#define OH_TW_MHVP(NTv, Rv)                                                                                                                            \
+  do {                                                                                                                                                 \
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_merit_hvp<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
+    if (e != hipSuccess) return e;                                                                                                                     \
+    hipLaunchKernelGGL((k_tape_wave_merit_hvp<NTv, Rv>), dim3((unsigned)U), dim3(NTv), bytes, s, T, S, nv, x, p, lam, mu, rho, V, rg, HV);                         \
+  } while (0)
+  if (!reg_lds) OH_TW_MHVP(256, false);
+  else if (W.nt == 64) OH_TW_MHVP(64, true);
+  else OH_TW_MHVP(256, true);
+#undef OH_TW_MHVP
+  return hipGetLastError();
+}
+
+// code-object facts of the product kernel and of the Newton-CG solve kernel: four wavefronts, the columns in LDS at the largest register file the device's LDS takes
 bool oh_kernel_info_tape_wave(const char* name, OhKernelInfo* out) {
+  if (std::string(name) == "k_tape_wave_newton") {
+    int dev = 0, lds_limit = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
+    const void* fn = reinterpret_cast<const void*>(k_tape_wave_newton<256, true>);
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess) { (void)hipGetLastError(); return false; }
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, fn) != hipSuccess) return false;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tape_wave_newton<256, true>, 256, (size_t)lds_limit) != hipSuccess) nb = 0;
+    *out = OhKernelInfo{a.numRegs, (int)a.localSizeBytes, (int)(a.sharedSizeBytes + lds_limit), 256, nb};
+    return true;
+  }
   if (std::string(name) != "k_tape_wave_hvp") return false;
   int dev = 0, lds_limit = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;

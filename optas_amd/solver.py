@@ -344,7 +344,8 @@ class HIPSolver(Solver):
             #  already rebalanced for the wavefront path, left backend.wave / backend.jit stale and overrode tape_backend's own tape_lbfgs default)
             # (the inner solver's choice, tape_newton / tape_newton_cg, may stand among the solver options themselves: it travels the same way)
             # (tape_hvp_wave: lagrangian_hessian() on the wavefront evaluator; it decides which handle of the problem as written is created)
-            handle_options.update({k: o.pop(k) for k in ("tape_newton", "tape_newton_cg", "tape_hvp_wave") if k in o})
+            # (tape_newton_wave: with tape_newton, the Newton-CG solve on the wavefront evaluator; it decides whether the tape is re-associated)
+            handle_options.update({k: o.pop(k) for k in ("tape_newton", "tape_newton_cg", "tape_newton_wave", "tape_hvp_wave") if k in o})
             tape_opts = {k: handle_options.pop(k) for k in [k for k in handle_options if k.startswith("tape_")]}
             self._backend = tape_backend(spec.tape, options=tape_opts or None, eliminate=bool(o.pop("eliminate", True)), max_iter=int(o.pop("max_iter", tape_default_max_iter(spec.tape.nx))),
                                          tol=float(o.pop("tol", 1e-6)), tol_feas=float(o.pop("tol_feas", 1e-9)), rho0=(float(o.pop("rho0")) if "rho0" in o else None), jit=bool(o.pop("jit", True)), metric=o.pop("metric", None))
