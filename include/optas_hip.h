@@ -32,7 +32,9 @@ extern "C" {
    5: round 5 -- OH_STATUS_INFEASIBLE / OH_STATUS_ACCEPTABLE, oh_set_option / oh_get_option, oh_tq_rollout, tape opcodes 25-26.
    6: round 5 -- oh_tape_set_metric.
    7: round 6 -- OH_MAX_T 256, oh_comm_allgather, options tol / pipe / pipe_chunk, OH_STATUS_INFEASIBLE from the point-mass iteration, oh_solve in chunks on two lanes.
-   8: oh_tape_phi. */
+   8: oh_tape_phi.  Still 8: oh_ik_desc.orientation (full-pose goal of OH_PROBLEM_IK) sits in what was four bytes of padding after max_iter, so
+      the size of the struct and the offset of every other member are as they were, and a zero-initialised descriptor of an older caller reads as
+      orientation = 0; flag "ik_orientation". */
 #define OH_ABI_VERSION 8
 
 #define OH_MAX_CHAIN 16 /* actuated joints on one root->link chain */
@@ -74,7 +76,13 @@ enum {
   OH_PROBLEM_POINT_MASS_MPC = 2,
   /* example/example.py:13-60 (BASELINE configs[0]): one configuration q of a serial chain,
      f = w ||q - q_nominal||^2, h = p_goal - p_link(q) (builder.py:354), k = [q - lo; up - q] (builder.py:471-509);
-     created with oh_create_ik.  x = q (nx = ndof), p = [q_nominal(ndof); p_goal(3)] (np = ndof + 3). */
+     created with oh_create_ik.  x = q (nx = ndof), p = [q_nominal(ndof); p_goal(3)] (np = ndof + 3).
+     With oh_ik_desc.orientation set the goal is a full pose, written in the reference as a second equality on get_global_link_quaternion
+     (figure_eight_plan.py:105-107, simple_joint_space_planner.py:33): h = [p_goal - p_link(q); quat_goal - quat_link(q)] (seven rows),
+     p = [q_nominal(ndof); p_goal(3); quat_goal(4, xyzw)] (np = ndof + 7).  quat_link is the reference's chain product with the reference's sign
+     (what oh_fk_jac returns), and the goal is taken literally: quat_goal and -quat_goal describe the same rotation but are different goals here,
+     exactly as in the reference's h = rhs - lhs; pass the quaternion of a configuration near the expected answer (or flip it onto the hemisphere
+     of quat_link(q_nominal)). */
   OH_PROBLEM_IK = 3,
   /* the QuadraticCost{Unconstrained, LinearConstraints} classes with small dense data (optimization.py:312-388; what the reference hands to
      OSQP / CVXOPT / qpOASES, solver.py:421-584): min x^T P x + q^T x s.t. M x + c >= 0, A x + b = 0; created with oh_create_qp.
@@ -228,11 +236,13 @@ typedef struct oh_guards {
 } oh_guards;
 
 typedef struct oh_ik_desc {
-  int ndof;         /* 6 or 7; the chain must cover every model joint in order */
+  int ndof;         /* 2 ... 8; the chain must cover every model joint in order */
   double w_nominal; /* weight of ||q - q_nominal||^2, 1.0 in example.py:30 */
   double q_lo[OH_MAX_CHAIN]; /* enforce_model_limits (example.py:33; RobotModel limits, models.py:332-368) */
   double q_up[OH_MAX_CHAIN];
   int max_iter;     /* kinematics evaluations per instance; <= 0: 200 */
+  int orientation;  /* 0: position goal (above); non-zero: full-pose goal, p = [q_nominal; p_goal; quat_goal], tol_feas over all seven rows.
+                       (In the four bytes that were padding before tol: zero-initialise the descriptor, as for every struct of this header.) */
   double tol;       /* KKT stationarity (projected gradient of the Lagrangian, inf-norm); <= 0: 1e-6 */
   double tol_feas;  /* ||p_goal - p_link(q)||_inf; <= 0: 1e-9 */
   double rho0;      /* initial augmented-Lagrangian penalty; <= 0: 100 w */
@@ -553,7 +563,7 @@ int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, double mu_warm,
    a failed call, OH_ERR_STATE.  In the reference's form: lam_h [B][4*T] for the rows
    h = quat_c - quat(q_t) (signed mu = lam+ - lam- of the (h,-h) pair, optimization.py:47-51). Host buffer.
    OH_PROBLEM_IK: lam_h [B][3 + 2*ndof] = (mu of h = p_goal - p_link(q) (3), multipliers of q - lo >= 0 (ndof),
-   multipliers of up - q >= 0 (ndof)).
+   multipliers of up - q >= 0 (ndof)); with oh_ik_desc.orientation [B][7 + 2*ndof]: mu of [p_goal - p_link(q); quat_goal - quat_link(q)] (7) first.
    Handles with oh_set_guards: lam_h [B][T][NC], NC = 2 ndof limits + n_links n_obstacles + 2 ndof velocity limits, row order
    of oh_guards (multipliers >= 0 of the g >= 0 rows; knots t < t0 carry zeros). */
 int oh_get_multipliers(oh_handle* h, int B, double* lam_h);

@@ -178,6 +178,7 @@ class oh_ik_desc(C.Structure):
         ("q_lo", C.c_double * OH_MAX_CHAIN),
         ("q_up", C.c_double * OH_MAX_CHAIN),
         ("max_iter", C.c_int),
+        ("orientation", C.c_int),  # in the former padding before tol: size and the other offsets are those of the struct without it
         ("tol", C.c_double),
         ("tol_feas", C.c_double),
         ("rho0", C.c_double),

@@ -502,14 +502,17 @@ class QPBackend(_SolveMixin):
 
 
 class IKBackend(_SolveMixin):
-    """OH_PROBLEM_IK handle (example/example.py): x = q, p = [q_nominal; p_goal]."""
+    """OH_PROBLEM_IK handle (example/example.py): x = q, p = [q_nominal; p_goal].  orientation=True: the goal is a full pose, p = [q_nominal; p_goal;
+    quat_goal (xyzw, the sign taken literally: include/optas_hip.h)], seven equality rows (examples/pose_ik.py)."""
 
-    def __init__(self, chain: _lib.oh_chain, lo, up, w_nominal=1.0, max_iter=200, tol=1e-6, tol_feas=1e-9, rho0=0.0):
+    def __init__(self, chain: _lib.oh_chain, lo, up, w_nominal=1.0, max_iter=200, tol=1e-6, tol_feas=1e-9, rho0=0.0, orientation=False):
         lib = _lib.load()
         self.ndof = int(chain.ndof)
-        self.nx, self.np_ = self.ndof, self.ndof + 3
+        self.orientation = bool(orientation)
+        self.nh = 7 if self.orientation else 3
+        self.nx, self.np_ = self.ndof, self.ndof + self.nh
         desc = _lib.oh_ik_desc(ndof=self.ndof, w_nominal=float(w_nominal), max_iter=int(max_iter), tol=float(tol), tol_feas=float(tol_feas),
-                               rho0=float(rho0))
+                               rho0=float(rho0), orientation=1 if self.orientation else 0)
         lo, up = np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(up, dtype=np.float64).reshape(-1)
         assert lo.shape == (self.ndof,) and up.shape == (self.ndof,)
         for i in range(self.ndof):
@@ -520,10 +523,17 @@ class IKBackend(_SolveMixin):
         self.chain = chain
 
     def multipliers(self, B: int):
-        """(mu_h (B,3), z_lo (B,ndof), z_up (B,ndof)) of the last solve, reference form."""
-        out = np.empty((B, 3 + 2 * self.ndof))
+        """(mu_h (B, 3 or 7), z_lo (B,ndof), z_up (B,ndof)) of the last solve, reference form."""
+        nh = self.nh
+        out = np.empty((B, nh + 2 * self.ndof))
         _lib.check(_lib.load().oh_get_multipliers(self._h, int(B), _lib._ptr(out)), "oh_get_multipliers")
-        return out[:, :3], out[:, 3 : 3 + self.ndof], out[:, 3 + self.ndof :]
+        return out[:, :nh], out[:, nh : nh + self.ndof], out[:, nh + self.ndof :]
+
+    def flag(self, name: str) -> int:
+        """oh_get_flag: 'ik_orientation' (1: the handle solves the full-pose problem)."""
+        v = C.c_int(0)
+        _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
+        return int(v.value)
 
 
 def tape_default_max_iter(nx: int) -> int:

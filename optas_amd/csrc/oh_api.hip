@@ -273,7 +273,7 @@ Shape shape_of(const oh_handle* h) {
     case OH_PROBLEM_TAPE: return {(size_t)tp.nx, (size_t)(tp.np > 0 ? tp.np : 1), (size_t)(tp.n_ineq + tp.n_eq)};
     case OH_PROBLEM_QP: return {(size_t)qp.n, h->qp.use_tape ? (size_t)(tp.np > 0 ? tp.np : 1) : qp_np(qp), (size_t)(qp.m + qp.me)};
     case OH_PROBLEM_POINT_MASS_MPC: return {4 * T, 4 + 4 * T, 0};
-    case OH_PROBLEM_IK: return {N, N + 3, 3 + 2 * N};
+    case OH_PROBLEM_IK: return {N, N + ik_rows(h->ik.desc), ik_rows(h->ik.desc) + 2 * N};
     case OH_PROBLEM_FIGURE_EIGHT: {
       const oh_guards& g = h->guards;
       const size_t nx = N * T + N * (T - 1);
@@ -1406,6 +1406,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_levels") *value = h->tape.wave.n_levels;
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;
   else if (n == "qp_block") *value = h->qp.last_block;
+  else if (n == "ik_orientation") *value = (h->desc.kind == OH_PROBLEM_IK && h->ik.desc.orientation) ? 1 : 0;
   else if (n == "free_sweep") *value = h->free_sweep_last;
   else if (n == "free_sweeps_used") *value = h->free_sweeps_used;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);
@@ -1429,7 +1430,7 @@ extern "C" int oh_kernel_info(const char* kernel, int* out5) {
   if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return fail(OH_ERR_HIP, "oh_kernel_info: no HIP device available (this library has no CPU path)");
   OhKernelInfo k{};
   if (!oh_kernel_info_figure8(kernel, &k) && !oh_kernel_info_fkjac(kernel, &k) && !oh_kernel_info_linkkin(kernel, &k) && !oh_kernel_info_torque(kernel, &k) &&
-      !oh_kernel_info_qp_block(kernel, &k) && !oh_kernel_info_tape_wave(kernel, &k))
+      !oh_kernel_info_qp_block(kernel, &k) && !oh_kernel_info_tape_wave(kernel, &k) && !oh_kernel_info_ik(kernel, &k))
     return fail(OH_ERR_INVALID, std::string("oh_kernel_info: unknown kernel or attribute query failed: ") + kernel);
   out5[0] = k.vgprs; out5[1] = k.scratch_bytes; out5[2] = k.lds_bytes; out5[3] = k.block; out5[4] = k.blocks_per_cu;
   return OH_OK;

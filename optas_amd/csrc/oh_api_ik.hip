@@ -1,6 +1,9 @@
 // Host side of the inverse-kinematics family (OH_PROBLEM_IK): creation and the solve.  State: oh_handle::ik.
 #include "oh_handle.h"
 
+// orientation took the padding after max_iter: the descriptor is laid out as before it existed (OH_ABI_VERSION unchanged)
+static_assert(sizeof(oh_ik_desc) == 48 + 2 * 8 * OH_MAX_CHAIN && offsetof(oh_ik_desc, tol) == 24 + 2 * 8 * OH_MAX_CHAIN, "oh_ik_desc layout");
+
 extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
   if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_ik: null argument");
   *out = nullptr;
@@ -13,6 +16,7 @@ extern "C" int oh_create_ik(const oh_ik_desc* desc, oh_handle** out) {
   if (!h) return rc;
   oh_ik_desc& d = h->ik.desc;
   d = *desc;
+  d.orientation = d.orientation ? 1 : 0;
   if (d.max_iter <= 0) d.max_iter = 200;
   if (!(d.tol > 0.0)) d.tol = 1e-6;
   if (!(d.tol_feas > 0.0)) d.tol_feas = 1e-9;
@@ -28,7 +32,7 @@ int ik_solve_device(oh_handle* h, const Solve& a) {
   HIPCHK(hipSetDevice(h->device));
   const oh_ik_desc& d = h->ik.desc;
   const int N = d.ndof;
-  HIPCHK(h->ik.mult.reserve((3 + 2 * (size_t)N) * a.B));
+  HIPCHK(h->ik.mult.reserve((ik_rows(d) + 2 * (size_t)N) * a.B));
   IkParams P{};
   P.ndof = N;
   P.max_iter = d.max_iter;
@@ -41,7 +45,7 @@ int ik_solve_device(oh_handle* h, const Solve& a) {
     P.up[i] = d.q_up[i];
   }
   HIPCHK(hipEventRecord(h->ev0, h->stream));
-  if (!oh_launch_ik_solve(h->stream, h->d_chain, P, a.B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, h->ik.mult))
+  if (!(d.orientation ? oh_launch_ik_pose_solve : oh_launch_ik_solve)(h->stream, h->d_chain, P, a.B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, h->ik.mult))
     return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
   return finish_solve(h, 1);
 }

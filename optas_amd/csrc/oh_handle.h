@@ -152,8 +152,10 @@ struct QpState {
 // Inverse-kinematics family (oh_api_ik.hip)
 struct IkState {
   oh_ik_desc desc{};
-  DevBuf<double> mult;  // [B][3 + 2 ndof]
+  DevBuf<double> mult;  // [B][ik_rows + 2 ndof]
 };
+// equality rows of an IK handle: 3 (position goal) or 7 (full pose, oh_ik_desc.orientation); p rows are ndof + ik_rows wide, multiplier rows ik_rows + 2 ndof
+inline size_t ik_rows(const oh_ik_desc& d) { return d.orientation ? 7 : 3; }
 
 // Torque-MPC family (oh_api_torque.hip)
 struct TqState {

@@ -18,6 +18,7 @@ bool oh_kernel_info_torque(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_linkkin(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_qp_block(const char* name, OhKernelInfo* out);
 bool oh_kernel_info_tape_wave(const char* name, OhKernelInfo* out);
+bool oh_kernel_info_ik(const char* name, OhKernelInfo* out);
 
 void oh_launch_fk_jac(hipStream_t s, bool soa, const oh_chain* d_chain, int n_chain, int ndof, int n, const double* q, double* pose, double* J);
 // What oh_set_link_frames keeps on the device for k_link_kin (oh_linkkin.hip): the chains root->link and root->base, and the number of leading
@@ -155,6 +156,9 @@ struct IkParams {
 };
 bool oh_launch_ik_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
                         double* kkt, int* iters, int* status, double* mult);
+// oh_ik_desc.orientation: p rows [q_nominal; p_goal; quat_goal] (ndof + 7), mult rows 7 + 2 ndof
+bool oh_launch_ik_pose_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
+                             double* kkt, int* iters, int* status, double* mult);
 
 // ---- OH_PROBLEM_QP -----------------------------------------------------------------------------------------
 struct QpParams {

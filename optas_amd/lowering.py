@@ -596,10 +596,13 @@ class IkSpec:
     qn_name: str
     pg_name: str
     q_name: str
+    orientation: bool = False  # full-pose goal: a second equality quat_link(q) == quat_goal (p = [q_nominal; p_goal; quat_goal])
+    qg_name: Optional[str] = None
 
 
 def match_ik(opt: Optimization) -> IkSpec:
-    """example/example.py:13-60: min w||q - q_nominal||^2 s.t. p_link(q) = p_goal, lo <= q <= up (T = 1)."""
+    """example/example.py:13-60: min w||q - q_nominal||^2 s.t. p_link(q) = p_goal, lo <= q <= up (T = 1); examples/pose_ik.py: the same with a second
+    equality quat_link(q) = quat_goal after the first (the reference's get_global_link_quaternion rows, figure_eight_plan.py:105-107)."""
 
     def no(msg):
         raise LoweringError(f"inverse-kinematics lowering: {msg}")
@@ -623,14 +626,22 @@ def match_ik(opt: Optimization) -> IkSpec:
     def is_q(e):
         return isinstance(e, StateRef) and e.var_name == q_name and e.time_deriv == 0 and (e.t in (None, 0))
 
-    # nonlinear equality: p_link(q) == p_goal
-    if len(opt.eq_constraints) != 1:
-        no("expected exactly one nonlinear equality (link position goal)")
-    (label, diff), = opt.eq_constraints.items()
-    if not (isinstance(diff, Sub) and isinstance(diff.a, ParamRef) and isinstance(diff.b, LinkFunction) and diff.b.what == "position"
-            and is_q(diff.b.q) and diff.b.robot is robot and diff.a.shape == (3, 1)):
-        no(f"equality '{label}' is not p(link, q) == p_goal with a 3-vector parameter")
-    pg, link = diff.a, diff.b.link
+    # nonlinear equalities: p_link(q) == p_goal, optionally followed by quat_link(q) == quat_goal (same link, same q)
+    def goal_row(label, diff, what, rows):
+        if not (isinstance(diff, Sub) and isinstance(diff.a, ParamRef) and isinstance(diff.b, LinkFunction) and diff.b.what == what
+                and is_q(diff.b.q) and diff.b.robot is robot and diff.a.shape == (rows, 1)):
+            no(f"equality '{label}' is not {what}(link, q) == goal with a {rows}-vector parameter")
+        return diff.a, diff.b.link
+
+    eqs = list(opt.eq_constraints.items())
+    if len(eqs) not in (1, 2):
+        no("expected one nonlinear equality (link position goal) or two (position goal, then quaternion goal)")
+    pg, link = goal_row(*eqs[0], "position", 3)
+    qg = None
+    if len(eqs) == 2:
+        qg, qlink = goal_row(*eqs[1], "quaternion", 4)
+        if qlink != link:
+            no(f"the quaternion goal is on link '{qlink}', the position goal on '{link}'")
 
     # cost: w * sumsqr(q - q_nominal)
     if len(opt.cost_terms) != 1:
@@ -653,9 +664,10 @@ def match_ik(opt: Optimization) -> IkSpec:
         else:
             no(f"linear inequality '{label}' is not a joint bound")
     params = [k for k, v in opt.parameters.items() if v.numel() > 0]
-    if params != [qn.name, pg.name]:
-        no(f"non-empty parameters must be ['{qn.name}', '{pg.name}'] in this order, found {params}")
-    return IkSpec(robot, link, float(w), lo, up, qn.name, pg.name, q_name)
+    want = [qn.name, pg.name] + ([qg.name] if qg is not None else [])
+    if params != want:
+        no(f"non-empty parameters must be {want} in this order, found {params}")
+    return IkSpec(robot, link, float(w), lo, up, qn.name, pg.name, q_name, qg is not None, None if qg is None else qg.name)
 
 
 @dataclass

@@ -322,7 +322,8 @@ class HIPSolver(Solver):
         elif isinstance(spec, IkSpec):
             o.pop("hessian", None)
             self._backend = IKBackend(spec.robot.kinematic_chain(spec.link), spec.lo, spec.up, w_nominal=spec.w_nominal,
-                                      max_iter=int(o.pop("max_iter", 200)), tol=float(o.pop("tol", 1e-6)), tol_feas=float(o.pop("tol_feas", 1e-9)))
+                                      max_iter=int(o.pop("max_iter", 200)), tol=float(o.pop("tol", 1e-6)), tol_feas=float(o.pop("tol_feas", 1e-9)),
+                                      orientation=spec.orientation)
         elif isinstance(spec, QpSpec):
             o.pop("hessian", None)
             qb = QPBackend(spec.n, spec.m, spec.me, max_iter=int(o.pop("max_iter", 100)), tol=float(o.pop("tol", 1e-9)))
