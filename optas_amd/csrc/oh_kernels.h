@@ -216,10 +216,10 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
 void oh_tape_wave_release(TapeWave* w);
 hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
                                int* iters, int* status, double* mult);
-// one WaveEval::phi per instance (oh_tape_phi): the register placement oh_launch_tape_wave would choose for this B
+// one WaveEval::phi (the level-schedule sweep without tangents) per instance (oh_tape_phi): the register placement oh_launch_tape_wave would choose for this B
 hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x, const double* p, const double* lam, const double* mu,
                                    double rho, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas);
-// forward-over-reverse on the level schedule, one block per unit (oh_tape_hvp with option tape_hvp_wave; k_tape_wave_hvp): oh_tape_wave_hvp_place says where
+// the same sweep with tangents and given weights, one block per unit (oh_tape_hvp with option tape_hvp_wave; k_tape_wave_hvp): oh_tape_wave_hvp_place says where
 // the four register columns go (0: the interpreter stays, 1: LDS, 2: global memory); a launch covers the units [u0, u0 + n),
 // regs (global placement only) is [n][4 n_reg]; x, p, seeds, V (null: the unit vectors), HV and grad (may be null) are the whole batch's arrays
 int oh_tape_wave_hvp_place(const TapeWave& W);

@@ -9,20 +9,16 @@
 //     planner's dense Hessian 0.5 % slower;
 //   * InterpEval::hess_vec (oh_tape.hip), the tangent and second-order lines of k_tape_hvp once more without the primal accumulations beside them:
 //     it runs on the adjoints a finished reverse sweep left and must not repeat them;
-//   * the two rare-path switches of WaveEval::phi (oh_tape_wave.hip), values and adjoint rules of the opcodes its straight-line path does not
-//     cover, on operands it has loaded already: through this header the forward one was 3 % slower on the planner and the reverse one kept its
-//     two contributions in scratch memory;
-//   * k_tape_wave_hvp (oh_tape_wave.hip), the tangent and second-order lines a third time, beside WaveEval::phi's two switches: the wavefront's reverse sweep has no
-//     accumulation to differentiate -- an instruction leaves its contribution to each operand as a VALUE in its own slots (ca, cb) and the consumers'
-//     slots are gathered later -- so each rule is the pair (contribution, its directional derivative) of one operand, on operands and tangents the pass has
-//     loaded already, and an accessor that stored them through a pointer put them in scratch memory as it did for phi;
-//   * WaveSweep::hvp (oh_tape_wave.hip; options tape_newton + tape_newton_wave), k_tape_wave_hvp's two switches a FOURTH time, with a seed for dadj: that kernel's text, its
-//     169 VGPRs without scratch and the bits of profiles/tape_hvp_wave_ab.json are pinned, so the copy could only be avoided by a function that takes
-//     the four contributions through references, the form that cost phi its scratch memory; as a copy the sweep compiles to the same 169 VGPRs
-//     (167 with the registers in global memory), 0 bytes of scratch, in k_tape_wave_merit_hvp;
+//   * WaveEval::sweep (oh_tape_wave.hip), the wavefront evaluator's ONE statement: the rare-path switches of its forward and reverse pass hold the value,
+//     the adjoint rule and, under `if constexpr (TAN)`, the tangent and second-order lines of the opcodes the straight-line path does not cover; every
+//     wavefront kernel (evaluation, products with given weights, products of the merit, both solvers) runs that one body.  It stays outside tape_value /
+//     tape_adjoint because it works on operands the pass has loaded already -- through this header the forward switch was 3 % slower on the planner --
+//     and because the wavefront's reverse sweep has no accumulation to differentiate: an instruction leaves its contribution to each operand as a VALUE
+//     in its own slots (ca, cb) and the consumers' slots are gathered later, so each rule is the pair (contribution, its directional derivative) of
+//     one operand, and an accessor that stored them through a pointer put them in scratch memory;
 //   * ADD, SUB and MUL in the two sweeps of the QP assembly (oh_qp.hip), 0.5 - 2 % faster as cases of their own.
 // The measured reasons are written at each.  All of them use the names below.
-// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit, tests/test_gpu_tape_hvp_wave.py k_tape_wave_hvp to the 60-digit reference, tests/test_gpu_tape_newton.py hess_vec and tests/test_gpu_tape_newton_wave.py WaveSweep::hvp to the 60-digit reference.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
+// tests/test_gpu_tape_evaluators.py and tests/test_gpu_tape_hvp.py hold all of them together bit for bit, tests/test_gpu_tape_hvp_wave.py k_tape_wave_hvp to the 60-digit reference, tests/test_gpu_tape_newton.py hess_vec and tests/test_gpu_tape_newton_wave.py the merit's products on WaveEval::sweep to the 60-digit reference; tests/test_gpu_tape_wave_bits.py pins the sweep's bits.  Independent restatements: optas_amd/tape.py, oracle/tape_ref.py, oracle/tape_mp.py.
 //
 // A rule takes its operands through a small accessor R of the caller -- values: cst(), x(), p() (what CONST, X and P load, from wherever the caller
 // keeps constants, the point and the parameters), a(), b(), self() (the instruction's own value); contributions: add_a(v), add_b(v), sub_a(v),

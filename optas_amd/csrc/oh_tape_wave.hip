@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "oh_kernels.h"
@@ -107,169 +108,317 @@ struct Red {
   __device__ double max(double v) { return run<true>(v); }
 };
 
+// Four schedule entries in flight, the loop unrolled by four so that each lives in its own registers: rotating them through moves (or loading under a
+// condition) makes the compiler wait for the entry it has just requested -- a full L2 round trip in every pass (measured: 460 ns per pass).
+// The host pads the schedules to a multiple of four passes; fetch(p) beyond the end re-reads the last pass.  The first four are requested apart from
+// the loop so that a sweep can ask for them before it fills in the variables.
+template <class E>
+struct Four {
+  E e0, e1, e2, e3;
+};
+template <class Fetch>
+__device__ __attribute__((always_inline)) auto fetch_four(Fetch fetch) {
+  return Four<decltype(fetch(0))>{fetch(0), fetch(1), fetch(2), fetch(3)};
+}
+template <class E, class Fetch, class Pass>
+__device__ __attribute__((always_inline)) void run_four(const int n_pass, Four<E> q, Fetch fetch, Pass pass) {
+  for (int p = 0; p < n_pass; p += 4) {
+    const E c0 = q.e0;
+    q.e0 = fetch(p + 4);
+    pass(c0);
+    const E c1 = q.e1;
+    q.e1 = fetch(p + 5);
+    pass(c1);
+    const E c2 = q.e2;
+    q.e2 = fetch(p + 6);
+    pass(c2);
+    const E c3 = q.e3;
+    q.e3 = fetch(p + 7);
+    pass(c3);
+  }
+}
+struct RvEntry {
+  int4 ins, meta;  // {register | op << 20, a, b, first overflow consumer}, {consumers | seeded << 16 | flags << 17, three consumer slots}
+};
+
+// the small index arrays, copied into LDS at `small` and split
+struct WaveIndex {
+  const int *row_reg, *seed_reg, *seed_off, *seed_rows;
+};
+template <int NT>
+__device__ inline WaveIndex wave_load_index(const WaveSchedDev& S, int* small, const int lane) {
+  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
+  return WaveIndex{small, small + S.nrows, small + S.nrows + S.n_seed, small + S.nrows + 2 * S.n_seed + 1};
+}
+// the registers nobody writes after the set-up, in COLS = 2 columns [val | adj] or 4 [val | adj | tan | dadj] of n_reg doubles: zero and trash in every
+// column, constants (the -1 register is among them) and parameters, with a zero tangent where there is one
+template <int NT, int COLS>
+__device__ inline void wave_setup_registers(const WaveSchedDev& S, double* val, const double* pb, const int lane) {
+  const size_t nr = S.n_reg;
+  if (lane == 0)
+    for (int c = 0; c < COLS; ++c) { val[c * nr + ZREG] = 0.0; val[c * nr + TRASH] = 0.0; }
+  for (int k = lane; k < S.n_cst; k += NT) {
+    val[S.cst_reg[k]] = S.cst_val[k];
+    if constexpr (COLS == 4) val[2 * nr + S.cst_reg[k]] = 0.0;
+  }
+  for (int k = lane; k < S.n_par; k += NT) {
+    val[S.par_reg[k]] = pb[S.par_k[k]];
+    if constexpr (COLS == 4) val[2 * nr + S.par_reg[k]] = 0.0;
+  }
+}
+
+enum { SEED_AL, SEED_GIVEN };  // the reverse sweep's seeds: the augmented Lagrangian's rows at (lam, mu, rho) | weights handed in
+
+// THE level-schedule sweep of this file, stated once: every kernel below runs sweep<>.
+//   forward  pass entries in schedule order; with TAN the tangent tan = (d val / d x) v beside every value.
+//   seeds    SEED_AL: the seed of row r is tape_al_ineq / tape_al_eq; its tangent (rowt) is rho tan[row_reg[r]] for an equality row and for an inequality
+//            row whose seed is not zero (lam - rho g > 0 by tape_al_ineq's own expression: a tie is inactive, as InterpEval::hess_vec has it), else 0.
+//            adj[seed_reg[s]] = [cost] + the rows' seeds in seed_rows order, dadj[seed_reg[s]] the same sum over rowt started from -0, the one value that
+//            leaves every addend's bits alone.  SEED_GIVEN: adj[seed_reg[s]] = sd[0] [cost] + sd[1 + row] in the same order (oh_tape_probe's weights in the order
+//            it adds them); they are constants: dadj has no seed and dw starts from its first slot -- the bits of a gather started from -0, so on a tape
+//            without rows both seed sources give the same product; loading and selecting a -0 seed instead cost the planner's dense Hessian 1.7 % (7.44 against 7.31 ms).
+//   reverse  without atomics and without a second register file (see the head of the file): instruction c leaves its contributions (ca, cb) to its operands
+//            in val[c], adj[c] and, with TAN, their directional derivatives (dca, dcb) in tan[c], dadj[c]; w gathers seed + slots, dw the same slot indices
+//            displaced by 2 n_reg.  The gather order is the schedule's: the bits depend on the instance and the direction alone, not on the batch, the
+//            launch, the register placement or the block width.  Kinks hold the base point's selection (k_tape_hvp's conventions, oh_tape.hip).
+// The variables' "+ zero" entries leave the gradient in val[XREG0 + k] and H v in tan[XREG0 + k].  With TAN off every tangent load, operation and store is
+// compiled out: the two left columns see the same arithmetic in the same order either way, so an evaluation and a product agree on the gradient's bits.
+// The rare-opcode rules are oh_tape_ops.h's (tape_value, tape_adjoint and the second-order rules of k_tape_hvp), written out in place on the operands the
+// pass has already loaded, each contribution assigned in its case: through tape_value the planner's solves took 3 % longer (B = 1024: 15.4 against 14.9 ms),
+// and behind an accessor that stores into ca / cb the compiler merges the cases' stores into one store through a pointer and the contributions end up in
+// scratch memory (24 bytes a lane).  This is the wavefront evaluator's ONE statement of them: a rule changed in oh_tape_ops.h is changed here, nowhere else in this file.
 template <int NT, bool REG_LDS>
 struct WaveEval {
   const TapeParams& T;
   const WaveSchedDev& S;
-  double *val, *adj, *lam, *mu, *rowv, *roww;
-  const int *row_reg, *seed_reg, *seed_off, *seed_rows;
+  double* val;                           // the columns, n_reg doubles each: [val | adj], with TAN [val | adj | tan | dadj]
+  double *lam, *mu, *rowv, *roww, *rowt;  // SEED_AL: multipliers, row values (EVAL), row seeds and (TAN) their tangents
+  const WaveIndex ix;
   const int lane;  // thread of the block
-  Red<NT>& red;
+  Red<NT>& red;    // EVAL only
 
   // registers in LDS: only the LDS counter is drained between passes; registers in global memory (tapes too big for the LDS): the full barrier
   __device__ static inline void pass_barrier() {
     if constexpr (REG_LDS) lds_barrier(); else __syncthreads();
   }
 
-  // merit value at xs, its gradient into gout (both LDS, element k anywhere); rows into rowv.  Uniform return values.
-  __device__ __attribute__((always_inline)) double phi(const double* xs, double* gout, const double rho, double* fout, double* cmax, double* meas) {
+  // xs: the point; vs: the direction (TAN; SEED_GIVEN: null = the unit vector `dir`); element k anywhere.  gout (TAN: may be null): the gradient; hout (TAN):
+  // H v.  sd (SEED_GIVEN): the weights [1 + nrows].  EVAL: the rows into rowv, f, the largest violation and the feasibility measure through the pointers, the
+  // merit's value returned -- all uniform.
+  template <bool TAN, int SEED, bool EVAL>
+  __device__ __attribute__((always_inline)) double sweep(const double* xs, const double* vs, double* gout, double* hout, const double rho, const double* sd = nullptr,
+                                                         const int dir = 0, double* fout = nullptr, double* cmax = nullptr, double* meas = nullptr) {
 #pragma clang fp contract(off)
-    __syncthreads();  // xs was written element-wise by its owner lanes
-    // Four entries in flight, the loop unrolled by four so that each lives in its own registers: rotating them through moves (or loading under a
-    // condition) makes the compiler wait for the entry it has just requested -- a full L2 round trip in every pass (measured: 460 ns per pass).
-    // The host pads the schedule to a multiple of four passes; requests beyond the end re-read the last pass.
+    const int n = T.nx, D2 = 2 * S.n_reg;  // D2: from a slot of [val | adj] to the same slot of [tan | dadj]
+    double* const adj = val + S.n_reg;
+    double* const tan = TAN ? val + D2 : nullptr;
+    double* const dadj = TAN ? tan + S.n_reg : nullptr;
+    const int* const seed_reg = ix.seed_reg;
+    __syncthreads();  // the set-up's registers; xs and vs were written element-wise by their owners
     const int last = S.n_fw_pass - 1;
     auto fwi = [&](int p) { return S.fw[(size_t)(p < last ? p : last) * NT + lane]; };
-    int4 q0 = fwi(0), q1 = fwi(1), q2 = fwi(2), q3 = fwi(3);
-    for (int k = lane; k < T.nx; k += NT) val[XREG0 + k] = xs[k];  // the variables' registers: 2 .. 2 + nx
+    const Four<int4> q = fetch_four(fwi);
+    for (int k = lane; k < n; k += NT) {  // the variables' registers: 2 .. 2 + nx
+      val[XREG0 + k] = xs[k];
+      if constexpr (TAN) tan[XREG0 + k] = (SEED == SEED_AL || vs) ? vs[k] : (k == dir ? 1.0 : 0.0);
+    }
     pass_barrier();
     auto fw_pass = [&](const int4 ins) __attribute__((always_inline)) {
-      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-      {  // straight-line: an idle slot adds the zero register to itself into the trash register
-        const double va = val[ins.y], vb = val[ins.z];
-        const int fl = ins.w;
-        const long long mM = fmask(fl, F_MUL);
-        const double b2 = bsel(fmask(fl, F_SQR), va, vb);
-        double v = bsel(mM, va * b2, bflip(va, fmask(fl, F_NEGA)) + bkeep(bflip(b2, fmask(fl, F_NEGB)), ~fmask(fl, F_ZB)));
-        if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
-          // tape_value's rules (oh_tape_ops.h) for the opcodes the straight-line path does not cover, on the operands loaded above: through tape_value
-          // itself the planner's solves took 3 % longer (B = 1024: 15.4 against 14.9 ms)
-          switch (o) {
-            case OP_DIV: v = va / vb; break;
-            case OP_SIN: v = sin(va); break;
-            case OP_COS: v = cos(va); break;
-            case OP_ATAN2: v = atan2(va, vb); break;
-            case OP_SQRT: v = sqrt(va); break;
-            case OP_ASIN: v = asin(va); break;
-            case OP_FABS: v = fabs(va); break;
-            case OP_FMIN: v = fmin(va, vb); break;
-            case OP_FMAX: v = fmax(va, vb); break;
-            case OP_LT: v = va < vb ? 1.0 : 0.0; break;
-            case OP_LE: v = va <= vb ? 1.0 : 0.0; break;
-            case OP_EQ: v = va == vb ? 1.0 : 0.0; break;
-            case OP_NE: v = va != vb ? 1.0 : 0.0; break;
-            case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; break;
-            case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; break;
-            case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; break;
-            case OP_IFZ: v = va != 0.0 ? vb : 0.0; break;
-            case OP_EXP: v = exp(va); break;
-            case OP_LOG: v = log(va); break;
-            default: break;
-          }
-        }
-        val[i] = v;
+#pragma clang fp contract(off)
+      // straight-line: an idle slot adds the zero register to itself into the trash register
+      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1), fl = ins.w;
+      const double va = val[ins.y], vb = val[ins.z];
+      double ta = 0.0, tb = 0.0, t = 0.0;
+      if constexpr (TAN) { ta = tan[ins.y]; tb = tan[ins.z]; }
+      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+      const double b2 = bsel(mS, va, vb);
+      double v = bsel(mM, va * b2, bflip(va, mA) + bkeep(bflip(b2, mB), mZ));
+      if constexpr (TAN) {  // product rule; a square is ta va + va ta = 2 va ta to the bit
+        const double tb2 = bsel(mS, ta, tb);
+        t = bsel(mM, ta * b2 + va * tb2, bflip(ta, mA) + bkeep(bflip(tb2, mB), mZ));
       }
+      if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
+        switch (o) {
+          case OP_DIV: v = va / vb; if constexpr (TAN) t = (ta - v * tb) / vb; break;
+          case OP_SIN: v = sin(va); if constexpr (TAN) t = cos(va) * ta; break;
+          case OP_COS: v = cos(va); if constexpr (TAN) t = -(sin(va) * ta); break;
+          case OP_ATAN2: v = atan2(va, vb); if constexpr (TAN) t = (vb * ta - va * tb) / (va * va + vb * vb); break;
+          case OP_SQRT: v = sqrt(va); if constexpr (TAN) t = 0.5 / v * ta; break;
+          case OP_ASIN: v = asin(va); if constexpr (TAN) t = ta / sqrt((1.0 - va) * (1.0 + va)); break;
+          case OP_FABS: v = fabs(va); if constexpr (TAN) t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * ta; break;
+          case OP_FMIN: v = fmin(va, vb); if constexpr (TAN) t = va <= vb ? ta : tb; break;
+          case OP_FMAX: v = fmax(va, vb); if constexpr (TAN) t = va >= vb ? ta : tb; break;
+          case OP_LT: v = va < vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_LE: v = va <= vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_EQ: v = va == vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_NE: v = va != vb ? 1.0 : 0.0; t = 0.0; break;
+          case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; t = 0.0; break;
+          case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+          case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
+          case OP_IFZ: v = va != 0.0 ? vb : 0.0; if constexpr (TAN) t = va != 0.0 ? tb : 0.0; break;
+          case OP_EXP: v = exp(va); if constexpr (TAN) t = v * ta; break;
+          case OP_LOG: v = log(va); if constexpr (TAN) t = ta / va; break;
+          default: break;
+        }
+      }
+      val[i] = v;
+      if constexpr (TAN) tan[i] = t;
       pass_barrier();
     };
-    for (int p = 0; p < S.n_fw_pass; p += 4) {
-      const int4 i0 = q0;
-      q0 = fwi(p + 4);
-      fw_pass(i0);
-      const int4 i1 = q1;
-      q1 = fwi(p + 5);
-      fw_pass(i1);
-      const int4 i2 = q2;
-      q2 = fwi(p + 6);
-      fw_pass(i2);
-      const int4 i3 = q3;
-      q3 = fwi(p + 7);
-      fw_pass(i3);
-    }
-    // rows: value, share of the merit, seed of the reverse sweep
-    const double f = val[S.seed_cost >= 0 ? seed_reg[S.seed_cost] : 0];
+    run_four(S.n_fw_pass, q, fwi, fw_pass);
+    // ---- seeds of the reverse sweep; SEED_AL: the rows' values and their share of the merit on the way
+    const double f = EVAL ? val[S.seed_cost >= 0 ? seed_reg[S.seed_cost] : 0] : 0.0;
     double v = 0.0, cm = 0.0, ms = 0.0;
-    for (int r = lane; r < S.nrows; r += NT) {
-      const double g = val[row_reg[r]];
-      rowv[r] = g;
-      roww[r] = r < T.n_ineq ? tape_al_ineq(g, lam[r], rho, v, cm, ms) : tape_al_eq(g, mu[r - T.n_ineq], rho, v, cm, ms);
+    if constexpr (SEED == SEED_AL) {
+      for (int r = lane; r < S.nrows; r += NT) {
+        const double g = val[ix.row_reg[r]];
+        if constexpr (EVAL) rowv[r] = g;
+        const bool ineq = r < T.n_ineq;
+        const double w = ineq ? tape_al_ineq(g, lam[r], rho, v, cm, ms) : tape_al_eq(g, mu[r - T.n_ineq], rho, v, cm, ms);
+        roww[r] = w;
+        if constexpr (TAN) rowt[r] = (!ineq || w < 0.0) ? rho * tan[ix.row_reg[r]] : 0.0;  // (an inequality row: the seed planted is not zero -- active)
+      }
+      __syncthreads();
     }
-    __syncthreads();
     for (int s = lane; s < S.n_seed; s += NT) {
-      double acc = s == S.seed_cost ? 1.0 : 0.0;
-      for (int e = seed_off[s]; e < seed_off[s + 1]; ++e) acc += roww[seed_rows[e]];
+      double acc = s == S.seed_cost ? (SEED == SEED_GIVEN ? sd[0] : 1.0) : 0.0, dacc = -0.0;
+      for (int e = ix.seed_off[s]; e < ix.seed_off[s + 1]; ++e) {
+        const int r = ix.seed_rows[e];
+        acc += SEED == SEED_GIVEN ? sd[1 + r] : roww[r];
+        if constexpr (TAN && SEED == SEED_AL) dacc += rowt[r];
+      }
       adj[seed_reg[s]] = acc;
+      if constexpr (TAN && SEED == SEED_AL) dadj[seed_reg[s]] = dacc;
     }
     __syncthreads();
+    // ---- reverse
     const int rlast = S.n_rv_pass - 1;
-    auto rvi = [&](int p, int h) { return S.rv[((size_t)(p < rlast ? p : rlast) * NT + lane) * 2 + h]; };
-    int4 a0 = rvi(0, 0), b0 = rvi(0, 1), a1 = rvi(1, 0), b1 = rvi(1, 1), a2 = rvi(2, 0), b2 = rvi(2, 1), a3 = rvi(3, 0), b3 = rvi(3, 1);
-    auto rv_pass = [&](const int4 ins, const int4 meta) __attribute__((always_inline)) {
+    auto rvi = [&](int p) {
+      const int4* e = S.rv + ((size_t)(p < rlast ? p : rlast) * NT + lane) * 2;
+      return RvEntry{e[0], e[1]};
+    };
+    auto rv_pass = [&](const RvEntry en) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+      // straight-line: absent consumers point at the zero register (every column of it is 0), idle slots write the trash register
+      const int4 ins = en.ins, meta = en.meta;
       const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-      {  // straight-line: absent consumers point at the zero register (val[0] = adj[0] = 0), idle slots write the trash register
-        const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
-        // a consumer's slot is an index into [val | adj] (adj = val + n_reg), an absent one the zero register
-        const double sd = adj[i], s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
-        double w = bkeep(sd, fmask(meta.x >> 16, 1));
-        w += s0;
-        w += s1;
-        w += s2;
-        if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
-          for (int e = 3; e < nc; ++e) w += val[S.cons[ins.w + e - 3]];
-        {
-          const double va = val[ins.y], vb = val[ins.z];
-          const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR);
-          double ca = bsel(mM, w * bsel(mS, va + va, vb), bflip(w, fmask(fl, F_NEGA)));
-          double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, fmask(fl, F_NEGB)), ~fmask(fl, F_ZB)));
-          const bool rare = (fl & F_RARE) != 0;
-          if (__builtin_amdgcn_ballot_w64(rare) != 0) {
-            if (rare) { ca = 0.0; cb = 0.0; }
-            // tape_adjoint's rules (oh_tape_ops.h), each contribution a value, not an accumulation: behind an accessor that stores into ca / cb the
-            // compiler merges the cases' stores into one store through a pointer and both variables end up in scratch memory (24 bytes a lane)
-            switch (o) {
-              case OP_DIV: ca = w / vb; cb = -(w * va / (vb * vb)); break;
-              case OP_SIN: ca = w * cos(va); break;
-              case OP_COS: ca = -(w * sin(va)); break;
-              case OP_ATAN2: { const double d = va * va + vb * vb; ca = w * vb / d; cb = -(w * va / d); } break;
-              case OP_SQRT: ca = w * 0.5 / val[i]; break;
-              case OP_ASIN: ca = w / sqrt((1.0 - va) * (1.0 + va)); break;
-              case OP_FABS: ca = w * (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)); break;
-              case OP_FMIN: if (va <= vb) ca = w; else cb = w; break;
-              case OP_FMAX: if (va >= vb) ca = w; else cb = w; break;
-              case OP_IFZ: if (va != 0.0) cb = w; break;
-              case OP_EXP: ca = w * val[i]; break;
-              case OP_LOG: ca = w / va; break;
-              default: break;  // LT .. OR: piecewise constant
-            }
-          }
-          val[i] = ca;
-          adj[i] = cb;
+      const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
+      const long long mSeed = fmask(meta.x >> 16, 1);
+      // a consumer's slot is an index into [val | adj] (adj = val + n_reg), an absent one the zero register
+      // (every load ahead of the two chains: with the tangents' loads after the w chain the planner's Newton-CG solve measured 1 - 2 % slower)
+      const double sd_ = adj[i];
+      double dsd_ = -0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
+      if constexpr (TAN && SEED == SEED_AL) dsd_ = dadj[i];  // (constant weights: no seed to load)
+      const double s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
+      if constexpr (TAN) { e0 = val[meta.y + D2]; e1 = val[meta.z + D2]; e2 = val[meta.w + D2]; }
+      double w = bkeep(sd_, mSeed);
+      w += s0;
+      w += s1;
+      w += s2;
+      double dw = 0.0;
+      if constexpr (TAN) {
+        if constexpr (SEED == SEED_AL) dw = bsel(mSeed, dsd_, -0.0) + e0;  // (-0 + e0 is e0 to the bit)
+        else dw = e0;
+        dw += e1;
+        dw += e2;
+      }
+      if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
+        for (int e = 3; e < nc; ++e) {
+          const int sl = S.cons[ins.w + e - 3];
+          w += val[sl];
+          if constexpr (TAN) dw += val[sl + D2];
+        }
+      const double va = val[ins.y], vb = val[ins.z];
+      double ta = 0.0, tb = 0.0;
+      if constexpr (TAN) { ta = tan[ins.y]; tb = tan[ins.z]; }
+      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
+      const double qa = bsel(mS, va + va, vb);  // d (a b) / d a = b, d (a a) / d a = 2 a
+      double ca = bsel(mM, w * qa, bflip(w, mA));
+      double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, mB), mZ));
+      double dca = 0.0, dcb = 0.0;
+      if constexpr (TAN) {
+        const double dqa = bsel(mS, ta + ta, tb);
+        dca = bsel(mM, dw * qa + w * dqa, bflip(dw, mA));
+        dcb = bsel(mM, bkeep(dw * va + w * ta, ~mS), bkeep(bflip(dw, mB), mZ));
+      }
+      const bool rare = (fl & F_RARE) != 0;
+      if (__builtin_amdgcn_ballot_w64(rare) != 0) {
+        if (rare) { ca = 0.0; cb = 0.0; dca = 0.0; dcb = 0.0; }
+        switch (o) {
+          case OP_DIV:
+            ca = w / vb; cb = -(w * va / (vb * vb));
+            if constexpr (TAN) { dca = (dw - w * tb / vb) / vb; dcb = -((dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb)); }
+            break;
+          case OP_SIN: { const double c = cos(va); ca = w * c; if constexpr (TAN) dca = dw * c - w * sin(va) * ta; } break;
+          case OP_COS: { const double s = sin(va); ca = -(w * s); if constexpr (TAN) dca = -(dw * s + w * cos(va) * ta); } break;
+          case OP_ATAN2: {
+            const double d = va * va + vb * vb;
+            ca = w * vb / d; cb = -(w * va / d);
+            if constexpr (TAN) { const double dd = 2.0 * (va * ta + vb * tb); dca = (dw * vb + w * (tb - vb * dd / d)) / d; dcb = -((dw * va + w * (ta - va * dd / d)) / d); }
+          } break;
+          case OP_SQRT: { const double r = val[i]; ca = w * 0.5 / r; if constexpr (TAN) { const double q2 = 0.5 / r; dca = dw * q2 - w * (q2 * tan[i] / r); } } break;  // own value and tangent, read before the stores below
+          case OP_ASIN: { const double s = (1.0 - va) * (1.0 + va), r = sqrt(s); ca = w / r; if constexpr (TAN) dca = dw / r + w * (va * ta / (s * r)); } break;
+          case OP_FABS: { const double sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0); ca = w * sg; if constexpr (TAN) dca = dw * sg; } break;
+          case OP_FMIN: if (va <= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+          case OP_FMAX: if (va >= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
+          case OP_IFZ: if (va != 0.0) { cb = w; dcb = dw; } break;
+          case OP_EXP: { const double r = val[i]; ca = w * r; if constexpr (TAN) dca = dw * r + w * tan[i]; } break;
+          case OP_LOG: ca = w / va; if constexpr (TAN) dca = (dw - w * ta / va) / va; break;
+          default: break;  // LT .. OR: piecewise constant
         }
       }
+      val[i] = ca;
+      adj[i] = cb;
+      if constexpr (TAN) { tan[i] = dca; dadj[i] = dcb; }
       pass_barrier();
     };
-    for (int p = 0; p < S.n_rv_pass; p += 4) {
-      const int4 x0 = a0, y0 = b0;
-      a0 = rvi(p + 4, 0); b0 = rvi(p + 4, 1);
-      rv_pass(x0, y0);
-      const int4 x1 = a1, y1 = b1;
-      a1 = rvi(p + 5, 0); b1 = rvi(p + 5, 1);
-      rv_pass(x1, y1);
-      const int4 x2 = a2, y2 = b2;
-      a2 = rvi(p + 6, 0); b2 = rvi(p + 6, 1);
-      rv_pass(x2, y2);
-      const int4 x3 = a3, y3 = b3;
-      a3 = rvi(p + 7, 0); b3 = rvi(p + 7, 1);
-      rv_pass(x3, y3);
-    }
-    for (int k = lane; k < T.nx; k += NT) gout[k] = val[XREG0 + k];  // a variable's entry is "+ the zero register": it leaves its adjoint in its own slot
+    run_four(S.n_rv_pass, fetch_four(rvi), rvi, rv_pass);
+    // a variable's entry is "+ the zero register": it leaves its adjoint, and its adjoint's tangent, in its own slots
+    if (!TAN || gout)
+      for (int k = lane; k < n; k += NT) gout[k] = val[XREG0 + k];
+    if constexpr (TAN)
+      for (int k = lane; k < n; k += NT) hout[k] = tan[XREG0 + k];
     __syncthreads();
-    v = f + red.sum(v);
-    *fout = f;
-    *cmax = red.max(cm);
-    *meas = red.max(ms);
+    if constexpr (EVAL) {
+      v = f + red.sum(v);
+      *fout = f;
+      *cmax = red.max(cm);
+      *meas = red.max(ms);
+    }
     return v;
   }
+
+  // the merit's value at xs, its gradient into gout, the rows into rowv: the two left columns only
+  __device__ __attribute__((always_inline)) double phi(const double* xs, double* gout, const double rho, double* fout, double* cmax, double* meas) {
+    return sweep<false, SEED_AL, true>(xs, nullptr, gout, nullptr, rho, nullptr, 0, fout, cmax, meas);
+  }
+  // H v of the merit at xs along vs into hout, from (xs, vs, lam, mu, rho) alone: phi destroys val[] in its reverse sweep, so nothing of an evaluation
+  // survives for a product to reuse (the interpreter's hess_vec reuses all of it)
+  __device__ __attribute__((always_inline)) void hvp(const double* xs, const double* vs, double* hout, const double rho) {
+    sweep<true, SEED_AL, false>(xs, vs, nullptr, hout, rho);
+  }
 };
+
+// LDS layout of k_tape_wave and k_tape_wave_phi (oh_tape_wave_lds_bytes): [val | adj, when in LDS] x xt g gt d | lam | mu | rowv | roww | 1 / s.y [m], the two-loop
+// alphas [m] | reduction buffer | the (s, y) pairs [2 m n], when in LDS | index arrays.  A register file beyond the LDS is regs_slice: [val | adj] of this instance in
+// global memory (the block's own lines, L2 / L1 resident).
+struct SolveLds {
+  double *val, *X, *XT, *G, *GT, *D, *lam, *mu, *rowv, *roww, *RA, *redbuf, *Hs;
+  int* small;
+};
+template <bool REG_LDS, bool HIST_LDS>
+__device__ inline SolveLds solve_carve(const TapeParams& T, const WaveSchedDev& S, double* lds, double* regs_slice, double* hist_slice) {
+  const size_t n = T.nx, m = T.lbfgs, ni = T.n_ineq > 0 ? T.n_ineq : 1, ne = T.n_eq > 0 ? T.n_eq : 1, nr = S.nrows > 0 ? S.nrows : 1;
+  SolveLds L;
+  double* w = lds;
+  if constexpr (REG_LDS) { L.val = w; w += 2 * (size_t)S.n_reg; } else { L.val = regs_slice; }
+  auto take = [&](size_t k) { double* o = w; w += k; return o; };
+  L.X = take(n); L.XT = take(n); L.G = take(n); L.GT = take(n); L.D = take(n);
+  L.lam = take(ni); L.mu = take(ne); L.rowv = take(nr); L.roww = take(nr); L.RA = take(2 * m); L.redbuf = take(8);
+  L.Hs = HIST_LDS ? take(2 * m * n) : hist_slice;
+  L.small = reinterpret_cast<int*>(w);
+  return L;
+}
 
 template <int NT, bool HIST_LDS, bool REG_LDS>
 __global__ __launch_bounds__(NT) void k_tape_wave(TapeParams T, WaveSchedDev S, int B, const double* __restrict__ x0, const double* __restrict__ par,
@@ -279,50 +428,16 @@ __global__ __launch_bounds__(NT) void k_tape_wave(TapeParams T, WaveSchedDev S, 
   const int gb = blockIdx.x, lane = threadIdx.x;
   if (gb >= B) return;
   const int n = T.nx, m = T.lbfgs, ni = T.n_ineq, ne = T.n_eq;
-  double *val, *adj, *X;
-  if constexpr (REG_LDS) {
-    val = lds;
-    adj = val + S.n_reg;
-    X = adj + S.n_reg;
-  } else {  // a register file beyond the LDS: [val | adj] of this instance in global memory (the block's own lines, L2 / L1 resident)
-    val = regs_g + (size_t)gb * 2 * S.n_reg;
-    adj = val + S.n_reg;
-    X = lds;
-  }
-  double* XT = X + n;
-  double* G = XT + n;
-  double* GT = G + n;
-  double* D = GT + n;
-  double* lam = D + n;
-  double* mu = lam + (ni > 0 ? ni : 1);
-  double* rowv = mu + (ne > 0 ? ne : 1);
-  double* roww = rowv + (S.nrows > 0 ? S.nrows : 1);
-  double* RA = roww + (S.nrows > 0 ? S.nrows : 1);  // 1 / s.y [m], the two-loop alphas [m]
-  double* redbuf = RA + 2 * m;
-  double* after = redbuf + 8;
-  double* Hs;
-  if constexpr (HIST_LDS) {
-    Hs = after;
-    after += 2 * (size_t)m * n;
-  } else {
-    Hs = hist_g + (size_t)gb * 2 * m * n;
-  }
-  int* small = reinterpret_cast<int*>(after);
-  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
-  const int* row_reg = small;
-  const int* seed_reg = row_reg + S.nrows;
-  const int* seed_off = seed_reg + S.n_seed;
-  const int* seed_rows = seed_off + S.n_seed + 1;
-  const double* pb = par + (size_t)gb * T.np;
-  if (lane == 0) { val[ZREG] = 0.0; adj[ZREG] = 0.0; val[TRASH] = 0.0; adj[TRASH] = 0.0; }
-  for (int k = lane; k < S.n_cst; k += NT) val[S.cst_reg[k]] = S.cst_val[k];
-  for (int k = lane; k < S.n_par; k += NT) val[S.par_reg[k]] = pb[S.par_k[k]];
+  const SolveLds L = solve_carve<REG_LDS, HIST_LDS>(T, S, lds, REG_LDS ? nullptr : regs_g + (size_t)gb * 2 * S.n_reg, HIST_LDS ? nullptr : hist_g + (size_t)gb * 2 * m * n);
+  double *X = L.X, *XT = L.XT, *G = L.G, *GT = L.GT, *D = L.D, *lam = L.lam, *mu = L.mu, *rowv = L.rowv, *RA = L.RA, *Hs = L.Hs;
+  const WaveIndex ix = wave_load_index<NT>(S, L.small, lane);
+  wave_setup_registers<NT, 2>(S, L.val, par + (size_t)gb * T.np, lane);
   for (int k = lane; k < n; k += NT) X[k] = x0[(size_t)gb * n + k];
   for (int i = lane; i < ni; i += NT) lam[i] = 0.0;
   for (int i = lane; i < ne; i += NT) mu[i] = 0.0;
   __syncthreads();
-  Red<NT> red{redbuf};
-  WaveEval<NT, REG_LDS> ev{T, S, val, adj, lam, mu, rowv, roww, row_reg, seed_reg, seed_off, seed_rows, lane, red};
+  Red<NT> red{L.redbuf};
+  WaveEval<NT, REG_LDS> ev{T, S, L.val, lam, mu, rowv, L.roww, nullptr, ix, lane, red};
 
   auto Sr = [&](int slot, int k) -> double& { return Hs[(size_t)slot * n + k]; };
   auto Yr = [&](int slot, int k) -> double& { return Hs[(size_t)(m + slot) * n + k]; };
@@ -530,446 +645,45 @@ __global__ __launch_bounds__(NT) void k_tape_wave_phi(TapeParams T, WaveSchedDev
   extern __shared__ double lds[];
   const int gb = blockIdx.x, lane = threadIdx.x;
   if (gb >= B) return;
-  const int n = T.nx, m = T.lbfgs, ni = T.n_ineq, ne = T.n_eq;
-  double *val, *adj, *X;
-  if constexpr (REG_LDS) {
-    val = lds;
-    adj = val + S.n_reg;
-    X = adj + S.n_reg;
-  } else {
-    val = regs_g + (size_t)gb * 2 * S.n_reg;
-    adj = val + S.n_reg;
-    X = lds;
-  }
-  double* G = X + 2 * n;
-  double* lam = X + 5 * n;
-  double* mu = lam + (ni > 0 ? ni : 1);
-  double* rowv = mu + (ne > 0 ? ne : 1);
-  double* roww = rowv + (S.nrows > 0 ? S.nrows : 1);
-  double* redbuf = roww + (S.nrows > 0 ? S.nrows : 1) + 2 * m;
-  int* small = reinterpret_cast<int*>(redbuf + 8);
-  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
-  const int* row_reg = small;
-  const int* seed_reg = row_reg + S.nrows;
-  const int* seed_off = seed_reg + S.n_seed;
-  const int* seed_rows = seed_off + S.n_seed + 1;
-  const double* pb = par + (size_t)gb * T.np;
-  if (lane == 0) { val[ZREG] = 0.0; adj[ZREG] = 0.0; val[TRASH] = 0.0; adj[TRASH] = 0.0; }
-  for (int k = lane; k < S.n_cst; k += NT) val[S.cst_reg[k]] = S.cst_val[k];
-  for (int k = lane; k < S.n_par; k += NT) val[S.par_reg[k]] = pb[S.par_k[k]];
-  for (int k = lane; k < n; k += NT) X[k] = x[(size_t)gb * n + k];
-  for (int i = lane; i < ni; i += NT) lam[i] = lam_in[(size_t)gb * ni + i];
-  for (int i = lane; i < ne; i += NT) mu[i] = mu_in[(size_t)gb * ne + i];
+  const int n = T.nx, ni = T.n_ineq, ne = T.n_eq;
+  const SolveLds L = solve_carve<REG_LDS, false>(T, S, lds, REG_LDS ? nullptr : regs_g + (size_t)gb * 2 * S.n_reg, nullptr);
+  const WaveIndex ix = wave_load_index<NT>(S, L.small, lane);
+  wave_setup_registers<NT, 2>(S, L.val, par + (size_t)gb * T.np, lane);
+  for (int k = lane; k < n; k += NT) L.X[k] = x[(size_t)gb * n + k];
+  for (int i = lane; i < ni; i += NT) L.lam[i] = lam_in[(size_t)gb * ni + i];
+  for (int i = lane; i < ne; i += NT) L.mu[i] = mu_in[(size_t)gb * ne + i];
   __syncthreads();
-  Red<NT> red{redbuf};
-  WaveEval<NT, REG_LDS> ev{T, S, val, adj, lam, mu, rowv, roww, row_reg, seed_reg, seed_off, seed_rows, lane, red};
+  Red<NT> red{L.redbuf};
+  WaveEval<NT, REG_LDS> ev{T, S, L.val, L.lam, L.mu, L.rowv, L.roww, nullptr, ix, lane, red};
   double f_, c_, m_;
-  const double v_ = ev.phi(X, G, rho, &f_, &c_, &m_);
+  const double v_ = ev.phi(L.X, L.G, rho, &f_, &c_, &m_);
   __syncthreads();
   if (lane == 0) { merit[gb] = v_; fo[gb] = f_; cmax[gb] = c_; meas[gb] = m_; }
-  for (int r = lane; r < S.nrows; r += NT) rows[(size_t)gb * S.nrows + r] = rowv[r];
-  for (int k = lane; k < n; k += NT) grad[(size_t)gb * n + k] = G[k];
+  for (int r = lane; r < S.nrows; r += NT) rows[(size_t)gb * S.nrows + r] = L.rowv[r];
+  for (int k = lane; k < n; k += NT) grad[(size_t)gb * n + k] = L.G[k];
 }
 
 // Exact Hessian-vector products by forward-over-reverse on the level schedule (oh_tape_hvp with option tape_hvp_wave): ONE BLOCK PER UNIT
-// u = b nv + d (instance b, direction d, the direction fastest), the launch covers the units [u0, u0 + gridDim.x).  The schedule is the one
-// WaveEval::phi runs, untouched; the register file has four columns [val | adj | tan | dadj] of n_reg doubles each, tan = (d val / d x) v,
-// dadj = (d adj / d x) v.  Forward: phi's passes with the tangent beside every value.  Reverse: phi's slot trick twice over -- when instruction
-// c is reached all its consumers are done, so c leaves its contributions (ca, cb) to its operands in val[c], adj[c] and their directional
-// derivatives (dca, dcb) in tan[c], dadj[c]; w gathers seed + slots as phi does, dw gathers the same slot indices displaced by 2 n_reg (the
-// weights are constants: no seed).  The gather order is the schedule's, every sum of a unit is that gather: a unit's bits do not depend on B, nv,
-// the other units, the launch it falls into, the register placement or the block width.  The variables' "+ zero" entries leave the gradient
-// in val[XREG0 + k] and H v in tan[XREG0 + k].  Conventions at kinks: k_tape_hvp's (oh_tape.hip).  A third statement of the second-order
-// rules (oh_tape_ops.h says why): here each is a pair of values per operand, not an accumulation.
+// u = b nv + d (instance b, direction d, the direction fastest), the launch covers the units [u0, u0 + gridDim.x).  One sweep over the four columns with
+// the weights of oh_tape_probe as seeds (SEED_GIVEN) along V_u, or along the unit vector d when V is null; the gradient is written by the units of
+// direction 0.  LDS: the four columns (or, with the columns in the launch's work area, nothing) and the index arrays.
 template <int NT, bool REG_LDS>
 __global__ __launch_bounds__(NT) void k_tape_wave_hvp(TapeParams T, WaveSchedDev S, int u0, int nv, const double* __restrict__ x, const double* __restrict__ par,
                                                       const double* __restrict__ seeds, const double* __restrict__ V, double* regs_g, double* __restrict__ HV,
                                                       double* __restrict__ grad) {
-#pragma clang fp contract(off)
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
   const size_t u = (size_t)u0 + blockIdx.x;
-  const size_t inst = u / (size_t)nv;
+  const size_t inst = u / (size_t)nv, n = T.nx, nr = S.n_reg;
   const int dir = (int)(u % (size_t)nv);
-  const int n = T.nx, nr = S.n_reg, D2 = 2 * S.n_reg;  // D2: from a slot of [val | adj] to the same slot of [tan | dadj]
-  double* val;
-  int* small;
-  if constexpr (REG_LDS) {
-    val = lds;
-    small = reinterpret_cast<int*>(lds + 4 * (size_t)nr);
-  } else {  // [val | adj | tan | dadj] of this block in the launch's work area
-    val = regs_g + (size_t)blockIdx.x * 4 * nr;
-    small = reinterpret_cast<int*>(lds);
-  }
-  double* adj = val + nr;
-  double* tan = val + D2;
-  double* dadj = tan + nr;
-  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
-  const int* seed_reg = small + S.nrows;
-  const int* seed_off = seed_reg + S.n_seed;
-  const int* seed_rows = seed_off + S.n_seed + 1;
-  const double* pb = par + inst * T.np;
-  const double* xb = x + inst * n;
-  const double* vd = V ? V + u * n : nullptr;
-  if (lane == 0) {
-    val[ZREG] = 0.0; adj[ZREG] = 0.0; tan[ZREG] = 0.0; dadj[ZREG] = 0.0;
-    val[TRASH] = 0.0; adj[TRASH] = 0.0; tan[TRASH] = 0.0; dadj[TRASH] = 0.0;
-  }
-  for (int k = lane; k < S.n_cst; k += NT) { val[S.cst_reg[k]] = S.cst_val[k]; tan[S.cst_reg[k]] = 0.0; }  // (the -1 register is among them)
-  for (int k = lane; k < S.n_par; k += NT) { val[S.par_reg[k]] = pb[S.par_k[k]]; tan[S.par_reg[k]] = 0.0; }
-  for (int k = lane; k < n; k += NT) { val[XREG0 + k] = xb[k]; tan[XREG0 + k] = vd ? vd[k] : (k == dir ? 1.0 : 0.0); }
-  auto pass_barrier = [] { WaveEval<NT, REG_LDS>::pass_barrier(); };
-  // ---- forward: four entries in flight, as in phi
-  const int last = S.n_fw_pass - 1;
-  auto fwi = [&](int p) { return S.fw[(size_t)(p < last ? p : last) * NT + lane]; };
-  int4 q0 = fwi(0), q1 = fwi(1), q2 = fwi(2), q3 = fwi(3);
-  __syncthreads();
-  auto fw_pass = [&](const int4 ins) __attribute__((always_inline)) {
-#pragma clang fp contract(off)
-    const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-    const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
-    const int fl = ins.w;
-    const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
-    const double b2 = bsel(mS, va, vb), tb2 = bsel(mS, ta, tb);
-    double v = bsel(mM, va * b2, bflip(va, mA) + bkeep(bflip(b2, mB), mZ));
-    // product rule; a square is ta va + va ta = 2 va ta to the bit
-    double t = bsel(mM, ta * b2 + va * tb2, bflip(ta, mA) + bkeep(bflip(tb2, mB), mZ));
-    if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
-      switch (o) {
-        case OP_DIV: v = va / vb; t = (ta - v * tb) / vb; break;
-        case OP_SIN: v = sin(va); t = cos(va) * ta; break;
-        case OP_COS: v = cos(va); t = -(sin(va) * ta); break;
-        case OP_ATAN2: v = atan2(va, vb); t = (vb * ta - va * tb) / (va * va + vb * vb); break;
-        case OP_SQRT: v = sqrt(va); t = 0.5 / v * ta; break;
-        case OP_ASIN: v = asin(va); t = ta / sqrt((1.0 - va) * (1.0 + va)); break;
-        case OP_FABS: v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * ta; break;
-        case OP_FMIN: v = fmin(va, vb); t = va <= vb ? ta : tb; break;
-        case OP_FMAX: v = fmax(va, vb); t = va >= vb ? ta : tb; break;
-        case OP_LT: v = va < vb ? 1.0 : 0.0; t = 0.0; break;
-        case OP_LE: v = va <= vb ? 1.0 : 0.0; t = 0.0; break;
-        case OP_EQ: v = va == vb ? 1.0 : 0.0; t = 0.0; break;
-        case OP_NE: v = va != vb ? 1.0 : 0.0; t = 0.0; break;
-        case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; t = 0.0; break;
-        case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-        case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-        case OP_IFZ: v = va != 0.0 ? vb : 0.0; t = va != 0.0 ? tb : 0.0; break;
-        case OP_EXP: v = exp(va); t = v * ta; break;
-        case OP_LOG: v = log(va); t = ta / va; break;
-        default: break;
-      }
-    }
-    val[i] = v;
-    tan[i] = t;
-    pass_barrier();
-  };
-  for (int p = 0; p < S.n_fw_pass; p += 4) {
-    const int4 i0 = q0;
-    q0 = fwi(p + 4);
-    fw_pass(i0);
-    const int4 i1 = q1;
-    q1 = fwi(p + 5);
-    fw_pass(i1);
-    const int4 i2 = q2;
-    q2 = fwi(p + 6);
-    fw_pass(i2);
-    const int4 i3 = q3;
-    q3 = fwi(p + 7);
-    fw_pass(i3);
-  }
-  // ---- seeds: oh_tape_probe's weights in the order it adds them; their tangent is zero, so dadj has no seed at all
-  const double* sd = seeds + inst * (size_t)(1 + S.nrows);
-  for (int s = lane; s < S.n_seed; s += NT) {
-    double acc = s == S.seed_cost ? sd[0] : 0.0;
-    for (int e = seed_off[s]; e < seed_off[s + 1]; ++e) acc += sd[1 + seed_rows[e]];
-    adj[seed_reg[s]] = acc;
-  }
-  __syncthreads();
-  // ---- reverse
-  const int rlast = S.n_rv_pass - 1;
-  auto rvi = [&](int p, int h) { return S.rv[((size_t)(p < rlast ? p : rlast) * NT + lane) * 2 + h]; };
-  int4 a0 = rvi(0, 0), b0 = rvi(0, 1), a1 = rvi(1, 0), b1 = rvi(1, 1), a2 = rvi(2, 0), b2 = rvi(2, 1), a3 = rvi(3, 0), b3 = rvi(3, 1);
-  auto rv_pass = [&](const int4 ins, const int4 meta) __attribute__((always_inline)) {
-#pragma clang fp contract(off)
-    const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-    const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
-    const double sd_ = adj[i], s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
-    const double e0 = val[meta.y + D2], e1 = val[meta.z + D2], e2 = val[meta.w + D2];
-    double w = bkeep(sd_, fmask(meta.x >> 16, 1));
-    w += s0;
-    w += s1;
-    w += s2;
-    double dw = e0;
-    dw += e1;
-    dw += e2;
-    if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
-      for (int e = 3; e < nc; ++e) {
-        const int sl = S.cons[ins.w + e - 3];
-        w += val[sl];
-        dw += val[sl + D2];
-      }
-    const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
-    const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
-    const double qa = bsel(mS, va + va, vb), dqa = bsel(mS, ta + ta, tb);  // d (a b) / d a = b, d (a a) / d a = 2 a, and their tangents
-    double ca = bsel(mM, w * qa, bflip(w, mA));
-    double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, mB), mZ));
-    double dca = bsel(mM, dw * qa + w * dqa, bflip(dw, mA));
-    double dcb = bsel(mM, bkeep(dw * va + w * ta, ~mS), bkeep(bflip(dw, mB), mZ));
-    const bool rare = (fl & F_RARE) != 0;
-    if (__builtin_amdgcn_ballot_w64(rare) != 0) {
-      if (rare) { ca = 0.0; cb = 0.0; dca = 0.0; dcb = 0.0; }
-      // each contribution a value, assigned in its case (an accessor that stores through a pointer puts the four in scratch memory, as in phi)
-      switch (o) {
-        case OP_DIV:
-          ca = w / vb; cb = -(w * va / (vb * vb));
-          dca = (dw - w * tb / vb) / vb; dcb = -((dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb));
-          break;
-        case OP_SIN: { const double c = cos(va); ca = w * c; dca = dw * c - w * sin(va) * ta; } break;
-        case OP_COS: { const double s = sin(va); ca = -(w * s); dca = -(dw * s + w * cos(va) * ta); } break;
-        case OP_ATAN2: {
-          const double d = va * va + vb * vb, dd = 2.0 * (va * ta + vb * tb);
-          ca = w * vb / d; cb = -(w * va / d);
-          dca = (dw * vb + w * (tb - vb * dd / d)) / d; dcb = -((dw * va + w * (ta - va * dd / d)) / d);
-        } break;
-        case OP_SQRT: { const double r = val[i], q = 0.5 / r; ca = w * 0.5 / r; dca = dw * q - w * (q * tan[i] / r); } break;  // own value and tangent, read before the stores below
-        case OP_ASIN: { const double s = (1.0 - va) * (1.0 + va), r = sqrt(s); ca = w / r; dca = dw / r + w * (va * ta / (s * r)); } break;
-        case OP_FABS: { const double sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0); ca = w * sg; dca = dw * sg; } break;
-        case OP_FMIN: if (va <= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
-        case OP_FMAX: if (va >= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
-        case OP_IFZ: if (va != 0.0) { cb = w; dcb = dw; } break;
-        case OP_EXP: { const double q = val[i]; ca = w * q; dca = dw * q + w * tan[i]; } break;
-        case OP_LOG: ca = w / va; dca = (dw - w * ta / va) / va; break;
-        default: break;  // LT .. OR: piecewise constant
-      }
-    }
-    val[i] = ca;
-    adj[i] = cb;
-    tan[i] = dca;
-    dadj[i] = dcb;
-    pass_barrier();
-  };
-  for (int p = 0; p < S.n_rv_pass; p += 4) {
-    const int4 x0 = a0, y0 = b0;
-    a0 = rvi(p + 4, 0); b0 = rvi(p + 4, 1);
-    rv_pass(x0, y0);
-    const int4 x1 = a1, y1 = b1;
-    a1 = rvi(p + 5, 0); b1 = rvi(p + 5, 1);
-    rv_pass(x1, y1);
-    const int4 x2 = a2, y2 = b2;
-    a2 = rvi(p + 6, 0); b2 = rvi(p + 6, 1);
-    rv_pass(x2, y2);
-    const int4 x3 = a3, y3 = b3;
-    a3 = rvi(p + 7, 0); b3 = rvi(p + 7, 1);
-    rv_pass(x3, y3);
-  }
-  for (int k = lane; k < n; k += NT) HV[u * n + k] = tan[XREG0 + k];
-  if (grad && dir == 0)
-    for (int k = lane; k < n; k += NT) grad[inst * n + k] = val[XREG0 + k];
+  double* val = REG_LDS ? lds : regs_g + (size_t)blockIdx.x * 4 * nr;
+  const WaveIndex ix = wave_load_index<NT>(S, reinterpret_cast<int*>(REG_LDS ? lds + 4 * nr : lds), lane);
+  wave_setup_registers<NT, 4>(S, val, par + inst * T.np, lane);
+  Red<NT> red{nullptr};
+  WaveEval<NT, REG_LDS> ev{T, S, val, nullptr, nullptr, nullptr, nullptr, nullptr, ix, lane, red};
+  ev.template sweep<true, SEED_GIVEN, false>(x + inst * n, V ? V + u * n : nullptr, (grad && dir == 0) ? grad + inst * n : nullptr, HV + u * n, 0.0,
+                                              seeds + inst * (size_t)(1 + S.nrows), dir);
 }
-
-// The product of the merit's generalised Hessian with a vector on the level schedule (options tape_newton + tape_newton_wave): k_tape_wave_hvp's
-// four-column sweep over [val | adj | tan | dadj] with SEED TANGENTS.  WaveEval::phi destroys val[] in its reverse sweep, so nothing of an evaluation
-// survives for a product to reuse (the interpreter's hess_vec reuses all of it): the sweep is self-contained, from (xs, vs, lam, mu, rho) alone.
-//   forward  phi's passes with the tangent beside every value (k_tape_wave_hvp's, to the letter);
-//   rows     the seed of row r is tape_al_ineq / tape_al_eq as in phi; its tangent is rho tan[row_reg[r]] for an equality row and for an inequality row
-//            whose seed is not zero (lam - rho g > 0 by tape_al_ineq's own expression: a tie is inactive, as InterpEval::hess_vec has it), else 0 (rowt);
-//   seeds    adj[seed_reg[s]] as phi fills it, dadj[seed_reg[s]] the same sum over rowt -- started from -0, the one value that leaves every addend's bits
-//            alone: a seed register without rows then gathers exactly what k_tape_wave_hvp, which has no dadj seed, gathers;
-//   reverse  k_tape_wave_hvp's passes, dw starting from that seed where the entry has one.  Kinks hold the base point's selection.
-// The variables' entries leave the merit's gradient in val[XREG0 + k] (phi's bits: the two left columns see phi's arithmetic in phi's order) and
-// H v in tan[XREG0 + k].  Contraction off, the gather order the schedule's: a product's bits depend on the instance and the direction alone.
-// A FOURTH statement of the second-order rare-opcode rules (oh_tape_ops.h): k_tape_wave_hvp's text, its 169 VGPRs without scratch and the bits of
-// profiles/tape_hvp_wave_ab.json are pinned, and a device function both would call has to take the four columns and the entry through pointers or
-// references -- the form that put phi's contributions into scratch memory (see the comment in phi's reverse pass).  Change one, change all four.
-template <int NT, bool REG_LDS>
-struct WaveSweep {
-  const TapeParams& T;
-  const WaveSchedDev& S;
-  double *val, *lam, *mu, *roww, *rowt;  // val: the four columns, n_reg doubles each
-  const int *row_reg, *seed_reg, *seed_off, *seed_rows;
-  const int lane;
-
-  // xs, vs: the point and the direction (element k anywhere); gout (may be null): the merit's gradient; hout: H v.  EVAL: also what phi returns -- the
-  // rows into rowv, the merit's value (uniform) -- so that the sweep can stand in for phi (the one-site variant of k_tape_wave_newton).
-  template <bool EVAL = false>
-  __device__ __attribute__((always_inline)) double hvp(const double* xs, const double* vs, double* gout, double* hout, const double rho, double* rowv = nullptr,
-                                                       Red<NT>* red = nullptr, double* fout = nullptr, double* cmax = nullptr, double* meas = nullptr) {
-#pragma clang fp contract(off)
-    const int n = T.nx, nr = S.n_reg, D2 = 2 * S.n_reg;
-    double* adj = val + nr;
-    double* tan = val + D2;
-    double* dadj = tan + nr;
-    auto pass_barrier = [] { WaveEval<NT, REG_LDS>::pass_barrier(); };
-    __syncthreads();  // xs and vs were written element-wise by their owners
-    const int last = S.n_fw_pass - 1;
-    auto fwi = [&](int p) { return S.fw[(size_t)(p < last ? p : last) * NT + lane]; };
-    int4 q0 = fwi(0), q1 = fwi(1), q2 = fwi(2), q3 = fwi(3);
-    for (int k = lane; k < n; k += NT) { val[XREG0 + k] = xs[k]; tan[XREG0 + k] = vs[k]; }
-    pass_barrier();
-    auto fw_pass = [&](const int4 ins) __attribute__((always_inline)) {
-#pragma clang fp contract(off)
-      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-      const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
-      const int fl = ins.w;
-      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
-      const double b2 = bsel(mS, va, vb), tb2 = bsel(mS, ta, tb);
-      double v = bsel(mM, va * b2, bflip(va, mA) + bkeep(bflip(b2, mB), mZ));
-      double t = bsel(mM, ta * b2 + va * tb2, bflip(ta, mA) + bkeep(bflip(tb2, mB), mZ));
-      if (__builtin_amdgcn_ballot_w64((fl & F_RARE) != 0) != 0) {
-        switch (o) {
-          case OP_DIV: v = va / vb; t = (ta - v * tb) / vb; break;
-          case OP_SIN: v = sin(va); t = cos(va) * ta; break;
-          case OP_COS: v = cos(va); t = -(sin(va) * ta); break;
-          case OP_ATAN2: v = atan2(va, vb); t = (vb * ta - va * tb) / (va * va + vb * vb); break;
-          case OP_SQRT: v = sqrt(va); t = 0.5 / v * ta; break;
-          case OP_ASIN: v = asin(va); t = ta / sqrt((1.0 - va) * (1.0 + va)); break;
-          case OP_FABS: v = fabs(va); t = (va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0)) * ta; break;
-          case OP_FMIN: v = fmin(va, vb); t = va <= vb ? ta : tb; break;
-          case OP_FMAX: v = fmax(va, vb); t = va >= vb ? ta : tb; break;
-          case OP_LT: v = va < vb ? 1.0 : 0.0; t = 0.0; break;
-          case OP_LE: v = va <= vb ? 1.0 : 0.0; t = 0.0; break;
-          case OP_EQ: v = va == vb ? 1.0 : 0.0; t = 0.0; break;
-          case OP_NE: v = va != vb ? 1.0 : 0.0; t = 0.0; break;
-          case OP_NOT: v = va == 0.0 ? 1.0 : 0.0; t = 0.0; break;
-          case OP_AND: v = (va != 0.0 && vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-          case OP_OR: v = (va != 0.0 || vb != 0.0) ? 1.0 : 0.0; t = 0.0; break;
-          case OP_IFZ: v = va != 0.0 ? vb : 0.0; t = va != 0.0 ? tb : 0.0; break;
-          case OP_EXP: v = exp(va); t = v * ta; break;
-          case OP_LOG: v = log(va); t = ta / va; break;
-          default: break;
-        }
-      }
-      val[i] = v;
-      tan[i] = t;
-      pass_barrier();
-    };
-    for (int p = 0; p < S.n_fw_pass; p += 4) {
-      const int4 i0 = q0;
-      q0 = fwi(p + 4);
-      fw_pass(i0);
-      const int4 i1 = q1;
-      q1 = fwi(p + 5);
-      fw_pass(i1);
-      const int4 i2 = q2;
-      q2 = fwi(p + 6);
-      fw_pass(i2);
-      const int4 i3 = q3;
-      q3 = fwi(p + 7);
-      fw_pass(i3);
-    }
-    // ---- rows: phi's seeds and their tangents
-    const double f = EVAL ? val[S.seed_cost >= 0 ? seed_reg[S.seed_cost] : 0] : 0.0;
-    double v0 = 0.0, c0 = 0.0, m0 = 0.0;
-    for (int r = lane; r < S.nrows; r += NT) {
-      const double g = val[row_reg[r]], tg = tan[row_reg[r]];
-      if constexpr (EVAL) rowv[r] = g;
-      if (r < T.n_ineq) {
-        const double sd = tape_al_ineq(g, lam[r], rho, v0, c0, m0);
-        roww[r] = sd;
-        rowt[r] = sd < 0.0 ? rho * tg : 0.0;  // the seed phi plants is not zero: active
-      } else {
-        roww[r] = tape_al_eq(g, mu[r - T.n_ineq], rho, v0, c0, m0);
-        rowt[r] = rho * tg;
-      }
-    }
-    __syncthreads();
-    for (int s = lane; s < S.n_seed; s += NT) {
-      double acc = s == S.seed_cost ? 1.0 : 0.0, dacc = -0.0;
-      for (int e = seed_off[s]; e < seed_off[s + 1]; ++e) { acc += roww[seed_rows[e]]; dacc += rowt[seed_rows[e]]; }
-      adj[seed_reg[s]] = acc;
-      dadj[seed_reg[s]] = dacc;
-    }
-    __syncthreads();
-    // ---- reverse
-    const int rlast = S.n_rv_pass - 1;
-    auto rvi = [&](int p, int h) { return S.rv[((size_t)(p < rlast ? p : rlast) * NT + lane) * 2 + h]; };
-    int4 a0 = rvi(0, 0), b0 = rvi(0, 1), a1 = rvi(1, 0), b1 = rvi(1, 1), a2 = rvi(2, 0), b2 = rvi(2, 1), a3 = rvi(3, 0), b3 = rvi(3, 1);
-    auto rv_pass = [&](const int4 ins, const int4 meta) __attribute__((always_inline)) {
-#pragma clang fp contract(off)
-      const int o = ins.x >> OPSH, i = ins.x & ((1 << OPSH) - 1);
-      const int nc = meta.x & 0xFFFF, fl = meta.x >> 17;
-      const long long mSeed = fmask(meta.x >> 16, 1);
-      const double sd_ = adj[i], dsd_ = dadj[i], s0 = val[meta.y], s1 = val[meta.z], s2 = val[meta.w];
-      const double e0 = val[meta.y + D2], e1 = val[meta.z + D2], e2 = val[meta.w + D2];
-      double w = bkeep(sd_, mSeed);
-      w += s0;
-      w += s1;
-      w += s2;
-      double dw = bsel(mSeed, dsd_, -0.0);  // (-0 + e0 is e0 to the bit)
-      dw += e0;
-      dw += e1;
-      dw += e2;
-      if (__builtin_amdgcn_ballot_w64(nc > 3) != 0)
-        for (int e = 3; e < nc; ++e) {
-          const int sl = S.cons[ins.w + e - 3];
-          w += val[sl];
-          dw += val[sl + D2];
-        }
-      const double va = val[ins.y], vb = val[ins.z], ta = tan[ins.y], tb = tan[ins.z];
-      const long long mM = fmask(fl, F_MUL), mS = fmask(fl, F_SQR), mA = fmask(fl, F_NEGA), mB = fmask(fl, F_NEGB), mZ = ~fmask(fl, F_ZB);
-      const double qa = bsel(mS, va + va, vb), dqa = bsel(mS, ta + ta, tb);
-      double ca = bsel(mM, w * qa, bflip(w, mA));
-      double cb = bsel(mM, bkeep(w * va, ~mS), bkeep(bflip(w, mB), mZ));
-      double dca = bsel(mM, dw * qa + w * dqa, bflip(dw, mA));
-      double dcb = bsel(mM, bkeep(dw * va + w * ta, ~mS), bkeep(bflip(dw, mB), mZ));
-      const bool rare = (fl & F_RARE) != 0;
-      if (__builtin_amdgcn_ballot_w64(rare) != 0) {
-        if (rare) { ca = 0.0; cb = 0.0; dca = 0.0; dcb = 0.0; }
-        switch (o) {
-          case OP_DIV:
-            ca = w / vb; cb = -(w * va / (vb * vb));
-            dca = (dw - w * tb / vb) / vb; dcb = -((dw * va + w * ta - 2.0 * (w * va) * tb / vb) / (vb * vb));
-            break;
-          case OP_SIN: { const double c = cos(va); ca = w * c; dca = dw * c - w * sin(va) * ta; } break;
-          case OP_COS: { const double s = sin(va); ca = -(w * s); dca = -(dw * s + w * cos(va) * ta); } break;
-          case OP_ATAN2: {
-            const double d = va * va + vb * vb, dd = 2.0 * (va * ta + vb * tb);
-            ca = w * vb / d; cb = -(w * va / d);
-            dca = (dw * vb + w * (tb - vb * dd / d)) / d; dcb = -((dw * va + w * (ta - va * dd / d)) / d);
-          } break;
-          case OP_SQRT: { const double r = val[i], q = 0.5 / r; ca = w * 0.5 / r; dca = dw * q - w * (q * tan[i] / r); } break;
-          case OP_ASIN: { const double s = (1.0 - va) * (1.0 + va), r = sqrt(s); ca = w / r; dca = dw / r + w * (va * ta / (s * r)); } break;
-          case OP_FABS: { const double sg = va > 0.0 ? 1.0 : (va < 0.0 ? -1.0 : 0.0); ca = w * sg; dca = dw * sg; } break;
-          case OP_FMIN: if (va <= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
-          case OP_FMAX: if (va >= vb) { ca = w; dca = dw; } else { cb = w; dcb = dw; } break;
-          case OP_IFZ: if (va != 0.0) { cb = w; dcb = dw; } break;
-          case OP_EXP: { const double q = val[i]; ca = w * q; dca = dw * q + w * tan[i]; } break;
-          case OP_LOG: ca = w / va; dca = (dw - w * ta / va) / va; break;
-          default: break;  // LT .. OR: piecewise constant
-        }
-      }
-      val[i] = ca;
-      adj[i] = cb;
-      tan[i] = dca;
-      dadj[i] = dcb;
-      pass_barrier();
-    };
-    for (int p = 0; p < S.n_rv_pass; p += 4) {
-      const int4 x0 = a0, y0 = b0;
-      a0 = rvi(p + 4, 0); b0 = rvi(p + 4, 1);
-      rv_pass(x0, y0);
-      const int4 x1 = a1, y1 = b1;
-      a1 = rvi(p + 5, 0); b1 = rvi(p + 5, 1);
-      rv_pass(x1, y1);
-      const int4 x2 = a2, y2 = b2;
-      a2 = rvi(p + 6, 0); b2 = rvi(p + 6, 1);
-      rv_pass(x2, y2);
-      const int4 x3 = a3, y3 = b3;
-      a3 = rvi(p + 7, 0); b3 = rvi(p + 7, 1);
-      rv_pass(x3, y3);
-    }
-    if (gout)
-      for (int k = lane; k < n; k += NT) gout[k] = val[XREG0 + k];
-    for (int k = lane; k < n; k += NT) hout[k] = tan[XREG0 + k];
-    __syncthreads();
-    if constexpr (EVAL) {
-      v0 = f + red->sum(v0);
-      *fout = f;
-      *cmax = red->max(c0);
-      *meas = red->max(m0);
-    }
-    return v0;
-  }
-};
 
 // LDS layout of the two Newton kernels: [the four columns, when in LDS] x xt g gt d r y p hp | lam | mu | rowv | roww | rowt | reduction buffer | index arrays
 struct NewtonLds {
@@ -989,21 +703,13 @@ __device__ inline NewtonLds newton_carve(const TapeParams& T, const WaveSchedDev
   L.small = reinterpret_cast<int*>(w);
   return L;
 }
-// the registers nobody writes after the set-up: zero and trash in all four columns, constants and parameters with a zero tangent
-template <int NT>
-__device__ inline void newton_setup_registers(const WaveSchedDev& S, double* val, const double* pb, const int lane) {
-  const int nr = S.n_reg;
-  if (lane == 0)
-    for (int c = 0; c < 4; ++c) { val[c * (size_t)nr + ZREG] = 0.0; val[c * (size_t)nr + TRASH] = 0.0; }
-  for (int k = lane; k < S.n_cst; k += NT) { val[S.cst_reg[k]] = S.cst_val[k]; val[2 * (size_t)nr + S.cst_reg[k]] = 0.0; }
-  for (int k = lane; k < S.n_par; k += NT) { val[S.par_reg[k]] = pb[S.par_k[k]]; val[2 * (size_t)nr + S.par_reg[k]] = 0.0; }
-}
 
 // Truncated Newton-CG on the level schedule (options tape_newton + tape_newton_wave): ONE BLOCK PER INSTANCE, the state machine of
 // oh_tape_newton.h:tape_newton_instance -- COPIED, as that one is copied from oh_tape_solver.h: a change to either must be made here too -- with every
-// vector spread over the threads (element k on thread k mod NT) and every dot product a Red.  Two sweep sites in one loop, each inlined once (against the
-// sweep as the only site, an evaluation being a product with a zero tangent -- 85 KB of code instead of 122 KB -- the planner is 4 - 5 % faster this way, 7.64 against 7.97 ms at B = 256): WaveEval::phi
-// for evaluations (why = EV_START .. EV_AGAIN) and WaveSweep::hvp for the CG's products (EV_HVP); what follows a site runs until the next sweep is
+// vector spread over the threads (element k on thread k mod NT) and every dot product a Red.  Two instantiations of WaveEval::sweep in one loop, each inlined once (against the
+// four-column one as the only site, an evaluation being sweep<true, SEED_AL, true> with a zero tangent -- 85 KB of code instead of 122 KB -- the planner is 4 - 5 % faster
+// this way, 7.64 against 7.97 ms at B = 256): WaveEval::phi for evaluations (why = EV_START .. EV_AGAIN) and WaveEval::hvp for the CG's products (EV_HVP), on the
+// same four columns, of which phi uses the left two; what follows a site runs until the next sweep is
 // needed, sets `why` and goes round.  Every decision that leaves the loop or chooses the site is taken from a Red result or a kernel argument:
 // block-uniform, no thread skips a barrier.  max_iter caps evaluations plus products, iters is their sum, stats [B][2] = (steps, products).
 template <int NT, bool REG_LDS>
@@ -1016,20 +722,14 @@ __global__ __launch_bounds__(NT) void k_tape_wave_newton(TapeParams T, WaveSched
   const int n = T.nx, ni = T.n_ineq, ne = T.n_eq;
   const NewtonLds L = newton_carve<REG_LDS>(T, S, lds, REG_LDS ? nullptr : regs_g + (size_t)gb * 4 * S.n_reg);
   double *val = L.val, *X = L.X, *XT = L.XT, *G = L.G, *GT = L.GT, *D = L.D, *R = L.R, *Y = L.Y, *PV = L.PV, *HP = L.HP, *lam = L.lam, *mu = L.mu, *rowv = L.rowv;
-  int* small = L.small;
-  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
-  const int* row_reg = small;
-  const int* seed_reg = row_reg + S.nrows;
-  const int* seed_off = seed_reg + S.n_seed;
-  const int* seed_rows = seed_off + S.n_seed + 1;
-  newton_setup_registers<NT>(S, val, par + (size_t)gb * T.np, lane);
+  const WaveIndex ix = wave_load_index<NT>(S, L.small, lane);
+  wave_setup_registers<NT, 4>(S, val, par + (size_t)gb * T.np, lane);
   for (int k = lane; k < n; k += NT) X[k] = x0[(size_t)gb * n + k];
   for (int i = lane; i < ni; i += NT) lam[i] = 0.0;
   for (int i = lane; i < ne; i += NT) mu[i] = 0.0;
   __syncthreads();
   Red<NT> red{L.redbuf};
-  WaveEval<NT, REG_LDS> ev{T, S, val, val + S.n_reg, lam, mu, rowv, L.roww, row_reg, seed_reg, seed_off, seed_rows, lane, red};
-  WaveSweep<NT, REG_LDS> sw{T, S, val, lam, mu, L.roww, L.rowt, row_reg, seed_reg, seed_off, seed_rows, lane};
+  WaveEval<NT, REG_LDS> ev{T, S, val, lam, mu, rowv, L.roww, L.rowt, ix, lane, red};
 
   // y = M r: the handle's metric (k_tape_wave's four-chain column loop for r = H0 q), else the identity.  r is spread over the threads: complete before
   // anyone reads all of it; y[k] is written by its owner.
@@ -1067,16 +767,8 @@ __global__ __launch_bounds__(NT) void k_tape_wave_newton(TapeParams T, WaveSched
   for (;;) {
     const bool prod = why == EV_HVP;
     double v_ = 0.0, f_ = 0.0, c_ = 0.0, m_ = 0.0;
-#ifdef OH_TAPE_NEWTON_WAVE_ONE_SITE
-    // variant (b) of DESIGN 2.6, kept buildable for the measurement: the four-column sweep is the ONLY site, an evaluation is a product with a zero tangent
-    if (!prod)
-      for (int k = lane; k < n; k += NT) PV[k] = 0.0;  // (free between two CG runs, as HP is)
-    v_ = sw.template hvp<true>(prod ? X : xs, PV, prod ? nullptr : gout, HP, rho, rowv, &red, &f_, &c_, &m_);
-    (void)ev;
-#else
-    if (prod) sw.hvp(X, PV, nullptr, HP, rho);
+    if (prod) ev.hvp(X, PV, HP, rho);
     else v_ = ev.phi(xs, gout, rho, &f_, &c_, &m_);
-#endif
     if (prod) {
       ++hvps;
       double pk_ = 0.0, pp_ = 0.0;
@@ -1250,7 +942,7 @@ __global__ __launch_bounds__(NT) void k_tape_wave_newton(TapeParams T, WaveSched
 }
 
 // The products oh_tape_phi_hvp grades (options tape_newton + tape_newton_wave): ONE BLOCK PER UNIT u = b nv + d, the work set of k_tape_wave_newton, one
-// WaveSweep::hvp at (x_b, V_u) under the given multipliers and penalty.  The sweep's gradient is left where oh_tape_phi_hvp's evaluation (k_tape_wave_phi,
+// WaveEval::hvp at (x_b, V_u) under the given multipliers and penalty.  The sweep's gradient is left where oh_tape_phi_hvp's evaluation (k_tape_wave_phi,
 // launched before this kernel) has already written the same bits.
 template <int NT, bool REG_LDS>
 __global__ __launch_bounds__(NT) void k_tape_wave_merit_hvp(TapeParams T, WaveSchedDev S, int nv, const double* __restrict__ x, const double* __restrict__ par,
@@ -1261,19 +953,15 @@ __global__ __launch_bounds__(NT) void k_tape_wave_merit_hvp(TapeParams T, WaveSc
   const size_t u = blockIdx.x, inst = u / (size_t)nv;
   const int n = T.nx, ni = T.n_ineq, ne = T.n_eq;
   const NewtonLds L = newton_carve<REG_LDS>(T, S, lds, REG_LDS ? nullptr : regs_g + u * 4 * S.n_reg);
-  int* small = L.small;
-  for (int k = lane; k < S.n_small; k += NT) small[k] = S.small[k];
-  const int* row_reg = small;
-  const int* seed_reg = row_reg + S.nrows;
-  const int* seed_off = seed_reg + S.n_seed;
-  const int* seed_rows = seed_off + S.n_seed + 1;
-  newton_setup_registers<NT>(S, L.val, par + inst * T.np, lane);
+  const WaveIndex ix = wave_load_index<NT>(S, L.small, lane);
+  wave_setup_registers<NT, 4>(S, L.val, par + inst * T.np, lane);
   for (int k = lane; k < n; k += NT) { L.X[k] = x[inst * n + k]; L.PV[k] = V[u * n + k]; }
   for (int i = lane; i < ni; i += NT) L.lam[i] = lam_in[inst * ni + i];
   for (int i = lane; i < ne; i += NT) L.mu[i] = mu_in[inst * ne + i];
   __syncthreads();
-  WaveSweep<NT, REG_LDS> sw{T, S, L.val, L.lam, L.mu, L.roww, L.rowt, row_reg, seed_reg, seed_off, seed_rows, lane};
-  sw.hvp(L.X, L.PV, nullptr, L.HP, rho);
+  Red<NT> red{L.redbuf};
+  WaveEval<NT, REG_LDS> ev{T, S, L.val, L.lam, L.mu, L.rowv, L.roww, L.rowt, ix, lane, red};
+  ev.hvp(L.X, L.PV, L.HP, rho);
   for (int k = lane; k < n; k += NT) HV[u * n + k] = L.HP[k];
 }
 
@@ -1284,6 +972,39 @@ int upload(V** dst, const std::vector<V>& src) {
   if (hipMalloc((void**)dst, bytes) != hipSuccess) return 1;
   if (!src.empty() && hipMemcpy(*dst, src.data(), sizeof(V) * src.size(), hipMemcpyHostToDevice) != hipSuccess) return 1;
   return 0;
+}
+
+WaveSchedDev wave_sched_dev(const TapeWave& W, const TapeParams& T) {
+  return WaveSchedDev{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
+                      T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+}
+
+// The three builds of every kernel: four wavefronts with the registers in global memory, one or four with the registers in LDS.  f(NT, REG_LDS) gets the pair
+// as two std::integral_constant.
+template <class F>
+hipError_t wave_dispatch(const int nt, const bool reg_lds, F f) {
+  if (!reg_lds) return f(std::integral_constant<int, 256>{}, std::false_type{});
+  if (nt == 64) return f(std::integral_constant<int, 64>{}, std::true_type{});
+  return f(std::integral_constant<int, 256>{}, std::true_type{});
+}
+// one launch with its dynamic LDS allowed first (the attribute is per kernel, the bytes change with the handle)
+template <class... P, class... A>
+hipError_t wave_launch(void (*kernel)(P...), const int nt, const size_t grid, const size_t bytes, hipStream_t s, A... args) {
+  if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nt), bytes, s, args...);
+  return hipGetLastError();
+}
+
+// Placement of a kernel's four columns given the LDS it needs with them and without: 0 the schedule cannot run it (not ready; NT = 64 and the work set does
+// not fit: the global placement is built for four wavefronts, as the solver's), 1 LDS, 2 global memory.  Option tape_wave_regs forces one where both are
+// possible; without it: LDS whenever the work set fits.
+int wave_place_columns(const TapeWave& W, const size_t lds_bytes, const size_t global_bytes) {
+  if (!W.ready) return 0;
+  const bool lds_ok = lds_bytes <= W.lds_limit, global_ok = W.nt == 256 && global_bytes <= W.lds_limit;
+  if (!lds_ok && !global_ok) return 0;
+  if (!global_ok) return 1;
+  if (!lds_ok) return 2;
+  return W.reg_choice == 0 ? 2 : 1;
 }
 
 }  // namespace
@@ -1495,11 +1216,11 @@ int oh_tape_wave_build(const TapeParams& T, const int* op, const int* a, const i
   }
   for (int rl = 0; rl < 2; ++rl) {
     if ((rl == 1 && !out->reg_lds_fits) || (rl == 0 && !global_ok)) continue;
-    const bool hl = out->hist_lds_by[rl];
-    const void* fn = rl == 0     ? (hl ? reinterpret_cast<const void*>(k_tape_wave<256, true, false>) : reinterpret_cast<const void*>(k_tape_wave<256, false, false>))
-                     : NT == 64  ? (hl ? reinterpret_cast<const void*>(k_tape_wave<64, true, true>) : reinterpret_cast<const void*>(k_tape_wave<64, false, true>))
-                                 : (hl ? reinterpret_cast<const void*>(k_tape_wave<256, true, true>) : reinterpret_cast<const void*>(k_tape_wave<256, false, true>));
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)out->lds_bytes_by[rl]) != hipSuccess) {
+    const hipError_t e = wave_dispatch(NT, rl == 1, [&](auto nt, auto r) {
+      const void* fn = out->hist_lds_by[rl] ? reinterpret_cast<const void*>(k_tape_wave<nt.value, true, r.value>) : reinterpret_cast<const void*>(k_tape_wave<nt.value, false, r.value>);
+      return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)out->lds_bytes_by[rl]);
+    });
+    if (e != hipSuccess) {
       (void)hipGetLastError();
       oh_tape_wave_release(out);
       return 0;
@@ -1535,8 +1256,7 @@ static hipError_t wave_place_registers(TapeWave& W, const int B) {
 
 hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x0, const double* p, double* x, double* f, double* kkt,
                                int* iters, int* status, double* mult) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
+  const WaveSchedDev S = wave_sched_dev(W, T);
   if (const hipError_t e = wave_place_registers(W, B)) return e;
   if (!W.hist_lds && B > W.hist_cap) {
     if (W.d_hist) hipFree(W.d_hist);
@@ -1548,32 +1268,24 @@ hipError_t oh_launch_tape_wave(hipStream_t s, TapeWave& W, const TapeParams& T, 
   }
   double* hg = W.hist_lds ? nullptr : W.d_hist;
   double* rg = W.reg_lds ? nullptr : W.d_regs;
-#define OH_TW_LAUNCH(NTv, Hv, Rv) hipLaunchKernelGGL((k_tape_wave<NTv, Hv, Rv>), dim3(B), dim3(NTv), W.lds_bytes, s, T, S, B, x0, p, hg, rg, x, f, kkt, iters, status, mult)
-  if (!W.reg_lds) { if (W.hist_lds) OH_TW_LAUNCH(256, true, false); else OH_TW_LAUNCH(256, false, false); }
-  else if (W.nt == 64) { if (W.hist_lds) OH_TW_LAUNCH(64, true, true); else OH_TW_LAUNCH(64, false, true); }
-  else { if (W.hist_lds) OH_TW_LAUNCH(256, true, true); else OH_TW_LAUNCH(256, false, true); }
-#undef OH_TW_LAUNCH
-  return hipGetLastError();
+  // (the dynamic LDS of these six was allowed when the schedule was built)
+  return wave_dispatch(W.nt, W.reg_lds, [&](auto nt, auto rl) {
+    auto go = [&](auto hl) {
+      hipLaunchKernelGGL((k_tape_wave<nt.value, hl.value, rl.value>), dim3(B), dim3(nt.value), W.lds_bytes, s, T, S, B, x0, p, hg, rg, x, f, kkt, iters, status, mult);
+      return hipGetLastError();
+    };
+    return W.hist_lds ? go(std::true_type{}) : go(std::false_type{});
+  });
 }
 
 hipError_t oh_launch_tape_wave_phi(hipStream_t s, TapeWave& W, const TapeParams& T, int B, const double* x, const double* p, const double* lam, const double* mu,
                                    double rho, double* merit, double* f, double* rowv, double* grad, double* cmax, double* meas) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
   if (const hipError_t e = wave_place_registers(W, B)) return e;
   const size_t bytes = oh_tape_wave_lds_bytes(T, W, false, W.reg_lds);  // the solve kernel's layout without the quasi-Newton pairs
   double* rg = W.reg_lds ? nullptr : W.d_regs;
-#define OH_TW_PHI(NTv, Rv)                                                                                                                       \
-  do {                                                                                                                                            \
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_phi<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
-    if (e != hipSuccess) return e;                                                                                                                \
-    hipLaunchKernelGGL((k_tape_wave_phi<NTv, Rv>), dim3(B), dim3(NTv), bytes, s, T, S, B, x, p, lam, mu, rho, rg, merit, f, rowv, grad, cmax, meas);      \
-  } while (0)
-  if (!W.reg_lds) OH_TW_PHI(256, false);
-  else if (W.nt == 64) OH_TW_PHI(64, true);
-  else OH_TW_PHI(256, true);
-#undef OH_TW_PHI
-  return hipGetLastError();
+  return wave_dispatch(W.nt, W.reg_lds, [&](auto nt, auto rl) {
+    return wave_launch(k_tape_wave_phi<nt.value, rl.value>, nt.value, B, bytes, s, T, wave_sched_dev(W, T), B, x, p, lam, mu, rho, rg, merit, f, rowv, grad, cmax, meas);
+  });
 }
 
 // ---- k_tape_wave_hvp: [val | adj | tan | dadj] and the small index arrays; in the global placement the LDS holds the index arrays only
@@ -1581,37 +1293,17 @@ size_t oh_tape_wave_hvp_lds_bytes(const TapeWave& W, bool reg_lds) {
   return (reg_lds ? 4 * (size_t)W.n_reg * sizeof(double) : 0) + sizeof(int) * (((size_t)W.n_small + 1) & ~(size_t)1);
 }
 
-// Placement of the four columns of k_tape_wave_hvp: 0 the schedule cannot run the product (not ready; NT = 64 and the columns do not fit), 1 LDS,
-// 2 global memory.  Option tape_wave_regs forces one where both are possible.  The rule without it: LDS whenever the columns fit, at every unit
-// count -- unlike the solver (wave_place_registers: global memory from 512 instances on), whose blocks live for thousands of evaluations; a unit
-// is two sweeps, and what global memory buys in resident blocks per CU it pays in every pass (dense Hessians, device time, LDS / global:
-// the planner as written, 71 680 units, 7.15 / 14.8 ms; the 65-variable shape tape, 266 240 units, 6.04 / 9.86 ms; profiles/tape_hvp_wave_rates.json).
-int oh_tape_wave_hvp_place(const TapeWave& W) {
-  if (!W.ready) return 0;
-  const bool lds_ok = oh_tape_wave_hvp_lds_bytes(W, true) <= W.lds_limit;
-  const bool global_ok = W.nt == 256 && oh_tape_wave_hvp_lds_bytes(W, false) <= W.lds_limit;  // (the global placement is built for four wavefronts, as the solver's)
-  if (!lds_ok && !global_ok) return 0;
-  if (!global_ok) return 1;
-  if (!lds_ok) return 2;
-  return W.reg_choice == 0 ? 2 : 1;
-}
+// wave_place_columns for k_tape_wave_hvp: LDS whenever the columns fit, at every unit count -- unlike the solver (wave_place_registers: global memory from
+// 512 instances on), whose blocks live for thousands of evaluations; a unit is two sweeps, and what global memory buys in resident blocks per CU it pays in
+// every pass (dense Hessians, device time, LDS / global: the planner as written, 71 680 units, 7.15 / 14.8 ms; the 65-variable shape tape, 266 240 units,
+// 6.04 / 9.86 ms; profiles/tape_hvp_wave_rates.json).
+int oh_tape_wave_hvp_place(const TapeWave& W) { return wave_place_columns(W, oh_tape_wave_hvp_lds_bytes(W, true), oh_tape_wave_hvp_lds_bytes(W, false)); }
 
 hipError_t oh_launch_tape_wave_hvp(hipStream_t s, const TapeWave& W, const TapeParams& T, bool reg_lds, int u0, int n, int nv, const double* x, const double* p,
                                    const double* seeds, const double* V, double* regs, double* HV, double* grad) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
-  const size_t bytes = oh_tape_wave_hvp_lds_bytes(W, reg_lds);
-#define OH_TW_HVP(NTv, Rv)                                                                                                                        \
-  do {                                                                                                                                            \
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_hvp<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
-    if (e != hipSuccess) return e;                                                                                                                \
-    hipLaunchKernelGGL((k_tape_wave_hvp<NTv, Rv>), dim3(n), dim3(NTv), bytes, s, T, S, u0, nv, x, p, seeds, V, regs, HV, grad);                         \
-  } while (0)
-  if (!reg_lds) OH_TW_HVP(256, false);
-  else if (W.nt == 64) OH_TW_HVP(64, true);
-  else OH_TW_HVP(256, true);
-#undef OH_TW_HVP
-  return hipGetLastError();
+  return wave_dispatch(W.nt, reg_lds, [&](auto nt, auto rl) {
+    return wave_launch(k_tape_wave_hvp<nt.value, rl.value>, nt.value, n, oh_tape_wave_hvp_lds_bytes(W, reg_lds), s, T, wave_sched_dev(W, T), u0, nv, x, p, seeds, V, regs, HV, grad);
+  });
 }
 
 // ---- k_tape_wave_newton, k_tape_wave_merit_hvp: the layout of newton_carve
@@ -1621,20 +1313,12 @@ size_t oh_tape_wave_newton_lds_bytes(const TapeParams& T, const TapeWave& W, boo
   return d * sizeof(double) + sizeof(int) * (((size_t)W.n_small + 1) & ~(size_t)1);
 }
 
-// Placement of the four columns of the Newton kernels: 0 the schedule cannot run them (not ready; NT = 64 and the work
-// set does not fit), 1 LDS, 2 a slice per block of the global register buffer.  Option tape_wave_regs forces one where both are possible.  Without it:
-// LDS whenever the work set fits, at every batch size -- NOT the quasi-Newton solver's rule (wave_place_registers: global memory beyond 512 instances).
-// That rule buys resident blocks per CU with the LDS it frees; k_tape_wave_newton holds 256 VGPRs and 44 AGPRs, one wavefront per SIMD, so a CU
-// runs one block of four wavefronts wherever the registers are, and global memory only costs in every pass.  Eliminated planner, device ms,
-// LDS / global: B = 256 7.62 / 10.69, B = 4096 105.2 / 149.5 (profiles/tape_newton_wave_rates.json).
+// wave_place_columns for the Newton kernels (2: a slice per block of the global register buffer): LDS whenever the work set fits, at every batch size -- NOT
+// the quasi-Newton solver's rule (wave_place_registers: global memory beyond 512 instances).  That rule buys resident blocks per CU with the LDS it frees;
+// k_tape_wave_newton holds 256 VGPRs and 44 AGPRs, one wavefront per SIMD, so a CU runs one block of four wavefronts wherever the registers are, and global
+// memory only costs in every pass.  Eliminated planner, device ms, LDS / global: B = 256 7.62 / 10.69, B = 4096 105.2 / 149.5 (profiles/tape_newton_wave_rates.json).
 int oh_tape_wave_newton_place(const TapeWave& W, const TapeParams& T) {
-  if (!W.ready) return 0;
-  const bool lds_ok = oh_tape_wave_newton_lds_bytes(T, W, true) <= W.lds_limit;
-  const bool global_ok = W.nt == 256 && oh_tape_wave_newton_lds_bytes(T, W, false) <= W.lds_limit;
-  if (!lds_ok && !global_ok) return 0;
-  if (!global_ok) return 1;
-  if (!lds_ok) return 2;
-  return W.reg_choice == 0 ? 2 : 1;
+  return wave_place_columns(W, oh_tape_wave_newton_lds_bytes(T, W, true), oh_tape_wave_newton_lds_bytes(T, W, false));
 }
 
 // the global register buffer, counted in slices of 2 n_reg doubles (what wave_place_registers allocates per instance): a block of the Newton kernels takes two
@@ -1652,32 +1336,20 @@ static hipError_t wave_grow_registers(TapeWave& W, const size_t slices) {
 
 hipError_t oh_launch_tape_wave_newton(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int cg_cap, const double* x0, const double* p, double* x,
                                       double* f, double* kkt, int* iters, int* status, double* mult, int* stats) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
   const bool reg_lds = place == 1;
   if (!reg_lds)
     if (const hipError_t e = wave_grow_registers(W, 2 * (size_t)B)) return e;
-  const size_t bytes = oh_tape_wave_newton_lds_bytes(T, W, reg_lds);
   double* rg = reg_lds ? nullptr : W.d_regs;
-#define OH_TW_NEWTON(NTv, Rv)                                                                                                                       \
-  do {                                                                                                                                              \
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_newton<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
-    if (e != hipSuccess) return e;                                                                                                                  \
-    hipLaunchKernelGGL((k_tape_wave_newton<NTv, Rv>), dim3(B), dim3(NTv), bytes, s, T, S, B, cg_cap, x0, p, rg, x, f, kkt, iters, status, mult, stats);         \
-  } while (0)
-  if (!reg_lds) OH_TW_NEWTON(256, false);
-  else if (W.nt == 64) OH_TW_NEWTON(64, true);
-  else OH_TW_NEWTON(256, true);
-#undef OH_TW_NEWTON
-  return hipGetLastError();
+  return wave_dispatch(W.nt, reg_lds, [&](auto nt, auto rl) {
+    return wave_launch(k_tape_wave_newton<nt.value, rl.value>, nt.value, B, oh_tape_wave_newton_lds_bytes(T, W, reg_lds), s, T, wave_sched_dev(W, T), B, cg_cap, x0, p, rg, x, f,
+                       kkt, iters, status, mult, stats);
+  });
 }
 
 // one k_tape_wave_phi over the B instances (grad: the evaluation's gradient; the other outputs go to scratch [4 B + max(nrows, 1) B]), then one block per
 // (instance, direction) of k_tape_wave_merit_hvp
 hipError_t oh_launch_tape_wave_phi_hvp(hipStream_t s, TapeWave& W, const TapeParams& T, int place, int B, int nv, const double* x, const double* p, const double* lam,
                                        const double* mu, double rho, const double* V, double* HV, double* grad, double* scratch) {
-  WaveSchedDev S{W.d_fw, W.d_rv, W.d_cons, W.d_cst_reg, W.d_cst_val, W.d_par_reg, W.d_par_k, W.d_small, W.n_fw_pass, W.n_rv_pass, W.n_cst, W.n_par, W.n_reg,
-                 T.n_ineq + T.n_eq, W.n_seed, W.n_seed_rows, W.seed_cost, W.n_small};
   const bool reg_lds = place == 1;
   const size_t U = (size_t)B * nv;
   // (before the evaluation is launched: its own placement may read the same buffer, which must not be reallocated under it)
@@ -1685,44 +1357,27 @@ hipError_t oh_launch_tape_wave_phi_hvp(hipStream_t s, TapeWave& W, const TapePar
     if (const hipError_t e = wave_grow_registers(W, 2 * U)) return e;
   double* sc = scratch;
   if (const hipError_t e = oh_launch_tape_wave_phi(s, W, T, B, x, p, lam, mu, rho, sc, sc + B, sc + 4 * (size_t)B, grad, sc + 2 * (size_t)B, sc + 3 * (size_t)B)) return e;
-  const size_t bytes = oh_tape_wave_newton_lds_bytes(T, W, reg_lds);
   double* rg = reg_lds ? nullptr : W.d_regs;
-#define OH_TW_MHVP(NTv, Rv)                                                                                                                            \
-  do {                                                                                                                                                 \
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_wave_merit_hvp<NTv, Rv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
-    if (e != hipSuccess) return e;                                                                                                                     \
-    hipLaunchKernelGGL((k_tape_wave_merit_hvp<NTv, Rv>), dim3((unsigned)U), dim3(NTv), bytes, s, T, S, nv, x, p, lam, mu, rho, V, rg, HV);                         \
-  } while (0)
-  if (!reg_lds) OH_TW_MHVP(256, false);
-  else if (W.nt == 64) OH_TW_MHVP(64, true);
-  else OH_TW_MHVP(256, true);
-#undef OH_TW_MHVP
-  return hipGetLastError();
+  return wave_dispatch(W.nt, reg_lds, [&](auto nt, auto rl) {
+    return wave_launch(k_tape_wave_merit_hvp<nt.value, rl.value>, nt.value, U, oh_tape_wave_newton_lds_bytes(T, W, reg_lds), s, T, wave_sched_dev(W, T), nv, x, p, lam, mu, rho, V,
+                       rg, HV);
+  });
 }
 
 // code-object facts of the product kernel and of the Newton-CG solve kernel: four wavefronts, the columns in LDS at the largest register file the device's LDS takes
 bool oh_kernel_info_tape_wave(const char* name, OhKernelInfo* out) {
-  if (std::string(name) == "k_tape_wave_newton") {
-    int dev = 0, lds_limit = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
-    const void* fn = reinterpret_cast<const void*>(k_tape_wave_newton<256, true>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess) { (void)hipGetLastError(); return false; }
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, fn) != hipSuccess) return false;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tape_wave_newton<256, true>, 256, (size_t)lds_limit) != hipSuccess) nb = 0;
-    *out = OhKernelInfo{a.numRegs, (int)a.localSizeBytes, (int)(a.sharedSizeBytes + lds_limit), 256, nb};
-    return true;
-  }
-  if (std::string(name) != "k_tape_wave_hvp") return false;
+  const void* fn = std::string(name) == "k_tape_wave_newton" ? reinterpret_cast<const void*>(k_tape_wave_newton<256, true>)
+                   : std::string(name) == "k_tape_wave_hvp"  ? reinterpret_cast<const void*>(k_tape_wave_hvp<256, true>)
+                                                             : nullptr;
+  if (!fn) return false;
   int dev = 0, lds_limit = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
-  const void* fn = reinterpret_cast<const void*>(k_tape_wave_hvp<256, true>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess) { (void)hipGetLastError(); return false; }
   hipFuncAttributes a;
   if (hipFuncGetAttributes(&a, fn) != hipSuccess) return false;
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tape_wave_hvp<256, true>, 256, (size_t)lds_limit) != hipSuccess) nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, (size_t)lds_limit) != hipSuccess) nb = 0;
   *out = OhKernelInfo{a.numRegs, (int)a.localSizeBytes, (int)(a.sharedSizeBytes + lds_limit), 256, nb};
   return true;
 }
+

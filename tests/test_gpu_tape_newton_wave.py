@@ -1,4 +1,4 @@
-"""Truncated Newton-CG on the wavefront evaluator (options tape_newton + tape_newton_wave; optas_amd/csrc/oh_tape_wave.hip: WaveSweep::hvp, k_tape_wave_newton,
+"""Truncated Newton-CG on the wavefront evaluator (options tape_newton + tape_newton_wave; optas_amd/csrc/oh_tape_wave.hip: WaveEval::hvp, k_tape_wave_newton,
 k_tape_wave_merit_hvp): one block per instance runs the state machine of oh_tape_newton.h on the handle's level schedule, every CG iteration one self-contained
 forward-over-reverse sweep of the merit with seed tangents; oh_tape_phi_hvp on such a handle runs that sweep, one block per (instance, direction).
 

@@ -6,10 +6,18 @@ selects the other one) after a change that must not alter either.  One process p
                    (tests/test_gpu_tape_evaluators.py's handles); oh_tape_hvp with its gradient and the dense Hessian on tape_hvp_ref's composite
                    cases; oh_tape_probe's values, adjoints and gradient on the opcode table; solves of the 7-joint IK goldens with and without
                    generated code; a QP handle fed by an opcode-rich tape (cost |x|^2 / 2 + sum_j op_j(p_2j, p_2j+1) x_(j mod n), rows x_i + 2 >= 0)
-                   at n = 2 (B = 32: a lane per probe, B = 256: a lane per instance) and n = 40 (block assembly): x, f, multipliers.
+                   at n = 2 (B = 32: a lane per probe, B = 256: a lane per instance) and n = 40 (block assembly): x, f, multipliers;
+                   the wavefront evaluator's sweeps (tests/test_gpu_tape_wave_bits.py:wave_outputs) on the opcode table, every composite case, a tape
+                   with a row of each kind and one without rows, at one wavefront and at four, registers in LDS and in global memory: oh_tape_phi,
+                   oh_tape_hvp with tape_hvp_wave (given V and the unit directions, with the gradient), oh_tape_phi_hvp with tape_newton_wave; one
+                   Newton-CG solve on the wavefront evaluator (nx65, B = 32): x, f, kkt, multipliers, counts, oh_tape_newton_stats.
+  pin OUT.npz      the part of `dump` that tests/test_gpu_tape_wave_bits.py compares against (tests/golden/tape_wave_parent_bits.npz).
   time OUT.json N  N device times (ms, the handle's event timer, after one warm-up call) of: the 7-joint IK tape at B = 65 536 on the interpreter and
                    on generated code; the perturbed planner batches B = 256 and 1024 of tools/gpu_tape_rates.py (wavefront evaluator); both points
-                   of tools/gpu_tape_hvp_rates.py at the default budget; the dense_qp leg of tools/gpu_qp_rates.py (72 variables, B = 256).
+                   of tools/gpu_tape_hvp_rates.py at the default budget; the dense_qp leg of tools/gpu_qp_rates.py (72 variables, B = 256); the
+                   planner's dense Hessian on the wavefront evaluator (tools/gpu_tape_hvp_wave_rates.py: planner, default placement); the Newton-CG
+                   solve of the eliminated planner on it at B = 256 (tools/gpu_tape_newton_wave_rates.py); one oh_tape_phi of the eliminated planner
+                   at B = 1024 (no event timer in that call: the host clock around it, copies included).
   report PARENT.npz NEW.npz OUT.json TIMES...   arrays compared byte for byte; per point the new library's median against the parent's maximum
                    (TIMES: the json files of `time`, told apart by their "library" entry).  Exit status 1 if an array differs or a point is slower.
 """
@@ -65,6 +73,7 @@ def dump(path):
     env, out = Env(), {}
 
     def put(prefix, d):
+        print(prefix, len(d), flush=True)
         for k, v in d.items():
             out[prefix + "/" + k] = np.asarray(v)
 
@@ -113,12 +122,41 @@ def dump(path):
         r = be.solve(np.zeros((B, n)), pv)
         put("qp/n%d_B%d" % (n, B), {"x": r.x, "f": r.f, "iters": r.iters, "status": r.status, "lam": be.multipliers(B)[0], "block": be.flag("qp_block")})
         be.close()
+    import test_gpu_tape_wave_bits as wb
+
+    cases = wb.pin_cases(composites=[c[0] for c in R.composite_cases()])
+    tp = shapes["rows_none"]
+    cases.setdefault("rows_none", wb._batch("rows_none", tp, *tc.shape_point(tp, 11)[:2], 3))
+    put("wave", wb.wave_outputs(env, cases, tuple(wb.WAVE_OPTS), dense_max_nx=1 << 30))
+    tp = shapes["nx65"]
+    x, p = tc.shape_point(tp, 11)[:2]
+    rng = np.random.default_rng(65)
+    x0 = x[None] * rng.uniform(0.9, 1.1, (32, 1)) + rng.uniform(-0.01, 0.01, (32, int(tp.nx)))
+    be = TapeBackend(tp, jit=False, wave=True, max_iter=600, options={"tape_newton": 1, "tape_newton_wave": 1})
+    r = be.solve(x0, np.tile(p, (32, 1)))
+    steps, hvps = be.newton_stats(32)
+    la, m_ = be.multipliers(32)
+    put("solve/newton_wave_nx65", {"x": r.x, "f": r.f, "iters": r.iters, "status": r.status, "kkt": r.kkt, "lam": la, "mu": m_, "steps": steps, "products": hvps,
+                                   "path": be.flag("tape_newton_path")})
+    be.close()
     np.savez(path, **out)
     print("dumped", len(out), "arrays to", path)
 
 
+def pin(path):
+    import test_gpu_tape_wave_bits as wb
+
+    out = wb.wave_outputs(Env(), wb.pin_cases(), wb.PIN_VARIANTS)
+    np.savez_compressed(path, **out)
+    print("pinned", len(out), "arrays to", path)
+
+
 def time_points(path, reps):
+    import time
+
     import gpu_tape_hvp_rates as hv
+    import gpu_tape_hvp_wave_rates as hvw
+    import gpu_tape_newton_wave_rates as nw
     import qp_planted_large as L
     from examples.simple_joint_space_planner import setup_solver as planner_setup
     from optas_amd.backend import TapeBackend
@@ -174,6 +212,32 @@ def time_points(path, reps):
     s = HIPSolver(o).setup("hip_sqp", {"dense_qp": True})
     run("qp_dense_mpc_b256", lambda: s.solve_batch_arrays(x0, pv), s.backend.solve_ms)
     s.backend.close()
+    tp, B, x, p, seeds = hvw._workload("planner")
+    be = TapeBackend(tp, jit=False, wave=True, metric=False)
+    be.set_option("tape_hvp_wave", 1)
+    run("hvp_wave_planner", lambda: be.hessian(x, p, seeds), be.solve_ms)
+    assert be.flag("tape_hvp_path") >= 1
+    be.close()
+    make, x0, p = nw._planner(256, True)
+    be = make(nw.WAVE)
+    run("newton_wave_planner_b256", lambda: be.solve(x0, p), be.solve_ms)
+    assert be.flag("tape_newton_path") >= 1
+    be.close()
+    make, x0, p = nw._planner(1024, True)
+    be = make(None)
+    inner = be.inner
+    xi = np.random.default_rng(1024).uniform(-0.1, 0.1, (1024, inner.nx))
+    lam, mu = np.zeros((1024, int(inner.tape.n_ineq))), np.zeros((1024, int(inner.tape.n_eq)))
+    wall = [0.0]
+
+    def phi_call():
+        t0 = time.perf_counter()
+        inner.phi(xi, p, lam, mu, 10.0)
+        wall[0] = 1e3 * (time.perf_counter() - t0)
+
+    run("planner_phi_b1024_wall", phi_call, lambda: wall[0])
+    assert inner.flag("tape_wave") >= 1
+    be.close()
     with open(path, "w") as f:
         json.dump({"library": os.environ.get("OPTAS_HIP_LIBRARY", "in-tree"), "points_ms": pts}, f, indent=1)
 
@@ -205,6 +269,8 @@ def report(parent, new, path, times):
 if __name__ == "__main__":
     if sys.argv[1] == "dump":
         dump(sys.argv[2])
+    elif sys.argv[1] == "pin":
+        pin(sys.argv[2])
     elif sys.argv[1] == "time":
         time_points(sys.argv[2], int(sys.argv[3]))
     else:
