@@ -34,7 +34,8 @@ extern "C" {
    7: round 6 -- OH_MAX_T 256, oh_comm_allgather, options tol / pipe / pipe_chunk, OH_STATUS_INFEASIBLE from the point-mass iteration, oh_solve in chunks on two lanes.
    8: oh_tape_phi.  Still 8: oh_ik_desc.orientation (full-pose goal of OH_PROBLEM_IK) sits in what was four bytes of padding after max_iter, so
       the size of the struct and the offset of every other member are as they were, and a zero-initialised descriptor of an older caller reads as
-      orientation = 0; flag "ik_orientation". */
+      orientation = 0; flag "ik_orientation".  Still 8: oh_ik_set_axis_goal (position goal plus a link-axis goal) is one symbol added; no struct changes,
+      oh_ik_desc is as it was; flag "ik_goal". */
 #define OH_ABI_VERSION 8
 
 #define OH_MAX_CHAIN 16 /* actuated joints on one root->link chain */
@@ -429,6 +430,15 @@ int oh_create_torque(const oh_torque_desc* desc, oh_handle** out);
 
 /* Same for OH_PROBLEM_IK; needs oh_set_constants before the first solve. */
 int oh_create_ik(const oh_ik_desc* desc, oh_handle** out);
+/* Adds a goal for one axis of the link frame to an OH_PROBLEM_IK handle created with orientation = 0 (a 5-DoF task: "tool tip here, tool z pointing
+   there"; the reference's z = T[:3, 2] rows, example/sphere_collision_avoidance.py:20-43, get_global_link_axis): with u(q) = R_link(q) a and
+   a = axis_link / |axis_link| (the library normalises it, like models.py:1659),
+       h = [p_goal - p_link(q); u_goal - u(q)]  (six rows),  p = [q_nominal(ndof); p_goal(3); u_goal(3)]  (np = ndof + 6),
+   multiplier rows [mu of h (6); z_lo (ndof); z_up (ndof)], tol_feas over all six rows.  u_goal is taken literally, like quat_goal: a goal that is not of
+   unit length is infeasible as posed and the solve ends with a non-zero status.  Before the handle's first solve only (OH_ERR_STATE afterwards);
+   OH_ERR_INVALID on a handle with a full-pose goal or of another family, and for a null, zero or non-finite axis.  oh_get_flag "ik_goal": 0 position,
+   1 full pose, 2 position and axis ("ik_orientation" stays 0 on an axis handle). */
+int oh_ik_set_axis_goal(oh_handle* h, const double axis_link[3]);
 
 /* Kinematic constants from host memory / from device memory (the latter after an RCCL broadcast). */
 int oh_set_constants(oh_handle* h, const oh_chain* chain);
@@ -563,7 +573,8 @@ int oh_tq_rollout(oh_handle* h, int B, int n_ticks, int advance, double mu_warm,
    a failed call, OH_ERR_STATE.  In the reference's form: lam_h [B][4*T] for the rows
    h = quat_c - quat(q_t) (signed mu = lam+ - lam- of the (h,-h) pair, optimization.py:47-51). Host buffer.
    OH_PROBLEM_IK: lam_h [B][3 + 2*ndof] = (mu of h = p_goal - p_link(q) (3), multipliers of q - lo >= 0 (ndof),
-   multipliers of up - q >= 0 (ndof)); with oh_ik_desc.orientation [B][7 + 2*ndof]: mu of [p_goal - p_link(q); quat_goal - quat_link(q)] (7) first.
+   multipliers of up - q >= 0 (ndof)); with oh_ik_desc.orientation [B][7 + 2*ndof]: mu of [p_goal - p_link(q); quat_goal - quat_link(q)] (7) first;
+   after oh_ik_set_axis_goal [B][6 + 2*ndof]: mu of [p_goal - p_link(q); u_goal - u(q)] (6) first.
    Handles with oh_set_guards: lam_h [B][T][NC], NC = 2 ndof limits + n_links n_obstacles + 2 ndof velocity limits, row order
    of oh_guards (multipliers >= 0 of the g >= 0 rows; knots t < t0 carry zeros). */
 int oh_get_multipliers(oh_handle* h, int B, double* lam_h);

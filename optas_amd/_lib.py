@@ -217,6 +217,7 @@ SYMBOLS = [
     "oh_create",
     "oh_create_pointmass",
     "oh_create_ik",
+    "oh_ik_set_axis_goal",
     "oh_create_qp",
     "oh_qp_set_tape",
     "oh_create_tape",
@@ -314,6 +315,7 @@ def load() -> C.CDLL:
     lib.oh_create.argtypes = [C.POINTER(oh_problem_desc), C.POINTER(vp)]
     lib.oh_create_pointmass.argtypes = [C.POINTER(oh_pointmass_desc), C.POINTER(vp)]
     lib.oh_create_ik.argtypes = [C.POINTER(oh_ik_desc), C.POINTER(vp)]
+    lib.oh_ik_set_axis_goal.argtypes = [vp, dp]
     lib.oh_create_qp.argtypes = [C.POINTER(oh_qp_desc), C.POINTER(vp)]
     lib.oh_create_tape.argtypes = [C.POINTER(oh_tape_desc), C.POINTER(vp)]
     lib.oh_qp_set_tape.argtypes = [vp, C.POINTER(oh_tape_desc)]

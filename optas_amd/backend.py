@@ -503,13 +503,19 @@ class QPBackend(_SolveMixin):
 
 class IKBackend(_SolveMixin):
     """OH_PROBLEM_IK handle (example/example.py): x = q, p = [q_nominal; p_goal].  orientation=True: the goal is a full pose, p = [q_nominal; p_goal;
-    quat_goal (xyzw, the sign taken literally: include/optas_hip.h)], seven equality rows (examples/pose_ik.py)."""
+    quat_goal (xyzw, the sign taken literally: include/optas_hip.h)], seven equality rows (examples/pose_ik.py).  axis ('x' / 'y' / 'z' or a 3-vector in
+    the link frame, normalised by the library): a position goal plus a goal for that link axis in the root frame, p = [q_nominal; p_goal; axis_goal
+    (taken literally)], six equality rows (oh_ik_set_axis_goal, examples/axis_ik.py)."""
 
-    def __init__(self, chain: _lib.oh_chain, lo, up, w_nominal=1.0, max_iter=200, tol=1e-6, tol_feas=1e-9, rho0=0.0, orientation=False):
+    def __init__(self, chain: _lib.oh_chain, lo, up, w_nominal=1.0, max_iter=200, tol=1e-6, tol_feas=1e-9, rho0=0.0, orientation=False, axis=None):
         lib = _lib.load()
         self.ndof = int(chain.ndof)
         self.orientation = bool(orientation)
-        self.nh = 7 if self.orientation else 3
+        if axis is not None and self.orientation:
+            raise ValueError("IKBackend: a full-pose goal and an axis goal exclude each other")
+        self.axis = None if axis is None else (np.eye(3)["xyz".index(axis)] if isinstance(axis, str) and axis in ("x", "y", "z")
+                                               else np.asarray(axis, dtype=np.float64).reshape(3))
+        self.nh = 6 if self.axis is not None else 7 if self.orientation else 3
         self.nx, self.np_ = self.ndof, self.ndof + self.nh
         desc = _lib.oh_ik_desc(ndof=self.ndof, w_nominal=float(w_nominal), max_iter=int(max_iter), tol=float(tol), tol_feas=float(tol_feas),
                                rho0=float(rho0), orientation=1 if self.orientation else 0)
@@ -520,17 +526,19 @@ class IKBackend(_SolveMixin):
         self._h = C.c_void_p()
         _lib.check(lib.oh_create_ik(C.byref(desc), C.byref(self._h)), "oh_create_ik")
         _lib.check(lib.oh_set_constants(self._h, C.byref(chain)), "oh_set_constants")
+        if self.axis is not None:
+            _lib.check(lib.oh_ik_set_axis_goal(self._h, (C.c_double * 3)(*self.axis)), "oh_ik_set_axis_goal")
         self.chain = chain
 
     def multipliers(self, B: int):
-        """(mu_h (B, 3 or 7), z_lo (B,ndof), z_up (B,ndof)) of the last solve, reference form."""
+        """(mu_h (B, 3, 7 or 6), z_lo (B,ndof), z_up (B,ndof)) of the last solve, reference form."""
         nh = self.nh
         out = np.empty((B, nh + 2 * self.ndof))
         _lib.check(_lib.load().oh_get_multipliers(self._h, int(B), _lib._ptr(out)), "oh_get_multipliers")
         return out[:, :nh], out[:, nh : nh + self.ndof], out[:, nh + self.ndof :]
 
     def flag(self, name: str) -> int:
-        """oh_get_flag: 'ik_orientation' (1: the handle solves the full-pose problem)."""
+        """oh_get_flag: 'ik_orientation' (1: the handle solves the full-pose problem), 'ik_goal' (0 position, 1 full pose, 2 position and link axis)."""
         v = C.c_int(0)
         _lib.check(_lib.load().oh_get_flag(self._h, name.encode(), C.byref(v)), "oh_get_flag")
         return int(v.value)

@@ -273,7 +273,7 @@ Shape shape_of(const oh_handle* h) {
     case OH_PROBLEM_TAPE: return {(size_t)tp.nx, (size_t)(tp.np > 0 ? tp.np : 1), (size_t)(tp.n_ineq + tp.n_eq)};
     case OH_PROBLEM_QP: return {(size_t)qp.n, h->qp.use_tape ? (size_t)(tp.np > 0 ? tp.np : 1) : qp_np(qp), (size_t)(qp.m + qp.me)};
     case OH_PROBLEM_POINT_MASS_MPC: return {4 * T, 4 + 4 * T, 0};
-    case OH_PROBLEM_IK: return {N, N + ik_rows(h->ik.desc), ik_rows(h->ik.desc) + 2 * N};
+    case OH_PROBLEM_IK: return {N, N + ik_rows(h->ik), ik_rows(h->ik) + 2 * N};
     case OH_PROBLEM_FIGURE_EIGHT: {
       const oh_guards& g = h->guards;
       const size_t nx = N * T + N * (T - 1);
@@ -1386,6 +1386,7 @@ extern "C" int oh_specialize_info(oh_handle* h, double* info4) {
 // pairs in global memory / in LDS), "tape_levels", "tape_passes" (dependency levels and 64-instruction passes of one evaluation), "tape_jit_lds" (1: the last
 // oh_tape_phi ran the generated code's entry with the work set in LDS), "tape_hvp_launches" (launches of the last oh_tape_hvp),
 // "tape_hvp_path" (what the last oh_tape_hvp ran: 0 interpreter lanes, 1 / 2 k_tape_wave_hvp with its registers in LDS / in global memory); QP handles: "qp_block" (1: the last solve ran the workgroup-per-instance kernel);
+// IK handles: "ik_orientation" (1: full-pose goal), "ik_goal" (0 position, 1 full pose, 2 position and link axis);
 // position-tracking handles: "free_sweep" (the FreeSweep the last solve started with, -1 before the first), "free_sweeps_used" (bit mask over its launches).
 extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   if (!h || !name || !value) return fail(OH_ERR_INVALID, "oh_get_flag: null argument");
@@ -1407,6 +1408,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;
   else if (n == "qp_block") *value = h->qp.last_block;
   else if (n == "ik_orientation") *value = (h->desc.kind == OH_PROBLEM_IK && h->ik.desc.orientation) ? 1 : 0;
+  else if (n == "ik_goal") *value = h->desc.kind != OH_PROBLEM_IK ? 0 : h->ik.axis_goal ? 2 : h->ik.desc.orientation ? 1 : 0;
   else if (n == "free_sweep") *value = h->free_sweep_last;
   else if (n == "free_sweeps_used") *value = h->free_sweeps_used;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);

@@ -153,9 +153,13 @@ struct QpState {
 struct IkState {
   oh_ik_desc desc{};
   DevBuf<double> mult;  // [B][ik_rows + 2 ndof]
+  bool axis_goal = false;  // oh_ik_set_axis_goal: position rows plus three rows on a link axis
+  double axis_link[3] = {0.0, 0.0, 0.0};  // that axis in the link frame, unit length
+  bool solved = false;  // a solve has been launched: the goal shape is fixed from then on
 };
-// equality rows of an IK handle: 3 (position goal) or 7 (full pose, oh_ik_desc.orientation); p rows are ndof + ik_rows wide, multiplier rows ik_rows + 2 ndof
-inline size_t ik_rows(const oh_ik_desc& d) { return d.orientation ? 7 : 3; }
+// equality rows of an IK handle: 3 (position goal), 7 (full pose, oh_ik_desc.orientation) or 6 (position and link axis, oh_ik_set_axis_goal); p rows are
+// ndof + ik_rows wide, multiplier rows ik_rows + 2 ndof
+inline size_t ik_rows(const IkState& s) { return s.axis_goal ? 6 : s.desc.orientation ? 7 : 3; }
 
 // Torque-MPC family (oh_api_torque.hip)
 struct TqState {

@@ -493,6 +493,281 @@ __global__ void __launch_bounds__(64) k_ik_pose_solve(const oh_chain* __restrict
   if (status) status[b] = st;
 }
 
+// ---- the state machine over a rows policy (oh_ik_set_axis_goal is its first user) -----------------------------------------------------------------
+//
+// The two kernels above differ only in their equality rows.  ik_rows_solve is their state machine once more, with everything that knows the rows
+// behind a policy `Rows`; a new goal is a new policy, and the two older kernels can move onto theirs without touching the iteration (they stay as
+// they are for now: their code objects are the parent's).  A policy states, for h = goal - value(q) with NH rows, y the effective multipliers:
+//     NH                                  number of rows; p rows are [q_nominal (N); goal (NH)], multiplier rows [-lam (NH); z_lo (N); z_up (N)]
+//     eval(ch, P, q, v, Jp, om)           value v[NH] and the chain's linear columns Jp / joint axes om (om = 0 for a prismatic joint)
+//     Dual, dual(y, v, rho, D)            whatever of y the next two need, formed once per multiplier vector
+//     jty(i, Jp, om, y, D)                (J^T y)_i, J the Jacobian of the value: the rows' share of the gradient is -jty
+//     hess(a, c, Jp, om, v, y, rho, D)    rho (J^T J)_{ac} - sum_k y_k d2 value_k / dq_a dq_c for c not after a on the chain
+// The |y| sum of the Armijo slack and the feasibility norms run over all NH rows here.
+//
+// Axis goal: value = [p_link; u], u = R_link a, a the unit link-frame axis (P.a_tool = R_tool a: fk_chain's R stops before the tool).  With
+// yu = y[3..5]:
+//     du/dq_j = om_j x u                          yu . du/dq_j = om_j . (u x yu)
+//     (om_a x u) . (om_c x u) = |u|^2 om_a . om_c - (om_a . u)(om_c . u)           (|u|^2 kept as computed, like |quat|^2 in the pose kernel)
+//     d2u/dq_c dq_a = om_c x (om_a x u)           yu . d2u_{c,a} = (yu . om_a)(om_c . u) - (yu . u)(om_a . om_c)         (c not after a)
+// so with D.c = u x yu, D.r = rho u + yu, D.k = rho |u|^2 + yu . u the axis rows add  om_i . D.c  to jty and  D.k om_a . om_c - (om_c . u)(om_a . D.r)
+// to hess: one 3-vector per multiplier vector and dot products, no 3 x n Jacobian.  |u| = 1, so the three rows have rank 2 (u^T du/dq = 0); no
+// system in the rows is solved, and lam along u moves only at second order for a unit goal.  The goal is literal: one that is not of unit length is
+// infeasible as posed and ends with a non-zero status.  tests/axis_ik_ref.py restates the iteration in numpy with the Jacobian written out.
+struct IkAxisRows {
+  static constexpr int NH = 6;
+  struct Dual {
+    double c[3], r[3], k;
+  };
+
+  template <int N>
+  static OH_DEV void eval(const oh_chain* __restrict__ ch, const IkParams& P, const double (&q)[N], double (&v)[NH], double (&Jp)[N][3], double (&om)[N][3]) {
+    double R[9], p[3], pj[N][3];
+    fk_chain<N>(ch, q, R, p, om, pj);
+    double t[3];
+    mv3(R, ch->p_tool, t);
+    v[0] = p[0] + t[0]; v[1] = p[1] + t[1]; v[2] = p[2] + t[2];
+    mv3(R, P.a_tool, &v[3]);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      if (ch->jtype[k] == 0) {
+        const double d[3] = {v[0] - pj[k][0], v[1] - pj[k][1], v[2] - pj[k][2]};
+        cross3(om[k], d, Jp[k]);
+      } else {
+        Jp[k][0] = om[k][0]; Jp[k][1] = om[k][1]; Jp[k][2] = om[k][2];
+        om[k][0] = om[k][1] = om[k][2] = 0.0;
+      }
+    }
+  }
+
+  static OH_DEV void dual(const double (&y)[NH], const double (&v)[NH], const double rho, Dual& D) {
+    cross3(&v[3], &y[3], D.c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) D.r[k] = rho * v[3 + k] + y[3 + k];
+    D.k = rho * dot3(&v[3], &v[3]) + dot3(&y[3], &v[3]);
+  }
+
+  template <int N>
+  static OH_DEV double jty(const int i, const double (&Jp)[N][3], const double (&om)[N][3], const double (&y)[NH], const Dual& D) {
+    return dot3(Jp[i], y) + dot3(om[i], D.c);
+  }
+
+  template <int N>
+  static OH_DEV double hess(const int a, const int c, const double (&Jp)[N][3], const double (&om)[N][3], const double (&v)[NH], const double (&y)[NH],
+                            const double rho, const Dual& D) {
+    double t[3];
+    cross3(om[c], Jp[a], t);
+    return rho * dot3(Jp[a], Jp[c]) - dot3(y, t) + D.k * dot3(om[a], om[c]) - dot3(om[c], &v[3]) * dot3(om[a], D.r);
+  }
+};
+
+template <int N, int NH>
+OH_DEV double ik_rows_merit(const IkParams& P, const double (&q)[N], const double (&qn)[N], const double (&v)[NH], const double (&g)[NH],
+                            const double (&lam)[NH], double rho) {
+  double c = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) c += (q[i] - qn[i]) * (q[i] - qn[i]);
+  double m = P.w * c;
+#pragma unroll
+  for (int k = 0; k < NH; ++k) {
+    const double h = g[k] - v[k];
+    m += lam[k] * h + 0.5 * rho * h * h;
+  }
+  return m;
+}
+
+template <int N, class Rows>
+OH_DEV void ik_rows_solve(const oh_chain* __restrict__ ch, const IkParams& P, const int b, const double* __restrict__ x0, const double* __restrict__ par,
+                          double* __restrict__ x, double* __restrict__ f, double* __restrict__ kkt, int* __restrict__ iters, int* __restrict__ status,
+                          double* __restrict__ mult) {
+  constexpr int NH = Rows::NH, NP = N * (N + 1) / 2, NM = NH + 2 * N;
+  double q[N], qn[N], g[NH], lam[NH];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    qn[i] = par[(size_t)b * (N + NH) + i];
+    q[i] = fmin(fmax(x0[(size_t)b * N + i], P.lo[i]), P.up[i]);
+  }
+#pragma unroll
+  for (int k = 0; k < NH; ++k) {
+    g[k] = par[(size_t)b * (N + NH) + N + k];
+    lam[k] = 0.0;
+  }
+  double v[NH], Jp[N][3], om[N][3];
+  Rows::template eval<N>(ch, P, q, v, Jp, om);
+  int it = 1, st = OH_STATUS_MAX_ITER;
+  double rho = P.rho0, shift = 0.0, h_prev = 1e300;
+  double grad[N];
+  bool act[N];
+  typename Rows::Dual D;
+  {
+    // non-finite seed / parameters: report, do not iterate (as in k_ik_solve)
+    const double m_init = ik_rows_merit<N, NH>(P, q, qn, v, g, lam, rho);
+    if (!(m_init == m_init) || !(fabs(m_init) < 1e300)) st = OH_STATUS_NUMERICAL;
+  }
+  while (it < P.max_iter && st != OH_STATUS_NUMERICAL) {
+    const int it_pass = it;
+    // ---- inner: projected Newton on the augmented Lagrangian ----
+    while (it < P.max_iter) {
+      double y[NH], hmax = 0.0, ysum = 0.0;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        const double h = g[k] - v[k];
+        y[k] = lam[k] + rho * h;
+        hmax = fmax(hmax, fabs(h));
+        ysum += fabs(y[k]);
+      }
+      Rows::dual(y, v, rho, D);
+      double pgn = 0.0;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        grad[i] = 2.0 * P.w * (q[i] - qn[i]) - Rows::template jty<N>(i, Jp, om, y, D);
+        act[i] = (q[i] <= P.lo[i] && grad[i] > 0.0) || (q[i] >= P.up[i] && grad[i] < 0.0);
+        if (!act[i]) pgn = fmax(pgn, fabs(grad[i]));
+      }
+      if (pgn <= fmax(0.5 * P.tol, fmin(1e-2, 0.1 * hmax))) break;
+      // 2wI + rho J^T J - sum_k y_k d2 value_k  (h = goal - value: the curvature enters with the minus sign)
+      double H[NP];
+#pragma unroll
+      for (int a = 0; a < N; ++a) {
+#pragma unroll
+        for (int c = 0; c <= a; ++c) {
+          double e = Rows::template hess<N>(a, c, Jp, om, v, y, rho, D);
+          if (a == c) e += 2.0 * P.w;
+          H[tri(a, c)] = e;
+        }
+      }
+      double L[NP];
+      for (;;) {
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+#pragma unroll
+          for (int c = 0; c <= a; ++c) {
+            double e = H[tri(a, c)];
+            if (a == c) e += shift;
+            if (act[a] || act[c]) e = (a == c) ? 1.0 : 0.0;
+            L[tri(a, c)] = e;
+          }
+        }
+        if (chol_packed<N>(L, 0.0)) break;
+        shift = fmax(10.0 * shift, 1e-3 * rho);
+        if (!(shift < 1e300)) break;
+      }
+      double d[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) d[i] = act[i] ? 0.0 : -grad[i];
+      fsub<N>(L, d);
+      bsub<N>(L, d);
+      const double m0 = ik_rows_merit<N, NH>(P, q, qn, v, g, lam, rho);
+      double alpha = 1.0;
+      bool ok = false;
+      double qt[N], vt[NH], Jt[N][3], ot[N][3];
+      for (int ls = 0; ls < 30; ++ls) {
+        double slope = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          qt[i] = fmin(fmax(q[i] + alpha * d[i], P.lo[i]), P.up[i]);
+          slope += grad[i] * (qt[i] - q[i]);
+        }
+        Rows::template eval<N>(ch, P, qt, vt, Jt, ot);
+        ++it;
+        // (rounding slack as in k_ik_solve, |y| summed over all rows)
+        if (ik_rows_merit<N, NH>(P, qt, qn, vt, g, lam, rho) <= m0 + 1e-4 * slope + 4e-16 * fmax(1.0, fabs(m0)) + 8e-16 * ysum) {
+          ok = true;
+          break;
+        }
+        alpha *= 0.5;
+        if (it >= P.max_iter) break;
+      }
+      if (!ok) {
+        shift = fmax(10.0 * shift, 1e-3 * rho);
+        if (shift > 1e12 * rho) {
+          st = OH_STATUS_NUMERICAL;
+          break;
+        }
+        continue;
+      }
+      shift = shift > 1e-12 ? 0.1 * shift : 0.0;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        q[i] = qt[i];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          Jp[i][k] = Jt[i][k];
+          om[i][k] = ot[i][k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < NH; ++k) v[k] = vt[k];
+    }
+    if (st == OH_STATUS_NUMERICAL) break;
+    // ---- outer: multiplier update ----
+    double hn = 0.0;
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+      const double h = g[k] - v[k];
+      lam[k] += rho * h;
+      hn = fmax(hn, fabs(h));
+    }
+    Rows::dual(lam, v, 0.0, D);
+    double stat = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const double gi = 2.0 * P.w * (q[i] - qn[i]) - Rows::template jty<N>(i, Jp, om, lam, D);
+      const bool a = (q[i] <= P.lo[i] && gi > 0.0) || (q[i] >= P.up[i] && gi < 0.0);
+      if (!a) stat = fmax(stat, fabs(gi));
+    }
+    if (hn <= P.tol_feas && stat <= P.tol) {
+      st = OH_STATUS_CONVERGED;
+      break;
+    }
+    if (hn > 0.1 * h_prev) rho = fmin(rho * 10.0, 1e8);
+    h_prev = hn;
+    // a pass whose inner loop had nothing to do counts as one evaluation towards the cap: pinned at an infeasible stationary point with every free
+    // joint's gradient below the inner tolerance (a goal out of reach, all joints on their bounds) such passes only grow lam, and would do so
+    // without end (the two older kernels share the loop and not this line; there the case has not been seen)
+    if (it == it_pass) ++it;
+  }
+  // ---- results in the reference's form: v = [q - lo; up - q; h; -h] >= 0 (optimization.py:47-51), h of NH rows ----
+  double stat = 0.0, feas = 0.0, cost = 0.0;
+  Rows::dual(lam, v, 0.0, D);
+#pragma unroll
+  for (int k = 0; k < NH; ++k) feas = fmax(feas, fabs(g[k] - v[k]));
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const double gi = 2.0 * P.w * (q[i] - qn[i]) - Rows::template jty<N>(i, Jp, om, lam, D);
+    const bool lo = q[i] <= P.lo[i] && gi > 0.0, up = q[i] >= P.up[i] && gi < 0.0;
+    if (!(lo || up)) stat = fmax(stat, fabs(gi));
+    cost += (q[i] - qn[i]) * (q[i] - qn[i]);
+    if (x) x[(size_t)b * N + i] = q[i];
+    if (mult) {
+      mult[(size_t)b * NM + NH + i] = lo ? gi : 0.0;
+      mult[(size_t)b * NM + NH + N + i] = up ? -gi : 0.0;
+    }
+  }
+  if (mult) {
+#pragma unroll
+    for (int k = 0; k < NH; ++k) mult[(size_t)b * NM + k] = -lam[k];
+  }
+  if (f) f[b] = P.w * cost;
+  if (kkt) {
+    kkt[(size_t)b * 3 + 0] = stat;
+    kkt[(size_t)b * 3 + 1] = feas;
+    kkt[(size_t)b * 3 + 2] = 0.0;
+  }
+  if (iters) iters[b] = it;
+  if (status) status[b] = st;
+}
+
+template <int N>
+__global__ void __launch_bounds__(64) k_ik_axis_solve(const oh_chain* __restrict__ ch, IkParams P, int B, const double* __restrict__ x0,
+                                                      const double* __restrict__ par, double* __restrict__ x, double* __restrict__ f,
+                                                      double* __restrict__ kkt, int* __restrict__ iters, int* __restrict__ status,
+                                                      double* __restrict__ mult) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  ik_rows_solve<N, IkAxisRows>(ch, P, b, x0, par, x, f, kkt, iters, status, mult);
+}
+
 template <typename K>
 bool ik_kernel_info(K kernel, OhKernelInfo* out) {
   hipFuncAttributes a{};
@@ -505,7 +780,7 @@ bool ik_kernel_info(K kernel, OhKernelInfo* out) {
 
 }  // namespace
 
-// "k_ik_solve" / "k_ik_pose_solve": the 7-joint instantiations; "k_ik_solve_N" / "k_ik_pose_solve_N": N = 2 ... 8
+// "k_ik_solve" / "k_ik_pose_solve" / "k_ik_axis_solve": the 7-joint instantiations; with "_N" appended: N = 2 ... 8
 bool oh_kernel_info_ik(const char* name, OhKernelInfo* out) {
   std::string n(name);
   int N = 7;
@@ -513,10 +788,10 @@ bool oh_kernel_info_ik(const char* name, OhKernelInfo* out) {
     N = n.back() - '0';
     n.resize(n.size() - 2);
   }
-  const bool pose = n == "k_ik_pose_solve";
-  if (!pose && n != "k_ik_solve") return false;
+  const bool pose = n == "k_ik_pose_solve", axis = n == "k_ik_axis_solve";
+  if (!pose && !axis && n != "k_ik_solve") return false;
   switch (N) {
-#define C(NN) case NN: return pose ? ik_kernel_info(k_ik_pose_solve<NN>, out) : ik_kernel_info(k_ik_solve<NN>, out)
+#define C(NN) case NN: return axis ? ik_kernel_info(k_ik_axis_solve<NN>, out) : pose ? ik_kernel_info(k_ik_pose_solve<NN>, out) : ik_kernel_info(k_ik_solve<NN>, out)
     C(2); C(3); C(4); C(5); C(6); C(7); C(8);
 #undef C
   }
@@ -528,6 +803,18 @@ bool oh_launch_ik_pose_solve(hipStream_t stream, const oh_chain* d_chain, const 
   const dim3 block(64), grid((B + 63) / 64);
   switch (P.ndof) {
 #define C(NN) case NN: hipLaunchKernelGGL(k_ik_pose_solve<NN>, grid, block, 0, stream, d_chain, P, B, x0, p, x, f, kkt, iters, status, mult); break
+    C(2); C(3); C(4); C(5); C(6); C(7); C(8);
+#undef C
+    default: return false;
+  }
+  return true;
+}
+
+bool oh_launch_ik_axis_solve(hipStream_t stream, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x,
+                             double* f, double* kkt, int* iters, int* status, double* mult) {
+  const dim3 block(64), grid((B + 63) / 64);
+  switch (P.ndof) {
+#define C(NN) case NN: hipLaunchKernelGGL(k_ik_axis_solve<NN>, grid, block, 0, stream, d_chain, P, B, x0, p, x, f, kkt, iters, status, mult); break
     C(2); C(3); C(4); C(5); C(6); C(7); C(8);
 #undef C
     default: return false;

@@ -153,11 +153,15 @@ struct IkParams {
   int ndof, max_iter;
   double w, tol, tol_feas, rho0;
   double lo[OH_MAX_CHAIN], up[OH_MAX_CHAIN];
+  double a_tool[3];  // axis goal (oh_ik_set_axis_goal): R_tool times the unit link-frame axis, so that u = R a_tool with fk_chain's R
 };
 bool oh_launch_ik_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
                         double* kkt, int* iters, int* status, double* mult);
 // oh_ik_desc.orientation: p rows [q_nominal; p_goal; quat_goal] (ndof + 7), mult rows 7 + 2 ndof
 bool oh_launch_ik_pose_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
+                             double* kkt, int* iters, int* status, double* mult);
+// oh_ik_set_axis_goal: p rows [q_nominal; p_goal; u_goal] (ndof + 6), mult rows 6 + 2 ndof
+bool oh_launch_ik_axis_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
                              double* kkt, int* iters, int* status, double* mult);
 
 // ---- OH_PROBLEM_QP -----------------------------------------------------------------------------------------

@@ -71,6 +71,8 @@ def _evaluate(e: Expr, opt, x: np.ndarray, p: np.ndarray) -> np.ndarray:
             return np.asarray(e.robot.get_global_link_quaternion(e.link, q)).reshape(4, -1)
         if e.what == "geometric_jacobian":
             return np.asarray(e.robot.get_global_link_geometric_jacobian(e.link, q.reshape(-1)))
+        if e.what == "axis":  # R_link(q) a, column by column
+            return np.stack([np.asarray(e.robot.get_global_link_rotation(e.link, q[:, c])) @ e.axis for c in range(q.shape[1])], axis=1)
         return np.asarray(e.robot.get_global_link_rotation(e.link, q.reshape(-1)))
     if isinstance(e, RneaFunction):
         return np.asarray(e.robot.rnea(evaluate(e.q, opt, x, p), evaluate(e.qd, opt, x, p), evaluate(e.qdd, opt, x, p))).reshape(e.shape)
@@ -225,6 +227,10 @@ def jacobian(e: Expr, opt, x: np.ndarray, p: np.ndarray):
                 qx, qy, qz, qw = pose[c, 3:]
                 Lq = 0.5 * np.array([[qw, qz, -qy], [-qz, qw, qx], [qy, -qx, qw], [-qx, -qy, -qz]])  # d quat = 1/2 (omega, 0) (x) quat
                 J[4 * c : 4 * c + 4] = Lq @ Jg[c, 3:] @ Jqc
+            elif e.what == "axis":  # d u = omega x u
+                u = val[:, c]
+                K = np.array([[0.0, u[2], -u[1]], [-u[2], 0.0, u[0]], [u[1], -u[0], 0.0]])  # omega x u = K omega
+                J[3 * c : 3 * c + 3] = K @ Jg[c, 3:] @ Jqc
             elif e.what == "rotation":
                 R = val
                 W = Jg[c, 3:] @ Jqc  # omega per unit dx, (3, nx)
@@ -293,7 +299,7 @@ def _hamilton_left(o, quat):
 def weighted_hessian(e: Expr, opt, x: np.ndarray, p: np.ndarray, W: np.ndarray) -> np.ndarray:
     """sum over the entries of node ``e`` of W[r, c] * (Hessian of that entry w.r.t. x), nx x nx, exact: the weights travel down the tree
     (transposed through the linear nodes), every nonlinear node adds its own curvature from the first derivatives of its operands.  Second-order
-    kinematics come out of the geometric Jacobian oh_fk_jac returns: d2 p / dq_i dq_j = z_i x Jp_j (i <= j), d2 quat and d2 R from the same axes.
+    kinematics come out of the geometric Jacobian oh_fk_jac returns: d2 p / dq_i dq_j = z_i x Jp_j (i <= j), d2 quat, d2 R and d2 (R a) from the same axes.
     Inverse dynamics: oh_rnea_hess (round 4).  Raises NotImplementedError for nodes without a rule (the Jacobian-valued link function): the caller
     differences."""
     nx = opt.nx
@@ -412,6 +418,13 @@ def weighted_hessian(e: Expr, opt, x: np.ndarray, p: np.ndarray, W: np.ndarray) 
                         dz = np.cross(Jw[:, i], Jw[:, j]) if i < j else np.zeros(3)
                         S[i, j] = S[j, i] = float(w4 @ (0.5 * _hamilton_left(dz, quat) + 0.25 * _hamilton_left(Jw[:, j], hi)))
                 Wq[:, c] = np.array([0.5 * float(w4 @ _hamilton_left(Jw[:, k], quat)) for k in range(nd)])
+            elif e.what == "axis":  # u = R a: d u = z x u, d2 u / dq_i dq_j = z_i x (z_j x u) for i not after j
+                u = np.asarray(evaluate(e, opt, x, p))[:, c]
+                w3 = W[:, c]
+                for i in range(nd):
+                    for j in range(i, nd):
+                        S[i, j] = S[j, i] = float(w3 @ np.cross(Jw[:, i], np.cross(Jw[:, j], u)))
+                Wq[:, c] = np.array([float(w3 @ np.cross(Jw[:, k], u)) for k in range(nd)])
             else:  # rotation: a single configuration, W is 3 x 3; d R = [omega]x R, d2 R / dq_i dq_j = [z_i x z_j]x R (i < j) + [z_j]x [z_i]x R
                 R = np.asarray(evaluate(e, opt, x, p))
 

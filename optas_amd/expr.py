@@ -259,16 +259,20 @@ class VarRef(Expr):
 
 @dataclass(eq=False)
 class LinkFunction(Expr):
-    """robot.get_global_link_{position,rotation,quaternion}(link, q) of a symbolic q
-    (models.py:924-933, 986-995, 1049-1088; mapped over columns like .map(n), :786-787)."""
+    """robot.get_global_link_{position,rotation,quaternion,axis}(link, q) of a symbolic q
+    (models.py:924-933, 986-995, 1049-1088, 1698-1710; mapped over columns like .map(n), :786-787)."""
 
     robot: object
     link: str
-    what: str  # "position" | "rotation" | "quaternion"
+    what: str  # "position" | "rotation" | "quaternion" | "geometric_jacobian" | "axis"
     q: Expr = None
+    axis: Optional[np.ndarray] = None  # what == "axis": the unit direction a in the link frame; the node is R_link(q) a
 
     def __post_init__(self):
-        rows = {"position": 3, "quaternion": 4, "rotation": 3, "geometric_jacobian": 6}[self.what]
+        rows = {"position": 3, "quaternion": 4, "rotation": 3, "geometric_jacobian": 6, "axis": 3}[self.what]
+        if self.what == "axis":
+            a = np.asarray(self.axis, dtype=np.float64).reshape(3)
+            self.axis = a / np.linalg.norm(a)  # the reference normalises it (models.py:1659)
         cols = self.q.shape[1]
         if self.what == "geometric_jacobian":
             if cols != 1:
@@ -283,6 +287,38 @@ class LinkFunction(Expr):
 
     def degree(self):
         return 0 if self.q.degree() == 0 else 3
+
+
+@dataclass(eq=False)
+class LinkTransform(Expr):
+    """robot.get_global_link_transform(link, q) of a symbolic q (models.py:826-868): a 4 x 4 node that exists to be taken apart --
+    T[:3, 3] is the position node, T[:3, :3] the rotation node and T[:3, c] the link-axis node of column c (``z = T[:3, 2]``,
+    example/sphere_collision_avoidance.py:20-43)."""
+
+    robot: object
+    link: str
+    q: Expr = None
+
+    def __post_init__(self):
+        if self.q.shape[1] != 1:
+            raise NotImplementedError("the transform of a trajectory is a list in the reference; only one configuration is lowered")
+        self.shape = (4, 4)
+
+    def degree(self):
+        return 0 if self.q.degree() == 0 else 3
+
+    def __getitem__(self, key):
+        def top(k):  # :3, 0:3
+            return isinstance(k, slice) and k.indices(4) == (0, 3, 1)
+
+        if isinstance(key, tuple) and len(key) == 2 and top(key[0]):
+            if isinstance(key[1], int) and key[1] in (3, -1):
+                return LinkFunction(self.robot, self.link, "position", self.q)
+            if isinstance(key[1], int) and key[1] in (0, 1, 2):
+                return LinkFunction(self.robot, self.link, "axis", self.q, np.eye(3)[key[1]])
+            if top(key[1]):
+                return LinkFunction(self.robot, self.link, "rotation", self.q)
+        raise NotImplementedError("a symbolic link transform is indexed as T[:3, 3] (position), T[:3, :3] (rotation) or T[:3, c] (axis c of the link frame)")
 
 
 @dataclass(eq=False)

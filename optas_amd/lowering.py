@@ -11,7 +11,7 @@ match -- there is no generic/CPU evaluation path to fall back to.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
@@ -593,16 +593,29 @@ class IkSpec:
     w_nominal: float
     lo: np.ndarray
     up: np.ndarray
-    qn_name: str
-    pg_name: str
+    qn_name: Optional[str]  # None: the nominal configuration is a constant (consts["qn"])
+    pg_name: Optional[str]
     q_name: str
     orientation: bool = False  # full-pose goal: a second equality quat_link(q) == quat_goal (p = [q_nominal; p_goal; quat_goal])
     qg_name: Optional[str] = None
+    goal: int = 0  # 0 position, 1 full pose, 2 position and link axis (oh_get_flag "ik_goal")
+    axis: Optional[np.ndarray] = None  # goal 2: the unit axis in the link frame; a second equality R_link(q) axis == axis_goal (p = [q_nominal; p_goal; axis_goal])
+    ug_name: Optional[str] = None
+    consts: dict = field(default_factory=dict)  # "qn" / "pg" / "ug": values written as numeric constants, which the backend puts into every instance's row
+    pinned: dict = field(default_factory=dict)  # further decision blocks that one linear equality pins to a constant: block name -> value (returned as such)
+
+    @property
+    def plain(self) -> bool:
+        """x is q and p is the kernel's row: the backend takes the problem's vectors as they are."""
+        return not self.consts and not self.pinned
 
 
 def match_ik(opt: Optimization) -> IkSpec:
     """example/example.py:13-60: min w||q - q_nominal||^2 s.t. p_link(q) = p_goal, lo <= q <= up (T = 1); examples/pose_ik.py: the same with a second
-    equality quat_link(q) = quat_goal after the first (the reference's get_global_link_quaternion rows, figure_eight_plan.py:105-107)."""
+    equality quat_link(q) = quat_goal after the first (the reference's get_global_link_quaternion rows, figure_eight_plan.py:105-107); examples/axis_ik.py:
+    with a second equality on one axis of the link frame instead, R_link(q) a = axis_goal (``z = T[:3, 2]`` or get_global_link_axis;
+    sphere_collision_avoidance.py:20-43).  q_nominal and the goals may be numeric constants instead of parameters, and the robot may carry further time
+    derivatives if one linear equality pins each of their blocks entirely to a constant (initial_configuration(name, time_deriv=d), T = 1, derivs_align)."""
 
     def no(msg):
         raise LoweringError(f"inverse-kinematics lowering: {msg}")
@@ -611,44 +624,64 @@ def match_ik(opt: Optimization) -> IkSpec:
     if len(opt.models or []) != 1 or len(robots) != 1:
         no("expected exactly one RobotModel and no task models")
     robot = robots[0]
-    if list(robot.time_derivs) != [0] or robot.num_param_joints != 0:
-        no("robot must have time_derivs=[0] and no parameterised joints")
+    if 0 not in list(robot.time_derivs) or robot.num_param_joints != 0:
+        no("robot must carry time derivative 0 and have no parameterised joints")
     q_name = robot.state_optimized_name(0)
-    if list(opt.decision_variables.keys()) != [q_name]:
-        no(f"decision variables must be exactly [{q_name}]")
+    blocks = list(opt.decision_variables.keys())
+    if not blocks or blocks[0] != q_name:
+        no(f"the first decision block must be {q_name}")
     Q: StateRef = opt.decision_variables[q_name]
     if Q.n != 1:
         no("T must be 1")
     n = robot.ndof
-    if opt.ng or opt.na:
-        no("nonlinear inequality / linear equality rows are not part of this family")
+    if opt.ng:
+        no("nonlinear inequality rows are not part of this family")
+
+    # linear equalities: only rows that pin a further decision block (dq, ddq) entirely to a constant; the cost must not see those blocks (checked below)
+    pinned = {}
+    for label, d in opt.lin_eq_constraints.items():
+        blk = d.b if isinstance(d, Sub) and isinstance(d.b, StateRef) else None
+        if not (blk is not None and isinstance(d.a, Const) and blk.var_name != q_name and blk.var_name in blocks and blk.n == 1
+                and d.a.value.shape == (blk.m, 1) and blk.var_name not in pinned):
+            no(f"linear equality '{label}' does not pin a whole further decision block to a constant")
+        pinned[blk.var_name] = d.a.value[:, 0].copy()
+    if set(blocks[1:]) != set(pinned):
+        no(f"decision variables must be [{q_name}] and blocks pinned by a linear equality; unpinned: {sorted(set(blocks[1:]) - set(pinned))}")
 
     def is_q(e):
         return isinstance(e, StateRef) and e.var_name == q_name and e.time_deriv == 0 and (e.t in (None, 0))
 
-    # nonlinear equalities: p_link(q) == p_goal, optionally followed by quat_link(q) == quat_goal (same link, same q)
+    def is_data(e, rows):
+        return isinstance(e, (ParamRef, Const)) and e.shape == (rows, 1)
+
+    # nonlinear equalities: p_link(q) == p_goal, optionally followed by quat_link(q) == quat_goal or by axis_link(q) == axis_goal (same link, same q)
     def goal_row(label, diff, what, rows):
-        if not (isinstance(diff, Sub) and isinstance(diff.a, ParamRef) and isinstance(diff.b, LinkFunction) and diff.b.what == what
-                and is_q(diff.b.q) and diff.b.robot is robot and diff.a.shape == (rows, 1)):
-            no(f"equality '{label}' is not {what}(link, q) == goal with a {rows}-vector parameter")
+        if not (isinstance(diff, Sub) and is_data(diff.a, rows) and isinstance(diff.b, LinkFunction) and diff.b.what == what
+                and is_q(diff.b.q) and diff.b.robot is robot):
+            no(f"equality '{label}' is not {what}(link, q) == goal with a {rows}-vector parameter or constant")
         return diff.a, diff.b.link
 
     eqs = list(opt.eq_constraints.items())
     if len(eqs) not in (1, 2):
-        no("expected one nonlinear equality (link position goal) or two (position goal, then quaternion goal)")
+        no("expected one nonlinear equality (link position goal) or two (position goal, then quaternion goal or link-axis goal)")
     pg, link = goal_row(*eqs[0], "position", 3)
-    qg = None
+    qg = ug = axis = None
     if len(eqs) == 2:
-        qg, qlink = goal_row(*eqs[1], "quaternion", 4)
-        if qlink != link:
-            no(f"the quaternion goal is on link '{qlink}', the position goal on '{link}'")
+        second = eqs[1][1].b if isinstance(eqs[1][1], Sub) else None
+        if isinstance(second, LinkFunction) and second.what == "axis":
+            ug, glink = goal_row(*eqs[1], "axis", 3)
+            axis = np.asarray(second.axis, dtype=np.float64).copy()
+        else:
+            qg, glink = goal_row(*eqs[1], "quaternion", 4)
+        if glink != link:
+            no(f"the {'axis' if ug is not None else 'quaternion'} goal is on link '{glink}', the position goal on '{link}'")
 
     # cost: w * sumsqr(q - q_nominal)
     if len(opt.cost_terms) != 1:
         no("expected exactly one cost term")
     (label, term), = opt.cost_terms.items()
     w, e = _unscale(term)
-    if not (isinstance(e, SumSqr) and isinstance(e.a, Sub) and is_q(e.a.a) and isinstance(e.a.b, ParamRef) and e.a.b.shape == (n, 1)):
+    if not (isinstance(e, SumSqr) and isinstance(e.a, Sub) and is_q(e.a.a) and is_data(e.a.b, n)):
         no(f"cost '{label}' is not w * sumsqr(q - q_nominal)")
     qn = e.a.b
     if not w > 0:
@@ -663,11 +696,15 @@ def match_ik(opt: Optimization) -> IkSpec:
             up = np.minimum(up, d.a.value[:, 0])
         else:
             no(f"linear inequality '{label}' is not a joint bound")
+    data = [("qn", qn), ("pg", pg)] + ([("qg", qg)] if qg is not None else []) + ([("ug", ug)] if ug is not None else [])
     params = [k for k, v in opt.parameters.items() if v.numel() > 0]
-    want = [qn.name, pg.name] + ([qg.name] if qg is not None else [])
+    want = [d.name for _, d in data if isinstance(d, ParamRef)]
     if params != want:
         no(f"non-empty parameters must be {want} in this order, found {params}")
-    return IkSpec(robot, link, float(w), lo, up, qn.name, pg.name, q_name, qg is not None, None if qg is None else qg.name)
+    consts = {k: d.value[:, 0].copy() for k, d in data if isinstance(d, Const)}
+    name = lambda d: d.name if isinstance(d, ParamRef) else None
+    return IkSpec(robot, link, float(w), lo, up, name(qn), name(pg), q_name, qg is not None, None if qg is None else name(qg),
+                  goal=2 if ug is not None else 1 if qg is not None else 0, axis=axis, ug_name=None if ug is None else name(ug), consts=consts, pinned=pinned)
 
 
 @dataclass

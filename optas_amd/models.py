@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import numpy as np
 
 from . import _lib
-from .expr import Expr, LinkFunction, Rows
+from .expr import Expr, LinkFunction, LinkTransform, Rows
 from .spatialmath import Quaternion, rpy2r, unit
 from .urdf import Joint, Link, RobotDescription, load_robot_description
 
@@ -551,7 +551,9 @@ class RobotModel(Model):
 
     # ---- 4x4 transforms ------------------------------------------------------------------------------------------------
     def get_global_link_transform(self, link: str, q) -> np.ndarray:
-        """models.py:826-868: homogeneous transform of the link in the root frame."""
+        """models.py:826-868: homogeneous transform of the link in the root frame.  A symbolic q gives a node to be indexed: T[:3, 3], T[:3, :3], T[:3, c]."""
+        if isinstance(q, Expr):
+            return LinkTransform(self, link, q)
         T = np.eye(4)
         T[:3, :3] = self.get_global_link_rotation(link, np.asarray(q, dtype=np.float64).reshape(-1))
         T[:3, 3] = self.get_global_link_position(link, np.asarray(q, dtype=np.float64).reshape(-1))
@@ -662,7 +664,9 @@ class RobotModel(Model):
         return self._columns(out["axis"], single)
 
     def get_global_link_axis(self, link: str, q, axis) -> np.ndarray:
-        """models.py:1698-1710."""
+        """models.py:1698-1710.  A symbolic q returns the link-axis node R_link(q) a, a the normalised axis."""
+        if isinstance(q, Expr):
+            return LinkFunction(self, link, "axis", q, self._axis3(axis))
         return self.get_link_axis(link, q, axis, self.get_root_link())
 
     def _knots(self, method):

@@ -233,6 +233,51 @@ class _QpAdapter:
         self.be.close()
 
 
+class _IkAdapter:
+    """IK family behind a problem whose vectors are not the kernel's rows (lowering.IkSpec.plain is False): numeric constants written where the family
+    has parameters (q_nominal, the goals) go into every instance's parameter row, and further decision blocks that a linear equality pins to a
+    constant (dq, ddq of a robot with time_derivs=[0, 1, 2]) are returned at their pinned values; the cost does not see them, so the multipliers of
+    their equality rows are zero."""
+
+    def __init__(self, opt, spec: IkSpec, backend: IKBackend):
+        self.opt, self.spec, self.be = opt, spec, backend
+        xo, po = opt.decision_variables.offsets(), opt.parameters.offsets()
+        n = spec.robot.ndof
+        self._q = slice(xo[spec.q_name], xo[spec.q_name] + n)
+        self._pinned = [(slice(xo[k], xo[k] + len(v)), np.asarray(v, dtype=np.float64)) for k, v in spec.pinned.items()]
+        entries = [("qn", spec.qn_name, n), ("pg", spec.pg_name, 3)] + {0: [], 1: [("qg", spec.qg_name, 4)], 2: [("ug", spec.ug_name, 3)]}[spec.goal]
+        # per entry of the kernel's row: (width, parameter offset or None, constant or None)
+        self._row = [(width, None if name is None else po[name], spec.consts.get(key)) for key, name, width in entries]
+
+    def solve(self, x0: np.ndarray, p: np.ndarray) -> BatchResult:
+        x0 = np.asarray(x0, dtype=np.float64).reshape(-1, int(self.opt.nx))
+        B = len(x0)
+        p = np.asarray(p, dtype=np.float64).reshape(B, -1)
+        row = np.concatenate([np.tile(c, (B, 1)) if off is None else p[:, off : off + w] for w, off, c in self._row], axis=1)
+        r = self.be.solve(np.ascontiguousarray(x0[:, self._q]), np.ascontiguousarray(row))
+        x = np.zeros((B, int(self.opt.nx)))
+        x[:, self._q] = r.x
+        for sl, v in self._pinned:
+            x[:, sl] = v
+        return BatchResult(x, r.f, r.kkt, r.iters, r.status)
+
+    def multipliers(self, B: int):
+        return self.be.multipliers(B)
+
+    def lin_eq_multipliers(self, B: int) -> np.ndarray:
+        """(B, na): zero -- the pinned blocks appear in no other row and not in the cost."""
+        return np.zeros((B, int(self.opt.na)))
+
+    def flag(self, name: str) -> int:
+        return self.be.flag(name)
+
+    def solve_ms(self) -> float:
+        return self.be.solve_ms()
+
+    def close(self) -> None:
+        self.be.close()
+
+
 def figure_eight_backend(spec: FigureEightSpec, o: dict, hessian: int) -> FigureEightBackend:
     """The OH_PROBLEM_FIGURE_EIGHT handle of a lowered problem (shared by HIPSolver.setup and the literal optas.solver.Solver subclass of
     optas_amd.casadi_tape); consumes its options from ``o``."""
@@ -323,7 +368,9 @@ class HIPSolver(Solver):
             o.pop("hessian", None)
             self._backend = IKBackend(spec.robot.kinematic_chain(spec.link), spec.lo, spec.up, w_nominal=spec.w_nominal,
                                       max_iter=int(o.pop("max_iter", 200)), tol=float(o.pop("tol", 1e-6)), tol_feas=float(o.pop("tol_feas", 1e-9)),
-                                      orientation=spec.orientation)
+                                      orientation=spec.orientation, axis=spec.axis)
+            if not spec.plain:
+                self._backend = _IkAdapter(self.opt, spec, self._backend)
         elif isinstance(spec, QpSpec):
             o.pop("hessian", None)
             qb = QPBackend(spec.n, spec.m, spec.me, max_iter=int(o.pop("max_iter", 100)), tol=float(o.pop("tol", 1e-9)))

@@ -458,6 +458,8 @@ class Compiler:
                     cols.append(p)
                 elif e.what == "rotation":
                     return R
+                elif e.what == "axis":  # the rotation rows times the constant a
+                    cols.append(tb.matmul(R, tb.mat_const(e.axis.reshape(3, 1))))
                 elif e.what == "geometric_jacobian":
                     J = np.full((6, e.robot.ndof), tb.const(0.0), dtype=np.int64)
                     for zw, pj, jt, idx in joints:
