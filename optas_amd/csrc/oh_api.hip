@@ -1408,7 +1408,7 @@ extern "C" int oh_get_flag(oh_handle* h, const char* name, int* value) {
   else if (n == "tape_passes") *value = h->tape.wave.n_fw_pass + h->tape.wave.n_rv_pass;
   else if (n == "qp_block") *value = h->qp.last_block;
   else if (n == "ik_orientation") *value = (h->desc.kind == OH_PROBLEM_IK && h->ik.desc.orientation) ? 1 : 0;
-  else if (n == "ik_goal") *value = h->desc.kind != OH_PROBLEM_IK ? 0 : h->ik.axis_goal ? 2 : h->ik.desc.orientation ? 1 : 0;
+  else if (n == "ik_goal") *value = h->desc.kind != OH_PROBLEM_IK ? 0 : (int)ik_goal(h->ik);
   else if (n == "free_sweep") *value = h->free_sweep_last;
   else if (n == "free_sweeps_used") *value = h->free_sweeps_used;
   else return fail(OH_ERR_INVALID, "oh_get_flag: unknown flag " + n);

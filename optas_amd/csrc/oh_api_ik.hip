@@ -62,10 +62,11 @@ int ik_solve_device(oh_handle* h, const Solve& a) {
     P.lo[i] = d.q_lo[i];
     P.up[i] = d.q_up[i];
   }
-  if (h->ik.axis_goal) mv3_host(h->chain_host.R_tool, h->ik.axis_link, P.a_tool);  // fk_chain's R stops before the tool transform
+  const IkGoal goal = ik_goal(h->ik);
+  if (goal == IkGoal::Axis) mv3_host(h->chain_host.R_tool, h->ik.axis_link, P.a_tool);  // fk_chain's R stops before the tool transform
   h->ik.solved = true;
   HIPCHK(hipEventRecord(h->ev0, h->stream));
-  if (!(h->ik.axis_goal ? oh_launch_ik_axis_solve : d.orientation ? oh_launch_ik_pose_solve : oh_launch_ik_solve)(h->stream, h->d_chain, P, a.B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, h->ik.mult))
+  if (!oh_launch_ik(h->stream, goal, h->d_chain, P, a.B, a.x0, a.p, a.x, a.f, a.kkt, a.iters, a.status, h->ik.mult))
     return fail(OH_ERR_INVALID, "oh_solve_device: unsupported ndof");
   return finish_solve(h, 1);
 }

@@ -157,9 +157,16 @@ struct IkState {
   double axis_link[3] = {0.0, 0.0, 0.0};  // that axis in the link frame, unit length
   bool solved = false;  // a solve has been launched: the goal shape is fixed from then on
 };
-// equality rows of an IK handle: 3 (position goal), 7 (full pose, oh_ik_desc.orientation) or 6 (position and link axis, oh_ik_set_axis_goal); p rows are
-// ndof + ik_rows wide, multiplier rows ik_rows + 2 ndof
-inline size_t ik_rows(const IkState& s) { return s.axis_goal ? 6 : s.desc.orientation ? 7 : 3; }
+// which goal a handle has, read here and nowhere else (oh_ik_set_axis_goal refuses a handle with a full-pose goal, so the two do not meet)
+inline IkGoal ik_goal(const IkState& s) { return s.axis_goal ? IkGoal::Axis : s.desc.orientation ? IkGoal::Pose : IkGoal::Position; }
+// equality rows of an IK handle; p rows are ndof + ik_rows wide, multiplier rows ik_rows + 2 ndof
+inline size_t ik_rows(const IkState& s) {
+  switch (ik_goal(s)) {
+    case IkGoal::Pose: return 7;
+    case IkGoal::Axis: return 6;
+    default: return 3;
+  }
+}
 
 // Torque-MPC family (oh_api_torque.hip)
 struct TqState {

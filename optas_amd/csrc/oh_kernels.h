@@ -155,14 +155,15 @@ struct IkParams {
   double lo[OH_MAX_CHAIN], up[OH_MAX_CHAIN];
   double a_tool[3];  // axis goal (oh_ik_set_axis_goal): R_tool times the unit link-frame axis, so that u = R a_tool with fk_chain's R
 };
-bool oh_launch_ik_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
-                        double* kkt, int* iters, int* status, double* mult);
-// oh_ik_desc.orientation: p rows [q_nominal; p_goal; quat_goal] (ndof + 7), mult rows 7 + 2 ndof
-bool oh_launch_ik_pose_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
-                             double* kkt, int* iters, int* status, double* mult);
-// oh_ik_set_axis_goal: p rows [q_nominal; p_goal; u_goal] (ndof + 6), mult rows 6 + 2 ndof
-bool oh_launch_ik_axis_solve(hipStream_t s, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
-                             double* kkt, int* iters, int* status, double* mult);
+// What the equality rows of an IK handle are, in the values of the "ik_goal" flag.  With nh rows, p rows are [q_nominal; goal] (ndof + nh) and
+// multiplier rows nh + 2 ndof:
+enum class IkGoal : int {
+  Position = 0,  // p_goal: 3 rows
+  Pose = 1,      // oh_ik_desc.orientation: [p_goal; quat_goal], 7 rows
+  Axis = 2,      // oh_ik_set_axis_goal: [p_goal; u_goal], 6 rows
+};
+bool oh_launch_ik(hipStream_t s, IkGoal goal, const oh_chain* d_chain, const IkParams& P, int B, const double* x0, const double* p, double* x, double* f,
+                  double* kkt, int* iters, int* status, double* mult);
 
 // ---- OH_PROBLEM_QP -----------------------------------------------------------------------------------------
 struct QpParams {

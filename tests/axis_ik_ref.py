@@ -2,11 +2,12 @@
 
     min_q  w ||q - qN||^2   s.t.  h(q) = [p_goal - p_link(q); u_goal - u(q)] = 0,   lo <= q <= up,      u(q) = R_link(q) a,  |a| = 1
 
-`solve_axis_ik_al` is oracle/ik_al.py's state machine (what k_ik_axis_solve runs) with six equality rows; `AxisIKNLP` is the literal reference form of
+`solve_axis_ik_al` is oracle/ik_al.py's iteration (solve_rows_al: what the kernel runs) on `AxisRows`, six equality rows; `AxisIKNLP` is the literal reference form of
 the same problem for kkt_reference_form.  The axis derivatives are written the long way -- the 3 x n Jacobian with columns om_j x u, the curvature
 y . (om_a x (om_b x u)) term by term -- not with the identities the kernel uses, so device against port also checks those."""
 import numpy as np
 
+from oracle.ik_al import solve_rows_al
 from oracle.problems import IKExampleNLP
 from oracle.robot import OracleRobot
 from oracle.structured import FoldedChain
@@ -51,98 +52,29 @@ def merit_derivatives(chain, w, q, qn, frames, y, rho, hessian=True):
     return grad, H, J
 
 
+class AxisRows:
+    """Rows of the position-plus-axis goal for oracle.ik_al.solve_rows_al: value = [p_link; R_link a], six rows, derivatives the long way
+    (merit_derivatives).  A pass without an evaluation counts as one towards the cap (IkAxisRows in oh_ik.hip: such passes only grow lam)."""
+
+    idle_pass_counts = True
+
+    def __init__(self, chain: FoldedChain, a):
+        self.chain, self.a = chain, a
+
+    def frames(self, q):
+        return axis_frames(self.chain, self.a, q)
+
+    def value(self, frames):
+        return np.concatenate([frames[0], frames[1]])
+
+    def merit_derivatives(self, w, q, qn, frames, y, rho, hessian=True):
+        return merit_derivatives(self.chain, w, q, qn, frames, y, rho, hessian)[:2]
+
+
 def solve_axis_ik_al(chain: FoldedChain, a, x0, qn, pg, ug, lo, up, w=1.0, tol=1e-6, tol_feas=1e-9, max_iter=200, rho0=100.0):
     """Returns dict(x, f, lam_h (6, signed multipliers of the h rows in the reference's v >= 0 form), z_lo, z_up, stationarity, feasibility,
     iterations (kinematics evaluations of accepted + rejected points, plus one for every outer pass that made none), status)."""
-    n = chain.ndof
-    goal = np.concatenate([pg, ug])
-    q = np.minimum(np.maximum(np.asarray(x0, dtype=np.float64), lo), up)
-    lam = np.zeros(6)
-    rho = rho0
-    it = 0
-    status = 1
-
-    def value(fr):
-        return np.concatenate([fr[0], fr[1]])
-
-    def merit(qq, fr):
-        hh = goal - value(fr)
-        return w * np.sum((qq - qn) ** 2) + lam @ hh + 0.5 * rho * hh @ hh
-
-    fr = axis_frames(chain, a, q)
-    it += 1
-    h_prev = np.inf
-    shift = 0.0
-    if not np.isfinite(merit(q, fr)):
-        status = 2
-    while it < max_iter and status != 2:
-        it_pass = it
-        # ---- inner: projected Newton on the augmented Lagrangian ----
-        while it < max_iter:
-            h = goal - value(fr)
-            y = lam + rho * h
-            grad, H, _ = merit_derivatives(chain, w, q, qn, fr, y, rho)
-            act = ((q <= lo) & (grad > 0.0)) | ((q >= up) & (grad < 0.0))
-            pgn = np.max(np.abs(np.where(act, 0.0, grad)))
-            if pgn <= max(tol * 0.5, min(1e-2, 0.1 * np.abs(h).max())):
-                break
-            free = ~act
-            while True:
-                Hs = H + shift * np.eye(n)
-                Hs[act, :] = 0.0
-                Hs[:, act] = 0.0
-                Hs[act, act] = 1.0
-                try:
-                    L = np.linalg.cholesky(Hs)
-                    break
-                except np.linalg.LinAlgError:
-                    shift = max(10.0 * shift, 1e-3 * rho)
-            d = -np.linalg.solve(L.T, np.linalg.solve(L, np.where(free, grad, 0.0)))
-            m0 = merit(q, fr)
-            alpha = 1.0
-            ok = False
-            for _ in range(30):
-                qt = np.minimum(np.maximum(q + alpha * d, lo), up)
-                frt = axis_frames(chain, a, qt)
-                it += 1
-                if merit(qt, frt) <= m0 + 1e-4 * grad @ (qt - q) + 4e-16 * max(1.0, abs(m0)) + 8e-16 * np.abs(y).sum():
-                    ok = True
-                    break
-                alpha *= 0.5
-                if it >= max_iter:
-                    break
-            if not ok:
-                shift = max(10.0 * shift, 1e-3 * rho)
-                if shift > 1e12 * rho:
-                    status = 2
-                    break
-                continue
-            shift *= 0.1 if shift > 1e-12 else 0.0
-            q, fr = qt, frt
-        if status == 2:
-            break
-        # ---- outer: multiplier update ----
-        h = goal - value(fr)
-        lam = lam + rho * h
-        hn = np.abs(h).max()
-        grad, _, _ = merit_derivatives(chain, w, q, qn, fr, lam, 0.0, hessian=False)
-        act = ((q <= lo) & (grad > 0.0)) | ((q >= up) & (grad < 0.0))
-        stat = np.max(np.abs(np.where(act, 0.0, grad)))
-        if hn <= tol_feas and stat <= tol:
-            status = 0
-            break
-        if hn > 0.1 * h_prev:
-            rho = min(rho * 10.0, 1e8)
-        h_prev = hn
-        if it == it_pass:  # a pass without an evaluation counts as one towards the cap (k_ik_axis_solve: such passes only grow lam)
-            it += 1
-    h = goal - value(fr)
-    grad, _, _ = merit_derivatives(chain, w, q, qn, fr, lam, 0.0, hessian=False)
-    at_lo, at_up = (q <= lo) & (grad > 0.0), (q >= up) & (grad < 0.0)
-    z_lo, z_up = np.where(at_lo, grad, 0.0), np.where(at_up, -grad, 0.0)
-    stat = np.max(np.abs(np.where(at_lo | at_up, 0.0, grad)))
-    return dict(x=q, f=float(w * np.sum((q - qn) ** 2)), lam_h=-lam, z_lo=z_lo, z_up=z_up, stationarity=float(stat),
-                feasibility=float(np.abs(h).max()), iterations=it, status=status)
+    return solve_rows_al(AxisRows(chain, a), x0, qn, np.concatenate([pg, ug]), lo, up, w, tol, tol_feas, max_iter, rho0)
 
 
 class AxisIKNLP(IKExampleNLP):

@@ -2,12 +2,13 @@
 
     min_q  w ||q - qN||^2   s.t.  h(q) = [p_goal - p_link(q); quat_goal - quat_link(q)] = 0,   lo <= q <= up
 
-`solve_pose_ik_al` is oracle/ik_al.py's state machine (what k_ik_pose_solve runs) with seven equality rows; `PoseIKNLP` is the literal reference
+`solve_pose_ik_al` is oracle/ik_al.py's iteration (solve_rows_al: what the kernel runs) on `PoseRows`, seven equality rows; `PoseIKNLP` is the literal reference
 form of the same problem for kkt_reference_form; `slsqp_six_rows` is the independent solver on the six-row (minimal) form of the pose error.
 The quaternion derivatives here are written the long way -- Jq_j = 1/2 (om_j, 0) (x) quat as a 4 x n matrix, d2quat = 1/4 (om_a, 0) (x) (om_b, 0) (x) quat
 term by term -- not with the identities the kernel uses, so the comparison also checks those."""
 import numpy as np
 
+from oracle.ik_al import solve_rows_al
 from oracle.problems import IKExampleNLP, _hamilton_left_pure
 from oracle.robot import OracleRobot
 from oracle.structured import FoldedChain
@@ -107,95 +108,28 @@ def merit_derivatives(chain, w, q, qn, goal, frames, y, rho, hessian=True):
     return grad, H, J
 
 
+class PoseRows:
+    """Rows of the full-pose goal for oracle.ik_al.solve_rows_al: value = [p_link; quat_link], seven rows, derivatives the long way (merit_derivatives)."""
+
+    idle_pass_counts = False
+
+    def __init__(self, robot: OracleRobot, link: str, chain: FoldedChain):
+        self.robot, self.link, self.chain = robot, link, chain
+
+    def frames(self, q):
+        return pose_frames(self.robot, self.link, self.chain, q)
+
+    def value(self, frames):
+        return np.concatenate([frames[0], frames[1]])
+
+    def merit_derivatives(self, w, q, qn, frames, y, rho, hessian=True):
+        return merit_derivatives(self.chain, w, q, qn, None, frames, y, rho, hessian)[:2]
+
+
 def solve_pose_ik_al(robot: OracleRobot, link: str, chain: FoldedChain, x0, qn, pg, qg, lo, up, w=1.0, tol=1e-6, tol_feas=1e-9, max_iter=200, rho0=100.0):
     """Returns dict(x, f, lam_h (7, signed multipliers of the h rows in the reference's v >= 0 form), z_lo, z_up, stationarity, feasibility,
     iterations (kinematics evaluations of accepted + rejected points), status)."""
-    n = chain.ndof
-    goal = np.concatenate([pg, qg])
-    q = np.minimum(np.maximum(np.asarray(x0, dtype=np.float64), lo), up)
-    lam = np.zeros(7)
-    rho = rho0
-    it = 0
-    status = 1
-
-    def value(fr):
-        return np.concatenate([fr[0], fr[1]])
-
-    def merit(qq, fr):
-        hh = goal - value(fr)
-        return w * np.sum((qq - qn) ** 2) + lam @ hh + 0.5 * rho * hh @ hh
-
-    fr = pose_frames(robot, link, chain, q)
-    it += 1
-    h_prev = np.inf
-    shift = 0.0
-    if not np.isfinite(merit(q, fr)):
-        status = 2
-    while it < max_iter and status != 2:
-        # ---- inner: projected Newton on the augmented Lagrangian ----
-        while it < max_iter:
-            h = goal - value(fr)
-            y = lam + rho * h
-            grad, H, _ = merit_derivatives(chain, w, q, qn, goal, fr, y, rho)
-            act = ((q <= lo) & (grad > 0.0)) | ((q >= up) & (grad < 0.0))
-            pgn = np.max(np.abs(np.where(act, 0.0, grad)))
-            if pgn <= max(tol * 0.5, min(1e-2, 0.1 * np.abs(h).max())):
-                break
-            free = ~act
-            while True:
-                Hs = H + shift * np.eye(n)
-                Hs[act, :] = 0.0
-                Hs[:, act] = 0.0
-                Hs[act, act] = 1.0
-                try:
-                    L = np.linalg.cholesky(Hs)
-                    break
-                except np.linalg.LinAlgError:
-                    shift = max(10.0 * shift, 1e-3 * rho)
-            d = -np.linalg.solve(L.T, np.linalg.solve(L, np.where(free, grad, 0.0)))
-            m0 = merit(q, fr)
-            alpha = 1.0
-            ok = False
-            for _ in range(30):
-                qt = np.minimum(np.maximum(q + alpha * d, lo), up)
-                frt = pose_frames(robot, link, chain, qt)
-                it += 1
-                if merit(qt, frt) <= m0 + 1e-4 * grad @ (qt - q) + 4e-16 * max(1.0, abs(m0)) + 8e-16 * np.abs(y).sum():
-                    ok = True
-                    break
-                alpha *= 0.5
-                if it >= max_iter:
-                    break
-            if not ok:
-                shift = max(10.0 * shift, 1e-3 * rho)
-                if shift > 1e12 * rho:
-                    status = 2
-                    break
-                continue
-            shift *= 0.1 if shift > 1e-12 else 0.0
-            q, fr = qt, frt
-        if status == 2:
-            break
-        # ---- outer: multiplier update ----
-        h = goal - value(fr)
-        lam = lam + rho * h
-        hn = np.abs(h).max()
-        grad, _, _ = merit_derivatives(chain, w, q, qn, goal, fr, lam, 0.0, hessian=False)
-        act = ((q <= lo) & (grad > 0.0)) | ((q >= up) & (grad < 0.0))
-        stat = np.max(np.abs(np.where(act, 0.0, grad)))
-        if hn <= tol_feas and stat <= tol:
-            status = 0
-            break
-        if hn > 0.1 * h_prev:
-            rho = min(rho * 10.0, 1e8)
-        h_prev = hn
-    h = goal - value(fr)
-    grad, _, _ = merit_derivatives(chain, w, q, qn, goal, fr, lam, 0.0, hessian=False)
-    at_lo, at_up = (q <= lo) & (grad > 0.0), (q >= up) & (grad < 0.0)
-    z_lo, z_up = np.where(at_lo, grad, 0.0), np.where(at_up, -grad, 0.0)
-    stat = np.max(np.abs(np.where(at_lo | at_up, 0.0, grad)))
-    return dict(x=q, f=float(w * np.sum((q - qn) ** 2)), lam_h=-lam, z_lo=z_lo, z_up=z_up, stationarity=float(stat),
-                feasibility=float(np.abs(h).max()), iterations=it, status=status)
+    return solve_rows_al(PoseRows(robot, link, chain), x0, qn, np.concatenate([pg, qg]), lo, up, w, tol, tol_feas, max_iter, rho0)
 
 
 class PoseIKNLP(IKExampleNLP):
