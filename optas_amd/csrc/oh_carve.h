@@ -133,9 +133,10 @@ inline void layout_tq(Carver& c, TqBuffers& D, const int B, const int T) {
   D.lam = c.take<double>(2 * BT * TQ_LAM);
   D.gains = c.take<double>(BT * TQ_GN);
   D.goal = c.take<double>(BT * 4);
-  for (double** p : {&D.f_cur, &D.f_true, &D.bsum, &D.mu, &D.nun, &D.mub, &D.stat, &D.alpha, &D.qk, &D.ndx, &D.viol}) *p = c.take<double>(B);
-  for (int** p : {&D.cur, &D.first, &D.curv, &D.status, &D.iters, &D.rejected, &D.n_barrier, &D.nrel, &D.n_back, &D.stall, &D.curv_age, &D.list})
-    *p = c.take<int>(B);
+#define X(type, name, init) D.name = c.take<type>(B);
+  OH_TQ_INST(X)  // the doubles, then the ints
+#undef X
+  D.list = c.take<int>(B);
   D.n_running = c.take<int>(1);
   D.n_list = c.take<int>(1);
   c.take<int>(14);  // slack the pool has always had behind its last array (12 B + 16 ints in all)

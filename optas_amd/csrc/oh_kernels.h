@@ -87,18 +87,42 @@ void oh_launch_pm_tick_params(hipStream_t s, int B, int T, int tick, int advance
 void oh_launch_pm_advance(hipStream_t s, int B, int T, int advance, const double* x, double* state_next);
 
 // ---- OH_PROBLEM_TORQUE_MPC (BASELINE configs[4]: RNEA dynamics rows) -------------------------------
-// Layouts are unit-contiguous ([instance][knot][...]): the evaluation kernel works with one lane per (instance, knot,
-// joint) and the Riccati kernel with 16 lanes per instance, so a wavefront reads whole stage records.
-#define TQ_XS 24    // per knot: q (N) at 0, dq (N) at 8, ddq (N) at 16
-// per knot stage record: H packed lower (3N)(3N+1)/2 at 0 | g_f (3N) at 231: gradient of the cost | f 252, barrier sum B 253, relaxed rows 254, viol 255 |
-// tau (N) at 256 | max lam s 263 | g_b (3N) at 272: gradient of the barrier per unit mu_b (the stage gradient is g_f + mu_b g_b) | d tau / d z (N x 3N
-// row-major) at 296: the step kernel's fraction-to-the-boundary rule needs the linearised rows
-#define TQ_SD 448
-#define TQ_SD_GB 272
-#define TQ_SD_J 296
-#define TQ_LAM 32   // per knot: multipliers of tau - lo >= 0 (N), then of up - tau >= 0 (N); at 16: of dq - dq_lo >= 0 (N), then of dq_up - dq >= 0 (N)
+// Layouts are unit-contiguous ([instance][knot][...]): the evaluation kernels work with one lane per (instance, knot,
+// joint) and the step kernel with one wavefront per instance, so a wavefront reads whole records.
+// The records, named once (offsets in doubles; every block of N joints has room for 8):
+struct TqKnot {  // per knot of D.xs
+  static constexpr int q = 0, dq = 8, ddq = 16, size = 24;
+  static constexpr int pad = 7;  // the 8th word of each block: zero
+};
+struct TqStage {  // per knot of D.st
+  static constexpr int H = 0;          // stage block, packed lower (3N)(3N+1)/2: tq_packed(row, col) over (q | dq | ddq)
+  static constexpr int g_f = 231;      // gradient of the cost (3N)
+  static constexpr int f = 252, barrier = 253, relaxed = 254, viol = 255;  // cost, barrier sum per unit mu_b, rows in the relaxed zone, worst violation
+  static constexpr int tau = 256;      // torques (N)
+  static constexpr int cmpl = 263;     // max lam s
+  static constexpr int g_b = 272;      // gradient of the barrier per unit mu_b (3N): the stage gradient is g_f + mu_b g_b
+  static constexpr int J = 296;        // d tau / d z, N x 3N row-major: the step kernel's fraction-to-the-boundary rule needs the linearised rows
+  static constexpr int size = 448;
+};
+struct TqLam {  // per knot of D.lam: multipliers of tau - lo >= 0 (N) at 0, of up - tau >= 0 (N) at N; velocity rows alike from `vel`
+  static constexpr int vel = 16, size = 32;
+};
+constexpr int tq_packed(const int row, const int col) { return row * (row + 1) / 2 + col; }  // row >= col
+constexpr int TQ_NZ_MAX = 3 * 7;  // (q | dq | ddq) of the longest chain
+static_assert(TqStage::g_f == tq_packed(TQ_NZ_MAX, 0) && TqStage::g_f == TQ_NZ_MAX * (TQ_NZ_MAX + 1) / 2, "the gradient follows the packed 21 x 21 block");
+static_assert(TqStage::f == TqStage::g_f + TQ_NZ_MAX && TqStage::barrier == TqStage::f + 1 && TqStage::relaxed == TqStage::barrier + 1 && TqStage::viol == TqStage::relaxed + 1,
+              "the four sums follow the gradient");
+static_assert(TqStage::tau == TqStage::viol + 1 && TqStage::cmpl == TqStage::tau + 7 && TqStage::g_b > TqStage::cmpl && TqStage::J >= TqStage::g_b + TQ_NZ_MAX &&
+                  TqStage::J + 7 * TQ_NZ_MAX <= TqStage::size,
+              "no two fields of the stage record overlap, the last one ends inside it");
+static_assert(TqKnot::dq >= TqKnot::q + 7 && TqKnot::ddq >= TqKnot::dq + 7 && TqKnot::size >= TqKnot::ddq + 7 && TqKnot::pad == 7, "three blocks of up to 7 joints");
+static_assert(TqLam::vel >= 2 * 7 && TqLam::size >= TqLam::vel + 2 * 7, "two blocks of 2 N multipliers");
+#define TQ_XS TqKnot::size
+#define TQ_SD TqStage::size
+#define TQ_LAM TqLam::size
 #define TQ_HC 232   // per knot: the packed lower triangle of the 3N x 3N curvature term (231 entries at N = 7)
 #define TQ_GN 128   // per knot: two doubles per lane of k_tq_step (lane 8 r + c: K_q[r][c], K_dq[r][c]; c = 7: k[r], 0)
+static_assert(TQ_HC >= TqStage::g_f, "the curvature term is a packed block of its own");
 struct TqParams {
   int T, N, max_iter;
   double dt, w_path, w_vel, w_tau, tol, tol_compl, mu_b0, mu0;
@@ -119,6 +143,31 @@ struct TqParams {
   int jac_closed_form;  // d tau / dz in closed form (rnea_idsva) -- the dynamics tables describe a rigid-body chain; 0: dual numbers through the recursion
   int nx, np;
 };
+// The per-instance scalars and counters, listed ONCE as (type, name, value at setup; P: the TqParams): TqBuffers' [B] arrays, layout_tq's takes (in this
+// order: the doubles, then the ints -- the pool's offsets depend on it), TqInst's fields, its load and its store all come from this table.
+#define OH_TQ_INST(X)                                                                                                                  \
+  X(double, f_cur, 0.0)    /* merit of the accepted point */                                                                           \
+  X(double, f_true, 0.0)   /* its cost */                                                                                              \
+  X(double, bsum, 0.0)     /* its barrier sum per unit mu_b */                                                                         \
+  X(double, mu, P.mu0)     /* Levenberg-Marquardt damping */                                                                           \
+  X(double, nun, 4.0)      /* its growth factor */                                                                                     \
+  X(double, mub, P.mu_b0)  /* barrier parameter */                                                                                     \
+  X(double, stat, 0.0)     /* reduced gradient */                                                                                      \
+  X(double, alpha, 1.0)    /* scale of the feed-forward of the pending trial */                                                        \
+  X(double, qk, 0.0)       /* q_u^T k of the unit step ... */                                                                          \
+  X(double, ndx, 0.0)      /* ... and its |dx|^2: predicted decrease of a scaled step */                                               \
+  X(double, viol, 0.0)     /* worst violation of a row at the accepted point */                                                        \
+  X(int, cur, 1)           /* slot of the accepted point (the seed sits in slot 0 = the first "trial") */                              \
+  X(int, first, 1)         /* the pending trial is accepted as it is */                                                                \
+  X(int, curv, 0)          /* exact curvature at the pending evaluation: 1 k_tq_curv computes it, 2 k_tq_eval3 adds the stored term */ \
+  X(int, status, -1)                                                                                                                   \
+  X(int, iters, 0)                                                                                                                     \
+  X(int, rejected, 0)                                                                                                                  \
+  X(int, n_barrier, 0)     /* barrier updates so far */                                                                                \
+  X(int, nrel, 0)          /* rows of the accepted point inside the relaxed zone */                                                    \
+  X(int, n_back, 0)        /* quarterings of the pending step */                                                                       \
+  X(int, stall, 0)         /* steps at this barrier parameter without reaching its test */                                             \
+  X(int, curv_age, -1)     /* evaluations since the stored curvature term was computed (-1: none stored) */
 struct TqBuffers {
   int B;
   const oh_chain* chain;
@@ -129,15 +178,38 @@ struct TqBuffers {
   double* gains;   // [B][T][TQ_GN]
   double* goal;    // [B][T][4]
   double* hc;      // [cap][T][TQ_HC]  the curvature term k_tq_curv last computed for a knot (entries it never writes stay 0)
-  // [B]: merit and cost of the accepted point, its barrier sum, Levenberg-Marquardt damping and its growth factor, barrier parameter, reduced gradient,
-  // scale of the feed-forward of the pending trial, q_u^T k and |dx|^2 of the unit step (predicted decrease of a scaled step), violation
-  double *f_cur, *f_true, *bsum, *mu, *nun, *mub, *stat, *alpha, *qk, *ndx, *viol;
-  int* curv_age;   // [B] evaluations since the stored curvature term was computed (-1: none stored)
-  int *cur, *first, *curv, *status, *iters, *rejected, *n_barrier, *nrel, *n_back, *stall;  // [B]
+#define X(type, name, init) type* name;
+  OH_TQ_INST(X)  // [B] each
+#undef X
   int* n_running;  // [1]
   int* list;       // [B] instances still running when the list was last rebuilt (kernels walk this list: finished instances cost nothing)
   int* n_list;     // [1]
   int n_run;       // length of the list the launches below cover
+};
+// One instance's scalars in registers: k_tq_setup stores a fresh one, k_tq_step loads one, walks its steps and stores it.
+struct TqInst {
+#define X(type, name, init) type name;
+  OH_TQ_INST(X)
+#undef X
+  static __device__ __forceinline__ TqInst fresh(const TqParams& P) {
+    TqInst S;
+#define X(type, name, init) S.name = init;
+    OH_TQ_INST(X)
+#undef X
+    return S;
+  }
+  static __device__ __forceinline__ TqInst load(const TqBuffers& D, const int b) {
+    TqInst S;
+#define X(type, name, init) S.name = D.name[b];
+    OH_TQ_INST(X)
+#undef X
+    return S;
+  }
+  __device__ __forceinline__ void store(const TqBuffers& D, const int b) const {
+#define X(type, name, init) D.name[b] = name;
+    OH_TQ_INST(X)
+#undef X
+  }
 };
 void oh_launch_tq_list(hipStream_t s, const TqBuffers& D);
 bool oh_launch_tq_setup(hipStream_t s, const TqParams& P, const TqBuffers& D, const double* x0, const double* p);

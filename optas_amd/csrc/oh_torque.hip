@@ -19,16 +19,25 @@
 //               the lanes of a unit exchange their columns through LDS and write the stage block H_t (packed lower 21 x 21), the gradients of cost
 //               and barrier, and d tau / d z.
 //   k_tq_curv   same mapping: second derivatives of the inverse dynamics and of the link position, added to H_t for instances in the Newton phase.
-//   k_tq_step   16 lanes per instance (4 instances per wavefront): ratio test, costate recursion for the stationarity measure, barrier update,
-//               Riccati sweep with the value matrix P (14 x 14) in LDS and one column per lane, fraction to the boundary, rollout of the trial.
+//   k_tq_step   one wavefront per instance, lane 8 r + c = entry (r, c) of every N x N block: ratio test, costate recursion for the stationarity measure,
+//               barrier update, Riccati sweep by Gauss-Jordan steps across the lanes (no LDS, no barrier), fraction to the boundary, rollout of the trial.
+//               Its scalar state machine is oh_tq_machine.h.
+// Records (TqKnot, TqStage, TqLam), the table of the per-instance scalars and TqInst: oh_kernels.h.
 #include "oh_kernels.h"
 #include "oh_rnea.h"
+#include "oh_tq_machine.h"
 
 namespace {
 using namespace oh_dyn;
 
-OH_DEV size_t xs_off(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return (((size_t)slot * D.B + b) * T + t) * TQ_XS; }
-OH_DEV size_t st_off(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return (((size_t)slot * D.B + b) * T + t) * TQ_SD; }
+// One address helper per array: the record of knot t of instance b (xs, st, lam: in slot 0 / 1).
+OH_DEV size_t tq_knot(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return ((size_t)slot * D.B + b) * T + t; }
+OH_DEV double* tq_xs(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return D.xs + tq_knot(D, T, slot, b, t) * TqKnot::size; }
+OH_DEV double* tq_st(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return D.st + tq_knot(D, T, slot, b, t) * TqStage::size; }
+OH_DEV double* tq_lam(const TqBuffers& D, const int T, const int slot, const int b, const int t) { return D.lam + tq_knot(D, T, slot, b, t) * TqLam::size; }
+OH_DEV double* tq_goal(const TqBuffers& D, const int T, const int b, const int t) { return D.goal + tq_knot(D, T, 0, b, t) * 4; }
+OH_DEV double* tq_hc(const TqBuffers& D, const int T, const int b, const int t) { return D.hc + tq_knot(D, T, 0, b, t) * TQ_HC; }
+OH_DEV double* tq_gains(const TqBuffers& D, const int T, const int b, const int t) { return D.gains + tq_knot(D, T, 0, b, t) * TQ_GN; }
 
 // ---- setup: reference layouts -> device records ---------------------------------------------------------------------------------
 // x0 [B][4 N T] = [vec(Q); vec(dQ); vec(ddQ); vec(TAU)] (only ddQ is a free variable: q, dq are rolled out, tau follows from the dynamics rows);
@@ -47,49 +56,25 @@ __global__ __launch_bounds__(64) void k_tq_setup(TqParams P, TqBuffers D, const 
     dq[j] = pb[N + j];
   }
   for (int t = 0; t < T; ++t) {
-    double* r = D.xs + xs_off(D, T, 0, b, t);
-    double* r1 = D.xs + xs_off(D, T, 1, b, t);
+    double* r = tq_xs(D, T, 0, b, t);
+    double* r1 = tq_xs(D, T, 1, b, t);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const double u = xb[2 * N * T + N * t + j];
-      r[j] = q[j];
-      r[8 + j] = dq[j];
-      r[16 + j] = u;
-      r1[j] = q[j];
-      r1[8 + j] = dq[j];
-      r1[16 + j] = u;
+      r[TqKnot::q + j] = r1[TqKnot::q + j] = q[j];
+      r[TqKnot::dq + j] = r1[TqKnot::dq + j] = dq[j];
+      r[TqKnot::ddq + j] = r1[TqKnot::ddq + j] = u;
       q[j] = q[j] + P.dt * dq[j];
       dq[j] = dq[j] + P.dt * u;
     }
-    r[7] = r[15] = r[23] = r1[7] = r1[15] = r1[23] = 0.0;
-    double* gl = D.goal + ((size_t)b * T + t) * 4;
+    for (const int blk : {TqKnot::q, TqKnot::dq, TqKnot::ddq}) r[blk + TqKnot::pad] = r1[blk + TqKnot::pad] = 0.0;
+    double* gl = tq_goal(D, T, b, t);
     gl[0] = pb[2 * N + 3 * t];
     gl[1] = pb[2 * N + 3 * t + 1];
     gl[2] = pb[2 * N + 3 * t + 2];
     gl[3] = 0.0;
   }
-  D.f_cur[b] = 0.0;
-  D.f_true[b] = 0.0;
-  D.bsum[b] = 0.0;
-  D.mu[b] = P.mu0;
-  D.nun[b] = 4.0;
-  D.mub[b] = P.mu_b0;
-  D.stat[b] = 0.0;
-  D.alpha[b] = 1.0;
-  D.qk[b] = 0.0;
-  D.ndx[b] = 0.0;
-  D.viol[b] = 0.0;
-  D.cur[b] = 1;  // the seed sits in slot 0 = the first "trial"
-  D.first[b] = 1;
-  D.curv[b] = 0;
-  D.curv_age[b] = -1;
-  D.status[b] = -1;
-  D.iters[b] = 0;
-  D.rejected[b] = 0;
-  D.n_barrier[b] = 0;
-  D.nrel[b] = 0;
-  D.n_back[b] = 0;
-  D.stall[b] = 0;
+  TqInst::fresh(P).store(D, b);
   D.list[b] = b;
 }
 
@@ -133,6 +118,62 @@ OH_DEV TqRow tq_row(const double s, const double s_old, const double lam_old, co
   return r;
 }
 
+// The lane map of both evaluation kernels: lane -> (unit in the wavefront, joint), unit -> (entry of the running list, knot).  64 / N units per
+// wavefront; the lanes behind the last whole unit (lane 63 of the 7-joint arm) have none: they ride along on the last unit and keep their hands off
+// LDS (lane_ok).  Units past the end of the list are clamped onto its last one and are not `active`, as are those of an instance that has finished.
+template <int N>
+struct TqUnit {
+  static constexpr int UPW = 64 / N;  // units per wavefront (9 of the 7-joint arm)
+  int ul, j, t, b;
+  bool lane_ok, active;
+  OH_DEV TqUnit(const TqBuffers& D, const int T, const int lane, const int block) {
+    ul = lane / N, j = lane - ul * N;
+    lane_ok = ul < UPW;
+    if (!lane_ok) {
+      ul = UPW - 1;
+      j = N - 1;
+    }
+    const long long n_units = (long long)D.n_run * T;
+    long long unit = (long long)block * UPW + ul;
+    active = lane_ok && unit < n_units;
+    if (unit >= n_units) unit = n_units - 1;
+    const int li = (int)(unit / T);
+    t = (int)(unit - (long long)li * T);
+    b = D.list[li];
+    if (D.status[b] >= 0) active = false;
+  }
+};
+
+// Link position e = p + R p_tool at the configuration qv (models.py:826-868), its residual r = e - goal and column j of its Jacobian (models.py:1211-1264:
+// z_j x (e - o_j) for a revolute joint, z_j for a prismatic one); z: the joint axes, which the second derivative needs as well.
+template <int N>
+OH_DEV void tq_link_column(const oh_chain* chain, const double (&qv)[N], const double* gl, const int j, double (&r)[3], double (&jp)[3], double (&z)[N][3]) {
+  double R[9], pp[3], pj[N][3];
+  fk_chain<N>(chain, qv, R, pp, z, pj);
+  double e[3], tv3[3];
+  mv3(R, chain->p_tool, tv3);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    e[k] = pp[k] + tv3[k];
+    r[k] = e[k] - gl[k];
+  }
+  double zd[3] = {0.0, 0.0, 0.0}, pd[3] = {0.0, 0.0, 0.0};
+  int jt_d = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    if (k == j) {
+      zd[0] = z[k][0]; zd[1] = z[k][1]; zd[2] = z[k][2];
+      pd[0] = pj[k][0]; pd[1] = pj[k][1]; pd[2] = pj[k][2];
+      jt_d = chain->jtype[k];
+    }
+  if (jt_d == 0) {
+    const double dd[3] = {e[0] - pd[0], e[1] - pd[1], e[2] - pd[2]};
+    cross3(zd, dd, jp);
+  } else {
+    jp[0] = zd[0]; jp[1] = zd[1]; jp[2] = zd[2];
+  }
+}
+
 // One lane per (instance, knot, JOINT): 9 units x 7 joints per wavefront.  Lane j runs the reference's Newton-Euler recursion once on (Jet<1>, Jet<3>)
 // scalars seeded with q_j, dq_j and ddq_j (d tau / d z is the tangent output: the derivative of the literal recursion by construction), so it ends up
 // with columns j, N + j and 2 N + j of d tau / d z; the chain walk for p_link adds column j of its Jacobian.  The columns meet in LDS and every lane
@@ -141,7 +182,7 @@ OH_DEV TqRow tq_row(const double s, const double s_old, const double lam_old, co
 template <int N, bool VEL = false, bool IDS = true>
 __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuffers D) {
   constexpr int NZ = 3 * N;
-  constexpr int UPW = 64 / N;  // units per wavefront (9)
+  constexpr int UPW = TqUnit<N>::UPW;
   // A unit's LDS.  Closed-form path: IdsWs<N> (277 doubles: two blocks per SIMD).  Jet path: tile [N + 3][NZ + 1], row coefficients, (q|dq|ddq).
   using L = IdsWs<N>;
   constexpr int TW = IDS ? L::TW : NZ + 1;                  // pitch of rows 0 .. N-1 of the tile (d tau / dz)
@@ -157,33 +198,23 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
   const int T = P.T;
   const int lane = threadIdx.x;
   if (blockIdx.x == 0 && lane == 0) *D.n_running = 0;  // k_tq_step, next in the stream, counts the instances that go on
-  int ul = lane / N, j = lane - ul * N;
-  const bool lane_ok = ul < UPW;
-  if (!lane_ok) {  // lane 63 has no unit: it rides along on the last unit and keeps its hands off LDS
-    ul = UPW - 1;
-    j = N - 1;
-  }
-  const long long n_units = (long long)D.n_run * T;
-  long long unit = (long long)blockIdx.x * UPW + ul;
-  bool active = lane_ok && unit < n_units;
-  if (unit >= n_units) unit = n_units - 1;
-  const int li = (int)(unit / T), t = (int)(unit - (long long)li * T);
-  const int b = D.list[li];
-  if (D.status[b] >= 0) active = false;
+  const TqUnit<N> U(D, T, lane, blockIdx.x);
+  const int ul = U.ul, j = U.j, t = U.t, b = U.b;
+  const bool lane_ok = U.lane_ok, active = U.active;
   if (!__any(active)) return;
   const int cur = D.cur[b], ts = 1 - cur;
-  const double* xr = D.xs + xs_off(D, T, ts, b, t);
+  const double* xr = tq_xs(D, T, ts, b, t);
   const bool have_old = D.first[b] == 0;
   const double mub = D.mub[b], delta = P.theta * mub;
 
   // 1. torques and their derivative: lane j leaves its three columns in the unit's tile and keeps tau_j
   double* tl = lds_raw + ul * WS;
   double* qs_u = tl + QS;
-  const double qj = xr[j], dqj = xr[8 + j];
-  if (lane_ok) {  // the recursions read (q | dq | ddq) of their unit by a loop counter: LDS, not a lane-private array
-    qs_u[j] = qj;
-    qs_u[8 + j] = dqj;
-    qs_u[16 + j] = xr[16 + j];
+  const double qj = xr[TqKnot::q + j], dqj = xr[TqKnot::dq + j];
+  if (lane_ok) {  // the recursions read (q | dq | ddq) of their unit by a loop counter: LDS, not a lane-private array (laid out as the knot record)
+    qs_u[TqKnot::q + j] = qj;
+    qs_u[TqKnot::dq + j] = dqj;
+    qs_u[TqKnot::ddq + j] = xr[TqKnot::ddq + j];
   }
   __syncthreads();
   double qv[N];
@@ -209,10 +240,10 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
 
   // 2. inequality rows under the barrier: lane j takes the rows of joint j (a row costs two divisions and a logarithm: ~350 instructions -- with every
   // lane computing all 14 of them, as until round 4, they were a third of the kernel); the unit shares cf, cb, dw and the sums through LDS
-  const double* lm_old = D.lam + (((size_t)cur * D.B + b) * T + t) * TQ_LAM;
-  double* lm_new = D.lam + (((size_t)ts * D.B + b) * T + t) * TQ_LAM;
-  const double* sr_old = D.st + st_off(D, T, cur, b, t);
-  const double* xr_old = D.xs + xs_off(D, T, cur, b, t);
+  const double* lm_old = tq_lam(D, T, cur, b, t);
+  double* lm_new = tq_lam(D, T, ts, b, t);
+  const double* sr_old = tq_st(D, T, cur, b, t);
+  const double* xr_old = tq_xs(D, T, cur, b, t);
   double cbv = 0.0, dvj = 0.0;
   {
     double tlo = 0.0, tup = 0.0, vlo = 0.0, vup = 0.0;
@@ -225,7 +256,7 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
         vup = (i == j) ? P.dq_up[i] : vup;
       }
     }
-    const double tv_old = have_old ? sr_old[256 + j] : 0.0;
+    const double tv_old = have_old ? sr_old[TqStage::tau + j] : 0.0;
     const TqRow lo = tq_row(tvj - tlo, tv_old - tlo, have_old ? lm_old[j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
     const TqRow up = tq_row(tup - tvj, tup - tv_old, have_old ? lm_old[N + j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
     double bar_j = lo.bar + up.bar;
@@ -238,9 +269,9 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
     }
     // joint-velocity rows on the velocity states (enforce_model_limits(name, time_deriv=1), builder.py:471-509): stage-local, linear in the state
     if constexpr (VEL) {
-      const double dv_old = have_old ? xr_old[8 + j] : 0.0;
-      const TqRow l2 = tq_row(dqj - vlo, dv_old - vlo, have_old ? lm_old[16 + j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
-      const TqRow u2 = tq_row(vup - dqj, vup - dv_old, have_old ? lm_old[16 + N + j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
+      const double dv_old = have_old ? xr_old[TqKnot::dq + j] : 0.0;
+      const TqRow l2 = tq_row(dqj - vlo, dv_old - vlo, have_old ? lm_old[TqLam::vel + j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
+      const TqRow u2 = tq_row(vup - dqj, vup - dv_old, have_old ? lm_old[TqLam::vel + N + j] : 0.0, have_old, mub, delta, 1.0 - P.tau_ftb);
       bar_j += l2.bar + u2.bar;
       nrel_j += (l2.relaxed ? 1.0 : 0.0) + (u2.relaxed ? 1.0 : 0.0);
       viol_j = fmax(viol_j, fmax(vlo - dqj, dqj - vup));
@@ -248,8 +279,8 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
       cbv = u2.bco - l2.bco;
       dvj = l2.sig + u2.sig;
       if (active) {
-        lm_new[16 + j] = l2.lam;
-        lm_new[16 + N + j] = u2.lam;
+        lm_new[TqLam::vel + j] = l2.lam;
+        lm_new[TqLam::vel + N + j] = u2.lam;
       }
     }
     __syncthreads();  // (the last row of d tau / dz is in its slot: the slots' spare words are free)
@@ -268,31 +299,8 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
   // 3. link position and column j of its Jacobian (models.py:826-868, 1211-1264); its rows take the place of the screws and of (q | dq | ddq)
   double jp[3], r[3];
   {
-    double R[9], pp[3], z[N][3], pj[N][3];
-    fk_chain<N>(D.chain, qv, R, pp, z, pj);
-    double e[3], tv3[3];
-    mv3(R, D.chain->p_tool, tv3);
-    const double* gl = D.goal + ((size_t)b * T + t) * 4;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      e[k] = pp[k] + tv3[k];
-      r[k] = e[k] - gl[k];
-    }
-    double zd[3] = {0.0, 0.0, 0.0}, pd[3] = {0.0, 0.0, 0.0};
-    int jt_d = 0;
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k == j) {
-        zd[0] = z[k][0]; zd[1] = z[k][1]; zd[2] = z[k][2];
-        pd[0] = pj[k][0]; pd[1] = pj[k][1]; pd[2] = pj[k][2];
-        jt_d = D.chain->jtype[k];
-      }
-    if (jt_d == 0) {
-      const double dd[3] = {e[0] - pd[0], e[1] - pd[1], e[2] - pd[2]};
-      cross3(zd, dd, jp);
-    } else {
-      jp[0] = zd[0]; jp[1] = zd[1]; jp[2] = zd[2];
-    }
+    double z[N][3];
+    tq_link_column<N>(D.chain, qv, tq_goal(D, T, b, t), j, r, jp, z);
   }
   if (lane_ok) {  // the link position has no dq / ddq columns
 #pragma unroll
@@ -331,9 +339,9 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
   g0 += 2.0 * P.w_path * dot3(jp, r);
   g1 += 2.0 * P.w_vel * dqj;
   h1 += cbv;
-  double* sr = D.st + st_off(D, T, ts, b, t);
+  double* sr = tq_st(D, T, ts, b, t);
   // exact curvature, stored term (D.curv = 2: k_tq_curv computed it at an earlier evaluation of this instance and skips this one): added as the block is written
-  const double* hc = D.hc + ((size_t)b * T + t) * TQ_HC;
+  const double* hc = tq_hc(D, T, b, t);
   const bool add_hc = D.curv[b] == 2;
   if (active) {
 #pragma unroll
@@ -356,26 +364,26 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
           hv += 2.0 * P.w_vel;
           hv += dvj;
         }
-        if (add_hc) hv += hc[rr * (rr + 1) / 2 + d];
-        sr[rr * (rr + 1) / 2 + d] = hv;
+        if (add_hc) hv += hc[tq_packed(rr, d)];
+        sr[TqStage::H + tq_packed(rr, d)] = hv;
       }
 #pragma unroll
-      for (int i = 0; i < N; ++i) sr[TQ_SD_J + i * NZ + d] = c3 == 0 ? J0[i] : (c3 == 1 ? J1[i] : J2[i]);
+      for (int i = 0; i < N; ++i) sr[TqStage::J + i * NZ + d] = c3 == 0 ? J0[i] : (c3 == 1 ? J1[i] : J2[i]);
     }
-    sr[231 + j] = g0;
-    sr[231 + N + j] = g1;
-    sr[231 + 2 * N + j] = g2;
-    sr[TQ_SD_GB + j] = h0;
-    sr[TQ_SD_GB + N + j] = h1;
-    sr[TQ_SD_GB + 2 * N + j] = h2;
+    sr[TqStage::g_f + j] = g0;
+    sr[TqStage::g_f + N + j] = g1;
+    sr[TqStage::g_f + 2 * N + j] = g2;
+    sr[TqStage::g_b + j] = h0;
+    sr[TqStage::g_b + N + j] = h1;
+    sr[TqStage::g_b + 2 * N + j] = h2;
     if (j == 0) {
-      sr[252] = P.w_path * dot3(r, r) + fsum;
-      sr[253] = bar;
-      sr[254] = (double)nrel;
-      sr[255] = viol;
-      sr[263] = cmpl;
+      sr[TqStage::f] = P.w_path * dot3(r, r) + fsum;
+      sr[TqStage::barrier] = bar;
+      sr[TqStage::relaxed] = (double)nrel;
+      sr[TqStage::viol] = viol;
+      sr[TqStage::cmpl] = cmpl;
     }
-    sr[256 + j] = tvj;
+    sr[TqStage::tau + j] = tvj;
   }
 }
 
@@ -392,63 +400,36 @@ __global__ __launch_bounds__(64, IDS ? 2 : 1) void k_tq_eval3(TqParams P, TqBuff
 #endif
 template <int N>
 __global__ __launch_bounds__(64, OH_TQ_CURV_WAVES) void k_tq_curv(TqParams P, TqBuffers D) {
-  constexpr int UPW = 64 / N;
-  __shared__ double zs_l[UPW][32];
+  constexpr int UPW = TqUnit<N>::UPW;
+  __shared__ double zs_l[UPW][TqKnot::size + 8];  // a unit's knot record (q | dq | ddq) and, behind it, cH
   const int T = P.T;
   const int lane = threadIdx.x;
-  int ul = lane / N, j = lane - ul * N;
-  const bool lane_ok = ul < UPW;
-  if (!lane_ok) {
-    ul = UPW - 1;
-    j = N - 1;
-  }
-  const long long n_units = (long long)D.n_run * T;
-  long long unit = (long long)blockIdx.x * UPW + ul;
-  bool active = lane_ok && unit < n_units;
-  if (unit >= n_units) unit = n_units - 1;
-  const int li = (int)(unit / T), t = (int)(unit - (long long)li * T);
-  const int b = D.list[li];
-  if (D.status[b] >= 0 || D.curv[b] != 1) active = false;  // (2: k_tq_eval3 has added the stored term already)
-  if (!__any(active)) return;
+  const TqUnit<N> U(D, T, lane, blockIdx.x);
+  const int ul = U.ul, j = U.j, t = U.t, b = U.b;
+  const bool lane_ok = U.lane_ok;
+  const bool comp = U.active && D.curv[b] == 1;  // (2: k_tq_eval3 has added the stored term already)
+  if (!__any(comp)) return;
   const int ts = 1 - D.cur[b];
-  const double* xr = D.xs + xs_off(D, T, ts, b, t);
-  double* sr = D.st + st_off(D, T, ts, b, t);
-  double* hc = D.hc + ((size_t)b * T + t) * TQ_HC;
-  const double* lm = D.lam + (((size_t)ts * D.B + b) * T + t) * TQ_LAM;
-  const bool comp = active;
+  const double* xr = tq_xs(D, T, ts, b, t);
+  double* sr = tq_st(D, T, ts, b, t);
+  double* H = sr + TqStage::H;
+  double* hc = tq_hc(D, T, b, t);
+  const double* lm = tq_lam(D, T, ts, b, t);
   const bool direct = P.curv_lag <= 0;
-  {
   if (lane_ok) {
-    zs_l[ul][j] = xr[j];
-    zs_l[ul][8 + j] = xr[8 + j];
-    zs_l[ul][16 + j] = xr[16 + j];
-    zs_l[ul][24 + j] = 2.0 * P.w_tau * sr[256 + j] - lm[j] + lm[N + j];
+    zs_l[ul][TqKnot::q + j] = xr[TqKnot::q + j];
+    zs_l[ul][TqKnot::dq + j] = xr[TqKnot::dq + j];
+    zs_l[ul][TqKnot::ddq + j] = xr[TqKnot::ddq + j];
+    zs_l[ul][TqKnot::size + j] = 2.0 * P.w_tau * sr[TqStage::tau + j] - lm[j] + lm[N + j];
   }
   __syncthreads();
   // curvature of the tracking term
-  double inner[3] = {0.0, 0.0, 0.0}, r[3], z[N][3];
+  double inner[3], r[3], z[N][3];
   {
-    double qv[N], R[9], pp[3], pj[N][3], e[3], tv3[3];
+    double qv[N];
 #pragma unroll
-    for (int k = 0; k < N; ++k) qv[k] = zs_l[ul][k];
-    fk_chain<N>(D.chain, qv, R, pp, z, pj);
-    mv3(R, D.chain->p_tool, tv3);
-    const double* gl = D.goal + ((size_t)b * T + t) * 4;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      e[k] = pp[k] + tv3[k];
-      r[k] = e[k] - gl[k];
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k == j) {
-        if (D.chain->jtype[k] == 0) {
-          const double dd[3] = {e[0] - pj[k][0], e[1] - pj[k][1], e[2] - pj[k][2]};
-          cross3(z[k], dd, inner);
-        } else {
-          inner[0] = z[k][0]; inner[1] = z[k][1]; inner[2] = z[k][2];
-        }
-      }
+    for (int k = 0; k < N; ++k) qv[k] = zs_l[ul][TqKnot::q + k];
+    tq_link_column<N>(D.chain, qv, tq_goal(D, T, b, t), j, r, inner, z);
   }
   if (comp) {
 #pragma unroll
@@ -457,29 +438,28 @@ __global__ __launch_bounds__(64, OH_TQ_CURV_WAVES) void k_tq_curv(TqParams P, Tq
         double x[3] = {0.0, 0.0, 0.0};
         if (D.chain->jtype[k] == 0) cross3(z[k], inner, x);
         const double v = 2.0 * P.w_path * dot3(r, x);
-        sr[j * (j + 1) / 2 + k] += v;
-        if (!direct) hc[j * (j + 1) / 2 + k] = v;
+        H[tq_packed(j, k)] += v;
+        if (!direct) hc[tq_packed(j, k)] = v;
       }
   }
   rnea_ctau_grad_inv<N + 1, Jet<2>, Jet<1>>(D.dyn, zs_l[ul], j, [&](const int k, const Jet<2> gq, const Jet<2> gqd, const Jet<2> gqdd) {
     if (!comp) return;
     // onto the stage block ...
     if (k <= j) {
-      sr[j * (j + 1) / 2 + k] += gq.d[0];
-      sr[(N + j) * (N + j + 1) / 2 + N + k] += gqd.d[1];
+      H[tq_packed(j, k)] += gq.d[0];
+      H[tq_packed(N + j, N + k)] += gqd.d[1];
     }
-    sr[(N + j) * (N + j + 1) / 2 + k] += gq.d[1];
-    sr[(2 * N + k) * (2 * N + k + 1) / 2 + j] += gqdd.d[0];
+    H[tq_packed(N + j, k)] += gq.d[1];
+    H[tq_packed(2 * N + k, j)] += gqdd.d[0];
     if (direct) return;  // curv_lag = 0: nothing is kept
     // ... and into the record the next evaluations of this instance add instead (k_tq_eval3)
     if (k <= j) {  // rows q_j and dq_j, columns up to the diagonal
-      hc[j * (j + 1) / 2 + k] += gq.d[0];
-      hc[(N + j) * (N + j + 1) / 2 + N + k] = gqd.d[1];
+      hc[tq_packed(j, k)] += gq.d[0];
+      hc[tq_packed(N + j, N + k)] = gqd.d[1];
     }
-    hc[(N + j) * (N + j + 1) / 2 + k] = gq.d[1];             // (dq_j, q_k)
-    hc[(2 * N + k) * (2 * N + k + 1) / 2 + j] = gqdd.d[0];   // (ddq_k, q_j)
+    hc[tq_packed(N + j, k)] = gq.d[1];        // (dq_j, q_k)
+    hc[tq_packed(2 * N + k, j)] = gqdd.d[0];  // (ddq_k, q_j)
   });
-  }
 }
 
 // ---- step ------------------------------------------------------------------------------------------------------------------------------
@@ -508,12 +488,269 @@ OH_DEV double row_sum8(double v) {  // sum over the 8 lanes of a row (lane = 8 r
 // One wavefront per instance (round 4; rounds 1-3: 16 lanes per instance around a value matrix in LDS, every lane factorising Q_uu for itself, three
 // block barriers per knot -- 105 us per sweep however small the batch).  Lane 8 r + c owns entry (r, c) of every N x N block of the stage matrix
 //     M = H_t + [A^T P A, A^T P B; B^T P A, B^T P B] + mu I_x   over (q, dq | u),
-// column c = 7 holds the vectors.  With A = [[I, dt I], [0, I]], B = [0; dt I] every block of M is an entry-wise combination of the four blocks of P,
+// column c = N holds the vectors.  With A = [[I, dt I], [0, I]], B = [0; dt I] every block of M is an entry-wise combination of the four blocks of P,
 // so forming M needs nothing from another lane; the N pivots of the u rows are then eliminated by Gauss-Jordan steps whose operands travel by lane
 // shuffles (row r of the pivot column, column c of the pivot row): no LDS, no barrier.  What remains in the x rows is the Schur complement
 // P' = Q_xx - Q_ux^T Q_uu^{-1} Q_ux (exactly symmetric: mirrored entries subtract the same product), in the u rows the gains K = Q_uu^{-1} Q_ux and
 // k = Q_uu^{-1} q_u; the pivots are those of the Cholesky factorisation (positive iff Q_uu is positive definite).  The roll-outs and the costate
 // recursion use the same layout: entry-wise work on the lanes that hold it, row sums by three shuffles.  numpy: oracle/torque_ipm.py.
+template <int N>
+struct TqLanes {
+  int lane, r, c;
+  bool mat, vec;  // an entry of the N x N blocks; an entry of the vectors
+  OH_DEV explicit TqLanes(const int l) : lane(l), r(l >> 3), c(l & 7), mat(r < N && c < N), vec(r < N && c == N) {}
+};
+
+// Step 1, lane-parallel part: the sums over the trial's stage records (knots over the lanes).
+OH_DEV TqTrial tq_trial_sums(const TqBuffers& D, const int T, const int b, const int ts, const int lane) {
+  TqTrial tr{0.0, 0.0, 0.0, 0.0};
+  for (int t = lane; t < T; t += 64) {
+    const double* sr = tq_st(D, T, ts, b, t);
+    tr.f += sr[TqStage::f];
+    tr.bsum += sr[TqStage::barrier];
+    tr.nrel += sr[TqStage::relaxed];
+    tr.viol = fmax(tr.viol, sr[TqStage::viol]);
+  }
+  tr.f = wave_sum(tr.f);
+  tr.bsum = wave_sum(tr.bsum);
+  tr.nrel = wave_sum(tr.nrel);
+  tr.viol = wave_max(tr.viol);
+  return tr;
+}
+
+// Step 2: reduced gradient of the accepted point: gradient of the rolled-out merit w.r.t. u_t by the costate recursion, for mu_b, for its successor and
+// for the watchdog's.  Entry-wise per joint: lanes (r, N) carry the costates of q_r and dq_r for the cost and the barrier part; what a knot needs from
+// memory is requested one knot ahead.
+template <int N>
+OH_DEV TqStat tq_reduced_gradient(const TqBuffers& D, const int T, const int b, const int cur, const TqLanes<N>& L, const double dt, const double mub, const TqBarrier& nb) {
+  constexpr int NX = 2 * N;
+  const int r = L.r;
+  const bool vec = L.vec;
+  double stat = 0.0, stat_next = 0.0, stat_up = 0.0;
+  double lfq = 0.0, lfd = 0.0, lbq = 0.0, lbd = 0.0;
+  double g_n[6] = {0, 0, 0, 0, 0, 0};
+  auto fetch = [&](const int t) {
+    if (vec) {
+      const double* sr = tq_st(D, T, cur, b, t);
+      g_n[0] = sr[TqStage::g_f + r]; g_n[1] = sr[TqStage::g_f + N + r]; g_n[2] = sr[TqStage::g_f + NX + r];
+      g_n[3] = sr[TqStage::g_b + r]; g_n[4] = sr[TqStage::g_b + N + r]; g_n[5] = sr[TqStage::g_b + NX + r];
+    }
+  };
+  fetch(T - 1);
+  for (int t = T - 1; t >= 0; --t) {
+    const double gfq = g_n[0], gfd = g_n[1], gfu = g_n[2], gbq = g_n[3], gbd = g_n[4], gbu = g_n[5];
+    if (t > 0) fetch(t - 1);
+    const double rf = fma(dt, lfd, gfu), rb = fma(dt, lbd, gbu);
+    stat = fmax(stat, fabs(fma(mub, rb, rf)));
+    stat_next = fmax(stat_next, fabs(fma(nb.next, rb, rf)));
+    stat_up = fmax(stat_up, fabs(fma(nb.up, rb, rf)));
+    const double nfd = gfd + fma(dt, lfq, lfd), nbd = gbd + fma(dt, lbq, lbd);
+    lfq = gfq + lfq;
+    lbq = gbq + lbq;
+    lfd = nfd;
+    lbd = nbd;
+  }
+  if (!vec) { stat = 0.0; stat_next = 0.0; stat_up = 0.0; }
+  stat = wave_max(stat);
+  stat_next = wave_max(stat_next);
+  stat_up = wave_max(stat_up);
+  if (!(stat == stat)) stat = 1e300;
+  if (!(stat_next == stat_next)) stat_next = 1e300;
+  if (!(stat_up == stat_up)) stat_up = 1e300;
+  return TqStat{stat, stat_next, stat_up};
+}
+
+// Step 4: Riccati sweep (uniform over the wavefront: one instance); the gains go to D.gains, q_u^T k to S.qk.  A stage block of the exact Hessian that
+// leaves Q_uu indefinite raises the damping and the sweep is repeated; true: twelve sweeps failed.
+template <int N>
+OH_DEV bool tq_riccati(const TqBuffers& D, const int T, const int b, const TqLanes<N>& L, const double dt, TqInst& S) {
+  constexpr int NX = 2 * N;
+  const int lane = L.lane, r = L.r, c = L.c, cur = S.cur;
+  const bool mat = L.mat;
+  const double mub = S.mub;
+  // offsets of this lane's entries in the packed lower stage block; q at 0, dq at N, u at 2 N
+  auto pk = [](const int row, const int col) { return TqStage::H + (row >= col ? tq_packed(row, col) : tq_packed(col, row)); };
+  const int rr = mat ? r : 0, cc = mat ? c : 0;
+  const int o_qq = pk(rr, cc), o_qd = pk(rr, N + cc), o_dq = pk(N + rr, cc), o_dd = pk(N + rr, N + cc), o_qu = pk(rr, NX + cc), o_du = pk(N + rr, NX + cc),
+            o_uq = pk(NX + rr, cc), o_ud = pk(NX + rr, N + cc), o_uu = pk(NX + rr, NX + cc);
+  const int rv = L.vec ? r : 0;
+  bool failed = true;
+  for (int attempt = 0; attempt < 12 && failed; ++attempt) {
+    failed = false;
+    S.qk = 0.0;
+    double Pqq = 0.0, Pqd = 0.0, Pdq = 0.0, Pdd = 0.0;  // mat lanes: blocks of P; vec lanes: Pqq = p_q[r], Pdd = p_d[r]
+    double h_n[9];
+    auto fetch_rec = [&](const int t) {
+      const double* sr = tq_st(D, T, cur, b, t);
+      if (mat) {
+        h_n[0] = sr[o_qq]; h_n[1] = sr[o_qd]; h_n[2] = sr[o_dq]; h_n[3] = sr[o_dd]; h_n[4] = sr[o_qu]; h_n[5] = sr[o_du]; h_n[6] = sr[o_uq]; h_n[7] = sr[o_ud];
+        h_n[8] = sr[o_uu];
+      } else {  // the stage gradient g_f + mu_b g_b
+        h_n[0] = fma(mub, sr[TqStage::g_b + rv], sr[TqStage::g_f + rv]);
+        h_n[1] = fma(mub, sr[TqStage::g_b + N + rv], sr[TqStage::g_f + N + rv]);
+        h_n[2] = fma(mub, sr[TqStage::g_b + NX + rv], sr[TqStage::g_f + NX + rv]);
+      }
+    };
+    fetch_rec(T - 1);
+    for (int t = T - 1; t >= 0; --t) {
+      double Mqq, Mqd, Mdq, Mdd, Mqu, Mdu, Muq, Mud, Muu;
+      if (c < N) {
+        const double dg = (r == c) ? S.mu : 0.0;
+        Mqq = h_n[0] + Pqq + dg;
+        Mqd = h_n[1] + fma(dt, Pqq, Pqd);
+        Mdq = h_n[2] + fma(dt, Pqq, Pdq);
+        Mdd = h_n[3] + fma(dt, fma(dt, Pqq, Pqd), fma(dt, Pdq, Pdd)) + dg;
+        Mqu = h_n[4] + dt * Pqd;
+        Mdu = h_n[5] + dt * fma(dt, Pqd, Pdd);
+        Muq = h_n[6] + dt * Pdq;
+        Mud = h_n[7] + dt * fma(dt, Pdq, Pdd);
+        Muu = h_n[8] + dt * dt * Pdd;
+      } else {  // vectors: m_q, m_d, m_u in the slots of column "u" of their block row (Mqu, Mdu, Muu)
+        Mqq = Mqd = Mdq = Mdd = Muq = Mud = 0.0;
+        Mqu = h_n[0] + Pqq;
+        Mdu = h_n[1] + fma(dt, Pqq, Pdd);
+        Muu = h_n[2] + dt * Pdd;
+      }
+      if (t > 0) fetch_rec(t - 1);
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        // column j of this lane's row (blocks X u) and row j of this lane's column (blocks u Y; for the vector column: m_u[j])
+        const double cq = __shfl(Mqu, 8 * r + j), cd = __shfl(Mdu, 8 * r + j), cu = __shfl(Muu, 8 * r + j);
+        const double rq = __shfl(Muq, 8 * j + c), rd = __shfl(Mud, 8 * j + c), ru = __shfl(Muu, 8 * j + c);
+        const double piv = readlane_f64(Muu, 9 * j);
+        if (!(piv > 0.0) || !isfinite(piv)) failed = true;
+        double d = __builtin_amdgcn_rcp(piv);  // reciprocal to the last bit or two (two Newton steps): an IEEE division is 30 instructions on the critical path of every pivot
+        d = d * fma(-piv, d, 2.0);
+        d = d * fma(-piv, d, 2.0);
+        if (c < N) {
+          Mqq = fma(-(cq * rq), d, Mqq);
+          Mqd = fma(-(cq * rd), d, Mqd);
+          Mdq = fma(-(cd * rq), d, Mdq);
+          Mdd = fma(-(cd * rd), d, Mdd);
+          Mqu = fma(-(cq * ru), d, Mqu);
+          Mdu = fma(-(cd * ru), d, Mdu);
+          if (r == j) {
+            Muq *= d;
+            Mud *= d;
+            Muu *= d;
+          } else {
+            Muq = fma(-(cu * rq), d, Muq);
+            Mud = fma(-(cu * rd), d, Mud);
+            Muu = fma(-(cu * ru), d, Muu);
+          }
+        } else {  // ru = m_u[j] (forward-eliminated: row j has only been updated by the pivots before it)
+          if (r == 0) S.qk = fma(ru * ru, d, S.qk);
+          Mqu = fma(-(cq * ru), d, Mqu);
+          Mdu = fma(-(cd * ru), d, Mdu);
+          if (r == j) Muu *= d;
+          else Muu = fma(-(cu * ru), d, Muu);
+        }
+      }
+      // gains of knot t: K_q[r][c], K_d[r][c] on the matrix lanes, k[r] on the vector lanes; two doubles per lane
+      double* gn = tq_gains(D, T, b, t);
+      gn[2 * lane] = c < N ? Muq : Muu;
+      gn[2 * lane + 1] = c < N ? Mud : 0.0;
+      if (c < N) {
+        Pqq = Mqq; Pqd = Mqd; Pdq = Mdq; Pdd = Mdd;
+      } else {
+        Pqq = Mqu; Pdd = Mdu; Pqd = Pdq = 0.0;
+      }
+    }
+    S.qk = __shfl(S.qk, N);  // lane (0, N)
+    failed = __any(failed && r < N) || !isfinite(S.qk);
+    if (failed) tq_raise_damping(S);  // an indefinite stage block of the exact Hessian: more damping, same point
+  }
+  return failed;
+}
+
+// Step 5: closed-loop rollout of the unit step (du to LDS), fraction to the boundary on the linearised rows.  Lane (r, c) carries the state step of joint
+// c (replicated over the rows) and multiplies it with its entries of the gains and of d tau / d z; row sums give du_r and d tau_r.  After a sweep
+// (do_gains) |dx|^2 goes to S.ndx and the fraction alpha to S.alpha; a step that is only retried shorter keeps both.
+template <int N, bool VEL>
+OH_DEV void tq_unit_step(const TqParams& P, const TqBuffers& D, const int T, const int b, const TqLanes<N>& L, const double delta, double (*du_all)[8], const bool do_gains, TqInst& S) {
+  constexpr int NX = 2 * N, NZ = 3 * N;
+  const int lane = L.lane, r = L.r, c = L.c, cur = S.cur;
+  const bool mat = L.mat;
+  const double dt = P.dt;
+  double dq = 0.0, dd = 0.0;
+  double a_ftb = 1.0, ndx_acc = 0.0;
+  double k_n[2], j_n[3], s_n[4] = {0, 0, 0, 0};
+  auto fetch_knot = [&](const int t) {
+    const double* gn = tq_gains(D, T, b, t);
+    k_n[0] = gn[2 * lane];
+    k_n[1] = gn[2 * lane + 1];
+    const double* sr = tq_st(D, T, cur, b, t);
+    if (mat) {
+      j_n[0] = sr[TqStage::J + r * NZ + c];
+      j_n[1] = sr[TqStage::J + r * NZ + N + c];
+      j_n[2] = sr[TqStage::J + r * NZ + NX + c];
+    } else {
+      j_n[0] = j_n[1] = j_n[2] = 0.0;
+    }
+    if (r < N && c == 0) {
+      const double tv = sr[TqStage::tau + r];
+      s_n[0] = tv - P.tau_lo[r];
+      s_n[1] = P.tau_up[r] - tv;
+      if constexpr (VEL) {
+        const double dv = tq_xs(D, T, cur, b, t)[TqKnot::dq + r];
+        s_n[2] = dv - P.dq_lo[r];
+        s_n[3] = P.dq_up[r] - dv;
+      }
+    }
+  };
+  fetch_knot(0);
+  for (int t = 0; t < T; ++t) {
+    const double kq = k_n[0], kd = k_n[1], jq = j_n[0], jd = j_n[1], ju = j_n[2];
+    const double s_lo = s_n[0], s_up = s_n[1], v_lo = s_n[2], v_up = s_n[3];
+    if (t + 1 < T) fetch_knot(t + 1);
+    // du_r = -k_r - sum_c (K_q[r][c] dq_c + K_d[r][c] dd_c): the vector lane contributes k_r (its kq slot)
+    const double part = c < N ? fma(kq, dq, kd * dd) : (c == N ? kq : 0.0);  // (columns beyond N exist on chains shorter than seven joints: idle lanes)
+    const double du_r = -row_sum8(r < N ? part : 0.0);
+    const double du_c = __shfl(du_r, 8 * c);  // du of joint c, from row c
+    if (r == 0 && c < N) du_all[t][c] = du_c;
+    if (r == 0 && c < N) ndx_acc = fma(dq, dq, fma(dd, dd, ndx_acc));
+    const double ds = row_sum8(mat ? fma(jq, dq, fma(jd, dd, ju * du_c)) : 0.0);  // d tau_r of the unit step
+    double dv = 0.0;
+    if constexpr (VEL) dv = __shfl(dd, r);  // the velocity step of joint r sits on lane (0, r) (every lane takes part in the shuffle)
+    if (r < N && c == 0) {
+      if (ds < 0.0 && s_lo >= delta) a_ftb = fmin(a_ftb, -P.tau_ftb * s_lo / ds);
+      if (ds > 0.0 && s_up >= delta) a_ftb = fmin(a_ftb, P.tau_ftb * s_up / ds);
+      if constexpr (VEL) {
+        if (dv < 0.0 && v_lo >= delta) a_ftb = fmin(a_ftb, -P.tau_ftb * v_lo / dv);
+        if (dv > 0.0 && v_up >= delta) a_ftb = fmin(a_ftb, P.tau_ftb * v_up / dv);
+      }
+    }
+    // dx_{t+1} = A dx_t + B du_t
+    dq = fma(dt, dd, dq);
+    dd = fma(dt, du_c, dd);
+  }
+  if (do_gains) {
+    S.ndx = wave_sum(ndx_acc);
+    S.alpha = wave_min(a_ftb);
+  }
+}
+
+// Step 6: open-loop rollout of u + alpha du from the fixed initial state into the slot of the next trial: lane c < N carries joint c.
+OH_DEV void tq_trial_rollout(const TqBuffers& D, const int T, const int b, const int cur, const int lane, const double dt, const double alpha, double (*du_all)[8]) {
+  const int nts = 1 - cur;
+  const double* x0r = tq_xs(D, T, cur, b, 0);
+  double q = x0r[TqKnot::q + lane], dqv = x0r[TqKnot::dq + lane];
+  double u_n = x0r[TqKnot::ddq + lane];
+  for (int t = 0; t < T; ++t) {
+    const double ucur = u_n;
+    if (t + 1 < T) u_n = tq_xs(D, T, cur, b, t + 1)[TqKnot::ddq + lane];
+    double* xn = tq_xs(D, T, nts, b, t);
+    const double un = fma(alpha, du_all[t][lane], ucur);
+    xn[TqKnot::ddq + lane] = un;
+    xn[TqKnot::q + lane] = q;
+    xn[TqKnot::dq + lane] = dqv;
+    // x_{t+1} = A x_t + B u_t on the trial values themselves
+    q = fma(dt, dqv, q);
+    dqv = fma(dt, un, dqv);
+  }
+}
+
+// The step of one instance (scalar steps: oh_tq_machine.h):
 //   1. merit of the trial  f + mu_b B  and the ratio test against the decrease the damped model predicted for the scaled step; Levenberg-Marquardt update
 //   2. reduced gradient of the accepted point by the costate recursion, for the barrier parameter in force and for the next one
 //   3. convergence / barrier update (the stage gradient is  g_f + mu_b g_b,  the merit  f + mu_b B:  a new mu_b needs no re-evaluation)
@@ -527,403 +764,35 @@ OH_DEV double row_sum8(double v) {  // sum over the 8 lanes of a row (lane = 8 r
 template <int N, bool VEL = false>
 __global__ __launch_bounds__(64, OH_TQ_STEP_WAVES) void k_tq_step(TqParams P, TqBuffers D) {
   static_assert(N >= 1 && N <= 7, "the lane layout is 8 rows x 8 columns: up to 7 joints and the vector column (column N)");
-  constexpr int NX = 2 * N, NZ = 3 * N;
   extern __shared__ double du_dyn[];  // [T][8]: the control steps of the unit step
+  double (*du_all)[8] = reinterpret_cast<double (*)[8]>(du_dyn);
   const int T = P.T;
-  const int lane = threadIdx.x;
-  const int r = lane >> 3, c = lane & 7;
-  const bool mat = r < N && c < N;  // an entry of the N x N blocks
-  const bool vec = r < N && c == N;  // an entry of the vectors
+  const TqLanes<N> L(threadIdx.x);
   if ((int)blockIdx.x >= D.n_run) return;
   const int b = D.list[blockIdx.x];
   if (D.status[b] >= 0) return;
-  const double dt = P.dt;
-  int cur = D.cur[b];
-  const int ts = 1 - cur;
-  // 1. merit of the trial point
-  double fsum = 0.0, bsum_t = 0.0, nrel_t = 0.0, viol_t = 0.0;
-  for (int t = lane; t < T; t += 64) {
-    const double* sr = D.st + st_off(D, T, ts, b, t);
-    fsum += sr[252];
-    bsum_t += sr[253];
-    nrel_t += sr[254];
-    viol_t = fmax(viol_t, sr[255]);
+  TqInst S = TqInst::load(D, b);
+  const TqTrial tr = tq_trial_sums(D, T, b, 1 - S.cur, L.lane);  // 1.
+  TqVerdict v;
+  tq_ratio_test(S, P, tr, v);
+  const TqBarrier nb = tq_barrier_candidates(S.mub, P);  // 2.
+  const TqStat st = tq_reduced_gradient<N>(D, T, b, S.cur, L, P.dt, S.mub, nb);
+  TqPlan pl;
+  tq_decide(S, P, v, st, nb, pl);  // 3.
+  if (pl.do_gains && tq_riccati<N>(D, T, b, L, P.dt, S)) {  // 4.
+    pl.status = OH_STATUS_NUMERICAL;
+    pl.do_roll = false;
   }
-  fsum = wave_sum(fsum);
-  bsum_t = wave_sum(bsum_t);
-  nrel_t = wave_sum(nrel_t);
-  viol_t = wave_max(viol_t);
-
-  const bool first = D.first[b] != 0;
-  double f_cur = D.f_cur[b], f_true = D.f_true[b], bsum = D.bsum[b], mu = D.mu[b], nun = D.nun[b], mub = D.mub[b], alpha = D.alpha[b], viol = D.viol[b];
-  double qk = D.qk[b], ndx = D.ndx[b];
-  int iters = D.iters[b], rejected = D.rejected[b], n_barrier = D.n_barrier[b], nrel = D.nrel[b], n_back = D.n_back[b], stall = D.stall[b];
-  const double f_t = fsum + mub * bsum_t;
-  bool accept, new_gains = true;
-  if (first) {
-    accept = true;
-  } else if (!isfinite(f_t)) {
-    accept = false;
-    new_gains = false;
-    alpha *= 0.1;
-    rejected += 1;
-  } else {
-    const double pred = (alpha - 0.5 * alpha * alpha) * qk + 0.5 * alpha * alpha * mu * ndx;
-    const double ratio = (f_cur - f_t) / fmax(pred, 1e-300);
-    accept = ratio > 1e-4 || (pred <= 1e-15 * fabs(f_cur) && f_t <= f_cur + 1e-14 * fabs(f_cur));
-    if (accept) {
-      const double w = 2.0 * ratio - 1.0;
-      mu *= ratio > 0.9 ? P.mu_dec : fmax(1.0 / 3.0, 1.0 - w * w * w);
-      if (mu < 1e-7) mu = 0.0;
-      nun = 4.0;
-    } else if ((alpha < 1.0 || (P.ls_curv && D.curv[b] != 0)) && n_back < P.max_back) {
-      // a step the boundary rule had shortened already: the rows near their bounds are to blame (the logarithm is far from its quadratic model
-      // there), not the model of the states -- a quarter of the feed-forward, same gains, same damping.  Round 5: likewise a full Newton step
-      // (exact curvature) that was rejected -- measured on stragglers (tools/gpu_tq_param_sweep.py, HISTORY): the full step gives up more barrier
-      // than it gains (a slack drops to a third), 0.3 of it follows the model to 8 %, and the damping, which acts on the states, does not shorten a
-      // step that lives in the accelerations: five rejections and six careful steps afterwards, or one quartering
-      new_gains = false;
-      alpha *= 0.25;
-      n_back += 1;
-      rejected += 1;
-    } else {
-      mu = fmax(mu * nun, 0.1);
-      nun *= 2.0;
-      rejected += 1;
-    }
-  }
-  if (accept || new_gains) n_back = 0;
-  if (accept) {
-    cur = ts;
-    f_cur = f_t;
-    f_true = fsum;
-    bsum = bsum_t;
-    nrel = (int)nrel_t;
-    viol = viol_t;
-  }
-  const int nts = 1 - cur;  // slot of the next trial
-
-  // 2. reduced gradient of the accepted point: gradient of the rolled-out merit w.r.t. u_t by the costate recursion, for mu_b and for its successor.
-  // Entry-wise per joint: lanes (r, 7) carry the costates of q_r and dq_r for the cost and the barrier part; what a knot needs from memory is
-  // requested one knot ahead.
-  const double mu_min = 0.1 * P.tol_compl;
-  const double mub_next = fmax(mu_min, fmin(P.kappa_mu * mub, pow(mub, P.theta_mu)));
-  const double mub_up = fmin(P.mu_b0, 100.0 * mub);  // the watchdog's way back up (step 3)
-  double stat = 0.0, stat_next = 0.0, stat_up = 0.0;
-  {
-    double lfq = 0.0, lfd = 0.0, lbq = 0.0, lbd = 0.0;
-    double g_n[6] = {0, 0, 0, 0, 0, 0};
-    auto fetch = [&](const int t) {
-      if (vec) {
-        const double* sr = D.st + st_off(D, T, cur, b, t);
-        g_n[0] = sr[231 + r]; g_n[1] = sr[231 + N + r]; g_n[2] = sr[231 + NX + r];
-        g_n[3] = sr[TQ_SD_GB + r]; g_n[4] = sr[TQ_SD_GB + N + r]; g_n[5] = sr[TQ_SD_GB + NX + r];
-      }
-    };
-    fetch(T - 1);
-    for (int t = T - 1; t >= 0; --t) {
-      const double gfq = g_n[0], gfd = g_n[1], gfu = g_n[2], gbq = g_n[3], gbd = g_n[4], gbu = g_n[5];
-      if (t > 0) fetch(t - 1);
-      const double rf = fma(dt, lfd, gfu), rb = fma(dt, lbd, gbu);
-      stat = fmax(stat, fabs(fma(mub, rb, rf)));
-      stat_next = fmax(stat_next, fabs(fma(mub_next, rb, rf)));
-      stat_up = fmax(stat_up, fabs(fma(mub_up, rb, rf)));
-      const double nfd = gfd + fma(dt, lfq, lfd), nbd = gbd + fma(dt, lbq, lbd);
-      lfq = gfq + lfq;
-      lbq = gbq + lbq;
-      lfd = nfd;
-      lbd = nbd;
-    }
-    if (!vec) { stat = 0.0; stat_next = 0.0; stat_up = 0.0; }
-    stat = wave_max(stat);
-    stat_next = wave_max(stat_next);
-    stat_up = wave_max(stat_up);
-    if (!(stat == stat)) stat = 1e300;
-    if (!(stat_next == stat_next)) stat_next = 1e300;
-    if (!(stat_up == stat_up)) stat_up = 1e300;
-  }
-
-  // 3. convergence, barrier update
-  int status = -1;
-  bool do_gains = false, do_roll = false;
-  bool reeval = false;  // the next "trial" is this point itself under a lower barrier parameter (round 6)
-  int curv = D.curv[b] != 0;  // the pending trial was evaluated with exact curvature (1 computed, 2 the stored term: k_tq_curv)
-  if (!isfinite(f_cur)) {
-    status = OH_STATUS_NUMERICAL;
-  } else if (stat <= P.tol && mub <= P.tol_compl && nrel == 0) {
-    status = OH_STATUS_CONVERGED;
-  } else if (iters >= P.max_iter) {
-    status = OH_STATUS_MAX_ITER;
-  } else {
-    iters += 1;
-    do_roll = true;
-    if (new_gains) {
-      do_gains = true;
-      if (accept && stat <= P.kappa_eps * mub && nrel == 0 && mub > mu_min) {
-        mub = mub_next;
-        f_cur = f_true + mub * bsum;
-        stat = stat_next;
-        n_barrier += 1;
-        stall = 0;
-      } else if (accept && stat <= P.kappa_eps * mub && nrel > 0 && mub > mu_min) {
-        // Round 6: stationary for this mu_b with rows inside the relaxed zone (slack below theta mu_b: a row whose multiplier exceeds 1 / theta -- a velocity limit
-        // the tracking cost pushes hard against).  Merit and gradient are not affine in mu_b there, so the update above does not apply; without one the instance sat at
-        // this point until the cap (null steps "rejected" at rounding level, the damping doubling).  The barrier parameter is lowered all the same and the point itself
-        // evaluated again under it: a null step (alpha = 0 on the gains of the last sweep), accepted as it is (D.first).  oracle/torque_ipm.py alike.
-        mub = mub_next;
-        n_barrier += 1;
-        stall = 0;
-        reeval = true;
-        do_gains = false;
-        alpha = 0.0;
-      } else if (accept && stat <= 10.0 * P.tol && nrel > 0 && mub <= mu_min && viol > P.tol_compl) {
-        // ... and at the floor of the barrier parameter a stationary point that still violates a row has no feasible neighbour (the relaxed barrier is a penalty of
-        // weight 1 / (theta^2 mu_b) by now): IPOPT's Infeasible_Problem_Detected, did_solve() False (solver.py:133-134, 407-412)
-        status = OH_STATUS_INFEASIBLE;
-        iters -= 1;
-        do_roll = false;
-        do_gains = false;
-      } else {
-        stall += 1;
-        if (stall >= P.stall_max && nrel == 0 && mub <= mu_min && stat <= 10.0 * P.tol) {
-          // "acceptable level" (IPOPT's acceptable_tol / acceptable_iter in spirit): stall_max steps at the floor of the barrier parameter without
-          // meeting tol while within ten times of it -- the arithmetic floor of the reduced gradient: an active row with slack s carries mu_b / s,
-          // and s = up - tau inherits the ~1e-14 of the recursion, so at s ~ 1e-8 the multiplier is good to ~1e-6 relative and the reduced gradient to
-          // ~1e-6 absolute.  Without this such an instance (1 of 8192 in one of nine batches) fed the watchdog below and ended NUMERICAL at the optimum.
-          status = OH_STATUS_ACCEPTABLE;
-          iters -= 1;
-          do_roll = false;
-          do_gains = false;
-        } else if (stall >= P.stall_max && nrel == 0 && accept) {
-          // watchdog: stall_max steps without reaching the barrier test -- the iterate sits far from the central path of this mu_b (slacks of the active
-          // rows collapse and recover in turn).  Back to a larger barrier parameter: the path is regained there and followed down again.
-          mub = mub_up;
-          f_cur = f_true + mub * bsum;
-          stat = stat_up;
-          stall = 0;
-        }
-      }
-      if (!reeval) curv = (stat <= P.curv_from || (n_barrier >= P.curv_after && stat <= P.curv_late)) ? 1 : 0;
-    }
-  }
-
-  // 4. Riccati sweep (everything below is uniform over the wavefront: one instance)
-  // offsets of this lane's entries in the packed lower stage block: row(row + 1) / 2 + col, row >= col; q at 0, dq at N, u at 2 N
-  auto pk = [](const int row, const int col) { return row >= col ? row * (row + 1) / 2 + col : col * (col + 1) / 2 + row; };
-  const int rr = mat ? r : 0, cc = mat ? c : 0;
-  const int o_qq = pk(rr, cc), o_qd = pk(rr, N + cc), o_dq = pk(N + rr, cc), o_dd = pk(N + rr, N + cc), o_qu = pk(rr, NX + cc), o_du = pk(N + rr, NX + cc),
-            o_uq = pk(NX + rr, cc), o_ud = pk(NX + rr, N + cc), o_uu = pk(NX + rr, NX + cc);
-  const int rv = vec ? r : 0;
-  if (do_gains) {
-    bool failed = true;
-    for (int attempt = 0; attempt < 12 && failed; ++attempt) {
-      failed = false;
-      qk = 0.0;
-      double Pqq = 0.0, Pqd = 0.0, Pdq = 0.0, Pdd = 0.0;  // mat lanes: blocks of P; vec lanes: Pqq = p_q[r], Pdd = p_d[r]
-      double h_n[9];
-      auto fetch_rec = [&](const int t) {
-        const double* sr = D.st + st_off(D, T, cur, b, t);
-        if (mat) {
-          h_n[0] = sr[o_qq]; h_n[1] = sr[o_qd]; h_n[2] = sr[o_dq]; h_n[3] = sr[o_dd]; h_n[4] = sr[o_qu]; h_n[5] = sr[o_du]; h_n[6] = sr[o_uq]; h_n[7] = sr[o_ud];
-          h_n[8] = sr[o_uu];
-        } else {  // the stage gradient g_f + mu_b g_b
-          h_n[0] = fma(mub, sr[TQ_SD_GB + rv], sr[231 + rv]);
-          h_n[1] = fma(mub, sr[TQ_SD_GB + N + rv], sr[231 + N + rv]);
-          h_n[2] = fma(mub, sr[TQ_SD_GB + NX + rv], sr[231 + NX + rv]);
-        }
-      };
-      fetch_rec(T - 1);
-      for (int t = T - 1; t >= 0; --t) {
-        double Mqq, Mqd, Mdq, Mdd, Mqu, Mdu, Muq, Mud, Muu;
-        if (c < N) {
-          const double dg = (r == c) ? mu : 0.0;
-          Mqq = h_n[0] + Pqq + dg;
-          Mqd = h_n[1] + fma(dt, Pqq, Pqd);
-          Mdq = h_n[2] + fma(dt, Pqq, Pdq);
-          Mdd = h_n[3] + fma(dt, fma(dt, Pqq, Pqd), fma(dt, Pdq, Pdd)) + dg;
-          Mqu = h_n[4] + dt * Pqd;
-          Mdu = h_n[5] + dt * fma(dt, Pqd, Pdd);
-          Muq = h_n[6] + dt * Pdq;
-          Mud = h_n[7] + dt * fma(dt, Pdq, Pdd);
-          Muu = h_n[8] + dt * dt * Pdd;
-        } else {  // vectors: m_q, m_d, m_u in the slots of column "u" of their block row (Mqu, Mdu, Muu)
-          Mqq = Mqd = Mdq = Mdd = Muq = Mud = 0.0;
-          Mqu = h_n[0] + Pqq;
-          Mdu = h_n[1] + fma(dt, Pqq, Pdd);
-          Muu = h_n[2] + dt * Pdd;
-        }
-        if (t > 0) fetch_rec(t - 1);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          // column j of this lane's row (blocks X u) and row j of this lane's column (blocks u Y; for the vector column: m_u[j])
-          const double cq = __shfl(Mqu, 8 * r + j), cd = __shfl(Mdu, 8 * r + j), cu = __shfl(Muu, 8 * r + j);
-          const double rq = __shfl(Muq, 8 * j + c), rd = __shfl(Mud, 8 * j + c), ru = __shfl(Muu, 8 * j + c);
-          const double piv = readlane_f64(Muu, 9 * j);
-          if (!(piv > 0.0) || !isfinite(piv)) failed = true;
-          double d = __builtin_amdgcn_rcp(piv);  // reciprocal to the last bit or two (two Newton steps): an IEEE division is 30 instructions on the critical path of every pivot
-          d = d * fma(-piv, d, 2.0);
-          d = d * fma(-piv, d, 2.0);
-          if (c < N) {
-            Mqq = fma(-(cq * rq), d, Mqq);
-            Mqd = fma(-(cq * rd), d, Mqd);
-            Mdq = fma(-(cd * rq), d, Mdq);
-            Mdd = fma(-(cd * rd), d, Mdd);
-            Mqu = fma(-(cq * ru), d, Mqu);
-            Mdu = fma(-(cd * ru), d, Mdu);
-            if (r == j) {
-              Muq *= d;
-              Mud *= d;
-              Muu *= d;
-            } else {
-              Muq = fma(-(cu * rq), d, Muq);
-              Mud = fma(-(cu * rd), d, Mud);
-              Muu = fma(-(cu * ru), d, Muu);
-            }
-          } else {  // ru = m_u[j] (forward-eliminated: row j has only been updated by the pivots before it)
-            if (r == 0) qk = fma(ru * ru, d, qk);
-            Mqu = fma(-(cq * ru), d, Mqu);
-            Mdu = fma(-(cd * ru), d, Mdu);
-            if (r == j) Muu *= d;
-            else Muu = fma(-(cu * ru), d, Muu);
-          }
-        }
-        // gains of knot t: K_q[r][c], K_d[r][c] on the matrix lanes, k[r] on the vector lanes; two doubles per lane
-        double* gn = D.gains + ((size_t)b * T + t) * TQ_GN;
-        gn[2 * lane] = c < N ? Muq : Muu;
-        gn[2 * lane + 1] = c < N ? Mud : 0.0;
-        if (c < N) {
-          Pqq = Mqq; Pqd = Mqd; Pdq = Mdq; Pdd = Mdd;
-        } else {
-          Pqq = Mqu; Pdd = Mdu; Pqd = Pdq = 0.0;
-        }
-      }
-      qk = __shfl(qk, N);  // lane (0, 7)
-      failed = __any(failed && r < N) || !isfinite(qk);
-      if (failed) {  // an indefinite stage block of the exact Hessian: more damping, same point
-        mu = fmax(mu * nun, 0.1);
-        nun *= 2.0;
-      }
-    }
-    if (failed) {
-      status = OH_STATUS_NUMERICAL;
-      do_roll = false;
-    }
-  }
-
-  // 5. closed-loop rollout of the unit step (du to LDS), fraction to the boundary on the linearised rows.  Lane (r, c) carries the state step of joint
-  // c (replicated over the rows) and multiplies it with its entries of the gains and of d tau / d z; row sums give du_r and d tau_r.
-  const double delta = P.theta * mub;
-  double (*du_all)[8] = reinterpret_cast<double (*)[8]>(du_dyn);
-  if (do_roll) {
-    double dq = 0.0, dd = 0.0;
-    double a_ftb = 1.0, ndx_acc = 0.0;
-    double k_n[2], j_n[3], s_n[4] = {0, 0, 0, 0};
-    auto fetch_knot = [&](const int t) {
-      const double* gn = D.gains + ((size_t)b * T + t) * TQ_GN;
-      k_n[0] = gn[2 * lane];
-      k_n[1] = gn[2 * lane + 1];
-      const double* sr = D.st + st_off(D, T, cur, b, t);
-      if (mat) {
-        j_n[0] = sr[TQ_SD_J + r * NZ + c];
-        j_n[1] = sr[TQ_SD_J + r * NZ + N + c];
-        j_n[2] = sr[TQ_SD_J + r * NZ + NX + c];
-      } else {
-        j_n[0] = j_n[1] = j_n[2] = 0.0;
-      }
-      if (r < N && c == 0) {
-        const double tv = sr[256 + r];
-        s_n[0] = tv - P.tau_lo[r];
-        s_n[1] = P.tau_up[r] - tv;
-        if constexpr (VEL) {
-          const double dv = D.xs[xs_off(D, T, cur, b, t) + 8 + r];
-          s_n[2] = dv - P.dq_lo[r];
-          s_n[3] = P.dq_up[r] - dv;
-        }
-      }
-    };
-    fetch_knot(0);
-    for (int t = 0; t < T; ++t) {
-      const double kq = k_n[0], kd = k_n[1], jq = j_n[0], jd = j_n[1], ju = j_n[2];
-      const double s_lo = s_n[0], s_up = s_n[1], v_lo = s_n[2], v_up = s_n[3];
-      if (t + 1 < T) fetch_knot(t + 1);
-      // du_r = -k_r - sum_c (K_q[r][c] dq_c + K_d[r][c] dd_c): the vector lane contributes k_r (its kq slot)
-      const double part = c < N ? fma(kq, dq, kd * dd) : (c == N ? kq : 0.0);  // (columns beyond N exist on chains shorter than seven joints: idle lanes)
-      const double du_r = -row_sum8(r < N ? part : 0.0);
-      const double du_c = __shfl(du_r, 8 * c);  // du of joint c, from row c
-      if (r == 0 && c < N) du_all[t][c] = du_c;
-      if (r == 0 && c < N) ndx_acc = fma(dq, dq, fma(dd, dd, ndx_acc));
-      const double ds = row_sum8(mat ? fma(jq, dq, fma(jd, dd, ju * du_c)) : 0.0);  // d tau_r of the unit step
-      double dv = 0.0;
-      if constexpr (VEL) dv = __shfl(dd, r);  // the velocity step of joint r sits on lane (0, r) (every lane takes part in the shuffle)
-      if (r < N && c == 0) {
-        if (ds < 0.0 && s_lo >= delta) a_ftb = fmin(a_ftb, -P.tau_ftb * s_lo / ds);
-        if (ds > 0.0 && s_up >= delta) a_ftb = fmin(a_ftb, P.tau_ftb * s_up / ds);
-        if constexpr (VEL) {
-          if (dv < 0.0 && v_lo >= delta) a_ftb = fmin(a_ftb, -P.tau_ftb * v_lo / dv);
-          if (dv > 0.0 && v_up >= delta) a_ftb = fmin(a_ftb, P.tau_ftb * v_up / dv);
-        }
-      }
-      // dx_{t+1} = A dx_t + B du_t
-      dq = fma(dt, dd, dq);
-      dd = fma(dt, du_c, dd);
-    }
-    if (do_gains) {
-      ndx = wave_sum(ndx_acc);
-      alpha = wave_min(a_ftb);
-    }
-  }
+  const double delta = P.theta * S.mub;  // rows below it are in the relaxed zone
+  if (pl.do_roll) tq_unit_step<N, VEL>(P, D, T, b, L, delta, du_all, pl.do_gains, S);  // 5.
   __syncthreads();  // du_all
-
-  // 6. open-loop rollout of u + alpha du from the fixed initial state: lane c < N carries joint c
-  if (do_roll && lane < N) {
-    const double* x0r = D.xs + xs_off(D, T, cur, b, 0);
-    double q = x0r[lane], dqv = x0r[8 + lane];
-    double u_n = x0r[16 + lane];
-    for (int t = 0; t < T; ++t) {
-      const double ucur = u_n;
-      if (t + 1 < T) u_n = D.xs[xs_off(D, T, cur, b, t + 1) + 16 + lane];
-      double* xn = D.xs + xs_off(D, T, nts, b, t);
-      const double un = fma(alpha, du_all[t][lane], ucur);
-      xn[16 + lane] = un;
-      xn[lane] = q;
-      xn[8 + lane] = dqv;
-      // x_{t+1} = A x_t + B u_t on the trial values themselves
-      q = fma(dt, dqv, q);
-      dqv = fma(dt, un, dqv);
-    }
-  }
-  if (lane == 0) {
-    D.cur[b] = cur;
-    D.first[b] = reeval ? 1 : 0;
-    {  // next evaluation: the curvature term afresh, or the stored one while it is younger than curv_lag evaluations
-      int age = D.curv_age[b], mode = 0;
-      if (!accept && D.curv[b] == 1) age = -1;  // a term computed at a point that was refused (possibly outside the domain of the arithmetic) is not kept
-      if (curv) {
-        if (age >= 0 && age < P.curv_lag) { mode = 2; age += 1; }
-        else { mode = 1; age = 0; }
-      } else age = -1;
-      D.curv[b] = mode;
-      D.curv_age[b] = age;
-    }
-    D.f_cur[b] = f_cur;
-    D.f_true[b] = f_true;
-    D.bsum[b] = bsum;
-    D.mu[b] = mu;
-    D.nun[b] = nun;
-    D.mub[b] = mub;
-    D.stat[b] = stat;
-    D.alpha[b] = alpha;
-    D.qk[b] = qk;
-    D.ndx[b] = ndx;
-    D.viol[b] = viol;
-    D.nrel[b] = nrel;
-    D.n_back[b] = n_back;
-    D.stall[b] = stall;
-    D.iters[b] = iters;
-    D.rejected[b] = rejected;
-    D.n_barrier[b] = n_barrier;
-    D.status[b] = status;
-    if (status < 0) atomicAdd(D.n_running, 1);
+  if (pl.do_roll && L.lane < N) tq_trial_rollout(D, T, b, S.cur, L.lane, P.dt, S.alpha, du_all);  // 6.
+  if (L.lane == 0) {
+    tq_next_curvature(S, P, v.accept, pl.curv);
+    S.first = pl.reeval ? 1 : 0;
+    S.status = pl.status;
+    S.store(D, b);
+    if (S.status < 0) atomicAdd(D.n_running, 1);
   }
 }
 
@@ -939,18 +808,18 @@ __global__ __launch_bounds__(64) void k_tq_finalize(TqParams P, TqBuffers D, dou
   const double mub = D.mub[b];
   double cmpl = 0.0;
   for (int t = 0; t < T; ++t) {
-    const double* xr = D.xs + xs_off(D, T, cur, b, t);
-    const double* sr = D.st + st_off(D, T, cur, b, t);
+    const double* xr = tq_xs(D, T, cur, b, t);
+    const double* sr = tq_st(D, T, cur, b, t);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       if (x) {
         double* xb = x + (size_t)b * P.nx;
-        xb[N * t + j] = xr[j];
-        xb[N * T + N * t + j] = xr[8 + j];
-        xb[2 * N * T + N * t + j] = xr[16 + j];
-        xb[3 * N * T + N * t + j] = sr[256 + j];
+        xb[N * t + j] = xr[TqKnot::q + j];
+        xb[N * T + N * t + j] = xr[TqKnot::dq + j];
+        xb[2 * N * T + N * t + j] = xr[TqKnot::ddq + j];
+        xb[3 * N * T + N * t + j] = sr[TqStage::tau + j];
       }
-      const double tv = sr[256 + j];
+      const double tv = sr[TqStage::tau + j];
       const double s_lo = tv - P.tau_lo[j], s_up = P.tau_up[j] - tv;
       const double l_lo = mub / fmax(s_lo, 1e-300), l_up = mub / fmax(s_up, 1e-300);
       cmpl = fmax(cmpl, fmax(fabs(l_lo * s_lo), fabs(l_up * s_up)));
@@ -960,7 +829,7 @@ __global__ __launch_bounds__(64) void k_tq_finalize(TqParams P, TqBuffers D, dou
         mult[((size_t)b * T + t) * NR + N + j] = l_up;
       }
       if (P.vel) {
-        const double v_lo = xr[8 + j] - P.dq_lo[j], v_up = P.dq_up[j] - xr[8 + j];
+        const double v_lo = xr[TqKnot::dq + j] - P.dq_lo[j], v_up = P.dq_up[j] - xr[TqKnot::dq + j];
         const double m_lo = mub / fmax(v_lo, 1e-300), m_up = mub / fmax(v_up, 1e-300);
         cmpl = fmax(cmpl, fmax(fabs(m_lo * v_lo), fabs(m_up * v_up)));
         if (mult) {
@@ -981,10 +850,10 @@ __global__ __launch_bounds__(64) void k_tq_finalize(TqParams P, TqBuffers D, dou
   if (P.vel) {
     // dq_0 = dqc is pinned (fix_configuration on the velocity state), so its velocity-limit rows are constants of the instance: outside them there is no
     // feasible point -- IPOPT's "infeasible problem" (solver.py:407-412); the interior point above can only sit in the relaxed barrier until its cap
-    const double* x0r = D.xs + xs_off(D, T, cur, b, 0);
+    const double* x0r = tq_xs(D, T, cur, b, 0);
     double worst = 0.0;
 #pragma unroll
-    for (int j = 0; j < N; ++j) worst = fmin(worst, fmin(x0r[8 + j] - P.dq_lo[j], P.dq_up[j] - x0r[8 + j]));
+    for (int j = 0; j < N; ++j) worst = fmin(worst, fmin(x0r[TqKnot::dq + j] - P.dq_lo[j], P.dq_up[j] - x0r[TqKnot::dq + j]));
     if (worst < -1e-9) {
       st = OH_STATUS_INFEASIBLE;
       if (kkt) kkt[3 * b + 1] = fmax(kkt[3 * b + 1], -worst);
@@ -1109,10 +978,21 @@ bool kernel_info(K kernel, int block, OhKernelInfo* out) {
   return true;
 }
 }  // namespace
+// "k_tq_eval", "k_tq_curv", "k_tq_step": the 7-joint arm's instantiations; with "_N" behind them (N = 2 .. 7) those of an N-joint chain
 bool oh_kernel_info_torque(const char* name, OhKernelInfo* out) {
-  const std::string n(name);
-  if (n == "k_tq_eval") return kernel_info(k_tq_eval3<7>, 64, out);
-  if (n == "k_tq_curv") return kernel_info(k_tq_curv<7>, 64, out);
-  if (n == "k_tq_step") return kernel_info(k_tq_step<7>, 64, out);
+  std::string n(name);
+  int N = 7;
+  if (n.size() > 2 && n[n.size() - 2] == '_' && n.back() >= '0' && n.back() <= '9') {
+    N = n.back() - '0';
+    n.resize(n.size() - 2);
+  }
+#define C(NN)                                                            \
+  {                                                                      \
+    if (n == "k_tq_eval") return kernel_info(k_tq_eval3<NN>, 64, out);   \
+    if (n == "k_tq_curv") return kernel_info(k_tq_curv<NN>, 64, out);    \
+    if (n == "k_tq_step") return kernel_info(k_tq_step<NN>, 64, out);    \
+  }
+  OH_TQ_DISPATCH(N, C)
+#undef C
   return false;
 }
