@@ -101,6 +101,7 @@ __global__ __launch_bounds__(64) void k_pm_solve(PmParams P, PmBuffers D, const 
     // ---- backward pass: residuals (adjoint) and Riccati recursion -----------------------------------------------
     double Pm[16], pv[4], padj[4];
     stat = 0.0; feas = 0.0; compl_ = 0.0; fval = 0.0;
+    bool bad = false;  // fmax drops NaNs: a NaN row residual (a NaN obstacle entry, say) is carried apart from the maxima, as in k_pm_solve_wave
     // every sweep below walks the knots in a dependent chain while what it reads depends on the knot alone: the next knot's values are
     // requested before this one's arithmetic (otherwise each of the 3 x T knot steps of an iteration is a memory round trip: the whole
     // solve was 7.2 ms for any batch up to ~16 k instances)
@@ -122,6 +123,7 @@ __global__ __launch_bounds__(64) void k_pm_solve(PmParams P, PmBuffers D, const 
         sig[i] = lam[i] / s[i];
         wq[i] = mu / s[i] - sig[i] * rc[i];
         if (t >= 1) { feas = fmax(feas, fabs(rc[i])); compl_ = fmax(compl_, lam[i] * s[i]); }
+        bad = bad || !(rc[i] == rc[i]) || !(lam[i] * s[i] == lam[i] * s[i]);
       }
       pm_JTw(lam, jx, jy, jl);
       pm_JTw(wq, jx, jy, jq);
@@ -225,6 +227,7 @@ __global__ __launch_bounds__(64) void k_pm_solve(PmParams P, PmBuffers D, const 
         for (int cc = 0; cc < 4; ++cc) Pm[4 * r + cc] = 0.5 * (Pn[4 * r + cc] + Pn[4 * cc + r]);
       for (int j = 0; j < 4; ++j) { pv[j] = pn[j]; padj[j] = pa[j]; }
     }
+    if (bad) feas = __builtin_nan("");
     if (!(stat == stat) || !(fval == fval) || !(fabs(fval) < 1e300) || !(feas == feas) || !(compl_ == compl_)) { status = OH_STATUS_NUMERICAL; break; }
     if (stat <= P.tol && feas <= P.tol && compl_ <= P.tol) { status = OH_STATUS_CONVERGED; break; }
     // No feasible plan (round 6; the reference: IPOPT's Infeasible_Problem_Detected -> did_solve() False, solver.py:407-412): the obstacle is a parameter of every
@@ -438,7 +441,7 @@ __global__ __launch_bounds__(64) void k_pm_solve_wave(PmParams P, int B, const d
     fval = pm_wave_sum(on ? fl : 0.0);
     feas = pm_wave_max(fe);
     compl_ = pm_wave_max(co);
-    {  // (fmax drops NaNs: carry them separately, the thread kernel's maxima see them through the comparison chain as well)
+    {  // (fmax drops NaNs: carry them separately, by the thread kernel's rule -- every knot's rows, knot 0 included)
       bool bad = false;
       for (int i = 0; i < 9; ++i) bad = bad || !(rc[i] == rc[i]) || !(lam[i] * s[i] == lam[i] * s[i]);
       if (__any(on && bad)) feas = __builtin_nan("");

@@ -72,6 +72,7 @@ def solve_pointmass_ipm(T, dt, w, ylim, vlim, safe_sq, curr, dcurr, goal, obs, V
     lam = mu / s
     status = 1
     it = 0
+    hist = []  # (stat, feas, compl) of every evaluation, the last one included
     for it in range(max_iter + 1):
         c, J = cons(X)
         rc = c - s
@@ -93,6 +94,7 @@ def solve_pointmass_ipm(T, dt, w, ylim, vlim, safe_sq, curr, dcurr, goal, obs, V
         feas = float(np.max(np.abs(rc[:, 1:])))
         compl = float(np.max(lam[:, 1:] * s[:, 1:]))
         fval = float(np.sum(wt[None] * (goal - X[:2]) ** 2) + w_vel * np.sum(X[2:] ** 2) + w * np.sum(a * a))
+        hist.append((stat, feas, compl))
         if verbose:
             print(f"  it {it:3d} f={fval:.10f} stat={stat:.2e} feas={feas:.2e} compl={compl:.2e} mu={mu:.2e}")
         if stat <= tol and feas <= tol and compl <= tol:
@@ -156,4 +158,4 @@ def solve_pointmass_ipm(T, dt, w, ylim, vlim, safe_sq, curr, dcurr, goal, obs, V
         gap = float(np.sum(s[:, 1:] * lam[:, 1:])) / (nI * (T - 1))
         sigma = 0.1 if min(ap, ad) > 0.9 else (0.3 if min(ap, ad) > 0.5 else 0.8)
         mu = max(sigma * gap, 1e-2 * tol)
-    return {"Y": X[:2], "V": X[2:], "f": fval, "iters": it, "kkt": (stat, feas, compl), "status": status, "lam": lam, "s": s}
+    return {"Y": X[:2], "V": X[2:], "f": fval, "iters": it, "kkt": (stat, feas, compl), "status": status, "lam": lam, "s": s, "kkt_history": hist}
