@@ -1,5 +1,6 @@
 // Host side of the dense QP family (OH_PROBLEM_QP): creation, the optional tape the QP data is read from, the solve.  State: oh_handle::qp.
 #include "oh_handle.h"
+#include "oh_qp_layout.h"
 
 extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
   if (!desc || !out) return fail(OH_ERR_INVALID, "oh_create_qp: null argument");
@@ -18,7 +19,7 @@ extern "C" int oh_create_qp(const oh_qp_desc* desc, oh_handle** out) {
 }
 
 // doubles of the parameter vector of a handle without a tape: [P | q | M | c | A | b]
-size_t qp_np(const oh_qp_desc& q) { return (size_t)q.n * q.n + q.n + (size_t)q.m * q.n + q.m + (size_t)q.me * q.n + q.me; }
+size_t qp_np(const oh_qp_desc& q) { return qp_row_doubles(q.n, q.m, q.me); }
 
 extern "C" int oh_qp_set_tape(oh_handle* h, const oh_tape_desc* d) {
   if (!h || !d) return fail(OH_ERR_INVALID, "oh_qp_set_tape: null argument");
@@ -58,7 +59,7 @@ int qp_solve_device(oh_handle* h, const Solve& a) {
   const int B = a.B;
   QpParams Q{};
   Q.n = q.n; Q.m = q.m; Q.me = q.me; Q.np = (int)qp_np(q); Q.max_iter = q.max_iter; Q.tol = q.tol;
-  Q.nwork = q.n + 2 * q.m + q.me + q.n * q.n + 2 * q.n + 2 * q.m + q.me * q.n + q.me * q.me + q.me + q.n;
+  Q.nwork = (int)qp_work_doubles(q.n, q.m, q.me);
   const int Bp = (B + 63) / 64 * 64;
   const int mode = (int)optv(h, "qp_mode");
   const bool large = oh_qp_is_large(Q), block = oh_qp_takes_block(Q, mode);

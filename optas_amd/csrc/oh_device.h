@@ -24,6 +24,23 @@ __device__ __forceinline__ double readlane_f64(const double v, const int lane) {
   return __hiloint2double(hi, lo);
 }
 
+// sum / maximum / minimum over the 64 lanes of a wavefront, the result on every lane (xor ladder from 32 down: every lane adds in the same order)
+__device__ __forceinline__ double wave64_sum(double v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k);
+  return v;
+}
+__device__ __forceinline__ double wave64_max(double v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v = fmax(v, __shfl_xor(v, k));
+  return v;
+}
+__device__ __forceinline__ double wave64_min(double v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v = fmin(v, __shfl_xor(v, k));
+  return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // 3-vectors / 3x3 row-major matrices
 // ---------------------------------------------------------------------------------------------

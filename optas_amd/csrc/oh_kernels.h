@@ -251,6 +251,9 @@ bool oh_qp_takes_block(const QpParams& Q, int mode);     // the solve runs k_qp_
 size_t oh_qp_block_work_doubles(const QpParams& Q);      // per instance: W^T [n][me] and the Schur complement
 int oh_launch_qp_solve_block(hipStream_t s, const QpParams& Q, int B, const double* x0, const double* p, double* work, double* x, double* f, double* kkt, int* iters,
                              int* status, double* mult, std::string* err);
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device and sticky: asks only when a launch of fn needs more than this device has been granted
+// (granted: the kernel's own [64], by device).  false: the request was refused.  (oh_qp.hip)
+bool grant_dynamic_lds(const void* fn, size_t bytes, size_t* granted);
 
 // ---- OH_PROBLEM_TAPE ---------------------------------------------------------------------------------------
 #define OH_TAPE_ST_CONVERGED OH_STATUS_CONVERGED

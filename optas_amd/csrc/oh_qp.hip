@@ -3,19 +3,24 @@
 //
 //     min_x  x^T P x + q^T x      s.t.  M x + c >= 0,   A x + b = 0           (optimization.py:219-260: no factor 1/2)
 //
-// One thread owns one instance: infeasible-start primal-dual interior point with slacks s = Mx + c, Newton system reduced to
-// H = P + P^T + M^T (lam/s) M (dense Cholesky, n <= 32, m <= 256, me <= 32; larger handles, up to OH_QP_MAX_N / _M / _ME, are solved by one workgroup per
-// instance: oh_qp_block.hip) and the Schur complement A H^{-1} A^T for the equality rows.
-// The matrices differ per instance (P, M, A may depend on the parameters: the Booth test has a * y in its cost), so every
-// instance brings its own [P | q | M | c | A | b] row; work arrays are thread-private slices of one global buffer.
-// numpy restatement of the same iteration: oracle/qp_ipm.py.
+// Infeasible-start primal-dual interior point with slacks s = Mx + c, Newton system reduced to H = P + P^T + M^T (lam/s) M (dense Cholesky,
+// n <= 32, m <= 256, me <= 32; larger handles, up to OH_QP_MAX_N / _M / _ME, are solved by one workgroup per instance: oh_qp_block.hip) and the
+// Schur complement A H^{-1} A^T for the equality rows.  The iteration is written ONCE, qp_ipm, over a team: the lanes that own one instance.
+//   QpThread  one thread per instance (k_qp_solve<0|1|2>: work set in the global buffer, in LDS, in LDS together with the instance's row)
+//   QpWave    one wavefront per instance, everything in LDS (k_qp_solve_wave: a few instances; a controller's tick is one)
+// The four kernels decide where the row and the work set lie and call it.  The scalar rules are those of oh_qp_rules.h, the layouts those of
+// oh_qp_layout.h.  The matrices differ per instance (P, M, A may depend on the parameters: the Booth test has a * y in its cost), so every
+// instance brings its own [P | q | M | c | A | b] row.  numpy restatement of the same iteration: oracle/qp_ipm.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <mutex>
 #include <string>
 
+#include "oh_device.h"
 #include "oh_kernels.h"
+#include "oh_qp_layout.h"
+#include "oh_qp_rules.h"
 
 namespace {
 
@@ -26,26 +31,75 @@ struct QArr {
   double* p;
   int stride;
   __device__ double& operator[](const int i) const { return p[(size_t)i * stride]; }
-  __device__ QArr at(const int off) const { return QArr{p + (size_t)off * stride, stride}; }
+  __device__ QArr operator+(const size_t off) const { return QArr{p + off * stride, stride}; }
 };
 
-// in-place Cholesky of the n x n row-major SPD matrix H (lower triangle); returns false on a non-positive pivot
-__device__ bool qp_chol(const QArr H, const int n) {
+// The lanes that own one instance.  Loops over rows, columns and entries run `for (i = lane; i < count; i += step)`: every entry has ONE owner,
+// which accumulates its dot product in ascending index -- the same arithmetic whatever the team.  A team says how its lanes agree (sync, the
+// reductions, all / any), who does the short serial parts (leader) and how the lower triangle of H and its rows are dealt (lower).
+struct QpThread {
+  static constexpr int lane = 0, step = 1;
+  // Nothing: the threads of a k_qp_solve block own different instances, return early (b >= B) and leave the iteration at different counts, so
+  // there must be NO barrier on this team's path.
+  __device__ static void sync() {}
+  __device__ static double max(const double v) { return v; }
+  __device__ static double min(const double v) { return v; }
+  __device__ static double sum(const double v) { return v; }
+  __device__ static bool all(const bool p) { return p; }
+  __device__ static bool any(const bool p) { return p; }
+  __device__ static bool leader() { return true; }
+  template <class F, class G>
+  __device__ static void lower(const int n, F entry, G row) {  // entry(i, j) for j <= i < n; row(i) right after row i (its column of M is at hand)
+    for (int i = 0; i < n; ++i) {
+      for (int j = 0; j <= i; ++j) entry(i, j);
+      row(i);
+    }
+  }
+};
+// The block IS the wavefront (64 threads): the barrier orders the LDS traffic of its lanes.  Every exit of the iteration is taken from a value
+// all 64 lanes hold (after a reduction, all(), or read from the same LDS word after a barrier), so every lane meets every barrier.
+struct QpWave {
+  const int lane;
+  static constexpr int step = 64;
+  __device__ static void sync() { __syncthreads(); }
+  __device__ static double max(const double v) { return wave64_max(v); }
+  __device__ static double min(const double v) { return wave64_min(v); }
+  __device__ static double sum(const double v) { return wave64_sum(v); }  // per-lane partial sums, then the ladder: equal to the thread's sum to rounding
+  __device__ static bool all(const bool p) { return __all(p); }
+  __device__ static bool any(const bool p) { return __any(p); }
+  __device__ bool leader() const { return lane == 0; }
+  template <class F, class G>
+  __device__ void lower(const int n, F entry, G row) const {  // entry e = i (i + 1) / 2 + j by lane e % 64, then row i by lane i % 64
+    for (int e = lane; e < n * (n + 1) / 2; e += 64) {
+      int i = 0, r = e;
+      while (r > i) { r -= i + 1; ++i; }
+      entry(i, r);
+    }
+    for (int i = lane; i < n; i += 64) row(i);
+  }
+};
+
+// in-place left-looking Cholesky of the n x n row-major SPD matrix H (lower triangle): the pivot of column j by every lane alike, the rows below
+// it dealt over the team; returns false (on every lane) on a non-positive pivot
+template <class Team>
+__device__ __forceinline__ bool qp_chol(const Team team, const QArr H, const int n) {
   for (int j = 0; j < n; ++j) {
     double d = H[j * n + j];
     for (int k = 0; k < j; ++k) d -= H[j * n + k] * H[j * n + k];
     if (!(d > 0.0)) return false;
     const double l = sqrt(d);
-    H[j * n + j] = l;
-    for (int i = j + 1; i < n; ++i) {
+    for (int i = j + 1 + team.lane; i < n; i += team.step) {  // (column j is read by its owners only: written in place)
       double v = H[i * n + j];
       for (int k = 0; k < j; ++k) v -= H[i * n + k] * H[j * n + k];
       H[i * n + j] = v / l;
     }
+    team.sync();  // every lane has read the pivot
+    if (team.leader()) H[j * n + j] = l;
+    team.sync();
   }
   return true;
 }
-__device__ void qp_solve_chol(const QArr L, const int n, const QArr x) {  // x <- (L L^T)^{-1} x
+__device__ void qp_solve_chol(const QArr L, const int n, const QArr x) {  // x <- (L L^T)^{-1} x, by one lane
   for (int i = 0; i < n; ++i) {
     double v = x[i];
     for (int k = 0; k < i; ++k) v -= L[i * n + k] * x[k];
@@ -58,7 +112,176 @@ __device__ void qp_solve_chol(const QArr L, const int n, const QArr x) {  // x <
   }
 }
 
-// MODE 0: work set in the global buffer; 1: in LDS; 2: in LDS together with the instance's [P | q | M | c | A | b] row
+// The iteration on instance b: `row` holds its [P | q | M | c | A | b] (read only), `work` its work set.
+template <class Team>
+__device__ __forceinline__ void qp_ipm(const Team team, const QpParams& Q, const int b, const QArr row, const QArr work, const double* __restrict__ x0,
+                                       double* __restrict__ xo, double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters,
+                                       int* __restrict__ status, double* __restrict__ mult) {
+  const int n = Q.n, m = Q.m, me = Q.me, lane = team.lane, step = team.step;
+  const QpRow<QArr> R = qp_row(row, n, m, me);
+  const QpWork<QArr> W = qp_work(work, n, m, me);
+  const QArr P = R.P, q = R.q, M = R.M, c = R.c, A = R.A, bv = R.b;
+  const QArr x = W.x, s = W.s, lam = W.lam, nu = W.nu, H = W.H, rhs = W.rhs, dx = W.dx, ds = W.ds, dl = W.dl, Y = W.Y, S = W.S, dnu = W.dnu, rd = W.rd;
+  for (int i = lane; i < n; i += step) x[i] = x0[(size_t)b * n + i];
+  for (int i = lane; i < me; i += step) nu[i] = 0.0;
+  team.sync();
+  double mu = 1.0;
+  for (int i = lane; i < m; i += step) {
+    double v = c[i];
+    for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
+    s[i] = qp_rules::initial_slack(v);
+    lam[i] = qp_rules::initial_multiplier(mu, s[i]);
+  }
+  team.sync();
+  int st = OH_STATUS_MAX_ITER, it = 0;
+  double stat = 0.0, feas = 0.0, gap = 0.0;
+  for (; it <= Q.max_iter; ++it) {
+    // residuals
+    stat = 0.0; feas = 0.0; gap = 0.0;
+    bool finite = true;
+    for (int i = lane; i < n; i += step) {
+      double v = q[i];
+      for (int j = 0; j < n; ++j) v += (P[i * n + j] + P[j * n + i]) * x[j];  // gradient of x^T P x: P need not be symmetric
+      for (int k = 0; k < m; ++k) v -= M[k * n + i] * lam[k];
+      for (int k = 0; k < me; ++k) v -= A[k * n + i] * nu[k];
+      rd[i] = v;
+      stat = fmax(stat, fabs(v));
+      finite = finite && qp_rules::finite(v);
+    }
+    for (int i = lane; i < m; i += step) {
+      double v = c[i] - s[i];
+      for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
+      ds[i] = v;  // r_p
+      feas = fmax(feas, fabs(v));
+      gap = fmax(gap, s[i] * lam[i]);
+      dl[i] = lam[i] / s[i];  // (dl is free until the step: one division per row instead of one per use)
+    }
+    for (int i = lane; i < me; i += step) {
+      double v = bv[i];
+      for (int j = 0; j < n; ++j) v += A[i * n + j] * x[j];
+      dnu[i] = v;  // r_e
+      feas = fmax(feas, fabs(v));
+    }
+    finite = team.all(finite);
+    const bool feas_nan = team.any(!(feas == feas));
+    stat = team.max(stat);
+    feas = team.max(feas);
+    gap = team.max(gap);
+    team.sync();
+    if (!finite || feas_nan) { st = OH_STATUS_NUMERICAL; break; }
+    if (qp_rules::converged(stat, feas, gap, Q.tol)) { st = OH_STATUS_CONVERGED; break; }
+    if (it == Q.max_iter) break;
+    // H = P + P^T + M^T diag(lam/s) M (+ tiny shift), rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
+    auto entry = [&](const int i, const int j) {
+      double v = P[i * n + j] + P[j * n + i];
+      for (int k = 0; k < m; ++k) v += M[k * n + i] * dl[k] * M[k * n + j];
+      H[i * n + j] = v;
+    };
+    team.lower(n, entry, [&](const int i) {
+      double r = -rd[i];
+      for (int k = 0; k < m; ++k) r += M[k * n + i] * ((mu / s[k] - lam[k]) - dl[k] * ds[k]);
+      rhs[i] = r;
+    });
+    team.sync();
+    double dmax = 0.0;
+    for (int i = 0; i < n; ++i) dmax = fmax(dmax, fabs(H[i * n + i]));
+    double shift = qp_rules::first_shift(dmax);
+    bool ok = false;
+    for (int attempt = 0; attempt < qp_rules::SHIFT_ATTEMPTS && !ok; ++attempt) {
+      if (attempt > 0) {  // rebuild with a larger shift (singular P without enough active rows)
+        team.sync();
+        team.lower(n, entry, [](const int) {});
+        shift *= qp_rules::SHIFT_GROWTH;
+        team.sync();
+      }
+      for (int i = lane; i < n; i += step) H[i * n + i] += shift;
+      team.sync();
+      ok = qp_chol(team, H, n);
+    }
+    if (!ok) { st = OH_STATUS_NUMERICAL; break; }
+    // the substitution for dx and the factor of S are short and serial: the leader's
+    for (int i = lane; i < n; i += step) dx[i] = rhs[i];
+    team.sync();
+    if (team.leader()) qp_solve_chol(H, n, dx);  // H^{-1} rhs
+    team.sync();
+    if (me > 0) {
+      // A dx = -r_e with dx = H^{-1}(rhs + A^T dnu):  (A H^{-1} A^T) dnu = -r_e - A H^{-1} rhs
+      for (int i = lane; i < me; i += step) {  // row i of Y = H^{-1} A_i
+        for (int j = 0; j < n; ++j) Y[i * n + j] = A[i * n + j];
+        qp_solve_chol(H, n, Y + (size_t)(i * n));
+      }
+      team.sync();
+      for (int i = lane; i < me; i += step) {
+        double r = -dnu[i];
+        for (int j = 0; j < n; ++j) r -= A[i * n + j] * dx[j];
+        for (int k = 0; k <= i; ++k) {
+          double v = 0.0;
+          for (int j = 0; j < n; ++j) v += A[i * n + j] * Y[k * n + j];
+          S[i * me + k] = v;
+        }
+        S[i * me + i] += qp_rules::schur_regularisation(S[i * me + i]);
+        dnu[i] = r;
+      }
+      team.sync();
+      bool oks = true;
+      if (team.leader()) {
+        oks = qp_chol(QpThread{}, S, me);
+        if (oks) {
+          qp_solve_chol(S, me, dnu);
+          for (int i = 0; i < me; ++i)
+            for (int j = 0; j < n; ++j) dx[j] += Y[i * n + j] * dnu[i];
+        }
+      }
+      oks = team.all(oks);
+      team.sync();
+      if (!oks) { st = OH_STATUS_NUMERICAL; break; }
+    }
+    // ds = M dx + r_p ; dlam = (mu/s - lam) - (lam/s) ds ; fraction to the boundary
+    double ap = 1.0, ad = 1.0;
+    for (int i = lane; i < m; i += step) {
+      double v = ds[i];
+      for (int j = 0; j < n; ++j) v += M[i * n + j] * dx[j];
+      const double d2 = (mu / s[i] - lam[i]) - dl[i] * v;
+      ds[i] = v;
+      dl[i] = d2;
+      if (v < 0.0) ap = fmin(ap, qp_rules::boundary_step(s[i], v));
+      if (d2 < 0.0) ad = fmin(ad, qp_rules::boundary_step(lam[i], d2));
+    }
+    ap = team.min(ap);
+    ad = team.min(ad);
+    for (int i = lane; i < n; i += step) x[i] += ap * dx[i];
+    double comp = 0.0;
+    for (int i = lane; i < m; i += step) {
+      s[i] += ap * ds[i];
+      lam[i] += ad * dl[i];
+      comp += s[i] * lam[i];
+    }
+    comp = team.sum(comp);
+    for (int i = lane; i < me; i += step) nu[i] += ad * dnu[i];
+    if (m > 0) mu = qp_rules::next_mu(ap, ad, comp, m, Q.tol);
+    team.sync();
+  }
+  double fval = 0.0;
+  for (int i = lane; i < n; i += step) {
+    double v = q[i];
+    for (int j = 0; j < n; ++j) v += P[i * n + j] * x[j];
+    fval += v * x[i];
+    if (xo) xo[(size_t)b * n + i] = x[i];
+  }
+  fval = team.sum(fval);
+  if (team.leader()) {
+    if (fo) fo[b] = fval;
+    if (kkt) { kkt[3 * (size_t)b] = stat; kkt[3 * (size_t)b + 1] = feas; kkt[3 * (size_t)b + 2] = gap; }
+    if (iters) iters[b] = it;
+    if (status) status[b] = st;
+  }
+  if (mult) {
+    for (int i = lane; i < m; i += step) mult[(size_t)b * (m + me) + i] = lam[i];
+    for (int i = lane; i < me; i += step) mult[(size_t)b * (m + me) + m + i] = nu[i];
+  }
+}
+
+// One thread per instance.  MODE 0: work set in the global buffer [k][Bp]; 1: in LDS [k][lane]; 2: in LDS together with the instance's row
 template <int MODE>
 __global__ __launch_bounds__(64) void k_qp_solve(QpParams Q, int B, int Bp, const double* __restrict__ x0, const double* __restrict__ par, double* __restrict__ work,
                                                  double* __restrict__ xo, double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters,
@@ -66,400 +289,27 @@ __global__ __launch_bounds__(64) void k_qp_solve(QpParams Q, int B, int Bp, cons
   extern __shared__ double qp_sm[];
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const int n = Q.n, m = Q.m, me = Q.me;
   QArr w = MODE ? QArr{qp_sm + threadIdx.x, (int)blockDim.x} : QArr{work + b, Bp};
   // (the row is read-only; const_cast only to share the accessor type)
-  QArr pr{const_cast<double*>(par) + (size_t)b * Q.np, 1};
+  QArr row{const_cast<double*>(par) + (size_t)b * Q.np, 1};
   if (MODE == 2) {
-    for (int k = 0; k < Q.np; ++k) w[k] = pr[k];
-    pr = w;
-    w = w.at(Q.np);
+    for (int k = 0; k < Q.np; ++k) w[k] = row[k];
+    row = w;
+    w = w + (size_t)Q.np;
   }
-  const QArr P = pr;                 // [n][n]
-  const QArr q = P.at(n * n);        // [n]
-  const QArr M = q.at(n);            // [m][n]
-  const QArr c = M.at(m * n);        // [m]
-  const QArr A = c.at(m);            // [me][n]
-  const QArr bv = A.at(me * n);      // [me]
-  const QArr x = w; w = w.at(n);
-  const QArr s = w; w = w.at(m);
-  const QArr lam = w; w = w.at(m);
-  const QArr nu = w; w = w.at(me);
-  const QArr H = w; w = w.at(n * n);
-  const QArr rhs = w; w = w.at(n);
-  const QArr dx = w; w = w.at(n);
-  const QArr ds = w; w = w.at(m);
-  const QArr dl = w; w = w.at(m);
-  const QArr Y = w; w = w.at(me * n);   // H^{-1} A^T, row i = H^{-1} A_i
-  const QArr S = w; w = w.at(me * me);
-  const QArr dnu = w; w = w.at(me);
-  const QArr rd = w; w = w.at(n);
-  for (int i = 0; i < n; ++i) x[i] = x0[(size_t)b * n + i];
-  double mu = 1.0;
-  for (int i = 0; i < m; ++i) {
-    double v = c[i];
-    for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
-    s[i] = fmax(v, 1.0);
-    lam[i] = mu / s[i];
-  }
-  for (int i = 0; i < me; ++i) nu[i] = 0.0;
-  int st = OH_STATUS_MAX_ITER, it = 0;
-  double stat = 0.0, feas = 0.0, gap = 0.0;
-  for (; it <= Q.max_iter; ++it) {
-    // residuals
-    stat = 0.0; feas = 0.0; gap = 0.0;
-    bool finite = true;
-    for (int i = 0; i < n; ++i) {
-      double v = q[i];
-      for (int j = 0; j < n; ++j) v += (P[i * n + j] + P[j * n + i]) * x[j];  // gradient of x^T P x: P need not be symmetric
-      for (int k = 0; k < m; ++k) v -= M[k * n + i] * lam[k];
-      for (int k = 0; k < me; ++k) v -= A[k * n + i] * nu[k];
-      rd[i] = v;
-      stat = fmax(stat, fabs(v));
-      finite = finite && (v == v) && (fabs(v) < 1e300);
-    }
-    for (int i = 0; i < m; ++i) {
-      double v = c[i] - s[i];
-      for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
-      ds[i] = v;  // r_p
-      feas = fmax(feas, fabs(v));
-      gap = fmax(gap, s[i] * lam[i]);
-    }
-    for (int i = 0; i < me; ++i) {
-      double v = bv[i];
-      for (int j = 0; j < n; ++j) v += A[i * n + j] * x[j];
-      dnu[i] = v;  // r_e
-      feas = fmax(feas, fabs(v));
-    }
-    if (!finite || !(feas == feas)) { st = OH_STATUS_NUMERICAL; break; }
-    if (stat <= Q.tol && feas <= Q.tol && gap <= Q.tol) { st = OH_STATUS_CONVERGED; break; }
-    if (it == Q.max_iter) break;
-    // H = P + P^T + M^T diag(lam/s) M (+ tiny shift), rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
-    double dmax = 0.0;
-    for (int k = 0; k < m; ++k) dl[k] = lam[k] / s[k];  // (dl is free until the step: one division per row instead of one per use)
-    for (int i = 0; i < n; ++i) {
-      for (int j = 0; j <= i; ++j) {
-        double v = P[i * n + j] + P[j * n + i];
-        for (int k = 0; k < m; ++k) v += M[k * n + i] * dl[k] * M[k * n + j];
-        H[i * n + j] = v;
-      }
-      dmax = fmax(dmax, fabs(H[i * n + i]));
-      double r = -rd[i];
-      for (int k = 0; k < m; ++k) r += M[k * n + i] * ((mu / s[k] - lam[k]) - dl[k] * ds[k]);
-      rhs[i] = r;
-    }
-    double shift = 1e-13 * fmax(dmax, 1.0);
-    bool ok = false;
-    for (int attempt = 0; attempt < 8 && !ok; ++attempt) {
-      if (attempt > 0) {  // rebuild with a larger shift (singular P without enough active rows)
-        for (int i = 0; i < n; ++i)
-          for (int j = 0; j <= i; ++j) {
-            double v = P[i * n + j] + P[j * n + i];
-            for (int k = 0; k < m; ++k) v += M[k * n + i] * dl[k] * M[k * n + j];
-            H[i * n + j] = v;
-          }
-        shift *= 1e3;
-      }
-      for (int i = 0; i < n; ++i) H[i * n + i] += shift;
-      ok = qp_chol(H, n);
-    }
-    if (!ok) { st = OH_STATUS_NUMERICAL; break; }
-    for (int i = 0; i < n; ++i) dx[i] = rhs[i];
-    qp_solve_chol(H, n, dx);  // H^{-1} rhs
-    if (me > 0) {
-      // A dx = -r_e with dx = H^{-1}(rhs + A^T dnu):  (A H^{-1} A^T) dnu = -r_e - A H^{-1} rhs
-      for (int i = 0; i < me; ++i) {
-        for (int j = 0; j < n; ++j) Y[i * n + j] = A[i * n + j];
-        qp_solve_chol(H, n, Y.at(i * n));
-      }
-      for (int i = 0; i < me; ++i) {
-        double r = -dnu[i];
-        for (int j = 0; j < n; ++j) r -= A[i * n + j] * dx[j];
-        for (int k = 0; k <= i; ++k) {
-          double v = 0.0;
-          for (int j = 0; j < n; ++j) v += A[i * n + j] * Y[k * n + j];
-          S[i * me + k] = v;
-        }
-        S[i * me + i] += 1e-14 * fmax(1.0, S[i * me + i]);
-        dnu[i] = r;
-      }
-      if (!qp_chol(S, me)) { st = OH_STATUS_NUMERICAL; break; }
-      qp_solve_chol(S, me, dnu);
-      for (int i = 0; i < me; ++i)
-        for (int j = 0; j < n; ++j) dx[j] += Y[i * n + j] * dnu[i];
-    }
-    // ds = M dx + r_p ; dlam = (mu/s - lam) - (lam/s) ds ; fraction to the boundary
-    double ap = 1.0, ad = 1.0;
-    for (int i = 0; i < m; ++i) {
-      double v = ds[i];
-      for (int j = 0; j < n; ++j) v += M[i * n + j] * dx[j];
-      const double d2 = (mu / s[i] - lam[i]) - dl[i] * v;
-      ds[i] = v;
-      dl[i] = d2;
-      if (v < 0.0) ap = fmin(ap, -0.995 * s[i] / v);
-      if (d2 < 0.0) ad = fmin(ad, -0.995 * lam[i] / d2);
-    }
-    for (int i = 0; i < n; ++i) x[i] += ap * dx[i];
-    double comp = 0.0;
-    for (int i = 0; i < m; ++i) {
-      s[i] += ap * ds[i];
-      lam[i] += ad * dl[i];
-      comp += s[i] * lam[i];
-    }
-    for (int i = 0; i < me; ++i) nu[i] += ad * dnu[i];
-    if (m > 0) {
-      const double am = fmin(ap, ad);
-      const double sigma = (am > 0.9) ? 0.1 : ((am > 0.5) ? 0.3 : 0.8);
-      mu = fmax(sigma * comp / m, 1e-2 * Q.tol);
-    }
-  }
-  double fval = 0.0;
-  for (int i = 0; i < n; ++i) {
-    double v = q[i];
-    for (int j = 0; j < n; ++j) v += P[i * n + j] * x[j];
-    fval += v * x[i];
-    if (xo) xo[(size_t)b * n + i] = x[i];
-  }
-  if (fo) fo[b] = fval;
-  if (kkt) { kkt[3 * (size_t)b] = stat; kkt[3 * (size_t)b + 1] = feas; kkt[3 * (size_t)b + 2] = gap; }
-  if (iters) iters[b] = it;
-  if (status) status[b] = st;
-  if (mult) {
-    for (int i = 0; i < m; ++i) mult[(size_t)b * (m + me) + i] = lam[i];
-    for (int i = 0; i < me; ++i) mult[(size_t)b * (m + me) + m + i] = nu[i];
-  }
+  qp_ipm(QpThread{}, Q, b, row, w, x0, xo, fo, kkt, iters, status, mult);
 }
 
-// The same iteration for a FEW instances (a controller's tick is one): one wavefront per instance, everything of the instance in LDS, the loops
-// over rows, columns and matrix entries spread over the lanes, the short serial parts (Cholesky factor, substitutions, the Schur complement of
-// the equality rows) executed by all lanes alike.  One thread per instance is a chain of ~3000 dependent LDS accesses per iteration (80 us);
-// here an iteration is a few hundred.  Sums over lanes associate differently than the thread's loop: results agree to rounding, not bit for bit.
-__device__ double qp_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ double qp_wave_max(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-  return v;
-}
-__device__ double qp_wave_min(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m));
-  return v;
-}
+// One wavefront per instance, row and work set in LDS [k].  One thread per instance is a chain of ~3000 dependent LDS accesses per iteration
+// (80 us); here an iteration is a few hundred.
 __global__ __launch_bounds__(64) void k_qp_solve_wave(QpParams Q, int B, const double* __restrict__ x0, const double* __restrict__ par, double* __restrict__ xo,
                                                       double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters, int* __restrict__ status,
                                                       double* __restrict__ mult) {
   extern __shared__ double qp_sm[];
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = Q.n, m = Q.m, me = Q.me;
-  QArr w{qp_sm, 1};
-  for (int k = lane; k < Q.np; k += 64) w[k] = par[(size_t)b * Q.np + k];
-  const QArr P = w;                  // [n][n]
-  const QArr q = P.at(n * n);        // [n]
-  const QArr M = q.at(n);            // [m][n]
-  const QArr c = M.at(m * n);        // [m]
-  const QArr A = c.at(m);            // [me][n]
-  const QArr bv = A.at(me * n);      // [me]
-  w = w.at(Q.np);
-  const QArr x = w; w = w.at(n);
-  const QArr s = w; w = w.at(m);
-  const QArr lam = w; w = w.at(m);
-  const QArr nu = w; w = w.at(me);
-  const QArr H = w; w = w.at(n * n);
-  const QArr rhs = w; w = w.at(n);
-  const QArr dx = w; w = w.at(n);
-  const QArr ds = w; w = w.at(m);
-  const QArr dl = w; w = w.at(m);
-  const QArr Y = w; w = w.at(me * n);
-  const QArr S = w; w = w.at(me * me);
-  const QArr dnu = w; w = w.at(me);
-  const QArr rd = w; w = w.at(n);
-  for (int i = lane; i < n; i += 64) x[i] = x0[(size_t)b * n + i];
-  for (int i = lane; i < me; i += 64) nu[i] = 0.0;
-  __syncthreads();
-  double mu = 1.0;
-  for (int i = lane; i < m; i += 64) {
-    double v = c[i];
-    for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
-    s[i] = fmax(v, 1.0);
-    lam[i] = mu / s[i];
-  }
-  __syncthreads();
-  int st = OH_STATUS_MAX_ITER, it = 0;
-  double stat = 0.0, feas = 0.0, gap = 0.0;
-  for (; it <= Q.max_iter; ++it) {
-    stat = 0.0; feas = 0.0; gap = 0.0;
-    bool finite = true;
-    for (int i = lane; i < n; i += 64) {
-      double v = q[i];
-      for (int j = 0; j < n; ++j) v += (P[i * n + j] + P[j * n + i]) * x[j];  // gradient of x^T P x: P need not be symmetric
-      for (int k = 0; k < m; ++k) v -= M[k * n + i] * lam[k];
-      for (int k = 0; k < me; ++k) v -= A[k * n + i] * nu[k];
-      rd[i] = v;
-      stat = fmax(stat, fabs(v));
-      finite = finite && (v == v) && (fabs(v) < 1e300);
-    }
-    for (int i = lane; i < m; i += 64) {
-      double v = c[i] - s[i];
-      for (int j = 0; j < n; ++j) v += M[i * n + j] * x[j];
-      ds[i] = v;  // r_p
-      feas = fmax(feas, fabs(v));
-      gap = fmax(gap, s[i] * lam[i]);
-      dl[i] = lam[i] / s[i];
-    }
-    for (int i = lane; i < me; i += 64) {
-      double v = bv[i];
-      for (int j = 0; j < n; ++j) v += A[i * n + j] * x[j];
-      dnu[i] = v;  // r_e
-      feas = fmax(feas, fabs(v));
-    }
-    finite = __all(finite);
-    const bool feas_nan = __any(!(feas == feas));
-    stat = qp_wave_max(stat);
-    feas = qp_wave_max(feas);
-    gap = qp_wave_max(gap);
-    __syncthreads();
-    if (!finite || feas_nan) { st = OH_STATUS_NUMERICAL; break; }
-    if (stat <= Q.tol && feas <= Q.tol && gap <= Q.tol) { st = OH_STATUS_CONVERGED; break; }
-    if (it == Q.max_iter) break;
-    // H = P + P^T + M^T diag(lam/s) M, entry (i, j <= i) per lane; rhs = -rd + M^T [(mu/s - lam) - (lam/s) r_p]
-    const int nh = n * (n + 1) / 2;
-    auto build = [&]() {
-      for (int e = lane; e < nh; e += 64) {
-        int i = 0, r = e;
-        while (r > i) { r -= i + 1; ++i; }  // e = i (i + 1) / 2 + j
-        const int j = r;
-        double v = P[i * n + j] + P[j * n + i];
-        for (int k = 0; k < m; ++k) v += M[k * n + i] * dl[k] * M[k * n + j];
-        H[i * n + j] = v;
-      }
-    };
-    build();
-    for (int i = lane; i < n; i += 64) {
-      double r = -rd[i];
-      for (int k = 0; k < m; ++k) r += M[k * n + i] * ((mu / s[k] - lam[k]) - dl[k] * ds[k]);
-      rhs[i] = r;
-    }
-    __syncthreads();
-    double dmax = 0.0;
-    for (int i = 0; i < n; ++i) dmax = fmax(dmax, fabs(H[i * n + i]));
-    double shift = 1e-13 * fmax(dmax, 1.0);
-    bool ok = false;
-    for (int attempt = 0; attempt < 8 && !ok; ++attempt) {
-      if (attempt > 0) {  // rebuild with a larger shift (singular P without enough active rows)
-        __syncthreads();
-        build();
-        shift *= 1e3;
-        __syncthreads();
-      }
-      for (int i = lane; i < n; i += 64) H[i * n + i] += shift;
-      __syncthreads();
-      // left-looking Cholesky: the pivot of column j by every lane alike, the rows below it one per lane
-      ok = true;
-      for (int j = 0; j < n && ok; ++j) {
-        double d = H[j * n + j];
-        for (int k = 0; k < j; ++k) d -= H[j * n + k] * H[j * n + k];
-        if (!(d > 0.0)) { ok = false; break; }
-        const double l = sqrt(d);
-        double vmine = 0.0;
-        const int i = j + 1 + lane;
-        if (i < n) {
-          vmine = H[i * n + j];
-          for (int k = 0; k < j; ++k) vmine -= H[i * n + k] * H[j * n + k];
-        }
-        __syncthreads();
-        if (lane == 0) H[j * n + j] = l;
-        if (i < n) H[i * n + j] = vmine / l;
-        __syncthreads();
-      }
-    }
-    if (!ok) { st = OH_STATUS_NUMERICAL; break; }
-    // the substitutions and the equality rows: short, serial, by all lanes alike (the same values land in the same places)
-    for (int i = lane; i < n; i += 64) dx[i] = rhs[i];
-    __syncthreads();
-    if (lane == 0) qp_solve_chol(H, n, dx);  // H^{-1} rhs
-    __syncthreads();
-    if (me > 0) {
-      for (int i = lane; i < me; i += 64) {  // row i of Y = H^{-1} A_i: one lane per equality row
-        for (int j = 0; j < n; ++j) Y[i * n + j] = A[i * n + j];
-        qp_solve_chol(H, n, Y.at(i * n));
-      }
-      __syncthreads();
-      for (int i = lane; i < me; i += 64) {
-        double r = -dnu[i];
-        for (int j = 0; j < n; ++j) r -= A[i * n + j] * dx[j];
-        for (int k = 0; k <= i; ++k) {
-          double v = 0.0;
-          for (int j = 0; j < n; ++j) v += A[i * n + j] * Y[k * n + j];
-          S[i * me + k] = v;
-        }
-        S[i * me + i] += 1e-14 * fmax(1.0, S[i * me + i]);
-        dnu[i] = r;
-      }
-      __syncthreads();
-      bool oks = true;
-      if (lane == 0) {
-        oks = qp_chol(S, me);
-        if (oks) {
-          qp_solve_chol(S, me, dnu);
-          for (int i = 0; i < me; ++i)
-            for (int j = 0; j < n; ++j) dx[j] += Y[i * n + j] * dnu[i];
-        }
-      }
-      oks = __all(oks);
-      __syncthreads();
-      if (!oks) { st = OH_STATUS_NUMERICAL; break; }
-    }
-    // ds = M dx + r_p ; dlam = (mu/s - lam) - (lam/s) ds ; fraction to the boundary
-    double ap = 1.0, ad = 1.0;
-    for (int i = lane; i < m; i += 64) {
-      double v = ds[i];
-      for (int j = 0; j < n; ++j) v += M[i * n + j] * dx[j];
-      const double d2 = (mu / s[i] - lam[i]) - dl[i] * v;
-      ds[i] = v;
-      dl[i] = d2;
-      if (v < 0.0) ap = fmin(ap, -0.995 * s[i] / v);
-      if (d2 < 0.0) ad = fmin(ad, -0.995 * lam[i] / d2);
-    }
-    ap = qp_wave_min(ap);
-    ad = qp_wave_min(ad);
-    for (int i = lane; i < n; i += 64) x[i] += ap * dx[i];
-    double comp = 0.0;
-    for (int i = lane; i < m; i += 64) {
-      s[i] += ap * ds[i];
-      lam[i] += ad * dl[i];
-      comp += s[i] * lam[i];
-    }
-    comp = qp_wave_sum(comp);
-    for (int i = lane; i < me; i += 64) nu[i] += ad * dnu[i];
-    if (m > 0) {
-      const double am = fmin(ap, ad);
-      const double sigma = (am > 0.9) ? 0.1 : ((am > 0.5) ? 0.3 : 0.8);
-      mu = fmax(sigma * comp / m, 1e-2 * Q.tol);
-    }
-    __syncthreads();
-  }
-  double fval = 0.0;
-  for (int i = lane; i < n; i += 64) {
-    double v = q[i];
-    for (int j = 0; j < n; ++j) v += P[i * n + j] * x[j];
-    fval += v * x[i];
-    if (xo) xo[(size_t)b * n + i] = x[i];
-  }
-  fval = qp_wave_sum(fval);
-  if (lane == 0) {
-    if (fo) fo[b] = fval;
-    if (kkt) { kkt[3 * (size_t)b] = stat; kkt[3 * (size_t)b + 1] = feas; kkt[3 * (size_t)b + 2] = gap; }
-    if (iters) iters[b] = it;
-    if (status) status[b] = st;
-  }
-  if (mult) {
-    for (int i = lane; i < m; i += 64) mult[(size_t)b * (m + me) + i] = lam[i];
-    for (int i = lane; i < me; i += 64) mult[(size_t)b * (m + me) + m + i] = nu[i];
-  }
+  const QArr row{qp_sm, 1};
+  for (int k = lane; k < Q.np; k += 64) row[k] = par[(size_t)b * Q.np + k];  // (qp_ipm's first barrier stands before the first read of it)
+  qp_ipm(QpWave{lane}, Q, b, row, row + (size_t)Q.np, x0, xo, fo, kkt, iters, status, mult);
 }
 
 // ---- QP data read off the problem's instruction tape on the device (oh_qp_set_tape) -----------------------------------------------------
@@ -478,7 +328,7 @@ struct QpTape {
   int n_xdep;                     // instructions whose value depends on x (the kinematics of a velocity-IK problem depend on p only:
   const int* __restrict__ xdep;   // 139 of its 474 instructions are left), in tape order
 };
-constexpr int QP_SMALL_N = 32;  // n of the handles these two kernels serve (their per-lane and static LDS arrays); larger ones: k_qp_assemble_block
+constexpr int QP_SMALL_N = 32;  // n of the handles the thread / wavefront kernels serve; bounds k_qp_assemble's per-thread arrays, nothing else
 #define QIDX(i) ((size_t)(i) * Bp + b)
 // What tape_value (oh_tape_ops.h) sees of an instruction here: operand values the caller has loaded (b only where the opcode has one).  CONST, X and P
 // never arrive (what X loads is what the two assemblies differ in), nor do ADD, SUB and MUL, which the callers keep as cases of their own.
@@ -518,12 +368,8 @@ __global__ __launch_bounds__(64) void k_qp_assemble(QpParams Q, QpTape tp, int n
   if (b >= B) return;
   const int n = Q.n, m = Q.m, me = Q.me;
   const double* pb = par + (size_t)b * np_raw;
-  double* P = rows_out + (size_t)b * Q.np;
-  double* q = P + n * n;
-  double* M = q + n;
-  double* c = M + m * n;
-  double* A = c + m;
-  double* bv = A + me * n;
+  const QpRow<double*> R = qp_row(rows_out + (size_t)b * Q.np, n, m, me);
+  double *const P = R.P, *const q = R.q, *const M = R.M, *const c = R.c, *const A = R.A, *const bv = R.b;
   double x[QP_SMALL_N], f1[QP_SMALL_N];
   for (int i = 0; i < n; ++i) x[i] = 0.0;
   const double f0 = qp_tape_forward<true>(tp, x, pb, val, Bp, b);
@@ -550,74 +396,12 @@ __global__ __launch_bounds__(64) void k_qp_assemble(QpParams Q, QpTape tp, int n
   }
   f0_out[b] = f0;
 }
-// The same for a few instances: one BLOCK per instance, one lane per probe point (1 + 2 n + n (n - 1) / 2 of them, 64 at a time), registers of
-// lane l of instance b at val[(i * B + b) * 64 + l].  A tick of a velocity-IK controller is one instance: 36 probes side by side instead of one
-// after the other (the sweep is a chain of dependent memory round trips either way).
-__device__ void qp_probe_point(const int pid, const int n, double* x, int* pi, int* pj) {  // x of probe pid; (i, j) of a pair probe, else (-1, -1)
-  for (int k = 0; k < n; ++k) x[k] = 0.0;
-  *pi = *pj = -1;
-  if (pid == 0) return;
-  if (pid <= n) { x[pid - 1] = 1.0; return; }
-  if (pid <= 2 * n) { x[pid - 1 - n] = -1.0; return; }
-  int k = pid - 1 - 2 * n, i = 1;
-  while (k >= i) { k -= i; ++i; }  // pair k of row i: (i, j = k), j < i
-  x[i] = x[k] = 1.0;
-  *pi = i;
-  *pj = k;
-}
-__global__ __launch_bounds__(64) void k_qp_assemble_par(QpParams Q, QpTape tp, int np_raw, int B, const double* __restrict__ par, double* __restrict__ val,
-                                                        double* __restrict__ rows_out, double* __restrict__ f0_out) {
-  __shared__ double fs[1 + 2 * QP_SMALL_N + QP_SMALL_N * (QP_SMALL_N - 1) / 2];
-  const int inst = blockIdx.x, lane = threadIdx.x;
-  const int n = Q.n, m = Q.m, me = Q.me;
-  const int n_probe = 1 + 2 * n + n * (n - 1) / 2;
-  const double* pb = par + (size_t)inst * np_raw;
-  double* P = rows_out + (size_t)inst * Q.np;
-  double* q = P + n * n;
-  double* M = q + n;
-  double* c = M + m * n;
-  double* A = c + m;
-  double* bv = A + me * n;
-  const int Bp = B * 64, b = inst * 64 + lane;  // QIDX(i) = (i * B + inst) * 64 + lane
-  double x[QP_SMALL_N];
-  for (int base = 0; base < n_probe; base += 64) {
-    const int pid = base + lane;
-    const bool live = pid < n_probe;
-    int pi, pj;
-    qp_probe_point(live ? pid : 0, n, x, &pi, &pj);
-    const double f = qp_tape_forward<true>(tp, x, pb, val, Bp, b);
-    if (live) fs[pid] = f;
-    if (base == 0) {  // the rows at 0 first, then the columns of M and A relative to them
-      if (lane == 0) {
-        for (int r = 0; r < m; ++r) c[r] = val[QIDX(tp.rows[r])];
-        for (int r = 0; r < me; ++r) bv[r] = val[QIDX(tp.rows[m + r])];
-      }
-      __syncthreads();
-    }
-    if (live && pid >= 1 && pid <= n) {
-      const int i = pid - 1;
-      for (int r = 0; r < m; ++r) M[r * n + i] = val[QIDX(tp.rows[r])] - c[r];
-      for (int r = 0; r < me; ++r) A[r * n + i] = val[QIDX(tp.rows[m + r])] - bv[r];
-    }
-  }
-  __syncthreads();
-  const double f0 = fs[0];
-  for (int i = lane; i < n; i += 64) {
-    const double qi = 0.5 * (fs[1 + i] - fs[1 + n + i]);
-    q[i] = qi;
-    P[i * n + i] = fs[1 + i] - f0 - qi;
-  }
-  for (int k = lane; k < n * (n - 1) / 2; k += 64) {
-    int kk = k, i = 1;
-    while (kk >= i) { kk -= i; ++i; }
-    P[i * n + kk] = P[kk * n + i] = 0.5 * (fs[1 + 2 * n + k] - fs[1 + i] - fs[1 + kk] + f0);
-  }
-  if (lane == 0) f0_out[inst] = f0;
-}
-// Handles beyond n = 32, m = 256, me = 32 (oh_qp_block.hip solves them): the mapping of k_qp_assemble_par for every B -- a block per instance,
-// a lane per probe point, 64 at a time -- without a per-lane x: the value of an `X a` instruction follows from the probe's (i, j, sign).  The
-// probes' values sit in dynamic LDS (8385 doubles at n = 128).  nb instances per launch: registers of lane l of instance b at
-// val[(i * nb + b) * 64 + l]; the host loop (oh_launch_qp_assemble_block) keeps nb * len * 64 doubles under a fixed budget.
+// The same with one BLOCK per instance and one lane per probe point (1 + 2 n + n (n - 1) / 2 of them, 64 at a time): every large handle
+// (oh_qp_block.hip solves them), and a small one with a few instances -- a tick of a velocity-IK controller is one: 36 probes side by side instead
+// of one after the other (the sweep is a chain of dependent memory round trips either way).  No per-lane x: the value of an `X a` instruction
+// follows from the probe's (i, j, sign).  The probes' values sit in dynamic LDS (8385 doubles at n = 128).  nb instances per launch: registers of
+// lane l of instance b at val[(i * nb + b) * 64 + l]; for large handles the host loop (oh_launch_qp_assemble_block) keeps nb * len * 64 doubles
+// under a fixed budget.
 __global__ __launch_bounds__(64) void k_qp_assemble_block(QpParams Q, QpTape tp, int np_raw, int nb, const double* __restrict__ par, double* __restrict__ val,
                                                           double* __restrict__ rows_out, double* __restrict__ f0_out) {
 #pragma clang fp contract(off)
@@ -627,12 +411,8 @@ __global__ __launch_bounds__(64) void k_qp_assemble_block(QpParams Q, QpTape tp,
   const int n = Q.n, m = Q.m, me = Q.me;
   const int n_probe = 1 + 2 * n + n * (n - 1) / 2;
   const double* pb = par + (size_t)inst * np_raw;
-  double* P = rows_out + (size_t)inst * Q.np;
-  double* q = P + n * n;
-  double* M = q + n;
-  double* c = M + (size_t)m * n;
-  double* A = c + m;
-  double* bv = A + me * n;
+  const QpRow<double*> R = qp_row(rows_out + (size_t)inst * Q.np, n, m, me);
+  double *const P = R.P, *const q = R.q, *const M = R.M, *const c = R.c, *const A = R.A, *const bv = R.b;
   const int Bp = nb * 64, b = inst * 64 + lane;  // QIDX(i) = (i * nb + inst) * 64 + lane
   for (int base = 0; base < n_probe; base += 64) {
     const int pid = base + lane;
@@ -701,16 +481,11 @@ __global__ __launch_bounds__(256) void k_qp_add_constant(int B, double* __restri
   if (b < B) f[b] += f0[b];
 }
 
+size_t assemble_lds_bytes(const int n) { return sizeof(double) * (size_t)(1 + 2 * n + n * (n - 1) / 2); }  // a double per probe point
+size_t g_assemble_lds[64];
+
 }  // namespace
 
-void oh_launch_qp_assemble(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
-                           const int* xdep, int n_xdep, int B, int Bp, const double* p_raw, double* val, double* rows_out, double* f0) {
-  const QpTape tp{T.len, T.out_cost, op, a, b, c, rows, n_xdep, xdep};
-  if ((size_t)B * 64 <= (size_t)Bp) hipLaunchKernelGGL(k_qp_assemble_par, dim3(B), dim3(64), 0, s, Q, tp, T.np, B, p_raw, val, rows_out, f0);  // room for a lane per probe
-  else hipLaunchKernelGGL(k_qp_assemble, dim3((B + 63) / 64), dim3(64), 0, s, Q, tp, T.np, B, Bp, p_raw, val, rows_out, f0);
-}
-namespace {
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and sticky: ask only when a launch needs more than this device has been granted
 bool grant_dynamic_lds(const void* fn, const size_t bytes, size_t* granted /* [64], by device */) {
   static std::mutex mtx;
   int dev = 0;
@@ -721,8 +496,14 @@ bool grant_dynamic_lds(const void* fn, const size_t bytes, size_t* granted /* [6
   granted[dev] = bytes;
   return true;
 }
-size_t g_assemble_lds[64];
-}  // namespace
+
+void oh_launch_qp_assemble(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
+                           const int* xdep, int n_xdep, int B, int Bp, const double* p_raw, double* val, double* rows_out, double* f0) {
+  const QpTape tp{T.len, T.out_cost, op, a, b, c, rows, n_xdep, xdep};
+  // room for a lane per probe: a block per instance (n <= QP_SMALL_N: 4488 bytes of LDS at the most, nothing to be granted)
+  if ((size_t)B * 64 <= (size_t)Bp) hipLaunchKernelGGL(k_qp_assemble_block, dim3(B), dim3(64), assemble_lds_bytes(Q.n), s, Q, tp, T.np, B, p_raw, val, rows_out, f0);
+  else hipLaunchKernelGGL(k_qp_assemble, dim3((B + 63) / 64), dim3(64), 0, s, Q, tp, T.np, B, Bp, p_raw, val, rows_out, f0);
+}
 
 int oh_qp_assemble_block_chunk(const TapeParams& T, int B) {
   // instances per launch: the register file (len * 64 doubles per instance in flight) stays under 256 MB whatever B is
@@ -734,7 +515,7 @@ int oh_qp_assemble_block_chunk(const TapeParams& T, int B) {
 int oh_launch_qp_assemble_block(hipStream_t s, const QpParams& Q, const TapeParams& T, const int* op, const int* a, const int* b, const double* c, const int* rows,
                                 const int* xdep, int n_xdep, int B, int chunk, const double* p_raw, double* val, double* rows_out, double* f0, std::string* err) {
   const QpTape tp{T.len, T.out_cost, op, a, b, c, rows, n_xdep, xdep};
-  const size_t lds = sizeof(double) * (size_t)(1 + 2 * Q.n + Q.n * (Q.n - 1) / 2);
+  const size_t lds = assemble_lds_bytes(Q.n);
   if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_qp_assemble_block), lds, g_assemble_lds)) {
     (void)hipGetLastError();
     *err = "k_qp_assemble_block: " + std::to_string(lds) + " bytes of LDS per block were refused";
@@ -762,24 +543,22 @@ int oh_launch_qp_solve(hipStream_t s, const QpParams& Q, int B, int Bp, const do
   // beyond n = 32, m = 256, me = 32 a workgroup per instance for every B (a forced 0 / 1 / 2 does not fit there and falls back to it); forced == 3: on any handle
   if (oh_qp_takes_block(Q, forced)) return oh_launch_qp_solve_block(s, Q, B, x0, p, work, x, f, kkt, iters, status, mult, err);
   // the work set of a block in LDS when it fits 48 KB at 64, 32 or 16 instances per block; for a few instances the problem row as well
-  auto fit = [](const size_t doubles) {
+  const size_t work_bytes = sizeof(double) * qp_work_doubles(Q.n, Q.m, Q.me), row_bytes = sizeof(double) * qp_row_doubles(Q.n, Q.m, Q.me);
+  auto fit = [](const size_t bytes) {
     for (int c : {64, 32, 16})
-      if (sizeof(double) * doubles * c <= 48 * 1024) return c;
+      if (bytes * c <= 48 * 1024) return c;
     return 0;
   };
-  const int bs2 = fit((size_t)Q.nwork + Q.np), bs1 = fit((size_t)Q.nwork);
-  const size_t wave_bytes = sizeof(double) * ((size_t)Q.nwork + Q.np);
-  if (forced != 0 && forced != 1 && forced != 2 && B <= 64 && wave_bytes <= 48 * 1024) {  // a few instances: one wavefront each
-    hipLaunchKernelGGL(k_qp_solve_wave, dim3(B), dim3(64), wave_bytes, s, Q, B, x0, p, x, f, kkt, iters, status, mult);
+  const int bs2 = fit(work_bytes + row_bytes), bs1 = fit(work_bytes);
+  if (forced != 0 && forced != 1 && forced != 2 && B <= 64 && work_bytes + row_bytes <= 48 * 1024) {  // a few instances: one wavefront each
+    hipLaunchKernelGGL(k_qp_solve_wave, dim3(B), dim3(64), work_bytes + row_bytes, s, Q, B, x0, p, x, f, kkt, iters, status, mult);
     return 0;
   }
-  int mode = bs2 ? 2 : (bs1 ? 1 : 0);  // forced: option "qp_mode" (experiments)  // (velocity-IK QP, n = 7, m = 16: B = 1 in 1.77 / 1.49 / 1.15 ms wall, 65 536 in 13.0 / 12.7 / 11.5 ms for modes 0 / 1 / 2)
+  int mode = bs2 ? 2 : (bs1 ? 1 : 0);  // forced: option "qp_mode" (experiments)
   if (forced == 0 || (forced == 1 && bs1) || (forced == 2 && bs2)) mode = forced;
   if (mode == 2)
-    hipLaunchKernelGGL(k_qp_solve<2>, dim3((B + bs2 - 1) / bs2), dim3(bs2), sizeof(double) * ((size_t)Q.nwork + Q.np) * bs2, s, Q, B, Bp, x0, p, work, x, f, kkt, iters,
-                       status, mult);
-  else if (mode == 1)
-    hipLaunchKernelGGL(k_qp_solve<1>, dim3((B + bs1 - 1) / bs1), dim3(bs1), sizeof(double) * (size_t)Q.nwork * bs1, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
+    hipLaunchKernelGGL(k_qp_solve<2>, dim3((B + bs2 - 1) / bs2), dim3(bs2), (work_bytes + row_bytes) * bs2, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
+  else if (mode == 1) hipLaunchKernelGGL(k_qp_solve<1>, dim3((B + bs1 - 1) / bs1), dim3(bs1), work_bytes * bs1, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
   else hipLaunchKernelGGL(k_qp_solve<0>, dim3((B + 63) / 64), dim3(64), 0, s, Q, B, Bp, x0, p, work, x, f, kkt, iters, status, mult);
   return 0;
 }

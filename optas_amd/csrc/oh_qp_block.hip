@@ -2,9 +2,9 @@
 //
 //     min_x  x^T P x + q^T x      s.t.  M x + c >= 0,   A x + b = 0
 //
-// The iteration is the one of k_qp_solve (oh_qp.hip) and of oracle/qp_ipm.py: infeasible start, the same residuals, stopping test, diagonal
-// shift and retries, Schur regularisation, fraction to the boundary, sigma rule and statuses.  Sums associate differently: results agree to
-// rounding, not bit for bit.
+// The iteration is the one of qp_ipm (oh_qp.hip) and of oracle/qp_ipm.py: infeasible start, the same residuals and statuses, and the scalar rules
+// of oh_qp_rules.h (start, stopping test, diagonal shift and retries, Schur regularisation, fraction to the boundary, next mu), which both call.
+// The algorithms are this mapping's own.  Sums associate differently: results agree to rounding, not bit for bit.
 //
 // What lives where:
 //   global, streamed   the instance's row [P | q | M | c | A | b] (1.3 MB at the maximum sizes; M alone 1 MB)
@@ -18,10 +18,12 @@
 // (or the work slice) after a barrier.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <string>
 
+#include "oh_device.h"
 #include "oh_kernels.h"
+#include "oh_qp_layout.h"
+#include "oh_qp_rules.h"
 
 namespace {
 
@@ -32,22 +34,6 @@ constexpr int NSLOT = 3;  // tiles per thread: 32 * 33 / 2 = 528 tiles of the 12
 constexpr int SCRATCH = 1024;  // doubles the staging area has at least (partial sums of the transposed passes)
 
 __device__ __forceinline__ int tri(const int i) { return i * (i + 1) / 2; }
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k);
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = fmax(v, __shfl_xor(v, k));
-  return v;
-}
-__device__ __forceinline__ double wmin(double v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = fmin(v, __shfl_xor(v, k));
-  return v;
-}
 
 // out(r, sum_j Mat[r][j] vec[j]) for every row r < rows of the row-major global matrix; 16 lanes share a row (128-byte segments)
 template <class Out>
@@ -217,9 +203,9 @@ __device__ __forceinline__ Red3 block_reduce(double a, double b, double c, doubl
   }
   return r;
 }
-struct OpMax { __device__ double operator()(double v) const { return wmax(v); } __device__ double pair(double x, double y) const { return fmax(x, y); } };
-struct OpMin { __device__ double operator()(double v) const { return wmin(v); } __device__ double pair(double x, double y) const { return fmin(x, y); } };
-struct OpSum { __device__ double operator()(double v) const { return wsum(v); } __device__ double pair(double x, double y) const { return x + y; } };
+struct OpMax { __device__ double operator()(double v) const { return wave64_max(v); } __device__ double pair(double x, double y) const { return fmax(x, y); } };
+struct OpMin { __device__ double operator()(double v) const { return wave64_min(v); } __device__ double pair(double x, double y) const { return fmin(x, y); } };
+struct OpSum { __device__ double operator()(double v) const { return wave64_sum(v); } __device__ double pair(double x, double y) const { return x + y; } };
 
 __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const double* __restrict__ x0, const double* __restrict__ par, double* __restrict__ work,
                                                        double* __restrict__ xo, double* __restrict__ fo, double* __restrict__ kkt, int* __restrict__ iters,
@@ -227,12 +213,8 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
   extern __shared__ double qb_sm[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = Q.n, m = Q.m, me = Q.me;
-  const double* P = par + (size_t)b * Q.np;  // [n][n]
-  const double* q = P + n * n;               // [n]
-  const double* M = q + n;                   // [m][n]
-  const double* c = M + (size_t)m * n;       // [m]
-  const double* A = c + m;                   // [me][n]
-  const double* bv = A + me * n;             // [me]
+  const QpRow<const double*> R = qp_row(par + (size_t)b * Q.np, n, m, me);
+  const double *const P = R.P, *const q = R.q, *const M = R.M, *const c = R.c, *const A = R.A, *const bv = R.b;
   double* Wt = work + (size_t)b * ((size_t)me * n + (size_t)me * me);  // [n][me]: column r = L^{-1} A_r
   double* S = Wt + (size_t)me * n;                                      // packed lower triangle, me (me + 1) / 2
   double* w = qb_sm;
@@ -256,9 +238,9 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
   __syncthreads();
   double mu = 1.0;
   row_pass(M, m, n, x, [&](const int r, const double v) {
-    const double sv = fmax(v + c[r], 1.0);
+    const double sv = qp_rules::initial_slack(v + c[r]);
     s[r] = sv;
-    lam[r] = mu / sv;
+    lam[r] = qp_rules::initial_multiplier(mu, sv);
   });
   __syncthreads();
   int st = OH_STATUS_MAX_ITER, it = 0;
@@ -290,7 +272,7 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
       rd[tid] = v;
       rhs[tid] = -v + mtw;
       l_stat = fabs(v);
-      finite = (v == v) && (fabs(v) < 1e300);
+      finite = qp_rules::finite(v);
     }
     bool feas_nan = false;
     for (int k = tid; k < m; k += NT) {
@@ -310,7 +292,7 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
       const Red3 f = block_reduce((finite && !feas_nan) ? 0.0 : 1.0, 0.0, 0.0, red, OpMax{}, OpMax{}, OpMax{});
       if (f.a != 0.0) { st = OH_STATUS_NUMERICAL; break; }
     }
-    if (stat <= Q.tol && feas <= Q.tol && gap <= Q.tol) { st = OH_STATUS_CONVERGED; break; }
+    if (qp_rules::converged(stat, feas, gap, Q.tol)) { st = OH_STATUS_CONVERGED; break; }
     if (it == Q.max_iter) break;
     // ---- H = P + P^T + M^T diag(lam/s) M (+ shift), factored in place; rebuilt with a 1000 x larger shift on a failed pivot -------------
     auto build = [&]() { rank_k(M, m, n, dl, stage, [&](const int i, const int j, const double v) { H[tri(i) + j] = v + P[i * n + j] + P[j * n + i]; }); };
@@ -318,12 +300,12 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
     double dmax = 0.0;
     for (int i = tid; i < n; i += NT) dmax = fmax(dmax, fabs(H[tri(i) + i]));
     dmax = block_reduce(dmax, 0.0, 0.0, red, OpMax{}, OpMax{}, OpMax{}).a;
-    double shift = 1e-13 * fmax(dmax, 1.0);
+    double shift = qp_rules::first_shift(dmax);
     bool ok = false;
-    for (int attempt = 0; attempt < 8 && !ok; ++attempt) {
+    for (int attempt = 0; attempt < qp_rules::SHIFT_ATTEMPTS && !ok; ++attempt) {
       if (attempt > 0) {
         build();
-        shift *= 1e3;
+        shift *= qp_rules::SHIFT_GROWTH;
       }
       for (int i = tid; i < n; i += NT) H[tri(i) + i] += shift;
       __syncthreads();
@@ -370,7 +352,7 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
     __syncthreads();
     if (me > 0) {
       // S = W^T W (+ regularisation), S dnu = -r_e - W^T y, z = y + W dnu
-      rank_k(Wt, n, me, nullptr, stage, [&](const int i, const int j, const double v) { S[tri(i) + j] = (i == j) ? v + 1e-14 * fmax(1.0, v) : v; });
+      rank_k(Wt, n, me, nullptr, stage, [&](const int i, const int j, const double v) { S[tri(i) + j] = (i == j) ? v + qp_rules::schur_regularisation(v) : v; });
       col_pass(Wt, n, me, stage, [&](const int k) { return rhs[k]; }, [&](const int) { return 0.0; });
       __syncthreads();
       if (tid < me) dnu[tid] = -re[tid] - col_sum(stage, me, tid);
@@ -400,8 +382,8 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
     double ap = 1.0, ad = 1.0;
     for (int k = tid; k < m; k += NT) {
       const double v = ds[k], d2 = dl[k];
-      if (v < 0.0) ap = fmin(ap, -0.995 * s[k] / v);
-      if (d2 < 0.0) ad = fmin(ad, -0.995 * lam[k] / d2);
+      if (v < 0.0) ap = fmin(ap, qp_rules::boundary_step(s[k], v));
+      if (d2 < 0.0) ad = fmin(ad, qp_rules::boundary_step(lam[k], d2));
     }
     {
       const Red3 r = block_reduce(ap, ad, 0.0, red, OpMin{}, OpMin{}, OpMin{});
@@ -416,11 +398,7 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
     }
     for (int k = tid; k < me; k += NT) nu[k] += ad * dnu[k];
     comp = block_reduce(comp, 0.0, 0.0, red, OpSum{}, OpSum{}, OpSum{}).a;
-    if (m > 0) {
-      const double am = fmin(ap, ad);
-      const double sigma = (am > 0.9) ? 0.1 : ((am > 0.5) ? 0.3 : 0.8);
-      mu = fmax(sigma * comp / m, 1e-2 * Q.tol);
-    }
+    if (m > 0) mu = qp_rules::next_mu(ap, ad, comp, m, Q.tol);
     __syncthreads();
   }
   // ---- outputs ---------------------------------------------------------------------------------------------------------------------------
@@ -445,18 +423,7 @@ __global__ __launch_bounds__(NT) void k_qp_solve_block(QpParams Q, int B, const 
   }
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and sticky: ask only when a launch needs more than this device has been granted
-bool grant_dynamic_lds(const void* fn, const size_t bytes, size_t* granted /* [64], by device */) {
-  static std::mutex mtx;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-  std::lock_guard<std::mutex> lock(mtx);
-  if (bytes <= granted[dev]) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
-  granted[dev] = bytes;
-  return true;
-}
-size_t g_block_lds[64];
+size_t g_block_lds[64];  // (grant_dynamic_lds, oh_kernels.h)
 
 size_t block_lds_bytes(const int n, const int m, const int me) {
   const int npad = (n + TS - 1) / TS * TS, mepad = (me + TS - 1) / TS * TS;

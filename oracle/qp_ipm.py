@@ -3,6 +3,7 @@ family (optas_amd/csrc/oh_qp.hip):   min x^T P x + q^T x   s.t.  M x + c >= 0,  
 Infeasible-start primal-dual interior point, slacks s = Mx + c, reduced Newton system H = P + P^T + M^T (lam/s) M, Schur
 complement on the equality rows.  Independent cross-checks: scipy SLSQP in the reference's wiring and, for the Booth
 function of the reference's own solver test (tests/test_solver.py:22-54), the known answer (1, 3).
+The scalar rules restated below (start, shift and retries, regularisation, 0.995, sigma) are the device's optas_amd/csrc/oh_qp_rules.h.
 
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import it.
 """
