@@ -1187,7 +1187,8 @@ OH_DEV bool step_instance_zc(const FigParams& P, const FigBuffers& D, const int 
     if (P.hessian != OH_HESSIAN_GAUSS_NEWTON && cur == ts) {
       // accepted in this launch: the gradient its evaluation took the multiplier estimate from is still in the other slot; this point's own is rebuilt by the
       // evaluation that follows.  The copy (T x N doubles) is k_defer_copy's, right after this kernel, a thread per (instance, knot) of the list: done here, by the
-      // one lane of the instance, it held the wavefront up for as long as the retry it replaced (k_step_zc 9 % slower over a solve)
+      // one lane of the instance, it held the wavefront up for as long as the retry it replaced (k_step_zc 9 % slower over a solve).
+      // A seed (no step counted yet) has no older gradient -- it was evaluated fresh, lam = 0: k_defer_copy / k_sweep_lists write zeros for it (oh_kernels.hip)
       D.defer_list[(size_t)ts * Bp + oh_take_ticket(D.n_defer + ts)] = b;
     }
     return true;

@@ -196,8 +196,11 @@ __global__ __launch_bounds__(256) void k_defer_copy(FigParams P, FigBuffers D, c
     const int cur = D.cur[b];
     const double* __restrict__ Gold = D.Gfull[1 - cur];
     double* __restrict__ Gnew = D.Gfull[cur];
+    // A seed that defers (exact curvature, no step counted yet) was evaluated fresh, without a multiplier estimate, and has no older gradient: the other
+    // slot holds what the handle's previous solve left there.  Zeros make the evaluation that follows take lam = 0 again, bit for bit.
+    const bool seed = D.iters[b] == 0;
 #pragma unroll
-    for (int k = 0; k < N; ++k) Gnew[IDX(t, N, k)] = Gold[IDX(t, N, k)];
+    for (int k = 0; k < N; ++k) Gnew[IDX(t, N, k)] = seed ? 0.0 : Gold[IDX(t, N, k)];
   }
 }
 
@@ -219,8 +222,9 @@ __global__ __launch_bounds__(256) void k_sweep_lists(FigParams P, FigBuffers D, 
       const int cur = D.cur[b];
       const double* __restrict__ Gold = D.Gfull[1 - cur];
       double* __restrict__ Gnew = D.Gfull[cur];
+      const bool seed = D.iters[b] == 0;  // (see k_defer_copy)
 #pragma unroll
-      for (int k = 0; k < N; ++k) Gnew[IDX(t, N, k)] = Gold[IDX(t, N, k)];
+      for (int k = 0; k < N; ++k) Gnew[IDX(t, N, k)] = seed ? 0.0 : Gold[IDX(t, N, k)];
     }
   }
   if (rescue) {

@@ -292,12 +292,14 @@ def _orient(prob, Q, Rc):
     return c, M @ Jw
 
 
-def retract(prob, Q, Rc, tol=1e-10, max_corr=4, e_tgt=None):
+def retract(prob, Q, Rc, tol=1e-10, max_corr=4, e_tgt=None, log=None):
     """Newton corrections per knot (k_eval's loop).  Without a target: q_t <- q_t - Jc^T (Jc Jc^T)^{-1} c, the minimum-norm way back
     onto R(q_t) = Rc.  With e_tgt (T, 3), the end-effector positions the linear model of the step predicted: minimum-norm Newton steps
     on the six rows [c(q); e(q) - e_tgt] = 0 (a second-order correction: the trial point follows the curved valley of the stiff
     tracking cost instead of leaving it at second order, which is what kept the Gauss-Newton model honest only for tiny steps along
-    the redundant direction).  The loop still stops on the orientation rows alone."""
+    the redundant direction).  The loop still stops on the orientation rows alone.
+    log: a list that receives the two kinds of decisions taken per free knot, as (kind, value / threshold): ("correct", max|c| / tol) for every
+    "another correction?" test and ("settled", ||dq||_1^2 / tol) for every settled test; an observer, it changes nothing."""
     Q = Q.copy()
     settled = np.zeros(Q.shape[0], dtype=bool)  # knots whose last correction was short enough to trust without another look
     settled[:2] = True
@@ -308,6 +310,8 @@ def retract(prob, Q, Rc, tol=1e-10, max_corr=4, e_tgt=None):
         trA = np.trace(A, axis1=1, axis2=2)
         Jc = (0.5 * (trA[:, None, None] * np.eye(3)[None] - A)) @ Jw
         bad = np.where((np.max(np.abs(c), axis=1) > tol) & ~settled)[0]
+        if log is not None:
+            log.extend(("correct", float(v) / tol) for v in np.max(np.abs(c), axis=1)[~settled])
         if bad.size == 0:
             break
         for t in bad:
@@ -322,6 +326,8 @@ def retract(prob, Q, Rc, tol=1e-10, max_corr=4, e_tgt=None):
             # what the step leaves behind is second order in dq, bounded by ||dq||_1^2: below the tolerance the kinematics pass that
             # would only confirm it is skipped (eval_knot, oh_figure8.h)
             settled[t] = np.abs(dq).sum() ** 2 <= tol
+            if log is not None:
+                log.append(("settled", float(np.abs(dq).sum() ** 2) / tol))
     return Q
 
 
@@ -343,8 +349,16 @@ def retract_tol(tol_feas, pred, far, tight=True):
     return min(floor, max(RETRACT_FLOOR, 1e-2 * pred)) if tight else floor  # tight: handles with inequality rows (FigParams.tol_retract_min)
 
 
-def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9, mu0=0.0, exact=False, rule="nielsen", verbose=False, hessian="hybrid", limits=None, rho0=None, guards=None, overrelax=1.5, overrelax_from=4, vlimits=None):
+def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9, mu0=0.0, exact=False, rule="nielsen", verbose=False, hessian="hybrid", limits=None, rho0=None, guards=None, overrelax=1.5, overrelax_from=4, vlimits=None,
+                        on_system=None):
     """Returns dict(Q, f, iters (= steps solved: accepted + rejected), rejected, stat, feas, status).
+    on_system(iteration, cur, mu, z, info): called after every linear solve (iteration = steps counted so far; z is None where the factorisation broke down
+    and the damping is raised).  cur is the record of the accepted point: Q, f, feas, Z, gt, Dr, Er, e, JZ and G, Dfull, Jc, wnext (the Lagrangian
+    gradient, the full curvature blocks, the Jacobian of the orientation rows and the velocity rows' coupling weights, all (T, ...)).  While a hook
+    is set, info tells what decided the evaluation before the solve: accept, ratio (the ratio test's; None on a first, outer or polish evaluation),
+    converged (violation of the trial / what lm_accept allows), polish_margin (violation of the accepted point / what asks for a polish), zero_step (a
+    polish evaluation), stat, hyb_switch, retraction (retract's log for the point evaluated), with velocity rows also rows (min |lam_v / vscale - rho g_v|
+    over the rows of the point evaluated).  An observer: it changes nothing.
     limits = (lo, up) or guards = oracle.guarded.Guards (joint limits and/or sphere clearances): inequality rows at the free
     knots through the augmented Lagrangian of oracle/guarded.py (k_eval_lg / k_step_lg); adds "lam" (T, NC), "meas", "outers".
     vlimits = (vlo, vup): joint-velocity rows dq_t - vlo >= 0, vup - dq_t >= 0 (enforce_model_limits(time_deriv=1), builder.py:471-509) on
@@ -412,6 +426,13 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
     path, Rc = prob.references(qc)
     kap = prob.kappa
     F = slice(2, T)
+    rlog = [] if on_system is not None else None
+
+    def _retract(Q, tol, e_tgt=None):
+        if rlog is not None:
+            del rlog[:]
+        return retract(prob, Q, Rc, tol=tol, e_tgt=e_tgt, log=rlog)
+
     Qc = np.tile(qc, (T, 1)) if Q0 is None else Q0.copy()
     Qc[0] = qc
     Qc[1] = qc
@@ -419,7 +440,7 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
     iters = rejected = 0
     first = True
     polish = False
-    Qt = retract(prob, Qc, Rc, tol=retract_tol(tol_feas, 0.0, False, tight))
+    Qt = _retract(Qc, tol=retract_tol(tol_feas, 0.0, False, tight))
     lam = np.zeros((T, 3))
     cur = None
     status = 1
@@ -430,6 +451,15 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
         use_exact = hessian == "exact" or (hessian == "hybrid" and not first and stat_prev <= hyb_switch)
         if guard and guards.links:
             use_exact = False  # no curvature of the sphere rows in the exact block: Gauss-Newton models them better
+        if use_exact:
+            # multipliers of the orientation rows as eval_knot takes them (csrc/oh_figure8.h): least squares of G_acc + Jc^T lam = 0 with the
+            # Lagrangian gradient of the last ACCEPTED point (lagged by one iteration) and the Jacobian of the point BEING EVALUATED; none on a fresh
+            # point (have_G = exact && !fresh in eval_unit).  Polish and outer evaluations are not fresh: they take the same form.
+            lam = np.zeros((T, 3))
+            if cur is not None:
+                _, Jc_t = _orient(prob, Qt, Rc)
+                for t in range(2, T):
+                    lam[t] = -np.linalg.solve(Jc_t[t] @ Jc_t[t].T + 1e-14 * np.eye(3), Jc_t[t] @ cur["G"][t])
         phi, g, W, c, Jc = prob.evaluate(Qt, path, Rc, lam=lam, exact=use_exact)
         if guard:
             if outer:  # multiplier refresh at the accepted point with the old penalty, evaluation with the new one
@@ -445,7 +475,7 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
             gv, psi_t, dgrad, dW, meas_t = guard_terms(Qt, lam_g, rho_g)
             wv_t = np.zeros((T - 1, n))
             if vel:
-                _, psi_v, sig, wv_t, meas_v = vel_terms(Qt, lam_v, rho_g)
+                gv_v, psi_v, sig, wv_t, meas_v = vel_terms(Qt, lam_v, rho_g)
                 psi_t = psi_t.copy()
                 psi_t[1:] += psi_v  # interval (t-1, t) is booked on knot t, like kappa ||q_t - q_{t-1}||^2
                 dgrad = dgrad.copy()
@@ -459,6 +489,10 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
         feas_t = float(np.max(np.abs(c[F])))
         # ---- k_step phase A
         polish_request = False
+        # what an observer is told about this evaluation (on_system): ratio / converged / polish_margin are None where no ratio test was taken
+        info = dict(ratio=None, converged=None, polish_margin=None, zero_step=bool(polish or (guard and outer)), feas=feas_t)
+        if vel:  # how far the nearest velocity row is from changing sides, in the units of the other rows: |lam_v / vscale - rho g_v| (tests/free_sweep_cases.py)
+            info["rows"] = float(np.abs(lam_v / vscale - rho_g * gv_v)[1:].min())
         if first or (guard and outer) or polish:
             accept = True
             first = False
@@ -469,11 +503,14 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
             rho = (cur["f"] - f_t) / max(pred, 1e-300)
             # (noise: what the orientation violations of the two points are worth, lm_accept in csrc/oh_figure8.h -- handles with inequality rows)
             noise = 10.0 * max(1.0, abs(cur["f"])) * (feas_t + cur["feas"]) if tight else 0.0
-            accept = np.isfinite(f_t) and (rho > 1e-4 or (pred <= max(1e-15 * abs(cur["f"]), noise) and f_t <= cur["f"] + 1e-14 * abs(cur["f"]) + noise))
+            # (a trial point whose retraction did not converge is refused; converged ones may keep up to retract_tol of violation: lm_accept)
+            feas_max = max(max(1e-8, 10.0 * tol_feas), 10.0 * retract_tol(tol_feas, pred, stat_prev > hyb_switch, tight))
+            accept = np.isfinite(f_t) and feas_t <= feas_max and (rho > 1e-4 or (pred <= max(1e-15 * abs(cur["f"]), noise) and f_t <= cur["f"] + 1e-14 * abs(cur["f"]) + noise))
             # a rejected trial against an accepted point that was retracted loosely: the accepted objective is off by (multiplier) x
             # violation, and steps that predict less than that can never be accepted.  Re-evaluate the accepted point itself at the
             # floor tolerance (zero step, accepted unconditionally) before blaming the model.
             polish_request = (not accept) and cur["feas"] > 10.0 * retract_tol(tol_feas, pred, False, tight)
+            info.update(ratio=float(rho), converged=feas_t / feas_max, polish_margin=cur["feas"] / (10.0 * retract_tol(tol_feas, pred, False, tight)))
             if polish_request:
                 pass
             elif rule == "hip":
@@ -497,7 +534,7 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
                 e_tgt = cur["e"].copy()
                 e_tgt[F] += np.einsum("tma,ta->tm", cur["JZ"], z_ls)
                 tol_r = retract_tol(tol_feas, pred, stat_prev > hyb_switch, tight)
-                Qt = retract(prob, Qt, Rc, tol=tol_r, e_tgt=e_tgt)
+                Qt = _retract(Qt, tol=tol_r, e_tgt=e_tgt)
                 if iters >= max_iter:
                     break
                 iters += 1
@@ -523,7 +560,8 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
                 rejected += 1
             if polish_request:
                 polish = True
-                Qt = retract(prob, cur["Q"], Rc, tol=retract_tol(tol_feas, 0.0, False, tight), e_tgt=cur["e"])
+                # (a zero step through k_retract: eval_unit takes retract_tol(P, true, 0, stat) -- far from the solution the floor, not the end game's)
+                Qt = _retract(cur["Q"], tol=retract_tol(tol_feas, 0.0, stat_prev > hyb_switch, tight), e_tgt=cur["e"])
                 pred = 0.0
                 iters += 1
                 continue
@@ -555,14 +593,14 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
             }
             e_acc, _, Jp_acc, _ = prob.chain.jac(Qt)
             cur["e"], cur["JZ"] = e_acc, np.einsum("tmi,tia->tma", Jp_acc[F], Zs[F])
-            if hessian != "gauss_newton":
-                for t in range(2, T):
-                    lam[t] = -np.linalg.solve(Jc[t] @ Jc[t].T + 1e-14 * np.eye(3), Jc[t] @ G[t])
+            cur["G"], cur["Dfull"], cur["Jc"], cur["wnext"] = G, Dfull, Jc, wnext
         # ---- k_step phase B
         stat = float(np.max(np.abs(cur["gt"])))
         stat_prev = stat
         while True:
             z, ok = block_tridiag_solve(cur["Dr"], cur["Er"], -cur["gt"], mu)
+            if on_system is not None:
+                on_system(iters, cur, mu, z if ok else None, dict(info, accept=bool(accept), stat=stat, hyb_switch=hyb_switch, retraction=list(rlog)))
             if ok:
                 break
             mu = max(4.0 * mu, 1e-2)
@@ -579,7 +617,7 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
                 meas_prev = cur["meas"]
                 omega = max(tol, min(omega, 0.1 * cur["meas"]))
                 outer = True
-                Qt = retract(prob, cur["Q"], Rc, tol=retract_tol(tol_feas, 0.0, stat > hyb_switch, tight), e_tgt=cur["e"])  # (zero step through k_retract)
+                Qt = _retract(cur["Q"], tol=retract_tol(tol_feas, 0.0, stat > hyb_switch, tight), e_tgt=cur["e"])  # (zero step through k_retract)
                 pred = 0.0
                 iters += 1
                 continue
@@ -601,7 +639,7 @@ def solve_structured_lm(prob, qc, Q0=None, max_iter=300, tol=1e-6, tol_feas=1e-9
         e_tgt[F] += np.einsum("tma,ta->tm", cur["JZ"], z)  # predicted end-effector positions: e + (Jp Z) z
         # far from the solution the violation a trial point may keep is tied to the decrease its step predicts (retract_tol in oh_figure8.h)
         tol_r = retract_tol(tol_feas, pred, stat > hyb_switch, tight)
-        Qt = retract(prob, Qt, Rc, tol=tol_r, e_tgt=e_tgt)
+        Qt = _retract(Qt, tol=tol_r, e_tgt=e_tgt)
         iters += 1
     out = {"Q": cur["Q"], "f": cur["f"] - cur["fpsi"], "iters": iters, "rejected": rejected, "stat": stat, "feas": cur["feas"], "status": status, "path": path, "Rc": Rc}
     if guard:

@@ -22,10 +22,14 @@ def test_compiled_port_matches_numpy_restatement():
         prob = StructuredFigureEight(OracleRobot(KUKA_KIN), "end_effector_ball", T=50)
         for b in range(0, B, 3):
             s = solve_structured_lm(prob, qc[b], max_iter=300, tol=1e-6, hessian=hessian)
-            # same optimum; the step at which the reduced gradient first dips under the hybrid switch (1e-2, approached as 1.2e-2, 7.4e-3 ...)
-            # and the fate of a borderline over-relaxed step depend on rounding, which differs between libm and the kernels' own sincos
-            assert abs(int(it[b]) - s["iters"]) <= 3 and abs(f[b] - s["f"]) <= 1e-9 * abs(s["f"])
-            assert np.abs(x[b, :350].reshape(50, 7) - s["Q"]).max() < 1e-4
+            # Hybrid: the numpy port takes the multipliers of the exact block as eval_knot does (lagged gradient of the accepted point, Jacobian of the
+            # point evaluated), so the two are the same iteration to rounding: equal step counts, knots measured at 5e-15 (1e-9: DESIGN 2.3's figure
+            # for two roundings of one iteration).  Gauss-Newton crawls to the tolerance along the weakly curved elbow-swivel direction: the step at
+            # which the reduced gradient dips under 1e-6 may differ by one (34 / 35 on instance 3), which leaves 7e-6 rad of play in the knots.
+            dQ = np.abs(x[b, :350].reshape(50, 7) - s["Q"]).max()
+            print(hessian, b, "steps", int(it[b]), s["iters"], "|Q - Q_port| %.2e" % dQ)
+            assert abs(int(it[b]) - s["iters"]) <= (0 if hessian == "hybrid" else 1) and abs(f[b] - s["f"]) <= 1e-9 * abs(s["f"])
+            assert dQ < (1e-9 if hessian == "hybrid" else 1e-4)
     x1, f1, _, it1, _ = cpu_port.solve(chain, 50, dt, lp, x0, qc, hessian=2, threads=1)
     x3, f3, _, it3, _ = cpu_port.solve(chain, 50, dt, lp, x0, qc, hessian=2, threads=3)
     assert np.array_equal(x1, x3) and np.array_equal(it1, it3)  # threading only partitions instances

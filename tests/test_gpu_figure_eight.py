@@ -231,13 +231,14 @@ def test_state_machine_matches_numpy_port(hip_lib, nlp, hessian, tail, monkeypat
     for b in range(B):
         s = solve_structured_lm(prob, qc[b], max_iter=300, tol=1e-6, hessian=hessian)
         assert s["status"] == res.status[b] == 0
-        # far from the solution trial points keep up to 1e-5 of orientation violation (retract_tol): which side of a ratio test a
-        # borderline step lands on depends on how that residue rounds, so the two implementations may part by a few steps on the
-        # long runs; they must still arrive at the same optimum.  (The compiled port, same code as the kernels, is compared step
-        # for step in test_batch_machinery_matches_serial_cpu_port.)
-        assert abs(int(res.iters[b]) - s["iters"]) <= max(1, s["iters"] // 4), (b, res.iters[b], s["iters"])
-        # stopping at |Z^T G| <= 1e-6 leaves ~1e-5 rad of play along the weakly curved elbow-swivel directions
-        assert abs(res.f[b] - s["f"]) <= 1e-9 * abs(s["f"]) and np.abs(res.x[b, : 7 * 50].reshape(50, 7) - s["Q"]).max() < 1e-4
+        # Hybrid: the port takes the multipliers of the exact block as eval_knot does, and the compiled host port (the kernels' own code) takes the
+        # port's steps one for one on these inputs (equal counts, knots to 3e-13): the kernels may part by one step where the reduced gradient meets
+        # the tolerance, no more, and end within 1e-8 rad.  Gauss-Newton crawls along the weakly curved elbow-swivel direction: a borderline last
+        # step (99 / 100 on instance 1 of the compiled port) leaves 5e-6 rad of play.
+        dQ = np.abs(res.x[b, : 7 * 50].reshape(50, 7) - s["Q"]).max()
+        print(hessian, tail, b, "steps", int(res.iters[b]), s["iters"], "|Q - Q_port| %.2e" % dQ, "f rel %.2e" % (abs(res.f[b] - s["f"]) / abs(s["f"])))
+        assert abs(int(res.iters[b]) - s["iters"]) <= (1 if hessian == "hybrid" else 2), (b, res.iters[b], s["iters"])
+        assert abs(res.f[b] - s["f"]) <= 1e-9 * abs(s["f"]) and dQ < (1e-8 if hessian == "hybrid" else 1e-4)
 
 
 def test_batch_machinery_matches_serial_cpu_port(hip_lib, nlp, monkeypatch):
